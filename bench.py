@@ -2,7 +2,19 @@
 Benchmark of the hot path: affinity voxels/sec of the sliding-window 3D-UNet
 prediction over a synthetic volume.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's
+output if --dump-outputs is given, and prints the result line: the contract fields,
+"config" and "roofline" (both read off the timed steps). Every extra measurement
+("pipelined", "parity", "host_to_host", "configs", "cpu_baseline" below) runs only
+with --full; the --no-* / --pipelined-streams options then switch single ones off.
+
+--dump-outputs DIR writes the affinities the last timed step computed (the rank's
+owned region of predict_shard()'s result) as DIR/affinity.npy (float32, flat; for
+N > 1 one DIR/affinity_rank<r>.npy per rank). An output larger than the budget
+(DUMP_BYTES over all ranks) is sampled at fixed seeded positions that depend only
+on its shape, so two builds run with the same arguments compare element for element.
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES: it
 starts N fresh child processes of this script (one rank per GPU, RANK /
@@ -33,7 +45,7 @@ meets north_star's 1e-3 against the reference (measured 2.7e-4 max, `parity`
 block); bf16 storage runs at the same speed but sits at 2.3e-3 .. 2.9e-3.
 
 Rank 0 prints ONE JSON line with the contract fields plus "roofline" (dominant
-kernel, HIP-event timed on the launch stream), "parity" (this dtype against the
+kernel, HIP-event timed on the launch stream) and, with --full, "parity" (this dtype against the
 reference's own 160^3 output, tests/golden/g6), "pipelined" (the same steps with
 three batches in flight on separate HIP streams -- what predict() does by default:
 faster, but kernels overlap, so it is reported beside `value`, never as it),
@@ -72,6 +84,8 @@ PROFILE_ROUND = "r03"  # profiles/<round>_pmc_hbm_<dtype>.json of the code this 
 # (z, y, x) extents in units of --size per world size: BASELINE.json configs[2], [3], -, [4]
 GLOBAL_SHAPES = {1: (1, 1, 1), 2: (2, 1, 1), 4: (2, 2, 1), 8: (4, 2, 2)}
 CONFIG_NAMES = {1: "configs[2]", 2: "configs[3]", 8: "configs[4]"}
+DUMP_BYTES = 32 << 20   # --dump-outputs: float32 bytes over all ranks (whole output if it fits)
+DUMP_SEED = 0
 
 
 def parse_args():
@@ -79,6 +93,11 @@ def parse_args():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's affinities to DIR/*.npy (float32, seeded sample if large)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra measurements (pipelined, parity, host_to_host, configs, "
+                        "cpu_baseline); a plain run measures the headline figure only")
     p.add_argument("--dtype", default="fp16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--size", type=int, default=1024, help="edge of the per-GPU cube (1024 = BASELINE)")
     p.add_argument("--batch", type=int, default=16)
@@ -96,7 +115,10 @@ def parse_args():
     p.add_argument("--input-halo", default=None, choices=["exchange", "synth"],
                    help="N > 1: fetch the input halo from the neighbours inside the timed step "
                         "(exchange, default) or synthesise every rank's halo in place (synth)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def zcol_main(ext, tile):
@@ -275,6 +297,24 @@ def synth_block(origin, dims, gshape, device):
     blk = _native.Block.make(tuple(dims), tuple(origin), tuple(gshape))
     _native.check(_native.lib().exaspim_synth_volume_u16(t.data_ptr(), blk, 0, None), "synth")
     return t
+
+
+def dump_output(path, t, max_elems):
+    """Writes device tensor t to path (.npy, float32, flattened in C order): all of it when it has
+    at most max_elems elements, else the elements at sorted positions drawn with DUMP_SEED from
+    its element count alone (the same positions in every run of the same shape)."""
+    import numpy as np
+    import torch
+
+    n = t.numel()
+    if n <= max_elems:
+        sample = t.float().reshape(-1)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        flat = np.unique(rng.integers(0, n, size=max_elems, dtype=np.int64))
+        idx = torch.unravel_index(torch.from_numpy(flat).to(t.device), tuple(t.shape))
+        sample = t[idx].float()
+    np.save(path, sample.cpu().numpy())
 
 
 def dominant_roofline(ms, cnt, dtype, batch, patches_per_step):
@@ -491,6 +531,11 @@ def main():
     exchange["seconds"] = 0.0
     elapsed, ms, cnt, out = timed_steps(model, timed_step, args.steps, 0, barrier)
     checksum = float(out.sum().item())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "affinity.npy" if world == 1 else f"affinity_rank{rank}.npy"
+        dump_output(os.path.join(args.dump_outputs, name), sharding.owned_result(out, shard),
+                    DUMP_BYTES // 4 // world)
     del out
     # The same K steps with several batches in flight (predict(..., n_streams=k), predict()'s
     # default): kernels of different batches then share the device, one kernel's ramp-down overlaps
@@ -498,7 +543,7 @@ def main():
     # which is why `value` and `roofline` above are single-stream. Reported next to them, never as
     # `value`.
     pipelined = None
-    if world == 1 and args.pipelined_streams > 1 and args.streams == 1:
+    if args.full and world == 1 and args.pipelined_streams > 1 and args.streams == 1:
         def step_pipelined():
             return step(n_streams=args.pipelined_streams, timings={"seconds": 0.0})
         out = step_pipelined()      # the worker streams' workspaces are allocated here
@@ -594,7 +639,7 @@ def main():
         }
         if pipelined is not None:
             result["pipelined"] = pipelined
-        if world == 1:
+        if args.full and world == 1:
             if not args.no_parity:
                 result["parity"] = parity_block(model, args.dtype)
             if not args.no_host_to_host:

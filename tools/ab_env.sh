@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 VAR=$1; VALS=$2; shift 2
 for v in $VALS $VALS; do
-  env $VAR=$v timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-to-host --pipelined-streams 0 --steps 3 "$@" 2>/dev/null | tail -1 | python -c "
+  env $VAR=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-host-to-host --pipelined-streams 0 --steps 3 "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 p=d.get('parity') or {}
