@@ -82,6 +82,58 @@ __device__ __forceinline__ void buf_store16_counted(const uint4& v, __amdgpu_buf
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// ---- device helpers shared by the fp16 stores and the max-pools ---------------
+// Saturating float -> half: beyond +-65504 the largest finite half instead of +-inf, a NaN stays
+// NaN. (v_med3_f32 alone returns the lower bound for a NaN input, and hipcc folds it so as well.)
+__device__ __forceinline__ float sat_f16(float v) {
+    return v != v ? v : __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
+}
+
+// The max-pools propagate NaN like torch's max_pool3d, with the same bits whatever the order in
+// which a window is reduced (the fused and the separate pool are held to each other bit for bit).
+// float32: fmaxf for numbers, the canonical quiet NaN if either input is one.
+__device__ __forceinline__ float max_nan(float a, float b) {
+    return (a != a || b != b) ? __uint_as_float(0x7fc00000u) : fmaxf(a, b);
+}
+__device__ __forceinline__ uint4 max_nan4(const uint4& a, const uint4& b) {
+    return make_uint4(__float_as_uint(max_nan(__uint_as_float(a.x), __uint_as_float(b.x))),
+                      __float_as_uint(max_nan(__uint_as_float(a.y), __uint_as_float(b.y))),
+                      __float_as_uint(max_nan(__uint_as_float(a.z), __uint_as_float(b.z))),
+                      __float_as_uint(max_nan(__uint_as_float(a.w), __uint_as_float(b.w))));
+}
+// bf16 and f16 order like sign-magnitude integers: flipping the magnitude bits of negative
+// values, x ^ ((x >> 15) & 0x7fff) per 16-bit half, makes them order like two's-complement
+// shorts, so a packed integer maximum picks the larger float; the map is its own inverse.
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned key16x2(unsigned x) {
+    const s16x2 m = __builtin_bit_cast(s16x2, x) >> (short)15;   // 0 or -1 per half
+    return x ^ (__builtin_bit_cast(unsigned, m) & 0x7fff7fffu);
+}
+// The ordering key of a value: key16x2 after the sign of a NaN is cleared, so that every NaN
+// (a magnitude above INF16, the bits of +inf: 0x7c00 f16, 0x7f80 bf16) orders above +inf.
+// The inverse of a key is key16x2.
+template <unsigned INF16>
+__device__ __forceinline__ unsigned okey16x2(unsigned x) {
+    const u16x2 mag = __builtin_bit_cast(u16x2, x & 0x7fff7fffu);
+    const auto nan = mag > (u16x2){(unsigned short)INF16, (unsigned short)INF16};   // -1 per NaN half
+    return key16x2(x & ~(__builtin_bit_cast(unsigned, nan) & 0x80008000u));
+}
+__device__ __forceinline__ unsigned maxkey16x2(unsigned ka, unsigned kb) {
+    return __builtin_bit_cast(
+        unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ka), __builtin_bit_cast(s16x2, kb)));
+}
+__device__ __forceinline__ uint4 key16(const uint4& v) {
+    return make_uint4(key16x2(v.x), key16x2(v.y), key16x2(v.z), key16x2(v.w));
+}
+template <unsigned INF16>
+__device__ __forceinline__ uint4 okey16(const uint4& v) {
+    return make_uint4(okey16x2<INF16>(v.x), okey16x2<INF16>(v.y), okey16x2<INF16>(v.z), okey16x2<INF16>(v.w));
+}
+__device__ __forceinline__ uint4 maxkey16(const uint4& a, const uint4& b) {
+    return make_uint4(maxkey16x2(a.x, b.x), maxkey16x2(a.y, b.y), maxkey16x2(a.z, b.z), maxkey16x2(a.w, b.w));
+}
+
 // ---- network plan ---------------------------------------------------------
 // Channel counts are padded to multiples of 32 inside the workspace so that
 // every MFMA convolution sees whole 32-wide output tiles and whole 32-byte
@@ -205,6 +257,18 @@ struct ConvArgs {
     unsigned long long* trace = nullptr;
 #endif
 };
+
+// Host-side record of the last convolution configuration this thread launched (the launcher's
+// __PRETTY_FUNCTION__, template arguments included) and its split-K factor: read by the tests'
+// layer probe (layer_probe.hip) to assert which dispatch path a case took.
+struct ConvLaunchRecord {
+    const char* config = "";
+    int ksplit = 0;
+};
+ConvLaunchRecord& last_conv_launch();
+// The same for the inc.0 and upsampling launchers (layers.hip): the name of the kernel variant
+// the last launch_conv_first / launch_upsample2 of this thread ran.
+const char*& last_layer_kernel();
 
 int launch_conv3x3x3(int dtype, const ConvArgs& a, hipStream_t stream);
 // Thin remainders of a region along y or x (at most 4 voxels thick) on 2-voxel-thick

@@ -51,9 +51,10 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
-struct F32Tag { static constexpr int kG = 4; static constexpr int kCode = EXASPIM_DT_F32; };
-struct BF16Tag { static constexpr int kG = 8; static constexpr int kCode = EXASPIM_DT_BF16; };
-struct F16Tag { static constexpr int kG = 8; static constexpr int kCode = EXASPIM_DT_F16; };
+// kInf16: the bits of +inf of a 16-bit type (the max-pools' NaN test, common.h: okey16)
+struct F32Tag { static constexpr int kG = 4; static constexpr int kCode = EXASPIM_DT_F32; static constexpr unsigned kInf16 = 0x7f80; };
+struct BF16Tag { static constexpr int kG = 8; static constexpr int kCode = EXASPIM_DT_BF16; static constexpr unsigned kInf16 = 0x7f80; };
+struct F16Tag { static constexpr int kG = 8; static constexpr int kCode = EXASPIM_DT_F16; static constexpr unsigned kInf16 = 0x7c00; };
 
 template <typename Tag>
 __device__ __forceinline__ void mma(f32x16& acc, const uint4& wf, const uint4& xf);
@@ -124,36 +125,16 @@ template <typename Tag>
 __device__ __forceinline__ uint4 max16(const uint4& a, const uint4& b);
 template <>
 __device__ __forceinline__ uint4 max16<F32Tag>(const uint4& a, const uint4& b) {
-    return make_uint4(__float_as_uint(fmaxf(__uint_as_float(a.x), __uint_as_float(b.x))),
-                      __float_as_uint(fmaxf(__uint_as_float(a.y), __uint_as_float(b.y))),
-                      __float_as_uint(fmaxf(__uint_as_float(a.z), __uint_as_float(b.z))),
-                      __float_as_uint(fmaxf(__uint_as_float(a.w), __uint_as_float(b.w))));
+    return max_nan4(a, b);
 }
-// bf16 (and f16) order like sign-magnitude integers: flipping the magnitude bits of negative
-// values, x ^ ((x >> 15) & 0x7fff) per 16-bit half, makes them order like two's-complement
-// shorts, so a packed integer maximum picks the larger float; the map is its own inverse.
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned key16x2(unsigned x) {
-    const s16x2 m = __builtin_bit_cast(s16x2, x) >> (short)15;   // 0 or -1 per half
-    return x ^ (__builtin_bit_cast(unsigned, m) & 0x7fff7fffu);
-}
-__device__ __forceinline__ unsigned maxkey16x2(unsigned ka, unsigned kb) {
-    return __builtin_bit_cast(
-        unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ka), __builtin_bit_cast(s16x2, kb)));
-}
-__device__ __forceinline__ uint4 key16(const uint4& v) {
-    return make_uint4(key16x2(v.x), key16x2(v.y), key16x2(v.z), key16x2(v.w));
-}
-__device__ __forceinline__ uint4 maxkey16(const uint4& a, const uint4& b) {
-    return make_uint4(maxkey16x2(a.x, b.x), maxkey16x2(a.y, b.y), maxkey16x2(a.z, b.z), maxkey16x2(a.w, b.w));
-}
+// bf16 and f16: on ordering keys (common.h: okey16 / key16x2), NaN above everything
 template <>
 __device__ __forceinline__ uint4 max16<BF16Tag>(const uint4& a, const uint4& b) {
-    return key16(maxkey16(key16(a), key16(b)));
+    return key16(maxkey16(okey16<BF16Tag::kInf16>(a), okey16<BF16Tag::kInf16>(b)));
 }
 template <>
 __device__ __forceinline__ uint4 max16<F16Tag>(const uint4& a, const uint4& b) {
-    return key16(maxkey16(key16(a), key16(b)));
+    return key16(maxkey16(okey16<F16Tag::kInf16>(a), okey16<F16Tag::kInf16>(b)));
 }
 
 // 16-byte buffer load with hardware range check: an offset at or beyond the
@@ -187,11 +168,11 @@ template <>
 __device__ __forceinline__ void store4<F16Tag>(void* dst, size_t off, float a, float b, float c, float d) {
     typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     // saturate to the largest finite half: an activation beyond +-65504 is stored as
-    // +-65504 instead of +-inf (one v_med3_f32 per value, epilogue only)
-    a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f);
-    b = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
-    c = __builtin_amdgcn_fmed3f(c, -65504.f, 65504.f);
-    d = __builtin_amdgcn_fmed3f(d, -65504.f, 65504.f);
+    // +-65504 instead of +-inf, a NaN as NaN (common.h: sat_f16, epilogue only)
+    a = sat_f16(a);
+    b = sat_f16(b);
+    c = sat_f16(c);
+    d = sat_f16(d);
     f16x4 v = {(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d};
     *reinterpret_cast<f16x4*>(static_cast<_Float16*>(dst) + off) = v;
 }
@@ -209,10 +190,10 @@ __device__ __forceinline__ uint2 pack4<BF16Tag>(float a, float b, float c, float
 template <>
 __device__ __forceinline__ uint2 pack4<F16Tag>(float a, float b, float c, float d) {
     typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-    a = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f);   // saturating, like store4
-    b = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
-    c = __builtin_amdgcn_fmed3f(c, -65504.f, 65504.f);
-    d = __builtin_amdgcn_fmed3f(d, -65504.f, 65504.f);
+    a = sat_f16(a);   // saturating, like store4
+    b = sat_f16(b);
+    c = sat_f16(c);
+    d = sat_f16(d);
     const f16x4 v = {(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d};
     return __builtin_bit_cast(uint2, v);
 }
@@ -647,7 +628,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_t14(
                     const int w_src = (m / (MT * 32)) * WAVES_N + pwn;      // wave that produced it
                     const uint4 v = *reinterpret_cast<const uint4*>(
                         lb + (size_t)((w_src * MT + (m / 32) % MT) * 32 + m % 32) * RECP + (ck * 2 + sub) * 16);
-                    if (ES == 2) mx = k == 0 ? key16(v) : maxkey16(mx, key16(v));   // order-preserving keys
+                    if (ES == 2) mx = k == 0 ? okey16<Tag::kInf16>(v) : maxkey16(mx, okey16<Tag::kInf16>(v));   // order-preserving keys
                     else mx = k == 0 ? v : max16<Tag>(mx, v);
                 }
                 if (ES == 2) mx = key16(mx);
@@ -1210,8 +1191,8 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
                                                 leaky(acc[2 * zp + zz][4 * q + 2], a.slope), leaky(acc[2 * zp + zz][4 * q + 3], a.slope));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {      // the pair's maximum, as keys, where the pooling pass finds it
-                    const uint2 km = make_uint2(maxkey16x2(key16x2(grp[0][q].x), key16x2(grp[1][q].x)),
-                                                maxkey16x2(key16x2(grp[0][q].y), key16x2(grp[1][q].y)));
+                    const uint2 km = make_uint2(maxkey16x2(okey16x2<Tag::kInf16>(grp[0][q].x), okey16x2<Tag::kInf16>(grp[1][q].x)),
+                                                maxkey16x2(okey16x2<Tag::kInf16>(grp[0][q].y), okey16x2<Tag::kInf16>(grp[1][q].y)));
                     *reinterpret_cast<uint2*>(wl + zp * (32 * RECP) + r_e * RECP + (8 * q + 4 * half_e) * ES) = km;
                 }
 #pragma unroll
@@ -1355,12 +1336,12 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
                             const char* rec = wl + (2 * zp) * (32 * RECP) + (2 * xp) * RECP + (ck * 2 + sb) * 16;
 #endif
                             uint4 m = *reinterpret_cast<const uint4*>(rec);
-                            if (ES == 2) m = key16(m);   // 16-bit types: compare order-preserving keys
+                            if (ES == 2) m = okey16<Tag::kInf16>(m);   // 16-bit types: compare order-preserving keys
 #pragma unroll
                             for (int k = 1; k < 8; ++k) {
                                 const uint4 v = *reinterpret_cast<const uint4*>(
                                     rec + (k >> 2) * (32 * RECP) + ((k >> 1) & 1) * 16 * RECP + (k & 1) * RECP);
-                                m = ES == 2 ? maxkey16(m, key16(v)) : max16<Tag>(m, v);
+                                m = ES == 2 ? maxkey16(m, okey16<Tag::kInf16>(v)) : max16<Tag>(m, v);
                             }
                             if (ES == 2) m = key16(m);
                             const int qz = (cur.z0 + zb) / 2 + zp, qy = cur.y0 / 2 + wave, qx = cur.x0 / 2 + xp;
@@ -1852,12 +1833,12 @@ __global__ __launch_bounds__(TY * 16 * 2, MINW) void conv3x3x3_zpair(
                         const int ck = rem / 16, xp = (rem % 16) >> 1, sb = rem & 1;
                         if (p < NP && zb + 2 * zp + 1 < TZ) {
                             const char* rec = wl + (2 * zp) * (32 * RECP) + (2 * xp) * RECP + (ck * 2 + sb) * 16;
-                            uint4 m = key16(*reinterpret_cast<const uint4*>(rec));
+                            uint4 m = okey16<Tag::kInf16>(*reinterpret_cast<const uint4*>(rec));
 #pragma unroll
                             for (int k = 1; k < 8; ++k) {
                                 const uint4 vq = *reinterpret_cast<const uint4*>(
                                     rec + (k >> 2) * (32 * RECP) + ((k >> 1) & 1) * 16 * RECP + (k & 1) * RECP);
-                                m = maxkey16(m, key16(vq));
+                                m = maxkey16(m, okey16<Tag::kInf16>(vq));
                             }
                             m = key16(m);
                             const int qz = (cur.z0 + zb) / 2 + zp, qy = cur.y0 / 2 + wave, qx = cur.x0 / 2 + xp;
@@ -2102,6 +2083,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3x3_t16(ConvArgs a, int tiles_z,
 int g_variant = 0;   // tools/conv_trace.hip: 3/5/6 = operand prefetch distance, +10 = one tile per workgroup
 #endif
 
+ConvLaunchRecord& last_conv_launch() {
+    static thread_local ConvLaunchRecord rec;
+    return rec;
+}
+
 // workgroup slots of the device for a kernel that runs MINW workgroups per CU
 static int resident_workgroups(int per_cu) {
     static int cus = 0;
@@ -2136,6 +2122,7 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     if (const char* e = getenv("EXASPIM_TRACE_WGS_PER_CU")) wgs = resident_workgroups(1) * (long long)atoi(e) / slices / 8 * 8;
 #endif
     dim3 grid((unsigned)wgs, slices);
+    last_conv_launch() = {__PRETTY_FUNCTION__, 1};
     conv3x3x3_zpipe<Tag, TZ, TY, TX, MINW, D, HEAD, POOL><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
@@ -2261,6 +2248,7 @@ static int launch_cfg(const ConvArgs& a, hipStream_t stream) {
         b.ksplit = ks;
     }
     dim3 grid((unsigned)blocks, a.cout / NWG, b.ksplit);
+    last_conv_launch() = {__PRETTY_FUNCTION__, b.ksplit};
     if (POOL && b.ksplit > 1) {
         // a split layer's output exists only after the reduction: its max-pool stays a launch of
         // its own (tiny layers; the split is a function of the layer, so is this choice)

@@ -1,0 +1,102 @@
+// Test-only C entry points over the internal layer launchers (common.h), so that the suite
+// (tests/test_gpu_layers.py) can drive every dispatch path of one layer on its own and check it
+// against a float64 reference. Linked from the product's objects into libexaspim_layer_probe.so;
+// not part of include/exaspim_affinity.h or its ABI.
+
+#include "common.h"
+
+using namespace exaspim;
+
+extern "C" {
+
+const char* probe_last_error(void) { return get_error(); }
+
+// __PRETTY_FUNCTION__ of the last convolution launcher this thread ran, and its split-K factor
+const char* probe_last_config(void) { return last_conv_launch().config; }
+int probe_last_ksplit(void) { return last_conv_launch().ksplit; }
+void probe_reset_config(void) {
+    last_conv_launch() = ConvLaunchRecord{};
+    last_layer_kernel() = "";
+}
+// kernel variant of the last launch_conv_first / launch_upsample2
+const char* probe_last_layer_kernel(void) { return last_layer_kernel(); }
+
+// One convolution through launch_conv3x3x3 (thin = 0) or launch_conv3x3x3_thin (thin = 1).
+// region: org[3], ext[3] (z, y, x); head_* may be null / 0, pool_dst and partial may be null.
+int probe_conv3x3x3(int thin, int dtype, const void* src_a, const void* src_b, int ca, int cb,
+                    const void* weights, const float* bias, void* dst, int cout, int n, int d, int h,
+                    int w, float slope, const int32_t* region, void* pool_dst, float* partial,
+                    size_t partial_patch_bytes, const float* head_w, const float* head_b,
+                    float* head_out, int head_oc, int head_sigmoid, hipStream_t stream) {
+    ConvArgs a{};
+    a.src_a = src_a;
+    a.src_b = src_b;
+    a.ca = ca;
+    a.cb = cb;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    for (int i = 0; i < 3; ++i) {
+        a.org[i] = region ? region[i] : 0;
+        a.ext[i] = region ? region[3 + i] : 0;
+    }
+    a.pool_dst = pool_dst;
+    a.partial = partial;
+    a.partial_patch_bytes = partial_patch_bytes;
+    a.head_w = head_w;
+    a.head_b = head_b;
+    a.head_out = head_out;
+    a.head_oc = head_oc;
+    a.head_sigmoid = head_sigmoid;
+    return thin ? launch_conv3x3x3_thin(dtype, a, stream) : launch_conv3x3x3(dtype, a, stream);
+}
+
+int probe_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
+                     void* dst, int n, int d, int h, int wd, int c0p, float slope, int per_group,
+                     hipStream_t stream) {
+    return launch_conv_first(dtype, x, xpad, w, bias, dst, n, d, h, wd, c0p, slope, stream, per_group != 0);
+}
+
+int probe_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,
+                   hipStream_t stream) {
+    return launch_maxpool2(dtype, src, dst, n, d, h, w, c, stream);
+}
+
+int probe_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,
+                    int margin, int plain_kernel, int per_thread, hipStream_t stream) {
+    return launch_upsample2(dtype, src, dst, n, d, h, w, c, margin, stream, plain_kernel != 0,
+                            per_thread != 0);
+}
+
+int probe_convt2(int dtype, const void* src, const void* weights, const float* bias, void* dst, int n,
+                 int d, int h, int w, int cin, int cout, hipStream_t stream) {
+    return launch_convt2(dtype, src, weights, bias, dst, n, d, h, w, cin, cout, stream);
+}
+
+int probe_head(int dtype, const void* src, const float* w, const float* bias, float* out, int n,
+               int d, int h, int wd, int c0p, int out_channels, int apply_sigmoid, hipStream_t stream) {
+    return launch_head(dtype, src, w, bias, out, n, d, h, wd, c0p, out_channels, apply_sigmoid, stream);
+}
+
+// The plan's view of MFMA convolution `layer` (0 = inc.3 .. 16 = up4.3): out[0..7] =
+// ca_real, cb_real, ca, cb, cout_real, cout, w_off, b_off (byte offsets into the packed image
+// of exaspim_unet_pack_weights with the same channels / out_channels / dtype).
+int probe_plan_conv(const int32_t channels[5], int32_t out_channels, int32_t dtype, int layer,
+                    int64_t out[8]) {
+    UNetPlan p;
+    if (!make_plan(channels, out_channels, dtype, &p)) return EXASPIM_E_INVALID;
+    EXA_CHECK_ARG(layer >= 0 && layer < kNumMfmaConvs, "probe: layer %d out of range", layer);
+    const ConvLayer& L = p.conv[layer];
+    const int64_t v[8] = {L.ca_real, L.cb_real, L.ca, L.cb, L.cout_real, L.cout, (int64_t)L.w_off,
+                          (int64_t)L.b_off};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return EXASPIM_OK;
+}
+
+}  // extern "C"

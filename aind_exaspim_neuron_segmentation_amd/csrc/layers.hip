@@ -22,6 +22,7 @@
 
 namespace exaspim {
 
+// kInf16: the bits of +inf of a 16-bit type (maxpool2_kernel's NaN test, common.h: okey16)
 struct F32T {
     static constexpr int kG = 4;
     using vec = float4;
@@ -36,6 +37,7 @@ struct F32T {
 };
 struct BF16T {
     static constexpr int kG = 8;
+    static constexpr unsigned kInf16 = 0x7f80;
     __device__ static void unpack(const uint4& u, float* f) {
         const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -57,6 +59,7 @@ struct BF16T {
 };
 struct F16T {
     static constexpr int kG = 8;
+    static constexpr unsigned kInf16 = 0x7c00;
     __device__ static void unpack(const uint4& u, float* f) {
         const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -69,9 +72,9 @@ struct F16T {
         unsigned w[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            // saturating conversion (largest finite half instead of +-inf)
-            const _Float16 lo = (_Float16)__builtin_amdgcn_fmed3f(f[2 * i], -65504.f, 65504.f);
-            const _Float16 hi = (_Float16)__builtin_amdgcn_fmed3f(f[2 * i + 1], -65504.f, 65504.f);
+            // saturating conversion (largest finite half instead of +-inf, NaN stays NaN)
+            const _Float16 lo = (_Float16)sat_f16(f[2 * i]);
+            const _Float16 hi = (_Float16)sat_f16(f[2 * i + 1]);
             w[i] = (unsigned)__builtin_bit_cast(unsigned short, lo) |
                    ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
         }
@@ -781,23 +784,18 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const uint4* __restrict__
     const int y = i / (ow * cg), ix = i - y * (ow * cg);
     const int x = ix / cg, g = ix - x * cg;
     const int nb = blockIdx.x / od, z = blockIdx.x - nb * od;
-    float m[T::kG];
-#pragma unroll
-    for (int j = 0; j < T::kG; ++j) m[j] = -INFINITY;
+    // NaN propagates; the same maxima, bit for bit, as the conv kernels' fused pools (common.h)
+    uint4 m;
     const size_t plane = (size_t)h * w;
     const uint4* base = src + (((size_t)nb * d + 2 * z) * plane + (size_t)(2 * y) * w + 2 * x) * cg + g;
 #pragma unroll
-    for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                float f[T::kG];
-                T::unpack(base[(dz * plane + (size_t)dy * w + dx) * cg], f);
-#pragma unroll
-                for (int j = 0; j < T::kG; ++j) m[j] = fmaxf(m[j], f[j]);
-            }
-    dst[((((size_t)nb * od + z) * oh + y) * ow + x) * cg + g] = T::pack(m);
+    for (int k = 0; k < 8; ++k) {
+        const uint4 v = base[(((k >> 2) & 1) * plane + (size_t)((k >> 1) & 1) * w + (k & 1)) * cg];
+        if constexpr (T::kG == 8) m = k == 0 ? okey16<T::kInf16>(v) : maxkey16(m, okey16<T::kInf16>(v));
+        else m = k == 0 ? v : max_nan4(m, v);
+    }
+    if constexpr (T::kG == 8) m = key16(m);
+    dst[((((size_t)nb * od + z) * oh + y) * ow + x) * cg + g] = m;
 }
 
 // ---- trilinear x2, align_corners=True ---------------------------------------
@@ -1422,6 +1420,11 @@ static inline unsigned stream_grid(size_t items) {
         default: set_error("unknown dtype %d", dtype); return EXASPIM_E_INVALID; \
     }
 
+const char*& last_layer_kernel() {
+    static thread_local const char* name = "";
+    return name;
+}
+
 int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                       void* dst, int n, int d, int h, int wd, int c0p, float slope,
                       hipStream_t stream, bool first_no_strips) {
@@ -1463,9 +1466,11 @@ int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, co
             default: if (bf) STRIP(BF16T, 4); else STRIP(F16T, 4); break;
         }
 #undef STRIP
+        last_layer_kernel() = "conv_first16_strip";
         EXA_CHECK_HIP(hipGetLastError());
         return EXASPIM_OK;
     }
+    last_layer_kernel() = dtype == EXASPIM_DT_F32 ? "conv_first" : rows ? "conv_first16_rows" : "conv_first16";
     switch (dtype) {
         case EXASPIM_DT_F32:
             conv_first_kernel<F32T, MT><<<grid, 256, 0, stream>>>(xpad, w, bias, dst, (int)nvox, d, h, wd, c0p, slope);
@@ -1546,10 +1551,12 @@ int launch_upsample2(int dtype, const void* src, void* dst, int n, int d, int h,
                           scale(h), scale(w), margin)))
             if (run == 14) { UPS_STRIP(14); } else { UPS_STRIP(12); }
 #undef UPS_STRIP
+            last_layer_kernel() = run == 14 ? "upsample2_strip14" : "upsample2_strip12";
             EXA_CHECK_HIP(hipGetLastError());
             return EXASPIM_OK;
         }
     }
+    last_layer_kernel() = pipe ? "upsample2_pipe" : "upsample2";
     if (pipe) {
         DISPATCH_T(dtype, (upsample2_pipe_kernel<T><<<grid, 256, 0, stream>>>(
                               static_cast<const uint4*>(src), static_cast<uint4*>(dst), d, h, w,
