@@ -17,6 +17,7 @@ IN_F32, IN_PADDED_F32, IN_PADDED_SPLIT_F16, IN_PADDED_SPLIT_BF16 = 0, 1, 2, 3   
 UP_CONVT = 0x100   # EXASPIM_UP_CONVT: OR into a dtype code for UNet3D(trilinear=False)
 OPT_SEPARATE_POOL, OPT_SEPARATE_DEEP_POOLS, OPT_PLAIN_UPSAMPLE, OPT_FIRST_PER_GROUP = 1, 2, 4, 8   # EXASPIM_OPT_*
 OPT_UPSAMPLE_PER_THREAD = 16
+OPT_PER_PATCH_ENCODER = 32
 
 DTYPE_CODES = {
     "fp32": DT_F32, "float32": DT_F32, "f32": DT_F32,
@@ -88,6 +89,8 @@ SIGNATURES = {
     "exaspim_unet_input_layout": (_i32, [_vp]),
     "exaspim_unet_forward_prepared": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "exaspim_unet_forward_prepared_row": (
+        _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "exaspim_unet_forward_absmax": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_unet_set_options": (_i32, [_vp, ctypes.c_uint32]),

@@ -246,6 +246,14 @@ struct ConvArgs {
     // pool_dst as (n, cout, d/2, h/2, w/2) in the same layout (every tile shape but 6^3:
     // ask conv_can_fuse_pool first); saves re-reading the whole skip tensor.
     void* pool_dst = nullptr;
+    // Row mode (z-column kernel with the fused max-pool, 16-bit types, whole patches): the n patches
+    // are one row along x, each starting row_stride voxels after the previous one. The tiles walk the
+    // row's 16-wide strip columns once instead of every patch's own: patch i computes local x in
+    // [o/2, row_stride + o/2) (o = w - row_stride; the first patch from 0, the last one to w) in its
+    // own frame, and a column that its neighbour holds too is stored to both, except the
+    // neighbour's two outermost x (and pooled x) whose inputs reach its zero padding. Those are left
+    // for launch_conv3x3x3_thin and launch_maxpool2_xcols. 0: off.
+    int row_stride = 0;
     // Optional scratch for split-K (t14 kernel): launches with too few workgroups to fill
     // the device cut the input-channel chunks into up to 4 ranges, every range writes its
     // float32 partial sums here and a second kernel adds them in a fixed order.
@@ -292,6 +300,10 @@ int launch_convt2(int dtype, const void* src, const void* weights, const float* 
                   int n, int d, int h, int w, int cin, int cout, hipStream_t stream);
 int launch_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, int w,
                     int c, hipStream_t stream);  // d,h,w = INPUT size
+// The same maxima (same bits, NaN included) for two output x columns only, ox0 and ox1, every
+// z and y: the pooled columns a row-mode launch leaves to this (ConvArgs::row_stride)
+int launch_maxpool2_xcols(int dtype, const void* src, void* dst, int n, int d, int h, int w,
+                          int c, int ox0, int ox1, hipStream_t stream);
 // d,h,w = INPUT size; output voxels within "margin" of a face are not computed
 int launch_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, int w,
                      int c, int margin, hipStream_t stream, bool plain_kernel = false, bool per_thread = false);

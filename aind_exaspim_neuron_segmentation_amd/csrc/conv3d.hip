@@ -732,9 +732,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_t14(
 //    layout a load instruction covers whole halo rows of contiguous bytes (the
 //    texture addresser works per 64-byte segment: 16 cycles per instruction
 //    instead of 64 with one voxel record per lane).
-template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD = 0, bool POOL = false>
-__global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
-    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD, bool POOL, bool ROW>
+__device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int tiles_y, int tiles_x) {
     constexpr int G = Tag::kG;
     constexpr int KC = 2 * G;
     constexpr int ES = 16 / G;
@@ -792,7 +791,10 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
     // the workgroups of an XCD walk their range together, slot by slot, so tiles that
     // share halo planes are resident in the same L2 at the same time. With as many
     // workgroups as tiles this is the plain one-tile-per-workgroup order.
-    const int total = tiles_z * tiles_y * tiles_x * a.n;
+    // row mode (ConvArgs::row_stride): tiles_x counts the strip columns of the whole row
+    constexpr bool row = ROW;
+    static_assert(!ROW || (POOL && ES == 2 && EXASPIM_POOL_DIRECT && HEAD == 0), "row mode: 16-bit fused-pool epilogue");
+    const int total = tiles_z * tiles_y * tiles_x * (row ? 1 : a.n);
     int t_first, t_count, t_step;
     {
         const int q = total >> 3, rem = total & 7;
@@ -808,7 +810,20 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
     struct Tile {
         int z0, y0, x0, nb;
     };
+    // row mode: strip column cx (row x = 16 cx) belongs to patch clamp((16 cx - o/2) / stride, 0, n - 1)
+    auto row_tile_at = [&](int id) {
+        Tile t;
+        const int s = a.row_stride, ho = (a.w - s) >> 1;
+        const int rx = (id % tiles_x) * TX; id /= tiles_x;
+        const int nb = min(max(rx - ho, 0) / s, a.n - 1);
+        t.x0 = __builtin_amdgcn_readfirstlane(rx - nb * s);
+        t.y0 = __builtin_amdgcn_readfirstlane((id % tiles_y) * TY); id /= tiles_y;
+        t.z0 = __builtin_amdgcn_readfirstlane((id % tiles_z) * TZ);
+        t.nb = __builtin_amdgcn_readfirstlane(nb);
+        return t;
+    };
     auto tile_at = [&](int id) {
+        if (row) return row_tile_at(id);
         Tile t;
         // (x fastest. Measured alternative, z fastest -- whole z-columns resident in an XCD's L2
         // together so that neighbours share their two halo planes: HBM reads 1363 -> 1429 MB per
@@ -1180,6 +1195,23 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
             const int gy = cur.y0 + pos_e / TX, gx = cur.x0 + pos_e % TX;
             const bool okyx = gy < a.org[1] + a.ext[1] && gx < a.org[2] + a.ext[2];
             const unsigned ovoff = okyx ? (unsigned)(gy * a.w + gx) * 32u + half_e * 16u : kOutOfRange;
+            // row mode, a column the neighbour holds too: the same records go to the neighbour's frame,
+            // but for its two outermost x (their receptive field reaches its own zero padding)
+            // [stride, stride + o/2) is the next patch's [0, o/2), [o/2, o) the previous one's [w - o/2, w)
+            // (wave-uniform, recomputed here rather than carried through the tap loop with the tile; the
+            // shift rides in the descriptor's base, so the lanes keep ovoff: no extra vector register)
+            const int rs = a.row_stride, rho = (a.w - rs) >> 1;
+            const bool nnext = row && cur.x0 >= rs && cur.x0 < rs + rho && cur.nb + 1 < a.n;
+            const bool nprev = row && cur.x0 >= rho && cur.x0 < 2 * rho && cur.nb >= 1;
+            const bool shared = nnext || nprev;
+            const int nshift = nnext ? -rs : nprev ? rs : 0;
+            const int nnb = cur.nb + (nnext ? 1 : nprev ? -1 : 0);
+            const int ngx = gx + nshift;
+            const bool nlane = ngx >= 2 && ngx < a.w - 2;
+            const int nbase = nshift * 32;   // (the records end where the neighbour's patch ends)
+            char* const nplane = static_cast<char*>(a.dst) + nbase +
+                                 ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+            const __amdgpu_buffer_rsrc_t nrsrc = make_rsrc(nplane, (size_t)((long long)2 * patch_vox * 32 - nbase));
 #pragma unroll
             for (int zp = 0; zp < TZ / 2; ++zp) {
                 uint2 grp[2][4];
@@ -1204,6 +1236,8 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
                     for (int ck = 0; ck < 2; ++ck) {
                         const uint4 rec = record_half(grp[zz][2 * ck], grp[zz][2 * ck + 1]);
                         buf_store16(rec, orsrc, ovoff, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                        if (shared)
+                            buf_store16(rec, nrsrc, nlane ? ovoff : kOutOfRange, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
                     }
                 }
             }
@@ -1218,6 +1252,9 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
                 char* const pplane = static_cast<char*>(a.pool_dst) +
                                      ((size_t)cur.nb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
                 const __amdgpu_buffer_rsrc_t prsrc = make_rsrc(pplane, (size_t)CPT * pvox * 32);
+                char* const npplane = static_cast<char*>(a.pool_dst) + nbase / 2 +
+                                      ((size_t)nnb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
+                const __amdgpu_buffer_rsrc_t nprsrc = make_rsrc(npplane, (size_t)((long long)CPT * pvox * 32 - nbase / 2));
 #pragma unroll
                 for (int p0 = 0; p0 < NP; p0 += 64) {
                     const int p = p0 + lane_e;
@@ -1236,6 +1273,10 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
                                                ? (unsigned)((ck * (int)pvox + (qz * ph + qy) * pw2 + qx) * 32 + sb * 16)
                                                : kOutOfRange;
                     buf_store16(m, prsrc, pvoff, 0u);
+                    if (shared) {   // (pooled x 0 and w / 2 - 1 of the neighbour: from its own outermost x)
+                        const int nqx = qx + nshift / 2;
+                        buf_store16(m, nprsrc, nqx >= 1 && nqx < pw2 - 1 ? pvoff : kOutOfRange, 0u);
+                    }
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1371,6 +1412,20 @@ __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
         tile_id += t_step;
         cur = nxt;
     }
+}
+
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD = 0, bool POOL = false>
+__global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    zpipe_body<Tag, TZ, TY, TX, MINW, D, HEAD, POOL, false>(a, tiles_z, tiles_y, tiles_x);
+}
+
+// Row mode (ConvArgs::row_stride) of the fused-pool instantiation, 16-bit types: a symbol of its own, so
+// the row walk and the neighbour stores cost the per-patch kernel no registers
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D>
+__global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe_row(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    zpipe_body<Tag, TZ, TY, TX, MINW, D, 0, true, true>(a, tiles_z, tiles_y, tiles_x);
 }
 
 // ---- measured-and-not-adopted kernels ------------------------------------
@@ -2104,8 +2159,11 @@ static int resident_workgroups(int per_cu) {
 template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD = 0, bool POOL = false>
 static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     // tiles cover the voxels the caller needs, [org, org + ext) on every axis
-    const int tz = (a.ext[0] + TZ - 1) / TZ, ty = (a.ext[1] + TY - 1) / TY, tx = (a.ext[2] + TX - 1) / TX;
-    const long long blocks = (long long)tz * ty * tx * a.n;
+    // (row mode: the strip columns of the row, launch_conv3x3x3 checked its geometry)
+    const bool row = POOL && HEAD == 0 && Tag::kG == 8 && a.row_stride > 0;
+    const int tz = (a.ext[0] + TZ - 1) / TZ, ty = (a.ext[1] + TY - 1) / TY;
+    const int tx = row ? (a.n * a.row_stride + a.w - a.row_stride) / TX : (a.ext[2] + TX - 1) / TX;
+    const long long blocks = (long long)tz * ty * tx * (row ? 1 : a.n);
     if (blocks <= 0 || blocks > 0x7fffffffLL) {
         set_error("conv: grid of %lld blocks out of range", blocks);
         return EXASPIM_E_INVALID;
@@ -2123,6 +2181,13 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
 #endif
     dim3 grid((unsigned)wgs, slices);
     last_conv_launch() = {__PRETTY_FUNCTION__, 1};
+    if constexpr (POOL && HEAD == 0 && Tag::kG == 8) {
+        if (row) {
+            conv3x3x3_zpipe_row<Tag, TZ, TY, TX, MINW, D><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
+            EXA_CHECK_HIP(hipGetLastError());
+            return EXASPIM_OK;
+        }
+    }
     conv3x3x3_zpipe<Tag, TZ, TY, TX, MINW, D, HEAD, POOL><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
@@ -2428,6 +2493,17 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
                   "float32: a 32-cout-slice layer)");
     EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc),
                   "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs");
+    if (a.row_stride > 0) {
+        // the strip columns must line up with the 16-wide z-column tiles of every patch, and a shared
+        // column must keep its neighbour's two outermost x inside it
+        const int o = a.w - a.row_stride;
+        EXA_CHECK_ARG(EXASPIM_POOL_DIRECT && dtype != EXASPIM_DT_F32 && a.pool_dst && whole &&
+                          a.cout % 64 != 0 && a.w % 16 == 0 && a.n >= 2 && o > 0 && o % 32 == 0 &&
+                          a.row_stride >= o,
+                      "conv: row mode needs a 16-bit fused-pool z-column layer, whole patches, n >= 2 and "
+                      "an overlap that is a multiple of 32 and at most the stride (w %d, stride %d, n %d)",
+                      a.w, a.row_stride, a.n);
+    }
     {   // the staging loads address one patch of one source with 32-bit buffer offsets
         const unsigned long long rec = (unsigned long long)a.d * a.h * a.w *
                                        (a.ca > a.cb ? a.ca : a.cb) * (dtype == EXASPIM_DT_F32 ? 4 : 2);
@@ -2469,7 +2545,7 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     EXA_CHECK_ARG(a.ca % kc == 0 && a.cb % kc == 0 && a.cout % 32 == 0 && a.ca > 0,
                   "conv: channels (%d,%d)->%d not padded", a.ca, a.cb, a.cout);
     EXA_CHECK_ARG(a.n > 0 && a.d > 0 && a.h > 0 && a.w > 0, "conv: empty input");
-    EXA_CHECK_ARG(!a.pool_dst && !a.head_out, "conv: thin tiles have no fused pool or head");
+    EXA_CHECK_ARG(!a.pool_dst && !a.head_out && a.row_stride == 0, "conv: thin tiles have no fused pool, head or row mode");
     if (int rc = resolve_region(a)) return rc;
     a.partial = nullptr;   // no split-K on a partial region
     switch (dtype) {

@@ -85,9 +85,11 @@ static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
 // x: float32 patches, or (x == nullptr) x_prepared: the first convolution's operand layout
 // absmax (optional): float[1 + kNumMfmaConvs + 4], the largest |activation| inc.0, every MFMA
 // convolution and every ConvTranspose3d stored (range probe: nothing is fused away, nothing trimmed)
+// row_stride > 0: the caller says the n patches are one row along x, row_stride voxels apart
 static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, int h, int w,
                    int apply_sigmoid, int trim, void* workspace, size_t workspace_bytes,
-                   hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr) {
+                   hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr,
+                   int row_stride = 0) {
     const UNetPlan& p = e->plan;
     const Workspace ws = make_workspace(p, n, d, h, w);
     if (workspace_bytes < ws.bytes) {
@@ -114,6 +116,15 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     bool fuse_pool[4];
     for (int l = 0; l < 4; ++l)
         fuse_pool[l] = !separate_pool && !(separate_deep && l > 0) && conv_can_fuse_pool(p.dtype, p.conv[2 * l].cout, d >> l, h >> l, w >> l);
+    // Row mode of inc.3 (ConvArgs::row_stride): a column two neighbours share is computed once, the
+    // two outermost x of every patch face that borders a neighbour and their pooled column are
+    // recomputed in the patch's own frame by the thin-tile and column max-pool launches below. Same
+    // bits: a voxel's products are summed in the same order on every tile shape.
+    // (EXASPIM_OPT_PER_PATCH_ENCODER: every patch on its own, as without a row.)
+    const int row_o = w - row_stride;
+    const bool row = row_stride > 0 && n >= 2 && !absmax && dt != EXASPIM_DT_F32 && fuse_pool[0] &&
+                     !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) && p.conv[0].cout % 64 != 0 &&
+                     w % 16 == 0 && row_o > 0 && row_o % 32 == 0 && row_stride >= row_o;
     auto conv = [&](int idx, const void* sa, const void* sb, void* dst, int l) -> int {
         const ConvLayer& L = p.conv[idx];
         ConvArgs a;
@@ -156,6 +167,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         a.dst = dst; a.cout = L.cout;
         a.n = n; a.d = d >> l; a.h = h >> l; a.w = w >> l;
         a.slope = kLeakySlope;
+        if (idx == 0 && row) a.row_stride = row_stride;
         LayerTimer* t = e->timer;
         const bool timed = t && (t->mask >> idx & 1u) && t->used < LayerTimer::kRing;
         int slot = 0;
@@ -164,6 +176,27 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
             EXA_CHECK_HIP(hipEventRecord(t->start[slot], stream));
         }
         int r = launch_conv3x3x3(dt, a, stream);
+        if (r == EXASPIM_OK && a.row_stride > 0) {
+            // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
+            // w/2 - 1 of every patch
+            ConvArgs b = a;
+            b.pool_dst = nullptr;
+            b.row_stride = 0;
+            b.n = n - 1;
+            b.ext[2] = 2;
+            const size_t vox = (size_t)a.d * a.h * a.w;
+            b.src_a = static_cast<const char*>(a.src_a) + vox * a.ca * dtype_size(dt);
+            b.dst = static_cast<char*>(a.dst) + vox * a.cout * dtype_size(dt);
+            r = launch_conv3x3x3_thin(dt, b, stream);
+            if (r == EXASPIM_OK) {
+                b.org[2] = a.w - 2;
+                b.src_a = a.src_a;
+                b.dst = a.dst;
+                r = launch_conv3x3x3_thin(dt, b, stream);
+            }
+            if (r == EXASPIM_OK)
+                r = launch_maxpool2_xcols(dt, a.dst, a.pool_dst, n, a.d, a.h, a.w, a.cout, 0, a.w / 2 - 1, stream);
+        }
         if (timed && r == EXASPIM_OK) {
             EXA_CHECK_HIP(hipEventRecord(t->stop[slot], stream));
             t->layer[slot] = idx;
@@ -399,6 +432,22 @@ extern "C" int exaspim_unet_forward_prepared(exaspim_unet* h, const void* x_prep
                    workspace_bytes, (hipStream_t)stream, x_prepared_dev);
 }
 
+extern "C" int exaspim_unet_forward_prepared_row(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                                 int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                                 int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                                 void* workspace_dev, size_t workspace_bytes,
+                                                 void* stream) {
+    EXA_CHECK_ARG(h && x_prepared_dev && out_dev && workspace_dev, "forward: NULL pointer");
+    EXA_CHECK_ARG(n > 0, "forward: empty batch");
+    EXA_CHECK_ARG(trim >= 0, "forward: negative trim %d", trim);
+    EXA_CHECK_ARG(row_stride >= 0, "forward: negative row stride %d", row_stride);
+    EXA_CHECK_ARG(level_dims_ok(d, hgt, w),
+                  "forward: patch %dx%dx%d: every dimension must be a positive multiple of 16",
+                  d, hgt, w);
+    return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
+                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride);
+}
+
 extern "C" int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out_dev,
                                             int32_t n, int32_t d, int32_t hgt, int32_t w,
                                             int32_t apply_sigmoid, int32_t trim,
@@ -430,7 +479,7 @@ extern "C" int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, 
 extern "C" int exaspim_unet_set_options(exaspim_unet* h, uint32_t options) {
     EXA_CHECK_ARG(h != nullptr, "set_options: NULL handle");
     EXA_CHECK_ARG((options & ~(uint32_t)(EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS | EXASPIM_OPT_PLAIN_UPSAMPLE | EXASPIM_OPT_FIRST_PER_GROUP |
-                                          EXASPIM_OPT_UPSAMPLE_PER_THREAD)) == 0,
+                                          EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER)) == 0,
                   "set_options: unknown option bits 0x%x", options);
     h->options = options;
     return EXASPIM_OK;

@@ -798,6 +798,32 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const uint4* __restrict__
     dst[((((size_t)nb * od + z) * oh + y) * ow + x) * cg + g] = m;
 }
 
+// maxpool2_kernel on the output columns x = ox0 and ox1 only. Grid: x = volumes, y = blocks of
+// (z, y, column, group) pieces.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2_xcols_kernel(const uint4* __restrict__ src,
+                                                             uint4* __restrict__ dst, int d, int h,
+                                                             int w, int cg, int ox0, int ox1) {
+    const int od = d / 2, oh = h / 2, ow = w / 2;
+    const int i = blockIdx.y * blockDim.x + threadIdx.x;
+    if (i >= od * oh * 2 * cg) return;
+    const int g = i % cg, xi = (i / cg) & 1, zy = i / (2 * cg);
+    const int z = zy / oh, y = zy - z * oh;
+    const int x = xi ? ox1 : ox0;
+    const size_t nb = blockIdx.x;
+    const size_t plane = (size_t)h * w;
+    const uint4* base = src + ((nb * d + 2 * z) * plane + (size_t)(2 * y) * w + 2 * x) * cg + g;
+    uint4 m;   // (maxpool2_kernel's maxima, NaN included)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint4 v = base[(((k >> 2) & 1) * plane + (size_t)((k >> 1) & 1) * w + (k & 1)) * cg];
+        if constexpr (T::kG == 8) m = k == 0 ? okey16<T::kInf16>(v) : maxkey16(m, okey16<T::kInf16>(v));
+        else m = k == 0 ? v : max_nan4(m, v);
+    }
+    if constexpr (T::kG == 8) m = key16(m);
+    dst[(((nb * od + z) * oh + y) * ow + x) * cg + g] = m;
+}
+
 // ---- trilinear x2, align_corners=True ---------------------------------------
 // torch (ATen UpSample.h): scale = (in - 1) / (out - 1) in float; src = scale *
 // dst_index; i0 = floor(src) clamped; lambda = src - i0 clamped to [0, 1];
@@ -1517,6 +1543,22 @@ int launch_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, 
     dim3 grid(nv * (d / 2), (unsigned)((plane + 255) / 256));
     DISPATCH_T(dtype, (maxpool2_kernel<T><<<grid, 256, 0, stream>>>(
                           static_cast<const uint4*>(src), static_cast<uint4*>(dst), d, h, w, cg)));
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+int launch_maxpool2_xcols(int dtype, const void* src, void* dst, int n, int d, int h, int w,
+                          int c, int ox0, int ox1, hipStream_t stream) {
+    EXA_CHECK_ARG(d % 2 == 0 && h % 2 == 0 && w % 2 == 0, "maxpool: odd size %dx%dx%d", d, h, w);
+    EXA_CHECK_ARG(ox0 >= 0 && ox0 < w / 2 && ox1 >= 0 && ox1 < w / 2, "maxpool: columns %d, %d outside %d",
+                  ox0, ox1, w / 2);
+    constexpr int cg = 2;
+    const int nv = n * (c * dtype_size(dtype) / 32);
+    const long long items = (long long)(d / 2) * (h / 2) * 2 * cg;
+    EXA_CHECK_ARG(nv > 0 && nv <= 0x7fffffff && (items + 255) / 256 <= 65535, "maxpool: grid too large");
+    dim3 grid(nv, (unsigned)((items + 255) / 256));
+    DISPATCH_T(dtype, (maxpool2_xcols_kernel<T><<<grid, 256, 0, stream>>>(
+                          static_cast<const uint4*>(src), static_cast<uint4*>(dst), d, h, w, cg, ox0, ox1)));
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
 }

@@ -523,6 +523,23 @@ class SlidingWindow:
         return list(generate_patch_starts(self.shape5, self.patch_shape, self.overlap))
 
 
+def batch_row_stride(starts, patch_shape, overlap):
+    """
+    x stride of a batch of patch starts that is one row along x -- at least two
+    patches, the same (z, y), consecutive x starts exactly patch - overlap apart --
+    else 0 (UNet3D.run_prepared's row_stride). Host-side, no device sync.
+    """
+    stride = int(patch_shape[2]) - int(overlap[2])
+    if len(starts) < 2 or stride <= 0:
+        return 0
+    z0, y0, x0 = (int(v) for v in starts[0])
+    for i, s in enumerate(starts):
+        z, y, x = (int(v) for v in s)
+        if z != z0 or y != y0 or x != x0 + i * stride:
+            return 0
+    return stride
+
+
 def _start_ranges(dims, patch_shape, overlap):
     """range(0, d - patch + stride, stride) per axis (inference.py:361-364)."""
     return [
@@ -851,6 +868,7 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
         prepared_layout = model.input_layout(device)    # (PLAIN_GATHER: tests hold the two paths to each other)
     for bi, i in enumerate(range(0, len(starts), batch_size)):
         batch = starts_dev[i:i + batch_size]
+        row_stride = batch_row_stride(starts[i:i + batch_size], plan.patch_shape, plan.overlap)
         worker = workers[bi % n_streams]
         with torch.cuda.stream(worker):
             if prepared_layout is not None:
@@ -859,7 +877,7 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                                            mn=mn, mx=mx, layout=prepared_layout)
                 pred = model.run_prepared(
                     inputs, (int(batch.shape[0]),) + tuple(plan.patch_shape), apply_sigmoid=True,
-                    trim=0 if FULL_PATCHES else plan.trim)
+                    trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride)
             else:
                 inputs = _get_batch_inputs(volume, batch, plan.patch_shape, device, clip=clip,
                                            mn=mn, mx=mx)

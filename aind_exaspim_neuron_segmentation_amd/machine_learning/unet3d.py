@@ -424,7 +424,7 @@ class UNet3D(nn.Module):
             raise RuntimeError("exaspim_unet_input_layout failed")
         return int(code)
 
-    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0):
+    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0, row_stride=0):
         """
         run() from a batch the gather kernel has already written in the first
         convolution's operand layout (inference._get_batch_inputs(..., layout=
@@ -437,6 +437,10 @@ class UNet3D(nn.Module):
             The prepared batch.
         shape : Tuple[int]
             (B, D, H, W) of the patches.
+        row_stride : int, optional
+            > 0 when the B patches are one row along x, each starting row_stride voxels
+            after the previous one (inference.batch_row_stride): the engine then computes
+            the columns neighbours share once in the first level. Same bits.
         """
         if self.training:
             raise RuntimeError(
@@ -462,13 +466,23 @@ class UNet3D(nn.Module):
                 out = torch.empty(
                     (n, self.output_channels, d, h, w), dtype=torch.float32, device=device
                 )
-            _native.check(
-                _native.lib().exaspim_unet_forward_prepared(
-                    self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
-                    1 if apply_sigmoid else 0, int(trim), ws.data_ptr(), ws.numel(), stream,
-                ),
-                "exaspim_unet_forward_prepared",
-            )
+            if row_stride > 0:
+                _native.check(
+                    _native.lib().exaspim_unet_forward_prepared_row(
+                        self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
+                        1 if apply_sigmoid else 0, int(trim), int(row_stride), ws.data_ptr(), ws.numel(),
+                        stream,
+                    ),
+                    "exaspim_unet_forward_prepared_row",
+                )
+            else:
+                _native.check(
+                    _native.lib().exaspim_unet_forward_prepared(
+                        self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
+                        1 if apply_sigmoid else 0, int(trim), ws.data_ptr(), ws.numel(), stream,
+                    ),
+                    "exaspim_unet_forward_prepared",
+                )
         return out
 
     def forward(self, x):

@@ -34,7 +34,8 @@ extern "C" {
 
 /* 3: exaspim_export_f16 added (entry points are only ever added within a major line);
  * 5: exaspim_unet_forward_absmax, exaspim_histogram_wide (EXASPIM_VOX_F64),
- *    exaspim_unet_set_options (replaces an environment switch) */
+ *    exaspim_unet_set_options (replaces an environment switch);
+ *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -157,6 +158,14 @@ int exaspim_unet_forward_prepared(exaspim_unet* h, const void* x_prepared_dev, f
                                   int32_t n, int32_t d, int32_t hgt, int32_t w,
                                   int32_t apply_sigmoid, int32_t trim, void* workspace_dev,
                                   size_t workspace_bytes, void* stream);
+/* The same, for a batch whose n patches are one row along x: the same (z, y) start, each x start
+ * row_stride after the previous one. Columns that neighbours share are computed once by the first
+ * level's convolutions (when the engine can: 16-bit modes, an overlap w - row_stride that is a
+ * multiple of 32 and at most the stride); out_dev gets the same bits. row_stride = 0: no row. */
+int exaspim_unet_forward_prepared_row(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                      int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                      int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Range probe for the 16-bit storage modes. The reference loads ANY trained state_dict
  * (inference.py:400-424) and runs it in float32; IEEE-half storage holds |v| <= 65504 (stores
@@ -181,6 +190,7 @@ int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, float* out_
 #define EXASPIM_OPT_PLAIN_UPSAMPLE 4u /* trilinear x2 on the un-pipelined kernel (same bits) */
 #define EXASPIM_OPT_FIRST_PER_GROUP 8u /* inc.0 of the 16-bit modes group by group instead of on row strips (same bits) */
 #define EXASPIM_OPT_UPSAMPLE_PER_THREAD 16u /* trimmed level-0 upsampling: per-thread pipeline instead of shared source rows (same bits) */
+#define EXASPIM_OPT_PER_PATCH_ENCODER 32u /* exaspim_unet_forward_prepared_row: every patch's first level on its own (same bits) */
 int exaspim_unet_set_options(exaspim_unet* h, uint32_t options);
 
 /* Measurement hooks (bench.py's roofline leg). timing_begin arms HIP-event
