@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libexaspim_affinity.so")
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+DT_BF16X3 = 3   # EXASPIM_DT_BF16X3: float32 storage, three bf16 MFMA products per convolution step
 VOX_U8, VOX_U16, VOX_I16, VOX_F32, VOX_F64 = 0, 1, 2, 3, 4
 IN_F32, IN_PADDED_F32, IN_PADDED_SPLIT_F16, IN_PADDED_SPLIT_BF16 = 0, 1, 2, 3   # EXASPIM_IN_*
 UP_CONVT = 0x100   # EXASPIM_UP_CONVT: OR into a dtype code for UNet3D(trilinear=False)
@@ -23,6 +24,7 @@ DTYPE_CODES = {
     "fp32": DT_F32, "float32": DT_F32, "f32": DT_F32,
     "bf16": DT_BF16, "bfloat16": DT_BF16,
     "fp16": DT_F16, "float16": DT_F16, "f16": DT_F16,
+    "bf16x3": DT_BF16X3,
 }
 
 

@@ -166,13 +166,17 @@ inline void paired_frag_taps(int frag, int* tap0, int* tap1) {
 
 inline int pad_channels(int c) { return (c + kChannelPad - 1) / kChannelPad * kChannelPad; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int dtype_size(int dtype) { return dtype == EXASPIM_DT_F32 ? 4 : 2; }
+// Type the activations are stored in between kernels: EXASPIM_DT_BF16X3 keeps them float32 (only
+// its 3x3x3 MFMA convolutions are its own; every other layer runs the float32 kernel).
+inline int storage_dtype(int dtype) { return dtype == EXASPIM_DT_BF16X3 ? EXASPIM_DT_F32 : dtype; }
+inline int dtype_size(int dtype) { return storage_dtype(dtype) == EXASPIM_DT_F32 ? 4 : 2; }
 
 struct ConvLayer {
     int ca_real = 0, cb_real = 0;  // real input channels from source A / B
     int ca = 0, cb = 0;            // padded
     int cout_real = 0, cout = 0;   // real / padded output channels
-    size_t w_off = 0;              // packed weights (compute dtype), bytes
+    size_t w_off = 0;              // packed weights (compute dtype; bf16x3: a hi and a lo bf16 fragment
+                                   // per (16-channel chunk, tap, 32-cout tile)), bytes
     size_t w2_off = 0;             // the same weights in paired-tap fragment order (16-bit modes,
                                    // 32-cout-slice layers: conv3x3x3_zpair), 0 if not packed
     size_t w3_off = 0;             // the same weights as K = 32 fragments for conv3x3x3_t16 (16-bit modes,
@@ -287,7 +291,7 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a, hipStream_t stream);
 // remainder goes to launch_conv3x3x3_thin: the largest multiple of the tile if the
 // remainder is 1..4 voxels, else ext itself
 int conv_zcol_main_extent(int ext, int axis);
-bool conv_can_fuse_head(int cout, int w, int head_oc);
+bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype = EXASPIM_DT_F32);
 bool conv_can_fuse_pool(int dtype, int cout, int d, int h, int w);
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats

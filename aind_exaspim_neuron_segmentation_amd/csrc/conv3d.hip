@@ -2449,16 +2449,374 @@ static int launch_typed(const ConvArgs& a, hipStream_t stream) {
     return launch_cfg<Tag, 6, 6, 6, 4, 1, 2, 1, 2>(a, stream);
 }
 
+// ---- conv3x3x3_x3: EXASPIM_DT_BF16X3, float32-grade sums on the bf16 matrix pipe ----------
+// Activations are float32 in memory (8 channels per 32-byte chunk plane, the F32Tag layout) and
+// the kernel stores float32; inside, one K = 16 step of v_mfma_f32_32x32x16_bf16 consumes TWO
+// chunk planes (lanes 0-31: the 8 channels of chunk 2p, lanes 32-63: those of chunk 2p + 1;
+// padded channel counts are multiples of 32, so a pair never straddles the two sources). While a
+// pair's halo block is staged global -> VGPR -> LDS every value v is split into
+//     hi = bf16(v) (round to nearest even),  lo = bf16(v - float(hi)),
+// and LDS holds a hi image and a lo image, each in the [group][halo voxel] form of 16-byte
+// (8 x bf16) slots the 16-bit kernels read with one ds_read_b128 per (tap, 32 voxels). The
+// weights come split the same way from the host (plan.cpp), a hi and a lo fragment per (pair,
+// tap, cout tile), through the register ring of conv3x3x3_t14.
+// Order of a voxel's sum, the same on every tile shape (main, thin, trimmed or not), so that
+// every dispatch path gives a voxel the same bits: chunk pairs ascending (a split-K range
+// after the other, the split being a function of the layer shape alone), taps dz-major, and per
+// (pair, tap) the three products w_hi * x_hi, w_hi * x_lo, w_lo * x_hi; w_lo * x_lo is dropped.
+// The rest is conv3x3x3_t14 without its DMA / POOL variants: the next pair's pieces are loaded
+// late in the tap loop and split + written to LDS after its last MFMA, x fragments are double-
+// buffered per tap, and float32 records leave through an LDS transposition.
+__device__ __forceinline__ unsigned bf16_pair(float a, float b) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 v = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, v);
+}
+// four float32 (bits in v) -> their four hi parts and four lo parts, 8 bytes each
+__device__ __forceinline__ void split_bf16x3(const uint4& v, uint2& hi, uint2& lo) {
+    const float f0 = __uint_as_float(v.x), f1 = __uint_as_float(v.y);
+    const float f2 = __uint_as_float(v.z), f3 = __uint_as_float(v.w);
+    hi.x = bf16_pair(f0, f1);
+    hi.y = bf16_pair(f2, f3);
+    lo.x = bf16_pair(f0 - __uint_as_float(hi.x << 16), f1 - __uint_as_float(hi.x & 0xffff0000u));
+    lo.y = bf16_pair(f2 - __uint_as_float(hi.y << 16), f3 - __uint_as_float(hi.y & 0xffff0000u));
+}
+
+template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2;
+    constexpr int PLS = HY * HX;                    // plane stride (slots)
+    constexpr int HV = HZ * PLS;                    // slots of one channel-group plane = halo voxels
+    constexpr int IMG = 2 * HV;                     // slots of one image (two channel groups)
+    constexpr int NWAVES = WAVES_M * WAVES_N;
+    constexpr int NTHREADS = NWAVES * 64;
+    constexpr int TILE_VOX = TZ * TY * TX;
+    constexpr int NITEMS = (2 * HV + NTHREADS - 1) / NTHREADS;   // 16-byte pieces per thread and chunk plane
+    constexpr int RECB = NT * 32 * 4;               // bytes of one voxel's output slice (float32)
+    constexpr int RECP = RECB + 16;                 // padded LDS stride
+    constexpr int EPI_UNITS = NWAVES * 32 * RECP / 16;
+    constexpr int LDS_UNITS = 2 * IMG > EPI_UNITS ? 2 * IMG : EPI_UNITS;
+    constexpr int ISSUE_T = 26 - PD > 0 ? 26 - PD : 0;
+    static_assert(WAVES_M * MT * 32 >= TILE_VOX, "tile not covered by the waves");
+
+    __shared__ __attribute__((aligned(16))) uint4 lds[LDS_UNITS];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WAVES_N;
+    const int wn = wave % WAVES_N;
+    const int half = lane >> 5;
+    // (16-wide rows: second row of a 32-voxel group in rotated x order, see conv3x3x3_t14)
+    const int r = (TX == 16 && (lane & 16)) ? 16 + (((lane & 15) - HX) & 15) : (lane & 31);
+
+    int bid;
+    {
+        const int nblk = gridDim.x, q = nblk >> 3, rem = nblk & 7;
+        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+        bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + slot;
+    }
+    const int tx = bid % tiles_x; bid /= tiles_x;
+    const int ty = bid % tiles_y; bid /= tiles_y;
+    const int tz = bid % tiles_z; bid /= tiles_z;
+    const int nb = bid;
+    const int z0 = a.org[0] + tz * TZ, y0 = a.org[1] + ty * TY, x0 = a.org[2] + tx * TX;
+    const int zend = a.org[0] + a.ext[0], yend = a.org[1] + a.ext[1], xend = a.org[2] + a.ext[2];
+
+    const int ntiles = a.cout >> 5;
+    const int ntile0 = (blockIdx.y * WAVES_N + wn) * NT;
+
+    int base[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        int m = (wm * MT + mt) * 32 + r;
+        m = m < TILE_VOX ? m : TILE_VOX - 1;
+        const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
+        base[mt] = z * PLS + y * HX + x + half * HV;
+    }
+
+    // staging piece i = tid + it * NTHREADS is 16-byte half i & 1 (channels 4 (i & 1) .. + 3) of halo
+    // voxel i >> 1 of a chunk plane: consecutive lanes read consecutive bytes of a halo row. The same
+    // offsets serve both planes of the pair.
+    const size_t patch_vox = (size_t)a.d * a.h * a.w;
+    unsigned voffs[NITEMS];
+#pragma unroll
+    for (int it = 0; it < NITEMS; ++it) {
+        const int i = tid + it * NTHREADS;
+        const int hv = i >> 1;
+        const int hz = hv / PLS, hy = (hv / HX) % HY, hx = hv % HX;
+        const int gz = z0 + hz - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
+        const bool ok = i < 2 * HV && (unsigned)gz < (unsigned)a.d &&
+                        (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+        voffs[it] = ok ? (unsigned)((gz * a.h + gy) * a.w + gx) * 32u + (i & 1) * 16u : kOutOfRange;
+    }
+
+    f32x16 acc[MT][NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            // (split-K ranges start from zero; the reduction adds the bias)
+            float4 b = *reinterpret_cast<const float4*>(a.bias + (ntile0 + nt) * 32 + 8 * q + 4 * half);
+            if (a.ksplit > 1) b = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                acc[mt][nt][4 * q + 0] = b.x; acc[mt][nt][4 * q + 1] = b.y;
+                acc[mt][nt][4 * q + 2] = b.z; acc[mt][nt][4 * q + 3] = b.w;
+            }
+        }
+
+    // this workgroup's range of chunk pairs (all of them unless split-K)
+    const int npairs_all = (a.ca + a.cb) / 16;
+    const int pbeg = (int)blockIdx.z * npairs_all / a.ksplit;
+    const int pend = ((int)blockIdx.z + 1) * npairs_all / a.ksplit;
+    uint4 stg[2][NITEMS];
+
+    auto stage_load = [&](int p) {
+        const char* src;
+        int cs, ch0;
+        if (p * 16 < a.ca) {
+            src = static_cast<const char*>(a.src_a); cs = a.ca; ch0 = p * 16;
+        } else {
+            src = static_cast<const char*>(a.src_b); cs = a.cb; ch0 = p * 16 - a.ca;
+        }
+        const size_t patchb = patch_vox * cs * 4;   // bytes of one patch of this source
+        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(src + (size_t)nb * patchb, patchb);
+        const unsigned plane = (unsigned)patch_vox * 32u;
+        const unsigned cbase = (unsigned)(ch0 / 8) * plane;   // chunk plane 2p of this source
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int it = 0; it < NITEMS; ++it) stg[g][it] = buf_load16(rsrc, voffs[it], cbase + g * plane);
+    };
+    // split and write: 8 bytes of the hi image and 8 of the lo image per piece
+    auto stage_store = [&]() {
+        uint2* const l8 = reinterpret_cast<uint2*>(lds);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int it = 0; it < NITEMS; ++it) {
+                const int i = tid + it * NTHREADS;
+                if (i < 2 * HV) {
+                    uint2 hi, lo;
+                    split_bf16x3(stg[g][it], hi, lo);
+                    l8[(g * HV) * 2 + i] = hi;
+                    l8[(IMG + g * HV) * 2 + i] = lo;
+                }
+            }
+    };
+
+    // weight ring: [tap][cout tile][hi, lo], primed for the first PD taps of a pair before the
+    // barriers in front of it
+    uint4 wring[PD + 1][NT][2];
+    auto wfrag = [&](int p, int t, int nt, int part) {
+        return static_cast<const uint4*>(a.weights) +
+               ((((size_t)p * 27 + t) * ntiles + ntile0 + nt) * 2 + part) * 64 + lane;
+    };
+    auto prime_weights = [&](int p) {
+#pragma unroll
+        for (int t = 0; t < PD; ++t)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                wring[t][nt][0] = *wfrag(p, t, nt, 0);
+                wring[t][nt][1] = *wfrag(p, t, nt, 1);
+            }
+    };
+    stage_load(pbeg);
+    prime_weights(pbeg);
+    stage_store();
+    __syncthreads();
+
+    for (int p = pbeg; p < pend; ++p) {
+        uint4 xf[2][MT][2];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            xf[0][mt][0] = lds[base[mt]];
+            xf[0][mt][1] = lds[IMG + base[mt]];
+        }
+        const bool more = p + 1 < pend;
+        if (EXASPIM_SETPRIO_T14) __builtin_amdgcn_s_setprio(EXASPIM_SETPRIO_T14);
+#pragma unroll
+        for (int t = 0; t < 27; ++t) {
+            if (t + PD < 27) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    wring[(t + PD) % (PD + 1)][nt][0] = *wfrag(p, t + PD, nt, 0);
+                    wring[(t + PD) % (PD + 1)][nt][1] = *wfrag(p, t + PD, nt, 1);
+                }
+            }
+            if (t == ISSUE_T && more) stage_load(p + 1);
+            if (t + 1 < 27) {
+                const int tn = t + 1;
+                const int tapoff = (tn / 9) * PLS + ((tn / 3) % 3) * HX + tn % 3;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    xf[tn & 1][mt][0] = lds[base[mt] + tapoff];
+                    xf[tn & 1][mt][1] = lds[IMG + base[mt] + tapoff];
+                }
+            }
+            // the three products, each over all of the wave's accumulators before the next one:
+            // consecutive MFMAs never depend on each other when the wave has more than one
+#pragma unroll
+            for (int part = 0; part < 3; ++part)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        mma<BF16Tag>(acc[mt][nt], wring[t % (PD + 1)][nt][part == 2], xf[t & 1][mt][part == 1]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (EXASPIM_SETPRIO_T14) __builtin_amdgcn_s_setprio(0);
+        if (more) prime_weights(p + 1);
+        __syncthreads();  // every wave is done reading this pair's images
+        if (more) {
+            stage_store();
+            __syncthreads();
+        }
+    }
+
+    if (a.ksplit > 1) {
+        // ---- split-K: float32 partial sums, [range][patch][voxel][cout] ------------------
+        float* const part = a.partial + ((size_t)blockIdx.z * a.n + nb) * patch_vox * a.cout;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int m = (wm * MT + mt) * 32 + r;
+            const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
+            const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+            if (m < TILE_VOX && gz < zend && gy < yend && gx < xend) {
+                float* rec = part + (((size_t)gz * a.h + gy) * a.w + gx) * a.cout;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        *reinterpret_cast<float4*>(rec + (ntile0 + nt) * 32 + 8 * q + 4 * half) =
+                            make_float4(acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2],
+                                        acc[mt][nt][4 * q + 3]);
+            }
+        }
+        return;
+    }
+
+    // ---- epilogue: LeakyReLU, float32 records transposed through LDS ------------------
+    char* wl = reinterpret_cast<char*>(lds) + wave * (32 * RECP);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int cl = nt * 32 + 8 * q + 4 * half;  // channel inside the slice
+                store4<F32Tag>(wl, (size_t)(r * RECP) / 4 + cl,
+                               leaky(acc[mt][nt][4 * q + 0], a.slope), leaky(acc[mt][nt][4 * q + 1], a.slope),
+                               leaky(acc[mt][nt][4 * q + 2], a.slope), leaky(acc[mt][nt][4 * q + 3], a.slope));
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // one store instruction = one chunk plane's 32 voxel records (32 B each)
+        constexpr int NPL = RECB / 32;           // chunk planes of this wave's output slice
+        const int vv = lane >> 1, sub = lane & 1;
+        const int m = (wm * MT + mt) * 32 + vv;
+        const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
+        const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+        const bool ok = m < TILE_VOX && gz < zend && gy < yend && gx < xend;
+        const size_t vox = ((size_t)gz * a.h + gy) * a.w + gx;
+        char* const dplane = static_cast<char*>(a.dst) +
+                             ((size_t)nb * (a.cout / 8) + ntile0 * 4) * patch_vox * 32;
+#pragma unroll
+        for (int ck = 0; ck < NPL; ++ck) {
+            const uint4 val = *reinterpret_cast<const uint4*>(wl + vv * RECP + (ck * 2 + sub) * 16);
+            if (ok)
+                *reinterpret_cast<uint4*>(dplane + ((size_t)ck * patch_vox + vox) * 32 + sub * 16) = val;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD>
+static int launch_x3(const ConvArgs& a, hipStream_t stream) {
+    constexpr int NWG = WAVES_N * NT * 32;
+    if (a.cout % NWG != 0) {
+        set_error("conv: cout %d not a multiple of the %d-channel tile", a.cout, NWG);
+        return EXASPIM_E_INVALID;
+    }
+    const int tz = cdiv(a.ext[0], TZ), ty = cdiv(a.ext[1], TY), tx = cdiv(a.ext[2], TX);
+    const long long blocks = (long long)tz * ty * tx * a.n;
+    if (blocks <= 0 || blocks > 0x7fffffffLL) {
+        set_error("conv: grid of %lld blocks out of range", blocks);
+        return EXASPIM_E_INVALID;
+    }
+    const bool whole = a.ext[0] == a.d && a.ext[1] == a.h && a.ext[2] == a.w;
+    // split-K by the rule of launch_cfg (a function of the layer and the patch size only), over
+    // chunk pairs
+    ConvArgs b = a;
+    b.ksplit = 1;
+    constexpr int kNominalBatch = 16;
+    const long long wgs = (long long)tz * ty * tx * kNominalBatch * (a.cout / NWG);
+    const int npairs = (a.ca + a.cb) / 16;
+    const size_t patch_vox_all = (size_t)a.d * a.h * a.w;
+    const size_t nvox_all = (size_t)a.n * patch_vox_all;
+    if (a.partial && whole && wgs * 2 <= resident_workgroups(2)) {
+        int ks = (int)(resident_workgroups(2) / wgs);
+        if (ks > 4) ks = 4;
+        if (ks > npairs) ks = npairs;
+        while (ks > 1 && (size_t)ks * patch_vox_all * a.cout * sizeof(float) > a.partial_patch_bytes) --ks;
+        b.ksplit = ks;
+    }
+    dim3 grid((unsigned)blocks, a.cout / NWG, b.ksplit);
+    last_conv_launch() = {__PRETTY_FUNCTION__, b.ksplit};
+    conv3x3x3_x3<TZ, TY, TX, WAVES_M, WAVES_N, MT, NT, MINW, PD>
+        <<<grid, WAVES_M * WAVES_N * 64, 0, stream>>>(b, tz, ty, tx);
+    EXA_CHECK_HIP(hipGetLastError());
+    if (b.ksplit > 1) {
+        const size_t items = nvox_all * (a.cout / 4);
+        splitk_reduce_kernel<F32Tag><<<(unsigned)((items + 255) / 256), 256, 0, stream>>>(
+            a.partial, a.bias, a.dst, nvox_all, patch_vox_all, a.cout, b.ksplit, a.slope);
+        EXA_CHECK_HIP(hipGetLastError());
+    }
+    return EXASPIM_OK;
+}
+
+// bf16x3: tile shapes by the x extent, like launch_typed; every layer on conv3x3x3_x3
+static int launch_typed_x3(const ConvArgs& a, hipStream_t stream) {
+    if (a.w >= 16 && a.w % 16 == 0) {
+        // 64 couts per workgroup on 2-plane tiles: with four 32-voxel groups per wave the two cout tiles'
+        // accumulators, the operand buffers and the staged pair do not fit 256 registers
+        if (a.cout % 64 == 0) return launch_x3<2, 8, 16, 4, 1, 2, 2, 2, 3>(a, stream);
+        return launch_x3<4, 8, 16, 4, 1, 4, 1, 2, 3>(a, stream);
+    }
+    if (a.w > 12) {
+        if (a.cout % 64 == 0) return launch_x3<4, 4, 24, 4, 1, 3, 2, 2, 1>(a, stream);
+        return launch_x3<4, 4, 24, 4, 1, 3, 1, 2, 3>(a, stream);
+    }
+    if (a.w > 6) {
+        // (the shapes of launch_typed at this level)
+        if (a.cout % 256 == 0) return launch_x3<4, 4, 12, 2, 1, 3, 1, 2, 3>(a, stream);
+        if (a.cout % 128 == 0) return launch_x3<4, 4, 12, 2, 2, 3, 2, 2, 2>(a, stream);
+        if (a.cout % 64 == 0) return launch_x3<4, 4, 12, 2, 2, 3, 1, 2, 3>(a, stream);
+        return launch_x3<4, 4, 12, 2, 1, 3, 1, 2, 3>(a, stream);
+    }
+    return launch_x3<6, 6, 6, 4, 1, 2, 1, 2, 3>(a, stream);
+}
+
+// thin remainders of a region: 8 x 2 x 16 (thin along y) or 8 x 16 x 2 (thin along x) tiles
+static int launch_thin_typed_x3(const ConvArgs& a, hipStream_t stream) {
+    if (a.ext[1] <= a.ext[2]) return launch_x3<8, 2, 16, 4, 1, 2, 1, 2, 3>(a, stream);
+    return launch_x3<8, 16, 2, 4, 1, 2, 1, 2, 3>(a, stream);
+}
+
 bool conv_can_fuse_pool(int dtype, int cout, int d, int h, int w) {
     if (d % 2 != 0 || h % 2 != 0 || w % 2 != 0) return false;
+    if (dtype == EXASPIM_DT_BF16X3) return false;   // conv3x3x3_x3 has no fused epilogues
     // the layers launch_typed sends to the z-column kernel (any dtype) ...
     if (cout % 64 != 0 && w >= 16 && w % 16 == 0) return true;
     // ... and, in the 16-bit modes, every other tile shape but the single-tile 6^3 one
     return dtype != EXASPIM_DT_F32 && w > 6;
 }
 
-bool conv_can_fuse_head(int cout, int w, int head_oc) {
-    return cout == 32 && w >= 16 && w % 16 == 0 && head_oc >= 1 && head_oc <= 4;
+bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype) {
+    return dtype != EXASPIM_DT_BF16X3 && cout == 32 && w >= 16 && w % 16 == 0 && head_oc >= 1 && head_oc <= 4;
 }
 
 // ext = 0 stands for the whole axis; the region must lie inside the patch
@@ -2481,7 +2839,7 @@ int conv_zcol_main_extent(int ext, int axis) {
 
 int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     ConvArgs a = a_in;
-    const int kc = dtype == EXASPIM_DT_F32 ? 8 : 16;
+    const int kc = dtype == EXASPIM_DT_F32 ? 8 : 16;   // (bf16x3: a pair of float32 chunk planes)
     EXA_CHECK_ARG(a.ca % kc == 0 && a.cb % kc == 0 && a.cout % 32 == 0 && a.ca > 0,
                   "conv: channels (%d,%d)->%d not padded", a.ca, a.cb, a.cout);
     EXA_CHECK_ARG(a.n > 0 && a.d > 0 && a.h > 0 && a.w > 0, "conv: empty input");
@@ -2491,13 +2849,13 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     EXA_CHECK_ARG(!a.pool_dst || (conv_can_fuse_pool(dtype, a.cout, a.d, a.h, a.w) && !a.head_out && whole),
                   "conv: fused max-pool needs an even, untrimmed patch (16-bit modes: wider than 6 voxels; "
                   "float32: a 32-cout-slice layer)");
-    EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc),
-                  "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs");
+    EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc, dtype),
+                  "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs (and not bf16x3)");
     if (a.row_stride > 0) {
         // the strip columns must line up with the 16-wide z-column tiles of every patch, and a shared
         // column must keep its neighbour's two outermost x inside it
         const int o = a.w - a.row_stride;
-        EXA_CHECK_ARG(EXASPIM_POOL_DIRECT && dtype != EXASPIM_DT_F32 && a.pool_dst && whole &&
+        EXA_CHECK_ARG(EXASPIM_POOL_DIRECT && dtype_size(dtype) == 2 && a.pool_dst && whole &&
                           a.cout % 64 != 0 && a.w % 16 == 0 && a.n >= 2 && o > 0 && o % 32 == 0 &&
                           a.row_stride >= o,
                       "conv: row mode needs a 16-bit fused-pool z-column layer, whole patches, n >= 2 and "
@@ -2506,13 +2864,14 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     }
     {   // the staging loads address one patch of one source with 32-bit buffer offsets
         const unsigned long long rec = (unsigned long long)a.d * a.h * a.w *
-                                       (a.ca > a.cb ? a.ca : a.cb) * (dtype == EXASPIM_DT_F32 ? 4 : 2);
+                                       (a.ca > a.cb ? a.ca : a.cb) * dtype_size(dtype);
         EXA_CHECK_ARG(rec < 0x80000000ULL, "conv: one patch of one source is %llu bytes (>= 2 GiB)", rec);
     }
     switch (dtype) {
         case EXASPIM_DT_F32: return launch_typed<F32Tag>(a, stream);
         case EXASPIM_DT_BF16: return launch_typed<BF16Tag>(a, stream);
         case EXASPIM_DT_F16: return launch_typed<F16Tag>(a, stream);
+        case EXASPIM_DT_BF16X3: return launch_typed_x3(a, stream);
     }
     set_error("conv: unknown dtype %d", dtype);
     return EXASPIM_E_INVALID;
@@ -2552,6 +2911,7 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a_in, hipStream_t stream) {
         case EXASPIM_DT_F32: return launch_thin_typed<F32Tag>(a, stream);
         case EXASPIM_DT_BF16: return launch_thin_typed<BF16Tag>(a, stream);
         case EXASPIM_DT_F16: return launch_thin_typed<F16Tag>(a, stream);
+        case EXASPIM_DT_BF16X3: return launch_thin_typed_x3(a, stream);
     }
     set_error("conv: unknown dtype %d", dtype);
     return EXASPIM_E_INVALID;

@@ -104,7 +104,9 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     int rc;
 
     // the last conv (up4.3) can run the 1x1x1 head on its accumulators
-    const bool fuse_head = !absmax && conv_can_fuse_head(p.conv[kNumMfmaConvs - 1].cout, w, p.out_channels);
+    // (not in the bf16x3 mode, whose convolution kernel has no fused epilogues: its head is the
+    // float32 launch of its own, its forward is never trimmed and its max-pools are launches too)
+    const bool fuse_head = !absmax && conv_can_fuse_head(p.conv[kNumMfmaConvs - 1].cout, w, p.out_channels, dt);
     // With the head fused, voxels within "trim" of a patch face are never read again:
     // up4.3 skips them, and up4.0 everything its 3x3x3 consumer does not reach.
     const bool trimmed = fuse_head && trim > 0 && 2 * trim < d && 2 * trim < h && 2 * trim < w;
@@ -122,7 +124,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     // bits: a voxel's products are summed in the same order on every tile shape.
     // (EXASPIM_OPT_PER_PATCH_ENCODER: every patch on its own, as without a row.)
     const int row_o = w - row_stride;
-    const bool row = row_stride > 0 && n >= 2 && !absmax && dt != EXASPIM_DT_F32 && fuse_pool[0] &&
+    const bool row = row_stride > 0 && n >= 2 && !absmax && dtype_size(dt) == 2 && fuse_pool[0] &&
                      !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) && p.conv[0].cout % 64 != 0 &&
                      w % 16 == 0 && row_o > 0 && row_o % 32 == 0 && row_stride >= row_o;
     auto conv = [&](int idx, const void* sa, const void* sb, void* dst, int l) -> int {
@@ -410,7 +412,8 @@ extern "C" int exaspim_unet_forward(exaspim_unet* h, const float* x_dev, float* 
 extern "C" int exaspim_unet_input_layout(const exaspim_unet* h) {
     if (!h) return EXASPIM_E_INVALID;
     switch (h->plan.dtype) {
-        case EXASPIM_DT_F32: return EXASPIM_IN_PADDED_F32;
+        case EXASPIM_DT_F32:
+        case EXASPIM_DT_BF16X3: return EXASPIM_IN_PADDED_F32;
         case EXASPIM_DT_F16: return EXASPIM_IN_PADDED_SPLIT_F16;
         case EXASPIM_DT_BF16: return EXASPIM_IN_PADDED_SPLIT_BF16;
     }

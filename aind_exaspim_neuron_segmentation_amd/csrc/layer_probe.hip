@@ -22,6 +22,7 @@ void probe_reset_config(void) {
 const char* probe_last_layer_kernel(void) { return last_layer_kernel(); }
 
 // One convolution through launch_conv3x3x3 (thin = 0) or launch_conv3x3x3_thin (thin = 1).
+// dtype: any EXASPIM_DT_* (EXASPIM_DT_BF16X3: float32 tensors, weights in its hi / lo fragments).
 // region: org[3], ext[3] (z, y, x); head_* may be null / 0, pool_dst and partial may be null.
 int probe_conv3x3x3(int thin, int dtype, const void* src_a, const void* src_b, int ca, int cb,
                     const void* weights, const float* bias, void* dst, int cout, int n, int d, int h,

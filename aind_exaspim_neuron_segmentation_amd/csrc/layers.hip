@@ -1440,7 +1440,8 @@ static inline unsigned stream_grid(size_t items) {
 
 #define DISPATCH_T(dtype, CALL)                                  \
     switch (dtype) {                                             \
-        case EXASPIM_DT_F32: { using T = F32T; CALL; } break;    \
+        case EXASPIM_DT_F32:                                     \
+        case EXASPIM_DT_BF16X3: { using T = F32T; CALL; } break; \
         case EXASPIM_DT_BF16: { using T = BF16T; CALL; } break;  \
         case EXASPIM_DT_F16: { using T = F16T; CALL; } break;    \
         default: set_error("unknown dtype %d", dtype); return EXASPIM_E_INVALID; \
@@ -1454,6 +1455,7 @@ const char*& last_layer_kernel() {
 int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                       void* dst, int n, int d, int h, int wd, int c0p, float slope,
                       hipStream_t stream, bool first_no_strips) {
+    dtype = storage_dtype(dtype);   // (bf16x3: inc.0 is the float32 kernel)
     const size_t nvox = (size_t)n * d * h * wd;
     constexpr int MT = 4;
     const size_t blocks = (nvox + 4 * MT * 32 - 1) / (4 * MT * 32);

@@ -58,7 +58,8 @@ bool make_plan(const int32_t channels[5], int32_t out_channels, int32_t dtype,
         set_error("out_channels = %d unsupported (1..4)", out_channels);
         return false;
     }
-    if (dtype != EXASPIM_DT_F32 && dtype != EXASPIM_DT_BF16 && dtype != EXASPIM_DT_F16) {
+    if (dtype != EXASPIM_DT_F32 && dtype != EXASPIM_DT_BF16 && dtype != EXASPIM_DT_F16 &&
+        dtype != EXASPIM_DT_BF16X3) {
         set_error("unknown compute dtype %d", dtype);
         return false;
     }
@@ -91,6 +92,8 @@ bool make_plan(const int32_t channels[5], int32_t out_channels, int32_t dtype,
     };
 
     size_t poff = 0, woff = 0;
+    // bytes per packed weight: the storage type's, which for bf16x3 (float32 storage) is also the
+    // size of a weight's two bf16 parts; its ConvTranspose3d weights are float32 fragments
     const int es = dtype_size(dtype);
     p.c0 = c[0];
     p.c0p = pad_channels(c[0]);
@@ -131,12 +134,12 @@ bool make_plan(const int32_t channels[5], int32_t out_channels, int32_t dtype,
 #ifdef EXASPIM_VARIANTS   // (the measured-and-not-adopted kernels' own fragment orders: variant builds only)
         // level-1 layers with 64-cout slices (down1.0, down1.3, up3.0): K = 32 fragments for the
         // 16x16x32 kernel, [pair of chunks][tap 27][16-cout group][lane 64][8 x 16 bit]
-        if (dtype != EXASPIM_DT_F32 && L.cout % 64 == 0 && (i == 1 || i == 2 || i == 13)) {
+        if (dtype_size(dtype) == 2 && L.cout % 64 == 0 && (i == 1 || i == 2 || i == 13)) {
             L.w3_off = woff;
             woff = align_up(woff + (size_t)27 * (L.ca + L.cb) * L.cout * es, 256);
         }
         // 32-cout-slice layers of the 16-bit modes also get the paired-tap order
-        if (dtype != EXASPIM_DT_F32 && L.cout % 64 != 0) {
+        if (dtype_size(dtype) == 2 && L.cout % 64 != 0) {
             L.w2_off = woff;
             woff = align_up(woff + (size_t)kPairedFrags * 1024 * ((L.ca + L.cb) / 16) * (L.cout / 32), 256);
         }
@@ -221,8 +224,43 @@ int pack_weights(const UNetPlan& plan, const float* params, void* packed_host) {
         float* b = reinterpret_cast<float*>(out + L.b_off);
         for (int o = 0; o < L.cout_real; ++o) b[o] = (float)f.bias[o];
         char* wbase = out + L.w_off;
-        const int nchunks = (L.ca + L.cb) / KC;
         const int ntiles = L.cout / 32;
+        if (plan.dtype == EXASPIM_DT_BF16X3) {
+            // [16-channel chunk][tap 27][32-cout tile][hi, lo][lane 64][8 x bf16]: the float32 folded
+            // weight split into hi = bf16(v) and lo = bf16(v - float(hi)); lane l holds cout l % 32
+            // and channels 8 * (l / 32) .. + 7 of the chunk (sources A and B are padded to multiples
+            // of 32 channels, so a chunk never straddles them)
+            const int nch16 = (L.ca + L.cb) / 16;
+            for (int c = 0; c < nch16; ++c)
+                for (int t = 0; t < 27; ++t)
+                    for (int n = 0; n < ntiles; ++n)
+                        for (int lane = 0; lane < 64; ++lane) {
+                            const int co = 32 * n + (lane & 31);
+                            const size_t frag = ((((size_t)c * 27 + t) * ntiles + n) * 2) * 64 + lane;
+                            for (int j = 0; j < 8; ++j) {
+                                const int pc = 16 * c + 8 * (lane >> 5) + j;
+                                int ci = -1;
+                                if (pc < L.ca) {
+                                    if (pc < L.ca_real) ci = pc;
+                                } else {
+                                    const int q = pc - L.ca;
+                                    if (q < L.cb_real) ci = L.ca_real + q;
+                                }
+                                float v = 0.f;
+                                if (ci >= 0 && co < L.cout_real)
+                                    v = (float)((double)blk[((size_t)co * cin_real + ci) * 27 + t] * f.scale[co]);
+                                const uint16_t hi = f32_to_bf16_rne(v);
+                                const uint32_t hbits = (uint32_t)hi << 16;
+                                float hf;
+                                std::memcpy(&hf, &hbits, 4);
+                                const uint16_t lo = f32_to_bf16_rne(v - hf);
+                                std::memcpy(wbase + (frag * 8 + j) * 2, &hi, 2);
+                                std::memcpy(wbase + ((frag + 64) * 8 + j) * 2, &lo, 2);
+                            }
+                        }
+            continue;
+        }
+        const int nchunks = (L.ca + L.cb) / KC;
         for (int c = 0; c < nchunks; ++c)
             for (int t = 0; t < 27; ++t)
                 for (int n = 0; n < ntiles; ++n)
@@ -352,7 +390,7 @@ int pack_weights(const UNetPlan& plan, const float* params, void* packed_host) {
                                 if (ci < U.cin_real && co < U.cout_real)
                                     v = w[((size_t)ci * U.cout_real + co) * 8 + ph];
                                 char* dst = out + U.w_off + (frag * G + j) * es;
-                                if (plan.dtype == EXASPIM_DT_F32) {
+                                if (es == 4) {   // float32 and bf16x3
                                     std::memcpy(dst, &v, 4);
                                 } else {
                                     const uint16_t hbits = plan.dtype == EXASPIM_DT_BF16

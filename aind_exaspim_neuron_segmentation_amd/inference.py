@@ -362,7 +362,10 @@ def load_model(path, affinity_mode=True, device="cuda", *, compute_dtype="fp32")
     device : str, optional
         Device to load the model onto. Default is "cuda" (the HIP device).
     compute_dtype : str, optional
-        "fp32" (default), "bf16" or "fp16" arithmetic of the network kernels, or
+        "fp32" (default), "bf16" or "fp16" arithmetic of the network kernels,
+        "bf16x3" (float32 activations, each 3x3x3 convolution as three bf16
+        matrix-core products of split operands: float32 range, probabilities
+        within about 4e-6 of the reference's; see UNet3D), or
         "auto": fp16 if this checkpoint, on the first batch of patches predict()
         gives it, stays inside half range and within 1e-3 of its own float32
         probabilities, float32 otherwise (UNet3D.resolve_compute_dtype).

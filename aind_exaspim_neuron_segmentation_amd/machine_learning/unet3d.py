@@ -96,7 +96,13 @@ class UNet3D(nn.Module):
         Factor that scales the number of channels in each layer. Default is 1.
     compute_dtype : str, optional
         "fp32" (exact fp32 matrix-core path, default), "bf16" or "fp16"
-        (16-bit activations and weights, fp32 accumulation), or "auto": fp16
+        (16-bit activations and weights, fp32 accumulation), "bf16x3"
+        (float32 activations in memory; every 3x3x3 convolution after the
+        first splits both operands into a bf16 high and a bf16 low part and
+        sums three bf16 matrix-core products, hi*hi + hi*lo + lo*hi, in
+        float32: float32's range and about 16 mantissa bits per operand on
+        the bf16 pipe, for checkpoints that do not fit half precision), or
+        "auto": fp16
         if THIS checkpoint stays inside half range and within 1e-3 of its own
         float32 result on the first batch of real patches it sees, float32
         otherwise (resolve_compute_dtype; until then the model runs float32).

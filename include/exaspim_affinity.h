@@ -33,9 +33,12 @@ extern "C" {
 #endif
 
 /* 3: exaspim_export_f16 added (entry points are only ever added within a major line);
+ * 4: exaspim_unet_forward_prepared, exaspim_unet_input_layout, exaspim_gather_patches_as
+ *    (EXASPIM_IN_*): batches written in the first convolution's operand layout;
  * 5: exaspim_unet_forward_absmax, exaspim_histogram_wide (EXASPIM_VOX_F64),
  *    exaspim_unet_set_options (replaces an environment switch);
- *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER */
+ *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER;
+ *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point) */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -50,6 +53,25 @@ extern "C" {
 #define EXASPIM_DT_F32 0  /* exact f32 MFMA (v_mfma_f32_32x32x2_f32)        */
 #define EXASPIM_DT_BF16 1 /* bf16 storage, v_mfma_f32_32x32x16_bf16         */
 #define EXASPIM_DT_F16 2  /* f16 storage,  v_mfma_f32_32x32x16_f16          */
+/* float32-grade convolutions on the bf16 matrix pipe. Activations stay float32 in memory
+ * (the blocked float32 layout; inc.0, max-pool, upsampling, ConvTranspose3d, the head and
+ * exaspim_unet_forward_absmax run the float32 kernels, the prepared input is
+ * EXASPIM_IN_PADDED_F32). Each of the 17 3x3x3 MFMA convolutions splits both operands,
+ *     hi = bf16(v) (round to nearest even),  lo = bf16(v - float(hi))
+ * -- the activations while they are staged, the folded float32 weights on the host (the
+ * convention of EXASPIM_IN_PADDED_SPLIT_BF16) -- and forms, per tap and 16 input channels,
+ * three v_mfma_f32_32x32x16_bf16 products into one float32 accumulator, in this order:
+ *     w_hi * x_hi,  w_hi * x_lo,  w_lo * x_hi        (w_lo * x_lo is dropped).
+ * That keeps float32's exponent range and about 16 mantissa bits per operand (a relative
+ * error of about 3 * 2^-18 per product). A value whose bf16 rounding is not finite (an
+ * infinity, or beyond 3.39e38) gets a NaN low part. The folded bias, the head and inc.0
+ * stay float32. The packed image holds, per (16-channel chunk, tap, 32-cout tile), a hi
+ * fragment and then a lo fragment (1 KiB each, lane l: cout l % 32, channels 8 * (l / 32) ..
+ * + 7 of the chunk), i.e. 4 bytes per padded weight.
+ * exaspim_unet_forward_trimmed / _prepared with trim > 0 run the full pass in this mode
+ * (every voxel of out_dev is written; the kept region has the bits of
+ * exaspim_unet_forward), like the other modes do for shapes whose head cannot be fused. */
+#define EXASPIM_DT_BF16X3 3
 /* OR-ed into "dtype" wherever a network is described: the Up blocks use
  * ConvTranspose3d(k=2, s=2) instead of trilinear upsampling, i.e. the
  * reference's UNet3D(trilinear=False) (unet3d.py:254-258; 136 state_dict
@@ -149,7 +171,7 @@ int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out
 
 /* The same forward pass from a batch that exaspim_gather_patches_as has already written in
  * the first convolution's operand layout (exaspim_unet_input_layout: EXASPIM_IN_PADDED_F32
- * for a float32 engine, EXASPIM_IN_PADDED_SPLIT_F16 / _BF16 for the 16-bit ones):
+ * for a float32 or bf16x3 engine, EXASPIM_IN_PADDED_SPLIT_F16 / _BF16 for the 16-bit ones):
  * x_prepared_dev is (n, d + 2, hgt + 2, w + 2) 4-byte words. _get_batch_inputs feeding
  * model(inputs) (inference.py:155-157) without the float32 patch tensor in between: one
  * launch and an 8-byte-per-voxel round trip less per batch; out_dev gets the same bits. */
