@@ -19,6 +19,7 @@ UP_CONVT = 0x100   # EXASPIM_UP_CONVT: OR into a dtype code for UNet3D(trilinear
 OPT_SEPARATE_POOL, OPT_SEPARATE_DEEP_POOLS, OPT_PLAIN_UPSAMPLE, OPT_FIRST_PER_GROUP = 1, 2, 4, 8   # EXASPIM_OPT_*
 OPT_UPSAMPLE_PER_THREAD = 16
 OPT_PER_PATCH_ENCODER = 32
+OPT_SEPARATE_HEAD = 64   # the head as its own launch, nothing trimmed (bf16x3: same bits)
 
 DTYPE_CODES = {
     "fp32": DT_F32, "float32": DT_F32, "f32": DT_F32,

@@ -134,6 +134,26 @@ __device__ __forceinline__ uint4 maxkey16(const uint4& a, const uint4& b) {
     return make_uint4(maxkey16x2(a.x, b.x), maxkey16x2(a.y, b.y), maxkey16x2(a.z, b.z), maxkey16x2(a.w, b.w));
 }
 
+// ---- the arithmetic of the 1x1x1 head --------------------------------------------
+// One definition for head_kernel (layers.hip) and the fused head of the bf16x3 convolution
+// (conv3d.hip: conv3x3x3_x3_head), which are held to each other bit for bit although the two files
+// are compiled with different -ffp-contract settings: nothing in here may be contracted or
+// reassociated, every fused multiply-add is written out.
+// acc + sum of f[j] * w[j], j ascending, one fmaf per channel
+template <int N>
+__device__ __forceinline__ float head_dot(float acc, const float (&f)[N], const float* w) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc = fmaf(f[j], w[j], acc);
+    return acc;
+}
+// the logit, or its sigmoid (inference.py:158)
+__device__ __forceinline__ float head_activation(float r, int apply_sigmoid) {
+#pragma clang fp contract(off)
+    if (apply_sigmoid) r = 1.f / (1.f + expf(-r));
+    return r;
+}
+
 // ---- network plan ---------------------------------------------------------
 // Channel counts are padded to multiples of 32 inside the workspace so that
 // every MFMA convolution sees whole 32-wide output tiles and whole 32-byte
@@ -292,6 +312,13 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a, hipStream_t stream);
 // remainder is 1..4 voxels, else ext itself
 int conv_zcol_main_extent(int ext, int axis);
 bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype = EXASPIM_DT_F32);
+// EXASPIM_DT_BF16X3 only: the convolution of launch_conv3x3x3 (same sums, same order) with the 1x1x1
+// head on its accumulators. head_out / head_w / head_b / head_oc / head_sigmoid must be set; dst is
+// never written; the region [org, org + ext) is covered with masked 4 x 8 x 16 tiles (no thin
+// remainders, no split-K). head_out gets the bits launch_head gives on the stored activations.
+// Needs conv_x3_can_fuse_head: cout 32, w a multiple of 16, 1..4 outputs.
+int launch_conv3x3x3_x3_head(const ConvArgs& a, hipStream_t stream);
+bool conv_x3_can_fuse_head(int cout, int w, int head_oc);
 bool conv_can_fuse_pool(int dtype, int cout, int d, int h, int w);
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats

@@ -2482,9 +2482,10 @@ __device__ __forceinline__ void split_bf16x3(const uint4& v, uint2& hi, uint2& l
     lo.y = bf16_pair(f2 - __uint_as_float(hi.y << 16), f3 - __uint_as_float(hi.y & 0xffff0000u));
 }
 
-template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD>
-__global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
-    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+// HEAD > 0 (conv3x3x3_x3_head): the epilogue runs the 1x1x1 head with HEAD outputs on the float32
+// records instead of storing them, see there.
+template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int PD, int HEAD>
+__device__ __forceinline__ void x3_body(const ConvArgs& a, int tiles_z, int tiles_y, int tiles_x) {
     constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2;
     constexpr int PLS = HY * HX;                    // plane stride (slots)
     constexpr int HV = HZ * PLS;                    // slots of one channel-group plane = halo voxels
@@ -2500,7 +2501,16 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
     constexpr int ISSUE_T = 26 - PD > 0 ? 26 - PD : 0;
     static_assert(WAVES_M * MT * 32 >= TILE_VOX, "tile not covered by the waves");
 
+    static_assert(HEAD == 0 || NT == 1, "the head reads whole 32-channel records");
+
     __shared__ __attribute__((aligned(16))) uint4 lds[LDS_UNITS];
+    // head weights [HEAD][32] and bias [HEAD], visible after the barrier behind the first stage_store;
+    // the HEAD == 0 kernels declare nothing, so their LDS size is that of `lds` alone
+    float* head_s = nullptr;
+    if constexpr (HEAD > 0) {
+        __shared__ __attribute__((aligned(16))) float head_lds[HEAD * 32 + 4];
+        head_s = head_lds;
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -2508,6 +2518,10 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
     const int wm = wave / WAVES_N;
     const int wn = wave % WAVES_N;
     const int half = lane >> 5;
+    if constexpr (HEAD > 0) {
+        if (tid < HEAD * 32) head_s[tid] = a.head_w[tid];
+        if (tid < HEAD) head_s[HEAD * 32 + tid] = a.head_b[tid];
+    }
     // (16-wide rows: second row of a 32-voxel group in rotated x order, see conv3x3x3_t14)
     const int r = (TX == 16 && (lane & 16)) ? 16 + (((lane & 15) - HX) & 15) : (lane & 31);
 
@@ -2676,7 +2690,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
         }
     }
 
-    if (a.ksplit > 1) {
+    if (HEAD == 0 && a.ksplit > 1) {
         // ---- split-K: float32 partial sums, [range][patch][voxel][cout] ------------------
         float* const part = a.partial + ((size_t)blockIdx.z * a.n + nb) * patch_vox * a.cout;
 #pragma unroll
@@ -2713,25 +2727,75 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
             }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // one store instruction = one chunk plane's 32 voxel records (32 B each)
-        constexpr int NPL = RECB / 32;           // chunk planes of this wave's output slice
-        const int vv = lane >> 1, sub = lane & 1;
-        const int m = (wm * MT + mt) * 32 + vv;
-        const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
-        const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
-        const bool ok = m < TILE_VOX && gz < zend && gy < yend && gx < xend;
-        const size_t vox = ((size_t)gz * a.h + gy) * a.w + gx;
-        char* const dplane = static_cast<char*>(a.dst) +
-                             ((size_t)nb * (a.cout / 8) + ntile0 * 4) * patch_vox * 32;
+        if constexpr (HEAD > 0) {
+            // ---- fused head: the two lanes of a voxel (lane, lane + 32) walk its record in channel
+            // order, lane half h for outputs h and h + 2: head_kernel's sum (common.h: head_dot,
+            // head_activation) on the values head_kernel would read back, hence its bits. Only
+            // head_out is written, NCDHW float32, voxels of the region only.
+            constexpr int NK = (HEAD + 1) / 2;
+            const int vv = lane & 31;
+            const int m = (wm * MT + mt) * 32 + vv;
+            const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
+            const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+            const bool ok = m < TILE_VOX && gz < zend && gy < yend && gx < xend;
+            const size_t vox = ((size_t)gz * a.h + gy) * a.w + gx;
+            const float4* const rec = reinterpret_cast<const float4*>(wl + vv * RECP);
+            int oc[NK];
+            float hacc[NK];
 #pragma unroll
-        for (int ck = 0; ck < NPL; ++ck) {
-            const uint4 val = *reinterpret_cast<const uint4*>(wl + vv * RECP + (ck * 2 + sub) * 16);
-            if (ok)
-                *reinterpret_cast<uint4*>(dplane + ((size_t)ck * patch_vox + vox) * 32 + sub * 16) = val;
+            for (int k = 0; k < NK; ++k) {
+                oc[k] = half + 2 * k < HEAD ? half + 2 * k : HEAD - 1;   // (a lane without an output repeats the last)
+                hacc[k] = head_s[HEAD * 32 + oc[k]];
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 lo4 = rec[2 * g], hi4 = rec[2 * g + 1];
+                const float f[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
+#pragma unroll
+                for (int k = 0; k < NK; ++k) hacc[k] = head_dot(hacc[k], f, head_s + oc[k] * 32 + g * 8);
+            }
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                if (ok && half + 2 * k < HEAD)
+                    a.head_out[((size_t)nb * HEAD + half + 2 * k) * patch_vox + vox] =
+                        head_activation(hacc[k], a.head_sigmoid);
+        } else {
+            // one store instruction = one chunk plane's 32 voxel records (32 B each)
+            constexpr int NPL = RECB / 32;           // chunk planes of this wave's output slice
+            const int vv = lane >> 1, sub = lane & 1;
+            const int m = (wm * MT + mt) * 32 + vv;
+            const int z = m / (TY * TX), y = (m / TX) % TY, x = m % TX;
+            const int gz = z0 + z, gy = y0 + y, gx = x0 + x;
+            const bool ok = m < TILE_VOX && gz < zend && gy < yend && gx < xend;
+            const size_t vox = ((size_t)gz * a.h + gy) * a.w + gx;
+            char* const dplane = static_cast<char*>(a.dst) +
+                                 ((size_t)nb * (a.cout / 8) + ntile0 * 4) * patch_vox * 32;
+#pragma unroll
+            for (int ck = 0; ck < NPL; ++ck) {
+                const uint4 val = *reinterpret_cast<const uint4*>(wl + vv * RECP + (ck * 2 + sub) * 16);
+                if (ok)
+                    *reinterpret_cast<uint4*>(dplane + ((size_t)ck * patch_vox + vox) * 32 + sub * 16) = val;
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_x3(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    x3_body<TZ, TY, TX, WAVES_M, WAVES_N, MT, NT, PD, 0>(a, tiles_z, tiles_y, tiles_x);
+}
+
+// The level-0 32-cout tile (4 x 8 x 16, four waves, four 32-voxel groups per wave) with the 1x1x1 head
+// (HEAD = 1 .. 4 outputs, optional sigmoid) in place of the store of the activations: up4.3 of the
+// bf16x3 mode. The stored activation of this mode IS the float32 register value, so the fused head
+// gives the bits of launch_head on the stored tensor.
+constexpr int kX3HeadTZ = 4, kX3HeadTY = 8, kX3HeadTX = 16;
+template <int HEAD>
+__global__ __launch_bounds__(256, 2) void conv3x3x3_x3_head(ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    x3_body<kX3HeadTZ, kX3HeadTY, kX3HeadTX, 4, 1, 4, 1, 3, HEAD>(a, tiles_z, tiles_y, tiles_x);
 }
 
 template <int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD>
@@ -2806,18 +2870,39 @@ static int launch_thin_typed_x3(const ConvArgs& a, hipStream_t stream) {
     return launch_x3<8, 16, 2, 4, 1, 2, 1, 2, 3>(a, stream);
 }
 
+template <int HEAD>
+static int launch_x3_head(const ConvArgs& a, hipStream_t stream) {
+    const int tz = cdiv(a.ext[0], kX3HeadTZ), ty = cdiv(a.ext[1], kX3HeadTY), tx = cdiv(a.ext[2], kX3HeadTX);
+    const long long blocks = (long long)tz * ty * tx * a.n;
+    if (blocks <= 0 || blocks > 0x7fffffffLL) {
+        set_error("conv: grid of %lld blocks out of range", blocks);
+        return EXASPIM_E_INVALID;
+    }
+    last_conv_launch() = {__PRETTY_FUNCTION__, 1};
+    conv3x3x3_x3_head<HEAD><<<dim3((unsigned)blocks, 1, 1), 256, 0, stream>>>(a, tz, ty, tx);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
 bool conv_can_fuse_pool(int dtype, int cout, int d, int h, int w) {
     if (d % 2 != 0 || h % 2 != 0 || w % 2 != 0) return false;
-    if (dtype == EXASPIM_DT_BF16X3) return false;   // conv3x3x3_x3 has no fused epilogues
+    if (dtype == EXASPIM_DT_BF16X3) return false;   // conv3x3x3_x3 has no fused max-pool
     // the layers launch_typed sends to the z-column kernel (any dtype) ...
     if (cout % 64 != 0 && w >= 16 && w % 16 == 0) return true;
     // ... and, in the 16-bit modes, every other tile shape but the single-tile 6^3 one
     return dtype != EXASPIM_DT_F32 && w > 6;
 }
 
-bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype) {
-    return dtype != EXASPIM_DT_BF16X3 && cout == 32 && w >= 16 && w % 16 == 0 && head_oc >= 1 && head_oc <= 4;
+// the layer shape every fused head runs on: the 32-cout level-0 tile on 16-wide rows, 1 .. 4 outputs
+static bool head_shape_ok(int cout, int w, int head_oc) {
+    return cout == 32 && w >= 16 && w % 16 == 0 && head_oc >= 1 && head_oc <= 4;
 }
+// (what launch_conv3x3x3 accepts: bf16x3 has its fused head behind a launcher of its own)
+bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype) {
+    return dtype != EXASPIM_DT_BF16X3 && head_shape_ok(cout, w, head_oc);
+}
+// (what launch_conv3x3x3_x3_head accepts)
+bool conv_x3_can_fuse_head(int cout, int w, int head_oc) { return head_shape_ok(cout, w, head_oc); }
 
 // ext = 0 stands for the whole axis; the region must lie inside the patch
 static int resolve_region(ConvArgs& a) {
@@ -2875,6 +2960,32 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     }
     set_error("conv: unknown dtype %d", dtype);
     return EXASPIM_E_INVALID;
+}
+
+int launch_conv3x3x3_x3_head(const ConvArgs& a_in, hipStream_t stream) {
+    ConvArgs a = a_in;
+    EXA_CHECK_ARG(a.ca % 16 == 0 && a.cb % 16 == 0 && a.ca > 0, "conv: channels (%d,%d)->%d not padded", a.ca,
+                  a.cb, a.cout);
+    EXA_CHECK_ARG(a.n > 0 && a.d > 0 && a.h > 0 && a.w > 0, "conv: empty input");
+    EXA_CHECK_ARG(a.slope >= 0.f && a.slope <= 1.f, "conv: LeakyReLU slope %g outside [0, 1]", a.slope);
+    EXA_CHECK_ARG(conv_x3_can_fuse_head(a.cout, a.w, a.head_oc),
+                  "conv: bf16x3 fused head needs cout 32, w %% 16 == 0 and 1..4 outputs (cout %d, w %d, %d outputs)",
+                  a.cout, a.w, a.head_oc);
+    EXA_CHECK_ARG(a.head_out && a.head_w && a.head_b, "conv: bf16x3 fused head: NULL head pointer");
+    EXA_CHECK_ARG(!a.pool_dst && a.row_stride == 0, "conv: bf16x3 fused head has no fused max-pool or row mode");
+    if (int rc = resolve_region(a)) return rc;
+    {   // the staging loads address one patch of one source with 32-bit buffer offsets
+        const unsigned long long rec = (unsigned long long)a.d * a.h * a.w * (a.ca > a.cb ? a.ca : a.cb) * 4;
+        EXA_CHECK_ARG(rec < 0x80000000ULL, "conv: one patch of one source is %llu bytes (>= 2 GiB)", rec);
+    }
+    a.partial = nullptr;   // no split-K: the head needs a voxel's whole sum
+    a.ksplit = 1;
+    switch (a.head_oc) {
+        case 1: return launch_x3_head<1>(a, stream);
+        case 2: return launch_x3_head<2>(a, stream);
+        case 3: return launch_x3_head<3>(a, stream);
+        default: return launch_x3_head<4>(a, stream);
+    }
 }
 
 template <typename Tag>

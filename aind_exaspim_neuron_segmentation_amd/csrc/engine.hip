@@ -104,9 +104,14 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     int rc;
 
     // the last conv (up4.3) can run the 1x1x1 head on its accumulators
-    // (not in the bf16x3 mode, whose convolution kernel has no fused epilogues: its head is the
-    // float32 launch of its own, its forward is never trimmed and its max-pools are launches too)
-    const bool fuse_head = !absmax && conv_can_fuse_head(p.conv[kNumMfmaConvs - 1].cout, w, p.out_channels, dt);
+    // (the bf16x3 mode through a launcher of its own, launch_conv3x3x3_x3_head, whose head has the bits
+    // of the separate launch; its max-pools are launches of their own and it has no row mode)
+    // EXASPIM_OPT_SEPARATE_HEAD: the head as its own launch over the whole patch, hence nothing trimmed
+    const bool x3 = dt == EXASPIM_DT_BF16X3;
+    const int last_cout = p.conv[kNumMfmaConvs - 1].cout;
+    const bool fuse_head = !absmax && !(e->options & EXASPIM_OPT_SEPARATE_HEAD) &&
+                           (x3 ? conv_x3_can_fuse_head(last_cout, w, p.out_channels)
+                               : conv_can_fuse_head(last_cout, w, p.out_channels, dt));
     // With the head fused, voxels within "trim" of a patch face are never read again:
     // up4.3 skips them, and up4.0 everything its 3x3x3 consumer does not reach.
     const bool trimmed = fuse_head && trim > 0 && 2 * trim < d && 2 * trim < h && 2 * trim < w;
@@ -147,7 +152,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         // tiles and two launches on 2-voxel-thick tiles the rest, instead of a ninth row and a
         // sixth column of mostly masked 8 x 16 tiles (924 tiles for 718 tiles' worth of voxels).
         int rem_y = 0, rem_x = 0;
-        const bool has_head = idx == kNumMfmaConvs - 1 && fuse_head;   // the head runs on z-column tiles only
+        const bool has_head = idx == kNumMfmaConvs - 1 && fuse_head;   // the head runs on masked main tiles only
         if (margin > 0 && !has_head && L.cout % 64 != 0 && full[2] % 16 == 0) {
             rem_y = a.ext[1] - conv_zcol_main_extent(a.ext[1], 1);
             rem_x = a.ext[2] - conv_zcol_main_extent(a.ext[2], 2);
@@ -177,7 +182,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
             slot = t->next;
             EXA_CHECK_HIP(hipEventRecord(t->start[slot], stream));
         }
-        int r = launch_conv3x3x3(dt, a, stream);
+        int r = x3 && has_head ? launch_conv3x3x3_x3_head(a, stream) : launch_conv3x3x3(dt, a, stream);
         if (r == EXASPIM_OK && a.row_stride > 0) {
             // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
             // w/2 - 1 of every patch
@@ -482,7 +487,8 @@ extern "C" int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, 
 extern "C" int exaspim_unet_set_options(exaspim_unet* h, uint32_t options) {
     EXA_CHECK_ARG(h != nullptr, "set_options: NULL handle");
     EXA_CHECK_ARG((options & ~(uint32_t)(EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS | EXASPIM_OPT_PLAIN_UPSAMPLE | EXASPIM_OPT_FIRST_PER_GROUP |
-                                          EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER)) == 0,
+                                          EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER |
+                                          EXASPIM_OPT_SEPARATE_HEAD)) == 0,
                   "set_options: unknown option bits 0x%x", options);
     h->options = options;
     return EXASPIM_OK;

@@ -58,6 +58,42 @@ int probe_conv3x3x3(int thin, int dtype, const void* src_a, const void* src_b, i
     return thin ? launch_conv3x3x3_thin(dtype, a, stream) : launch_conv3x3x3(dtype, a, stream);
 }
 
+// The bf16x3 convolution with its fused head (launch_conv3x3x3_x3_head); the argument list of
+// probe_conv3x3x3, of which thin, dtype, pool_dst and partial must be 0 / EXASPIM_DT_BF16X3 / null.
+int probe_conv3x3x3_x3_head(int thin, int dtype, const void* src_a, const void* src_b, int ca, int cb,
+                            const void* weights, const float* bias, void* dst, int cout, int n, int d, int h,
+                            int w, float slope, const int32_t* region, void* pool_dst, float* partial,
+                            size_t partial_patch_bytes, const float* head_w, const float* head_b,
+                            float* head_out, int head_oc, int head_sigmoid, hipStream_t stream) {
+    EXA_CHECK_ARG(!thin && dtype == EXASPIM_DT_BF16X3 && !partial,
+                  "probe: the bf16x3 head launcher has no thin tiles, no other dtype and no split-K");
+    ConvArgs a{};
+    a.src_a = src_a;
+    a.src_b = src_b;
+    a.ca = ca;
+    a.cb = cb;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    for (int i = 0; i < 3; ++i) {
+        a.org[i] = region ? region[i] : 0;
+        a.ext[i] = region ? region[3 + i] : 0;
+    }
+    a.pool_dst = pool_dst;
+    a.head_w = head_w;
+    a.head_b = head_b;
+    a.head_out = head_out;
+    a.head_oc = head_oc;
+    a.head_sigmoid = head_sigmoid;
+    return launch_conv3x3x3_x3_head(a, stream);
+}
+
 int probe_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                      void* dst, int n, int d, int h, int wd, int c0p, float slope, int per_group,
                      hipStream_t stream) {

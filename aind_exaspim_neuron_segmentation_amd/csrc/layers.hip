@@ -1393,17 +1393,11 @@ __global__ __launch_bounds__(256) void head_kernel(const uint4* __restrict__ src
         float f[T::kG];
         T::unpack(rec[(size_t)(g >> 1) * nvox_per_patch * 2 + (g & 1)], f);
 #pragma unroll
-        for (int o = 0; o < OC; ++o)
-#pragma unroll
-            for (int j = 0; j < T::kG; ++j)
-                acc[o] = fmaf(f[j], w[o * c0p + g * T::kG + j], acc[o]);
+        for (int o = 0; o < OC; ++o) acc[o] = head_dot(acc[o], f, w + o * c0p + g * T::kG);
     }
 #pragma unroll
-    for (int o = 0; o < OC; ++o) {
-        float r = acc[o];
-        if (apply_sigmoid) r = 1.f / (1.f + expf(-r));
-        out[((size_t)nb * OC + o) * nvox_per_patch + sp] = r;
-    }
+    for (int o = 0; o < OC; ++o)
+        out[((size_t)nb * OC + o) * nvox_per_patch + sp] = head_activation(acc[o], apply_sigmoid);
 }
 
 // ---- range probe: largest |value| of an activation tensor ----------------------

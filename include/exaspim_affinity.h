@@ -68,9 +68,11 @@ extern "C" {
  * stay float32. The packed image holds, per (16-channel chunk, tap, 32-cout tile), a hi
  * fragment and then a lo fragment (1 KiB each, lane l: cout l % 32, channels 8 * (l / 32) ..
  * + 7 of the chunk), i.e. 4 bytes per padded weight.
- * exaspim_unet_forward_trimmed / _prepared with trim > 0 run the full pass in this mode
- * (every voxel of out_dev is written; the kept region has the bits of
- * exaspim_unet_forward), like the other modes do for shapes whose head cannot be fused. */
+ * The last convolution runs the head on its float32 accumulators, which in this mode ARE the
+ * stored activations: same bits as the head launched on its own (EXASPIM_OPT_SEPARATE_HEAD).
+ * exaspim_unet_forward_trimmed / _prepared with trim > 0 keep their contract in this mode too:
+ * margin voxels of out_dev are left untouched and kept voxels have the bits of
+ * exaspim_unet_forward (shapes whose head cannot be fused run the full pass, as in every mode). */
 #define EXASPIM_DT_BF16X3 3
 /* OR-ed into "dtype" wherever a network is described: the Up blocks use
  * ConvTranspose3d(k=2, s=2) instead of trilinear upsampling, i.e. the
@@ -213,6 +215,12 @@ int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, float* out_
 #define EXASPIM_OPT_FIRST_PER_GROUP 8u /* inc.0 of the 16-bit modes group by group instead of on row strips (same bits) */
 #define EXASPIM_OPT_UPSAMPLE_PER_THREAD 16u /* trimmed level-0 upsampling: per-thread pipeline instead of shared source rows (same bits) */
 #define EXASPIM_OPT_PER_PATCH_ENCODER 32u /* exaspim_unet_forward_prepared_row: every patch's first level on its own (same bits) */
+/* The 1x1x1 head as a launch of its own instead of fused into the last convolution; nothing is
+ * trimmed then (the trimmed entry points run the full pass and write every voxel). In
+ * EXASPIM_DT_BF16X3 it gives the same bits as the fused head. In the other modes the fused head
+ * sums in a different order, and the 16-bit modes fuse on unrounded accumulators, so the values
+ * differ within rounding. For the bit-identity tests and A/B timing. */
+#define EXASPIM_OPT_SEPARATE_HEAD 64u
 int exaspim_unet_set_options(exaspim_unet* h, uint32_t options);
 
 /* Measurement hooks (bench.py's roofline leg). timing_begin arms HIP-event

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--modes", default="fp32,bf16x3")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--options", type=lambda s: int(s, 0), default=0, help="engine option bits (_native.OPT_*)")
     args = ap.parse_args()
 
     import torch
@@ -43,6 +44,7 @@ def main():
     for mode in args.modes.split(","):
         m = UNet3D(output_channels=3, compute_dtype=mode)
         m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+        m.engine_options = args.options
         models[mode] = m.to(dev).eval()
 
     import numpy as np
@@ -78,7 +80,8 @@ def main():
             times[mode].append(step(mode))
 
     vox = float(n) ** 3
-    res = {"size": n, "batch": args.batch, "steps": args.steps, "device": torch.cuda.get_device_name(0), "modes": {}}
+    res = {"size": n, "batch": args.batch, "steps": args.steps, "device": torch.cuda.get_device_name(0),
+           "options": args.options, "library": os.environ.get("EXASPIM_LIB", "in-tree"), "modes": {}}
     for mode, ts in times.items():
         med = statistics.median(ts)
         res["modes"][mode] = {"voxels_per_s": vox / med, "median_s": med, "step_s": ts,
