@@ -296,6 +296,7 @@ struct ConvArgs {
 struct ConvLaunchRecord {
     const char* config = "";
     int ksplit = 0;
+    bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride)
 };
 ConvLaunchRecord& last_conv_launch();
 // The same for the inc.0 and upsampling launchers (layers.hip): the name of the kernel variant
@@ -320,6 +321,20 @@ bool conv_can_fuse_head(int cout, int w, int head_oc, int dtype = EXASPIM_DT_F32
 int launch_conv3x3x3_x3_head(const ConvArgs& a, hipStream_t stream);
 bool conv_x3_can_fuse_head(int cout, int w, int head_oc);
 bool conv_can_fuse_pool(int dtype, int cout, int d, int h, int w);
+// Row mode (ConvArgs::row_stride) runs on this layer and row geometry: a 16-bit z-column layer whose
+// fused max-pool covers whole patches (fused_pool_whole_patch: the caller's conv_can_fuse_pool, a pool
+// destination and an untrimmed region), n >= 2 patches of width w a multiple of the 16-wide tiles, an
+// overlap w - row_stride that is a positive multiple of 32 and at most the stride. The one predicate of
+// launch_conv3x3x3's argument check and of the engine's choice between the row and the per-patch path.
+bool conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, bool fused_pool_whole_patch);
+// A row-mode convolution and the launches that finish it (a.row_stride > 0, a.pool_dst set), in this
+// order: the row launch (launch_conv3x3x3), launch_conv3x3x3_thin on x in [0, 2) of patches 1 .. n-1
+// and on x in [w - 2, w) of patches 0 .. n-2 in each patch's own frame, then launch_maxpool2_xcols on
+// the pooled columns 0 and w/2 - 1 of every patch. stages: which of them to run (the engine: all;
+// the tests' layer probe looks at what each one leaves behind).
+constexpr int kRowStageMain = 1, kRowStageThin = 2, kRowStagePool = 4;
+constexpr int kRowStagesAll = kRowStageMain | kRowStageThin | kRowStagePool;
+int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats
 // first_no_strips: keep the per-group kernel (the tests hold it to the row-strip kernel bit for bit)

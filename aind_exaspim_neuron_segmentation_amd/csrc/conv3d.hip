@@ -1211,7 +1211,7 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
             const int nbase = nshift * 32;   // (the records end where the neighbour's patch ends)
             char* const nplane = static_cast<char*>(a.dst) + nbase +
                                  ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
-            const __amdgpu_buffer_rsrc_t nrsrc = make_rsrc(nplane, (size_t)((long long)2 * patch_vox * 32 - nbase));
+            const size_t nbytes = (size_t)((long long)2 * patch_vox * 32 - nbase);
 #pragma unroll
             for (int zp = 0; zp < TZ / 2; ++zp) {
                 uint2 grp[2][4];
@@ -1232,6 +1232,9 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                     const int gz = cur.z0 + 2 * zp + zz;     // wave-uniform
                     const __amdgpu_buffer_rsrc_t orsrc =
                         make_rsrc(dplane, gz < a.org[0] + a.ext[0] ? (size_t)2 * patch_vox * 32 : (size_t)0);
+                    // (a plane beyond the patch of a masked last z tile must not reach the neighbour either: its
+                    // offset would still lie inside the descriptor, in the first planes of the second chunk)
+                    const __amdgpu_buffer_rsrc_t nrsrc = make_rsrc(nplane, gz < a.org[0] + a.ext[0] ? nbytes : (size_t)0);
 #pragma unroll
                     for (int ck = 0; ck < 2; ++ck) {
                         const uint4 rec = record_half(grp[zz][2 * ck], grp[zz][2 * ck + 1]);
@@ -2183,6 +2186,7 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     last_conv_launch() = {__PRETTY_FUNCTION__, 1};
     if constexpr (POOL && HEAD == 0 && Tag::kG == 8) {
         if (row) {
+            last_conv_launch().row = true;
             conv3x3x3_zpipe_row<Tag, TZ, TY, TX, MINW, D><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
             EXA_CHECK_HIP(hipGetLastError());
             return EXASPIM_OK;
@@ -2922,6 +2926,26 @@ int conv_zcol_main_extent(int ext, int axis) {
     return (axis != 0 && ext > tile && rem >= 1 && rem <= 4) ? ext - rem : ext;
 }
 
+bool conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, bool fused_pool_whole_patch) {
+    // the strip columns must line up with the 16-wide z-column tiles of every patch, and a shared
+    // column must keep its neighbour's two outermost x inside it
+    const int o = w - row_stride;
+    return EXASPIM_POOL_DIRECT && dtype_size(dtype) == 2 && fused_pool_whole_patch && cout % 64 != 0 &&
+           w % 16 == 0 && n >= 2 && row_stride > 0 && o > 0 && o % 32 == 0 && row_stride >= o;
+}
+
+// (a: region resolved)
+static int check_row_args(int dtype, const ConvArgs& a) {
+    const bool whole = a.ext[0] == a.d && a.ext[1] == a.h && a.ext[2] == a.w;
+    EXA_CHECK_ARG(conv_row_mode_ok(dtype, a.cout, a.n, a.w, a.row_stride,
+                                   a.pool_dst && !a.head_out && whole &&
+                                       conv_can_fuse_pool(dtype, a.cout, a.d, a.h, a.w)),
+                  "conv: row mode needs a 16-bit fused-pool z-column layer, whole patches, n >= 2 and "
+                  "an overlap that is a multiple of 32 and at most the stride (w %d, stride %d, n %d)",
+                  a.w, a.row_stride, a.n);
+    return EXASPIM_OK;
+}
+
 int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     ConvArgs a = a_in;
     const int kc = dtype == EXASPIM_DT_F32 ? 8 : 16;   // (bf16x3: a pair of float32 chunk planes)
@@ -2936,17 +2960,8 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
                   "float32: a 32-cout-slice layer)");
     EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc, dtype),
                   "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs (and not bf16x3)");
-    if (a.row_stride > 0) {
-        // the strip columns must line up with the 16-wide z-column tiles of every patch, and a shared
-        // column must keep its neighbour's two outermost x inside it
-        const int o = a.w - a.row_stride;
-        EXA_CHECK_ARG(EXASPIM_POOL_DIRECT && dtype_size(dtype) == 2 && a.pool_dst && whole &&
-                          a.cout % 64 != 0 && a.w % 16 == 0 && a.n >= 2 && o > 0 && o % 32 == 0 &&
-                          a.row_stride >= o,
-                      "conv: row mode needs a 16-bit fused-pool z-column layer, whole patches, n >= 2 and "
-                      "an overlap that is a multiple of 32 and at most the stride (w %d, stride %d, n %d)",
-                      a.w, a.row_stride, a.n);
-    }
+    if (a.row_stride > 0)
+        if (int rc = check_row_args(dtype, a)) return rc;
     {   // the staging loads address one patch of one source with 32-bit buffer offsets
         const unsigned long long rec = (unsigned long long)a.d * a.h * a.w *
                                        (a.ca > a.cb ? a.ca : a.cb) * dtype_size(dtype);
@@ -3026,6 +3041,36 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     }
     set_error("conv: unknown dtype %d", dtype);
     return EXASPIM_E_INVALID;
+}
+
+int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream) {
+    ConvArgs b = a;
+    EXA_CHECK_ARG(a.n > 0 && a.d > 0 && a.h > 0 && a.w > 0, "conv: empty input");
+    if (int rc = resolve_region(b)) return rc;
+    if (int rc = check_row_args(dtype, b)) return rc;
+    int r = EXASPIM_OK;
+    if (stages & kRowStageMain) r = launch_conv3x3x3(dtype, a, stream);
+    // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
+    // w/2 - 1 of every patch
+    b.pool_dst = nullptr;
+    b.row_stride = 0;
+    b.n = a.n - 1;
+    b.ext[2] = 2;
+    if (r == EXASPIM_OK && (stages & kRowStageThin)) {
+        const size_t vox = (size_t)a.d * a.h * a.w;
+        b.src_a = static_cast<const char*>(a.src_a) + vox * a.ca * dtype_size(dtype);
+        b.dst = static_cast<char*>(a.dst) + vox * a.cout * dtype_size(dtype);
+        r = launch_conv3x3x3_thin(dtype, b, stream);
+        if (r == EXASPIM_OK) {
+            b.org[2] = a.w - 2;
+            b.src_a = a.src_a;
+            b.dst = a.dst;
+            r = launch_conv3x3x3_thin(dtype, b, stream);
+        }
+    }
+    if (r == EXASPIM_OK && (stages & kRowStagePool))
+        r = launch_maxpool2_xcols(dtype, a.dst, a.pool_dst, a.n, a.d, a.h, a.w, a.cout, 0, a.w / 2 - 1, stream);
+    return r;
 }
 
 }  // namespace exaspim

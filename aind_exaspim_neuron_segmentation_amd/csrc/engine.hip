@@ -125,13 +125,12 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         fuse_pool[l] = !separate_pool && !(separate_deep && l > 0) && conv_can_fuse_pool(p.dtype, p.conv[2 * l].cout, d >> l, h >> l, w >> l);
     // Row mode of inc.3 (ConvArgs::row_stride): a column two neighbours share is computed once, the
     // two outermost x of every patch face that borders a neighbour and their pooled column are
-    // recomputed in the patch's own frame by the thin-tile and column max-pool launches below. Same
+    // recomputed in the patch's own frame by the thin-tile and column max-pool launches that follow
+    // (launch_conv3x3x3_row). Same
     // bits: a voxel's products are summed in the same order on every tile shape.
     // (EXASPIM_OPT_PER_PATCH_ENCODER: every patch on its own, as without a row.)
-    const int row_o = w - row_stride;
-    const bool row = row_stride > 0 && n >= 2 && !absmax && dtype_size(dt) == 2 && fuse_pool[0] &&
-                     !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) && p.conv[0].cout % 64 != 0 &&
-                     w % 16 == 0 && row_o > 0 && row_o % 32 == 0 && row_stride >= row_o;
+    const bool row = !absmax && !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) &&
+                     conv_row_mode_ok(dt, p.conv[0].cout, n, w, row_stride, fuse_pool[0]);
     auto conv = [&](int idx, const void* sa, const void* sb, void* dst, int l) -> int {
         const ConvLayer& L = p.conv[idx];
         ConvArgs a;
@@ -182,28 +181,10 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
             slot = t->next;
             EXA_CHECK_HIP(hipEventRecord(t->start[slot], stream));
         }
-        int r = x3 && has_head ? launch_conv3x3x3_x3_head(a, stream) : launch_conv3x3x3(dt, a, stream);
-        if (r == EXASPIM_OK && a.row_stride > 0) {
-            // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
-            // w/2 - 1 of every patch
-            ConvArgs b = a;
-            b.pool_dst = nullptr;
-            b.row_stride = 0;
-            b.n = n - 1;
-            b.ext[2] = 2;
-            const size_t vox = (size_t)a.d * a.h * a.w;
-            b.src_a = static_cast<const char*>(a.src_a) + vox * a.ca * dtype_size(dt);
-            b.dst = static_cast<char*>(a.dst) + vox * a.cout * dtype_size(dt);
-            r = launch_conv3x3x3_thin(dt, b, stream);
-            if (r == EXASPIM_OK) {
-                b.org[2] = a.w - 2;
-                b.src_a = a.src_a;
-                b.dst = a.dst;
-                r = launch_conv3x3x3_thin(dt, b, stream);
-            }
-            if (r == EXASPIM_OK)
-                r = launch_maxpool2_xcols(dt, a.dst, a.pool_dst, n, a.d, a.h, a.w, a.cout, 0, a.w / 2 - 1, stream);
-        }
+        // (row mode: the row launch, then the thin-tile and column max-pool launches that finish it)
+        int r = x3 && has_head      ? launch_conv3x3x3_x3_head(a, stream)
+                : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, kRowStagesAll, stream)
+                                   : launch_conv3x3x3(dt, a, stream);
         if (timed && r == EXASPIM_OK) {
             EXA_CHECK_HIP(hipEventRecord(t->stop[slot], stream));
             t->layer[slot] = idx;

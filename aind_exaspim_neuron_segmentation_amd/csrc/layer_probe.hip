@@ -18,6 +18,9 @@ void probe_reset_config(void) {
     last_conv_launch() = ConvLaunchRecord{};
     last_layer_kernel() = "";
 }
+// 1 if that launch was the row-mode kernel (conv3x3x3_zpipe_row), whose configuration string is the one
+// of the per-patch fused-pool launch
+int probe_last_row(void) { return last_conv_launch().row ? 1 : 0; }
 // kernel variant of the last launch_conv_first / launch_upsample2
 const char* probe_last_layer_kernel(void) { return last_layer_kernel(); }
 
@@ -94,6 +97,33 @@ int probe_conv3x3x3_x3_head(int thin, int dtype, const void* src_a, const void* 
     return launch_conv3x3x3_x3_head(a, stream);
 }
 
+// The engine's row-mode sequence (launch_conv3x3x3_row) on one source: stages is a mask of 1 = the row
+// launch, 2 = the two thin-tile launches, 4 = the column max-pool. After stage 1 alone the launch record
+// is the row launch's.
+int probe_conv3x3x3_row(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,
+                        int cout, int n, int d, int h, int w, float slope, int row_stride, void* pool_dst,
+                        int stages, hipStream_t stream) {
+    ConvArgs a{};
+    a.src_a = src;
+    a.ca = ca;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    a.row_stride = row_stride;
+    a.pool_dst = pool_dst;
+    return launch_conv3x3x3_row(dtype, a, stages, stream);
+}
+
+int probe_conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, int fused_pool_whole_patch) {
+    return conv_row_mode_ok(dtype, cout, n, w, row_stride, fused_pool_whole_patch != 0) ? 1 : 0;
+}
+
 int probe_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                      void* dst, int n, int d, int h, int wd, int c0p, float slope, int per_group,
                      hipStream_t stream) {
@@ -103,6 +133,11 @@ int probe_conv_first(int dtype, const float* x, float* xpad, const float* w, con
 int probe_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,
                    hipStream_t stream) {
     return launch_maxpool2(dtype, src, dst, n, d, h, w, c, stream);
+}
+
+int probe_maxpool2_xcols(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c, int ox0,
+                         int ox1, hipStream_t stream) {
+    return launch_maxpool2_xcols(dtype, src, dst, n, d, h, w, c, ox0, ox1, stream);
 }
 
 int probe_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,

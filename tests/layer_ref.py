@@ -1,5 +1,6 @@
 """
-Float64 references and the checker for the per-layer tests (test_gpu_layers.py).
+Float64 references and the checker for the per-layer tests (test_gpu_layers.py,
+test_gpu_row_layers.py).
 
 Plain helpers, no fixtures. Activations live in the library's blocked channels-last
 layout, (N, C / KC, D, H, W, KC): one 32-byte record per voxel and channel chunk, KC = 16
@@ -197,6 +198,26 @@ def maxpool_ref(x):
     return F.max_pool3d(torch.as_tensor(x, dtype=torch.float64), 2)
 
 
+# ---- operands of a row of overlapping patches ------------------------------------------
+def _uniform_pm(shape, gen, lo=0.5):
+    mag = lo + (1 - lo) * torch.rand(shape, generator=gen, dtype=torch.float64)
+    return mag * torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0).to(torch.float64)
+
+
+def row_inputs(n, c, d, h, w, stride, gen):
+    """(n, c, d, h, w) float64 inputs of n patches that are one row along x, `stride` voxels apart,
+    as inc.3 sees them in row mode (ConvArgs::row_stride): cut from one strip, so neighbours agree on
+    the columns they share, except each patch's own outermost x towards a neighbour (local x = 0 of
+    patches 1 .. n-1, x = w-1 of patches 0 .. n-2), where inc.0's zero padding makes them differ.
+    Those get fresh draws of twice the magnitude: an output computed in the wrong patch's frame is
+    then far outside any accumulation bound."""
+    strip = _uniform_pm((c, d, h, n * stride + (w - stride)), gen)
+    x = torch.stack([strip[..., i * stride: i * stride + w].clone() for i in range(n)])
+    x[1:, ..., 0] = 2 * _uniform_pm((n - 1, c, d, h), gen)
+    x[:-1, ..., w - 1] = 2 * _uniform_pm((n - 1, c, d, h), gen)
+    return x
+
+
 def load_probe():
     lib = ctypes.CDLL(PROBE_PATH)
     vp, i32, f32, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
@@ -210,6 +231,10 @@ def load_probe():
         "probe_conv3x3x3": (i32, [i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32,
                                   vp, vp, vp, sz, vp, vp, vp, i32, i32, vp]),
         "probe_conv_first": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+        "probe_last_row": (i32, []),
+        "probe_conv3x3x3_row": (i32, [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, i32, vp]),
+        "probe_conv_row_mode_ok": (i32, [i32, i32, i32, i32, i32, i32]),
+        "probe_maxpool2_xcols": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "probe_maxpool2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
         "probe_upsample2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "probe_head": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
