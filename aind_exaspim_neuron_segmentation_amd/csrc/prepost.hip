@@ -6,6 +6,7 @@
 //   stitch_accumulate -> trimmed overlap-add (inference.py:99-116)
 //   stitch_finalize   -> divide by the patch count (inference.py:120-125)
 //   synth_volume_u16  -> benchmark / test input (utils/synthetic.py)
+//   synth_neurite_u16 -> the neurite-like test / measurement input (utils/synthetic.py)
 
 #include "common.h"
 
@@ -32,6 +33,157 @@ __global__ __launch_bounds__(256) void synth_kernel(uint16_t* __restrict__ vol, 
             ((unsigned long long)(z + blk.origin[0]) * blk.global[1] + (y + blk.origin[1])) *
                 blk.global[2] + (x + blk.origin[2]);
         vol[i] = (uint16_t)(splitmix64(lin + seed) % 2000ULL);
+    }
+}
+
+// Neurite-like volume: sparse bright tubes on a dim noise floor, integer arithmetic only, the same
+// bits as utils/synthetic.py:synth_neurite_volume (golden g9 is made from it: frozen). g = global (z, y, x):
+//   floor(g)   = 8 + splitmix64(seed + global linear index) % 32
+//   cell       c = g >> 5 per axis; h(c) = splitmix64(key ^ splitmix64(seed ^ 0x6E65757269746573)),
+//              key = cz << 42 | cy << 21 | cx -- not a function of the volume's shape
+//   node(c)[a] = 32 c[a] + 4 + (byte a of h) % 24, a = 0 (z), 1 (y), 2 (x)
+//   edge c -> c + e_a: e = byte 3 + a of h, present iff (e & 7) < 3, radius r = 1 + (e >> 3) % 3,
+//              peak = 100 + (b^3 >> 14), b = byte a of splitmix64(h); segment A = node(c), B = node(c + e_a)
+//   a voxel p tests the 3 edges leaving its cell and the 3 arriving from the cell before it on each
+//   axis (none from index -1): d = B - A, w = p - A, dd = d.d, t = clamp(w.d, 0, dd),
+//   n = |w dd - d t|^2 (< 2^40): n <= r^2 dd^2 -> peak, n <= (r + 1)^2 dd^2 -> peak / 2, else 0
+//   voxel      = min(65535, floor + max over the edges)
+// Nodes keep 4 voxels from the cell faces, so a tube and its halo stay inside the two cells it joins.
+struct NeuriteSeg {
+    int a[3], d[3];   // A and B - A, (z, y, x)
+    int dd, r, peak;  // peak 0: no such edge
+};
+
+__device__ __forceinline__ unsigned long long neurite_hash(int cz, int cy, int cx, unsigned long long salt) {
+    const unsigned long long key =
+        ((unsigned long long)cz << 42) | ((unsigned long long)cy << 21) | (unsigned long long)cx;
+    return splitmix64(key ^ salt);
+}
+
+__device__ __forceinline__ void neurite_node(unsigned long long h, int cz, int cy, int cx, int n[3]) {
+    n[0] = (cz << 5) + 4 + (int)((h & 0xff) % 24);
+    n[1] = (cy << 5) + 4 + (int)(((h >> 8) & 0xff) % 24);
+    n[2] = (cx << 5) + 4 + (int)(((h >> 16) & 0xff) % 24);
+}
+
+// segment k of cell c: k = 0..2 leaves c along axis k, k = 3..5 arrives from the cell before c along axis k - 3
+__device__ __forceinline__ NeuriteSeg neurite_segment(int cz, int cy, int cx, unsigned long long salt, int k) {
+    NeuriteSeg s;
+    s.peak = 0;
+    const int a = k >= 3 ? k - 3 : k;
+    const bool back = k >= 3;
+    if (back && (a == 0 ? cz : a == 1 ? cy : cx) == 0) return s;
+    const int step = back ? -1 : 1;
+    const int oz = cz + (a == 0 ? step : 0), oy = cy + (a == 1 ? step : 0), ox = cx + (a == 2 ? step : 0);
+    const unsigned long long h = neurite_hash(cz, cy, cx, salt), ho = neurite_hash(oz, oy, ox, salt);
+    const unsigned long long he = back ? ho : h;   // the edge belongs to the cell it leaves
+    const unsigned e = (unsigned)(he >> (24 + 8 * a)) & 0xffu;
+    if ((e & 7u) >= 3u) return s;
+    int node[3], other[3];
+    neurite_node(h, cz, cy, cx, node);
+    neurite_node(ho, oz, oy, ox, other);
+    const unsigned b = (unsigned)(splitmix64(he) >> (8 * a)) & 0xffu;
+    s.dd = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        s.a[i] = back ? other[i] : node[i];
+        s.d[i] = back ? node[i] - other[i] : other[i] - node[i];
+        s.dd += s.d[i] * s.d[i];
+    }
+    s.r = 1 + (int)((e >> 3) % 3u);
+    s.peak = 100 + (int)((b * b * b) >> 14);
+    return s;
+}
+
+__device__ __forceinline__ int neurite_tube(const NeuriteSeg& s, int gz, int gy, int gx) {
+    const int wz = gz - s.a[0], wy = gy - s.a[1], wx = gx - s.a[2];
+    int t = wz * s.d[0] + wy * s.d[1] + wx * s.d[2];
+    t = t < 0 ? 0 : (t > s.dd ? s.dd : t);
+    const long long vz = wz * s.dd - s.d[0] * t, vy = wy * s.dd - s.d[1] * t, vx = wx * s.dd - s.d[2] * t;
+    const long long n = vz * vz + vy * vy + vx * vx, q = (long long)s.dd * s.dd;
+    if (n <= (long long)(s.r * s.r) * q) return s.peak;
+    if (n <= (long long)((s.r + 1) * (s.r + 1)) * q) return s.peak >> 1;
+    return 0;
+}
+
+// One item = 8 consecutive x of the rows of one z that lie in one cell along y (up to 32 rows). The
+// cell's six segments are derived once per item, but only to keep what a row needs to skip them: the
+// y range of each segment whose box, grown by r + 1, holds z and meets the x range. Most rows meet
+// none and only hash their floor; a row that meets one derives that segment again (three hashes)
+// and tests its 8 voxels, which keeps the registers of six segments out of the streaming loop.
+// One 16-byte store per row where the row pitch allows it (vec), element stores otherwise. A group
+// whose 8 voxels straddle two cells along x (an origin that is no multiple of 8) takes one pass per
+// cell, each with element stores.
+__global__ __launch_bounds__(256) void synth_neurite_u16_kernel(uint16_t* __restrict__ vol, exaspim_block blk,
+                                                                unsigned long long seed, int vec) {
+    const int D = blk.dims[0], H = blk.dims[1], W = blk.dims[2];
+    const int groups = (W + 7) / 8;
+    const int cy0 = blk.origin[1] >> 5;
+    const int ytiles = ((blk.origin[1] + H - 1) >> 5) - cy0 + 1;
+    const size_t items = (size_t)D * ytiles * groups;
+    const unsigned long long salt = splitmix64(seed ^ 0x6E65757269746573ULL);
+    for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items;
+         it += (size_t)gridDim.x * blockDim.x) {
+        const int xg = (int)(it % groups);
+        const size_t rest = it / groups;
+        const int cy = cy0 + (int)(rest % ytiles);
+        const int z = (int)(rest / ytiles);
+        const int x0 = xg * 8, nv = W - x0 < 8 ? W - x0 : 8;
+        const int gz = z + blk.origin[0], gx0 = x0 + blk.origin[2];
+        const int ylo = max(cy << 5, blk.origin[1]), yhi = min((cy + 1) << 5, blk.origin[1] + H);
+        const int cz = gz >> 5, cxa = gx0 >> 5, cxb = (gx0 + nv - 1) >> 5;
+        const bool whole = vec && cxa == cxb;   // vec: W % 8 == 0 and a 16-byte aligned base, so nv == 8
+        for (int cx = cxa; cx <= cxb; ++cx) {
+            // voxels [jlo, jhi) of the group lie in cell cx
+            const int jlo = max(0, (cx << 5) - gx0), jhi = min(nv, ((cx + 1) << 5) - gx0);
+            int yfrom[6], yto[6];   // rows segment k can reach; empty: it cannot reach this item
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const NeuriteSeg g = neurite_segment(cz, cy, cx, salt, k);
+                yfrom[k] = 1;
+                yto[k] = 0;
+                if (g.peak == 0) continue;
+                const int m = g.r + 1;
+                const int zl = min(g.a[0], g.a[0] + g.d[0]) - m, zh = max(g.a[0], g.a[0] + g.d[0]) + m;
+                const int xl = min(g.a[2], g.a[2] + g.d[2]) - m, xh = max(g.a[2], g.a[2] + g.d[2]) + m;
+                if (gz < zl || gz > zh || gx0 + jhi - 1 < xl || gx0 + jlo > xh) continue;
+                yfrom[k] = min(g.a[1], g.a[1] + g.d[1]) - m;
+                yto[k] = max(g.a[1], g.a[1] + g.d[1]) + m;
+            }
+            for (int gy = ylo; gy < yhi; ++gy) {
+                const unsigned long long lin =
+                    ((unsigned long long)gz * blk.global[1] + gy) * blk.global[2] + gx0 + seed;
+                int v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = 0;
+                unsigned hit = 0;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) hit |= (gy >= yfrom[k] && gy <= yto[k]) ? 1u << k : 0u;
+                while (hit) {
+                    const int k = __ffs(hit) - 1;
+                    hit &= hit - 1;
+                    const NeuriteSeg g = neurite_segment(cz, cy, cx, salt, k);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j >= jlo && j < jhi) v[j] = max(v[j], neurite_tube(g, gz, gy, gx0 + j));
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    v[j] += 8 + (int)(splitmix64(lin + j) & 31ULL);
+                    v[j] = v[j] > 65535 ? 65535 : v[j];
+                }
+                uint16_t* const row = vol + ((size_t)z * H + (gy - blk.origin[1])) * W + x0;
+                if (whole) {
+                    *reinterpret_cast<uint4*>(row) =
+                        make_uint4((unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16),
+                                   (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j >= jlo && j < jhi) row[j] = (uint16_t)v[j];
+                }
+            }
+        }
     }
 }
 
@@ -687,6 +839,18 @@ extern "C" int exaspim_synth_volume_u16(uint16_t* vol_dev, const exaspim_block* 
     EXA_CHECK_ARG(vol_dev != nullptr, "synth: NULL volume");
     const size_t total = (size_t)blk->dims[0] * blk->dims[1] * blk->dims[2];
     synth_kernel<<<stream_grid(total), 256, 0, (hipStream_t)stream>>>(vol_dev, *blk, seed);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_synth_volume_neurite_u16(uint16_t* vol_dev, const exaspim_block* blk,
+                                                uint64_t seed, void* stream) {
+    if (int rc = check_block(blk, "synth_neurite")) return rc;
+    EXA_CHECK_ARG(vol_dev != nullptr, "synth_neurite: NULL volume");
+    const int ytiles = ((blk->origin[1] + blk->dims[1] - 1) >> 5) - (blk->origin[1] >> 5) + 1;
+    const size_t items = (size_t)blk->dims[0] * ytiles * ((blk->dims[2] + 7) / 8);
+    const int vec = blk->dims[2] % 8 == 0 && ((uintptr_t)vol_dev & 15) == 0;
+    synth_neurite_u16_kernel<<<stream_grid(items), 256, 0, (hipStream_t)stream>>>(vol_dev, *blk, seed, vec);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
 }

@@ -22,7 +22,9 @@ sub-volume on the reference's GLOBAL patch grid:
 No other communication happens; the network never sees a neighbour's data.
 Sums of the overlap bands are associated differently from the single-device
 order at rank faces (float addition: differences of one ulp, far below the
-1e-3 parity bar); everything else is identical.
+1e-3 parity bar); everything else is identical. predict_shard(reference_order=True)
+removes that difference too, at the price of running the z ranks one after the
+other: a checking mode for results across world sizes.
 """
 
 import numpy as np
@@ -258,6 +260,30 @@ def exchange_output_bands(accum, shard, group):
             accum[recv_sl] += recv_buf
 
 
+def _z_band(accum, shard, group, receive):
+    """
+    One step of the z chain predict_shard(reference_order=True) runs: with "receive",
+    waits for the -z neighbour's overlap band and writes it over the (still zero)
+    accumulator; without, sends this rank's band to the +z neighbour. Same boxes as
+    exchange_output_bands' z phase.
+    """
+    peer = shard.neighbour(-1, 0) if receive else shard.neighbour(1, 0)
+    if peer is None:
+        return
+    lo, hi = (Shard(shard.plan, shard.grid, peer) if receive else shard).band_box(0)
+    sl = (slice(None),) + shard.local(lo, hi, shard.accum_origin)
+    if receive:
+        buf = torch.empty((accum.shape[0],) + tuple(b - a for a, b in zip(lo, hi)),
+                          dtype=accum.dtype, device=accum.device)
+    else:
+        buf = accum[sl].contiguous()
+    if not buf.numel():
+        return
+    _p2p([("recv" if receive else "send", buf, peer)], group)
+    if receive:
+        accum[sl] = buf
+
+
 def exchange_input_halo(core, shard, group):
     """
     Assembles a rank's input block (its disjoint sub-volume plus the halo its
@@ -338,7 +364,7 @@ def _timed(timings, key, device, fn):
 
 def predict_shard(volume, model, plan, shard, n_channels=3, batch_size=16,
                   brightness_clip=1000, normalization_percentiles=(1, 99.9), group=None,
-                  n_streams=1, timings=None, core=None):
+                  n_streams=1, timings=None, core=None, reference_order=False):
     """
     Runs one rank's share of predict() on its device: global percentiles
     (histogram all-reduce), the rank's patches, the band exchange and the final
@@ -367,9 +393,23 @@ def predict_shard(volume, model, plan, shard, n_channels=3, batch_size=16,
         device) when the caller holds it anyway (it fed exchange_input_halo):
         the histogram then runs over it instead of over a copy cut out of
         "volume".
+    reference_order : bool, optional
+        Reproduce the single-device predict() bit for bit instead of to one ulp.
+        By default every rank sums its own patches from zero and the overlap bands
+        are added afterwards, (a1 + ... + an) + (b1 + ... + bn), where the single
+        device adds ((a1 + ... + an) + b1) + ... + bn. With reference_order a rank
+        starts from the band of its -z neighbour and hands its own band on when
+        its patches are done, so every voxel sees the reference's order of
+        additions. The ranks then run one after the other: this is for checking
+        results across world sizes, not for throughput. Needs a rank grid that
+        splits z only (gy == 1; with a y split the single-device order alternates
+        between ranks within every patch layer).
     """
     from aind_exaspim_neuron_segmentation_amd import inference
 
+    if reference_order and shard.grid[1] != 1:
+        raise ValueError(
+            f"reference_order needs a rank grid that splits z only, got (gz, gy) = {shard.grid}")
     device = volume.tensor.device
     multi = group is not None and shard.grid[0] * shard.grid[1] > 1
     if multi:
@@ -395,11 +435,18 @@ def predict_shard(volume, model, plan, shard, n_channels=3, batch_size=16,
         mn, mx = inference.volume_percentiles(volume, brightness_clip, normalization_percentiles)
 
     accum_block = _native.Block.make(shard.accum_dims, shard.accum_origin, plan.shape)
+    chain = multi and reference_order
+    accum = None
+    if chain:
+        accum = torch.zeros((n_channels,) + tuple(shard.accum_dims), dtype=torch.float32, device=device)
+        _timed(timings, "output_bands_s", device, lambda: _z_band(accum, shard, group, receive=True))
     accum = inference.run_sliding_window(
         volume, model, plan, n_channels, batch_size, brightness_clip, mn, mx,
-        starts=shard.starts, accum_block=accum_block, n_streams=n_streams,
+        starts=shard.starts, accum=accum, accum_block=accum_block, n_streams=n_streams,
     )
-    if multi:
+    if chain:
+        _timed(timings, "output_bands_s", device, lambda: _z_band(accum, shard, group, receive=False))
+    elif multi:
         _timed(timings, "output_bands_s", device, lambda: exchange_output_bands(accum, shard, group))
     inference.stitch_finalize(accum, plan, accum_block)
     return accum

@@ -38,7 +38,8 @@ extern "C" {
  * 5: exaspim_unet_forward_absmax, exaspim_histogram_wide (EXASPIM_VOX_F64),
  *    exaspim_unet_set_options (replaces an environment switch);
  *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER;
- *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point) */
+ *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point);
+ *    later within 5: exaspim_synth_volume_neurite_u16 */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -321,6 +322,25 @@ int exaspim_export_f16(const float* src_dev, void* dst_dev, size_t n, void* stre
 /* vol[z,y,x] = splitmix64(seed + global linear index) % 2000 as uint16. */
 int exaspim_synth_volume_u16(uint16_t* vol_dev, const exaspim_block* blk,
                              uint64_t seed, void* stream);
+
+/* The neurite-like volume: sparse bright tubes on a dim noise floor, what a percentile-normalised
+ * ExaSPIM block looks like (mostly near zero, a few saturated structures). Integer arithmetic only;
+ * a pure function of (seed, global coordinate), so every shard writes its own block and
+ * utils/synthetic.py:synth_neurite_volume gives the same bits on the host. With g = global (z, y, x):
+ *   floor(g) = 8 + splitmix64(seed + global linear index) % 32;
+ *   cells c = g >> 5 per axis, h(c) = splitmix64((cz << 42 | cy << 21 | cx) ^
+ *     splitmix64(seed ^ 0x6E65757269746573)), independent of the volume's shape;
+ *   node(c)[a] = 32 c[a] + 4 + (byte a of h) % 24 for a = 0 (z), 1 (y), 2 (x);
+ *   the edge from c to the next cell along axis a exists iff (e & 7) < 3 with e = byte 3 + a of h,
+ *     has radius r = 1 + (e >> 3) % 3 and peak = 100 + (b * b * b >> 14), b = byte a of splitmix64(h),
+ *     and is the segment A = node(c), B = node(c + e_a);
+ *   a voxel p tests the three edges leaving its cell and the three arriving from the cell before it
+ *     on each axis: d = B - A, w = p - A, dd = d.d, t = clamp(w.d, 0, dd), n = |w dd - d t|^2;
+ *     n <= r^2 dd^2 gives peak, n <= (r + 1)^2 dd^2 gives peak / 2 (rounded down), else 0;
+ *   vol[g] = min(65535, floor(g) + the largest of the six).
+ * Nodes keep 4 voxels from the cell faces, so a tube and its halo lie inside the two cells it joins. */
+int exaspim_synth_volume_neurite_u16(uint16_t* vol_dev, const exaspim_block* blk,
+                                     uint64_t seed, void* stream);
 
 #ifdef __cplusplus
 }
