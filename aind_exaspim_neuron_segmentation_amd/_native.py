@@ -20,6 +20,7 @@ OPT_SEPARATE_POOL, OPT_SEPARATE_DEEP_POOLS, OPT_PLAIN_UPSAMPLE, OPT_FIRST_PER_GR
 OPT_UPSAMPLE_PER_THREAD = 16
 OPT_PER_PATCH_ENCODER = 32
 OPT_SEPARATE_HEAD = 64   # the head as its own launch, nothing trimmed (bf16x3: same bits)
+AFF_F32, AFF_F16 = 0, 1   # EXASPIM_AFF_*: element type of exaspim_components' input
 
 DTYPE_CODES = {
     "fp32": DT_F32, "float32": DT_F32, "f32": DT_F32,
@@ -111,6 +112,9 @@ SIGNATURES = {
                                          ctypes.POINTER(Block), _vp]),
     "exaspim_stitch_finalize": (_i32, [_vp, _i32, ctypes.POINTER(Window), ctypes.POINTER(Block), _vp]),
     "exaspim_export_f16": (_i32, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "exaspim_components_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_components": (_i32, [_vp, _i32, _i32, _I32x3, ctypes.c_float, ctypes.c_int64, _vp, _vp, _vp,
+                                  _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

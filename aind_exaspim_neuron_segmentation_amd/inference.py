@@ -207,6 +207,130 @@ def export_half(tensor, out=None):
     return out.view(tensor.shape)
 
 
+_AFF_CODES = {torch.float32: _native.AFF_F32, torch.float16: _native.AFF_F16}
+
+
+def _components_on_device(affinities, threshold=0.5, min_segment_size=100):
+    """
+    exaspim_components on a device tensor: the labels and the number of kept
+    segments, both left on the device (nothing is synchronised).
+
+    Parameters
+    ----------
+    affinities : torch.Tensor
+        float32 or float16 tensor on a HIP device, (3, D, H, W) affinities or
+        (D, H, W) foreground probabilities.
+    threshold : float, optional
+        Rounded to float32; an edge (a voxel, in foreground mode) is on iff
+        its value is >= it. Default is 0.5.
+    min_segment_size : int, optional
+        Components are kept iff they have more voxels than this. Default is 100.
+
+    Returns
+    -------
+    labels : torch.Tensor
+        int32 (D, H, W): 0 for background, 1 ... K in raster order of each
+        component's first voxel.
+    count : torch.Tensor
+        int32 (1,): K.
+    """
+    if not isinstance(affinities, torch.Tensor):
+        raise TypeError(f"_components_on_device needs a torch tensor, got {type(affinities).__name__}")
+    if affinities.dtype not in _AFF_CODES:
+        raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
+    if affinities.dim() == 4:
+        if affinities.shape[0] != 3:
+            raise ValueError(f"4-D affinities must be (3, D, H, W), got {tuple(affinities.shape)}")
+        channels = 3
+    elif affinities.dim() == 3:
+        channels = 1
+    else:
+        raise ValueError("affinities must be (3, D, H, W) or a (D, H, W) foreground map, "
+                         f"got {affinities.dim()} dimensions")
+    if affinities.device.type != "cuda":
+        raise RuntimeError(
+            "affinities_to_components (MI355X) has no CPU path: the tensor must be on a HIP device, "
+            f"got {affinities.device}"
+        )
+    dims = tuple(int(v) for v in affinities.shape[-3:])
+    if min(dims) < 1:
+        raise ValueError(f"empty volume {dims}")
+    affinities = affinities.contiguous()
+    device = affinities.device
+    lib = _native.lib()
+    need = lib.exaspim_components_workspace_bytes(_native.int3(dims))
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        labels = torch.empty(dims, dtype=torch.int32, device=device)
+        count = torch.empty(1, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_components(affinities.data_ptr(), _AFF_CODES[affinities.dtype], channels,
+                                   _native.int3(dims), float(np.float32(threshold)), int(min_segment_size),
+                                   labels.data_ptr(), count.data_ptr(), workspace.data_ptr(), need,
+                                   _stream(device)),
+            "exaspim_components",
+        )
+    return labels, count
+
+
+def affinities_to_components(affinities, threshold=0.5, min_segment_size=100, *,
+                             return_device_tensor=False):
+    """
+    Labels the connected components of thresholded affinities on the device
+    and removes small ones.
+
+    What this is: the affinity graph in the reference's own convention
+    (img_util.get_affinity_channels, img_util.py:159-216: channel c at voxel v
+    is the edge between v and v + e_c, e = z, y, x; the entries at the last
+    index along axis c are ignored) cut at "threshold", its connected
+    components, then the reference's size filter (img_util.py:555-558: kept
+    iff size > min_segment_size) and a contiguous renumbering in raster order
+    of each component's first voxel. A voxel without an on edge is background.
+    A 3-D input is a foreground map: voxels >= threshold are on and
+    6-connected, and an on voxel alone is a component of size 1.
+
+    What this is not: waterz's watershed / agglomeration, which the
+    reference's affinities_to_segmentation runs (inference.py:196-237). That
+    stays a CPU library; nothing here merges or splits by affinity scores.
+
+    Parameters
+    ----------
+    affinities : torch.Tensor or numpy.ndarray
+        float32 or float16, (3, D, H, W) or (D, H, W): a tensor on a HIP
+        device (e.g. from predict(..., return_device_tensor=True)), or a numpy
+        array, which is uploaded to cuda:0. D * H * W must not exceed 2^31 - 1.
+    threshold : float, optional
+        Rounded to float32; on iff float32(value) >= it, NaN is off. Default
+        is 0.5.
+    min_segment_size : int, optional
+        Default is 100.
+    return_device_tensor : bool, optional
+        Return the labels as a device tensor instead of a numpy array.
+        Default is False.
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W) labels: 4 bytes per voxel leave the device instead of
+        the 12 of the affinities.
+    """
+    if isinstance(affinities, np.ndarray):
+        if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
+        if affinities.ndim not in (3, 4):
+            raise ValueError("affinities must be (3, D, H, W) or a (D, H, W) foreground map, "
+                             f"got {affinities.ndim} dimensions")
+        if not torch.cuda.is_available():
+            raise RuntimeError("affinities_to_components (MI355X) has no CPU path and no HIP device is present")
+        affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
+    labels, _ = _components_on_device(affinities, threshold, min_segment_size)
+    if return_device_tensor:
+        return labels
+    return labels.cpu().numpy()
+
+
 def _predict_batch(img, model, starts, patch_shape, trim=8, *, clip=None, mn=0.0, mx=1.0):
     """
     Extracts a batch of 3D patches from a device-resident volume, runs them

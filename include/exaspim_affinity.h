@@ -39,7 +39,8 @@ extern "C" {
  *    exaspim_unet_set_options (replaces an environment switch);
  *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER;
  *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point);
- *    later within 5: exaspim_synth_volume_neurite_u16 */
+ *    later within 5: exaspim_synth_volume_neurite_u16;
+ *    later within 5: exaspim_components, exaspim_components_workspace_bytes (EXASPIM_AFF_*) */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -316,6 +317,47 @@ int exaspim_stitch_finalize(float* accum_dev, int32_t channels,
  * rounding error is at most 2.4e-4. src_dev float32, dst_dev 16-bit, both 16-byte
  * aligned. */
 int exaspim_export_f16(const float* src_dev, void* dst_dev, size_t n, void* stream);
+
+/* ---- consumer front-end: connected components of thresholded affinities ---
+ *      (the exactly defined part of what follows predict(): the affinity graph of
+ *      utils/img_util.py:159-216 get_affinity_channels, cut at a threshold, then the size
+ *      filter and renumbering of utils/img_util.py:536-559 remove_small_segments. It is NOT
+ *      waterz's watershed / agglomeration, inference.py:196-237, which stays on the host.) */
+
+/* element type of the affinities handed to exaspim_components */
+#define EXASPIM_AFF_F32 0 /* float32 (predict()'s default output)                 */
+#define EXASPIM_AFF_F16 1 /* IEEE half (exaspim_export_f16); widened exactly       */
+
+/* Scratch bytes exaspim_components needs for a dims[0] x dims[1] x dims[2] (z, y, x) volume:
+ * about 5 bytes per voxel. 0 (and a message) if a dim is not positive or the volume has more
+ * than 2^31 - 1 voxels. */
+size_t exaspim_components_workspace_bytes(const int32_t dims[3]);
+
+/* labels_dev (int32, dims) = the connected components of the graph of "on" edges, small ones
+ * removed, the rest numbered 1 .. K; *n_segments_dev = K.
+ *  - channels = 3: aff_dev is (3, dims). Channel c at voxel v is the edge between v and v + e_c,
+ *    e_0 = z, e_1 = y, e_2 = x (get_affinity_channels' convention); the entries at the last index
+ *    along axis c leave the volume and are ignored whatever they hold. An edge is on iff
+ *    float32(a) >= threshold; a NaN is off. A voxel without an on edge is background, label 0
+ *    (a one-voxel segment has no affinity).
+ *  - channels = 1: aff_dev is (dims), a foreground probability. A voxel is on iff p >= threshold, an
+ *    edge iff both of its ends are on (6-connectivity); an on voxel alone is a component of size 1.
+ *  - A component is kept iff size > min_size, strictly (img_util.py:555-558).
+ *  - Kept components are numbered in the order of their smallest C-order linear index (first
+ *    appearance in a raster scan); every other voxel gets 0.
+ * The output is a pure function of the input: it depends neither on launch geometry nor on the
+ * order in which atomics land. labels_dev doubles as the union-find's parent array while the passes
+ * run; workspace_dev must be 16-byte aligned, aff_dev aligned to its element (16 bytes to get
+ * the wide loads). Separate launches on "stream", no inter-workgroup waiting, nothing allocated,
+ * nothing synchronised. EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_components_workspace_bytes(dims), before anything is launched; EXASPIM_E_INVALID for a
+ * NULL pointer, an unknown aff_dtype, channels other than 3 or 1, a dim that is not positive, a
+ * volume of more than 2^31 - 1 voxels, or a misaligned buffer (workspace_dev not 16-byte aligned,
+ * labels_dev or aff_dev not aligned to its element). */
+int exaspim_components(const void* aff_dev, int32_t aff_dtype, int32_t channels,
+                       const int32_t dims[3], float threshold, int64_t min_size,
+                       int32_t* labels_dev, int32_t* n_segments_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
