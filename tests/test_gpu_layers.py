@@ -687,7 +687,7 @@ def _expected_configs():
         tz, ty, tx = tile
         return ("launch_cfg", (f"TZ = {tz}", f"TY = {ty}", f"TX = {tx}", f"WAVES_M = {wm}", f"WAVES_N = {wn}",
                                f"MT = {mt}", f"NT = {nt}", f"MINW = {minw}", f"PD = {pd}", f"ZORD = {zord}",
-                               "DMA = false", f"POOL = {pool}"))
+                               f"POOL = {pool}"))
 
     out = set()
     for dt in DTS:
