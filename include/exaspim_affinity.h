@@ -156,7 +156,9 @@ size_t exaspim_unet_workspace_bytes(const exaspim_unet* h, int32_t n, int32_t d,
 
 /* UNet3D.forward (unet3d.py:77-105): x_dev is float32 (n,1,d,h,w); out_dev
  * receives float32 (n,out_channels,d,h,w) logits, or sigmoid(logits) when
- * apply_sigmoid != 0 (inference.py:158). */
+ * apply_sigmoid != 0 (inference.py:158). What workspace_dev holds on entry is undefined
+ * (it is never cleared and the result does not depend on it), and nothing outside its first
+ * workspace_bytes bytes is touched; the same holds for every exaspim_unet_forward_* below. */
 int exaspim_unet_forward(exaspim_unet* h, const float* x_dev, float* out_dev,
                          int32_t n, int32_t d, int32_t hgt, int32_t w,
                          int32_t apply_sigmoid, void* workspace_dev,

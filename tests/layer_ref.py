@@ -77,6 +77,29 @@ def bits(t):
     return t.view({4: torch.int32, 2: torch.int16}[t.element_size()])
 
 
+# ---- read footprint of a region launch -----------------------------------------
+def grown_box(dhw, region):
+    """bool (D, H, W): the region (org + ext, six numbers) grown by one voxel on every face and
+    clipped to the patch -- the only source voxels the outputs in [org, org + ext) may depend on."""
+    m = torch.zeros(tuple(int(v) for v in dhw), dtype=torch.bool)
+    m[tuple(slice(max(0, o - 1), min(int(s), o + e + 1)) for o, e, s in zip(region[:3], region[3:], dhw))] = True
+    return m
+
+
+def poison_outside(x, region):
+    """Copy of the (N, C, D, H, W) values with every channel outside grown_box set to NaN."""
+    y = torch.as_tensor(x).clone()
+    y[:, :, ~grown_box(y.shape[2:], region)] = float("nan")
+    return y
+
+
+def poison_blocked(t, region):
+    """Sets, in place, every channel of a blocked source (N, C/KC, D, H, W, KC) outside grown_box to
+    all-ones bits: a NaN in float32, IEEE half and bfloat16."""
+    bits(t)[:, :, ~grown_box(t.shape[2:5], region)] = -1
+    return t
+
+
 # ---- packed weights ----------------------------------------------------------
 def decode_storage(raw, dt):
     """uint8 bytes of the storage type -> float64 numpy array."""

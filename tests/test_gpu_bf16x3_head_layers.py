@@ -44,13 +44,13 @@ def _head_params(oc, seed):
     return hw, hb
 
 
-def run_head(probe, L, hw, hb, sig, region=None, expect_rc=0, oc_arg=None):
-    """One launch of the head variant on sentinel-filled dst and head_out -> (head_out, dst) on the CPU."""
+def run_head(probe, L, hw, hb, sig, region=None, expect_rc=0, oc_arg=None, src_poison=None):
+    """One launch of the head variant on sentinel-filled dst and head_out -> (head_out, dst) on the CPU.
+    src_poison: a region; both packed sources are NaN bits outside that box grown by one voxel."""
     n, d, h, w = L.shape
     oc = hw.shape[0]
     dev = "cuda"
-    xa = R.pack_blocked(L.x[:, : L.ca], "f32").to(dev)
-    xb = R.pack_blocked(L.x[:, L.ca:], "f32").to(dev) if L.cb else None
+    xa, xb = L.packed_sources(src_poison)
     wt = L.packed_weights().to(dev)
     bt = L.b.to(torch.float32).to(dev)
     dst = torch.zeros((n, L.cout // 8, d, h, w, 8), dtype=torch.float32, device=dev)
@@ -129,12 +129,8 @@ def cases(probe):
     done.clear()
 
 
-@pytest.mark.parametrize("oc", [1, 2, 3, 4])
-@pytest.mark.parametrize("name", list(CASES))
-def test_fused_head(probe, cases, name, oc):
-    L, region = cases(name)
-    hw, hb = _head_params(oc, seed=oc * 100 + L.shape[1])
-    m = _mask(L.shape, oc, region)
+def _pre_and_tol(L, hw, hb):
+    """float64 head pre-activation of the layer's reference and the derived bound on it."""
     acc, s = L.ref()
     act = X.leaky(acc)
     bound = X.conv_bound(s, L.ca + L.cb)   # |leaky(v) - leaky(acc)| <= |v - acc|
@@ -143,6 +139,16 @@ def test_fused_head(probe, cases, name, oc):
     tol0 = (torch.einsum("oc,ncdhw->nodhw", hw64.abs(), bound) +
             (32 + 4) * 2.0 ** -24 * (torch.einsum("oc,ncdhw->nodhw", hw64.abs(), act.abs()) +
                                      hb64.abs()[None, :, None, None, None]))
+    return pre, tol0
+
+
+@pytest.mark.parametrize("oc", [1, 2, 3, 4])
+@pytest.mark.parametrize("name", list(CASES))
+def test_fused_head(probe, cases, name, oc):
+    L, region = cases(name)
+    hw, hb = _head_params(oc, seed=oc * 100 + L.shape[1])
+    m = _mask(L.shape, oc, region)
+    pre, tol0 = _pre_and_tol(L, hw, hb)
     for sig in (0, 1):
         got, dst = run_head(probe, L, hw, hb, sig, region)
         # nothing but the region of head_out is written
@@ -161,6 +167,33 @@ def test_fused_head(probe, cases, name, oc):
         rel = float((err / tol)[m].max())
         print(f"bf16x3 head {name} oc={oc} sig={sig}: max err / bound = {rel:.3f} over {int(m.sum())} outputs")
         assert bool((err <= tol)[m].all()), f"sig={sig}: max err {float(err[m].max()):.3e} ({rel:.3f} of the bound)"
+
+
+@pytest.mark.parametrize("oc", [1, 2, 3, 4])
+@pytest.mark.parametrize("name", [k for k, v in CASES.items() if v[5] is not None])
+def test_region_reads_only_its_grown_box(probe, cases, name, oc):
+    """The engine's contract for a region launch: head outputs in [org, org + ext) depend on source voxels
+    of that box grown by one voxel only. Everything else of both sources is NaN here, and the region still
+    lies within the derived bound of the float64 reference, has the bits of the launch on the clean
+    sources, and holds no NaN; nothing outside it is written."""
+    L, region = cases(name)
+    hw, hb = _head_params(oc, seed=oc * 100 + L.shape[1])
+    m = _mask(L.shape, oc, region)
+    pre, tol0 = _pre_and_tol(L, hw, hb)
+    for sig in (0, 1):
+        clean, _ = run_head(probe, L, hw, hb, sig, region)
+        got, dst = run_head(probe, L, hw, hb, sig, region, src_poison=region)
+        assert _untouched(dst, torch.ones(dst.shape, dtype=torch.bool)), "dst was written"
+        assert _untouched(got, ~m), "head_out written outside the region"
+        assert not torch.isnan(got[m]).any(), f"sig={sig}: NaN inside the region"
+        differ = got.view(torch.int32)[m] != clean.view(torch.int32)[m]
+        assert not differ.any(), f"sig={sig}: {int(differ.sum())} of {int(m.sum())} outputs changed with the poison"
+        want, tol = pre, tol0
+        if sig:   # sigmoid is 1/4-Lipschitz; expf and the division add a few float32 roundings
+            want = torch.sigmoid(pre)
+            tol = tol0 / 4 + 2.0 ** -21 * want.abs() + 2.0 ** -40
+        err = (got.to(torch.float64) - want).abs()
+        assert bool((err <= tol)[m].all()), f"sig={sig}: max err {float(err[m].max()):.3e}"
 
 
 @pytest.mark.parametrize("sig", [0, 1])

@@ -97,12 +97,22 @@ class Layer:
         assert np.array_equal(hi, self.w_hi.numpy()) and np.array_equal(lo, self.w_lo.numpy())
         return torch.from_numpy(img.view(np.int16).copy())
 
+    def packed_sources(self, src_poison=None):
+        xa = R.pack_blocked(self.x[:, : self.ca], "f32")
+        xb = R.pack_blocked(self.x[:, self.ca:], "f32") if self.cb else None
+        if src_poison is not None:
+            R.poison_blocked(xa, src_poison)
+            if xb is not None:
+                R.poison_blocked(xb, src_poison)
+        return xa.to("cuda"), xb.to("cuda") if xb is not None else None
+
     def run(self, probe, region=None, partial=False, thin=False, dst=None, expect_rc=0, pool=False, head=False,
-            ca_arg=None):
+            ca_arg=None, src_poison=None):
+        """src_poison: a region (org + ext); every channel of both packed sources outside that box grown
+        by one voxel is set to NaN bits (layer_ref.poison_blocked)."""
         n, d, h, w = self.shape
         dev = "cuda"
-        xa = R.pack_blocked(self.x[:, : self.ca], "f32").to(dev)
-        xb = R.pack_blocked(self.x[:, self.ca:], "f32").to(dev) if self.cb else None
+        xa, xb = self.packed_sources(src_poison)
         wt = self.packed_weights().to(dev)
         bt = self.b.to(torch.float32).to(dev)
         if dst is None:
@@ -307,6 +317,46 @@ def test_trimmed_region_with_thin_remainders_has_the_bits_of_the_whole_patch(pro
     assert torch.equal(R.bits(L.dst)[m], R.bits(whole.dst)[m])
     raw = L.dst.contiguous().view(torch.uint8).reshape(L.dst.shape + (4,))
     assert (raw[~m] == SENTINEL).all()
+
+
+def _trimmed_with_remainders(probe, poisoned):
+    """The three launches of the engine's trimmed region (main tiles, y remainder, x remainder) into one
+    sentinel-filled dst; poisoned: each launch's sources are NaN outside its own region's grown box."""
+    n, d, h, w = 2, 10, 24, 48
+    org, ext = (3, 3, 3), (4, 18, 36)
+    L = Layer(32, 32, 32, n, d, h, w, seed=11)
+    parts = [(org + (ext[0], 16, 32), False, A), ((org[0], org[1] + 16, org[2], ext[0], 2, 36), True, TY2),
+             ((org[0], org[1], org[2] + 32, ext[0], 16, 4), True, TX2)]
+    dst = None
+    for region, thin, config in parts:
+        L.run(probe, region=region, thin=thin, dst=dst, src_poison=region if poisoned else None)
+        assert L.config == config
+        dst = L.dst_dev
+    return L, org + ext
+
+
+@pytest.mark.parametrize("case", REGIONS + ["trimmed"],
+                         ids=lambda c: c if isinstance(c, str) else f"thin{c[0]}-" + "-".join(map(str, c[6])))
+def test_region_reads_only_its_grown_box(probe, case):
+    """The engine's contract for a region launch: outputs in [org, org + ext) depend on source voxels of
+    that box grown by one voxel only. Everything else of both sources is NaN here, and the region still
+    passes the float64 check, has the bits of the launch on the clean sources, and holds no NaN -- for
+    every region and thin-tile case above and the trimmed region cut into main tiles and remainders."""
+    if case == "trimmed":
+        clean, region = _trimmed_with_remainders(probe, poisoned=False)
+        L, _ = _trimmed_with_remainders(probe, poisoned=True)
+    else:
+        thin, ca, cout, d, h, w, region, config = case
+        clean = Layer(ca, 0, cout, 2, d, h, w, seed=sum(region)).run(probe, region=region, thin=bool(thin))
+        L = Layer(ca, 0, cout, 2, d, h, w, seed=sum(region)).run(probe, region=region, thin=bool(thin),
+                                                                 src_poison=region)
+        assert L.config == config == clean.config
+    _check_region(L, region)
+    m = _region_mask((L.shape[0], L.cout) + L.shape[1:], region)
+    assert not torch.isnan(R.unpack_blocked(L.dst)[m]).any(), "NaN inside the region"
+    mb = _blocked_mask(m)
+    differ = R.bits(L.dst)[mb] != R.bits(clean.dst)[mb]
+    assert not differ.any(), f"{int(differ.sum())} of {int(mb.sum())} outputs of the region changed with the poison"
 
 
 # ---- edge data -------------------------------------------------------------------------------

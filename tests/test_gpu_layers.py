@@ -101,12 +101,20 @@ class Layer:
         return self._ref
 
     def run(self, probe, region=None, pool=False, partial=False, head=None, thin=False, dst_fill=None,
-            expect_rc=0, ca_arg=None):
+            expect_rc=0, ca_arg=None, src_poison=None):
+        """src_poison: a region (org + ext); every channel of both packed sources outside that box grown
+        by one voxel is set to NaN bits (layer_ref.poison_blocked)."""
         dt, (n, d, h, w) = self.dt, self.shape
         k = R.kc(dt)
         dev = "cuda"
-        xa = R.pack_blocked(self.x[:, : self.ca], dt).to(dev)
-        xb = R.pack_blocked(self.x[:, self.ca:], dt).to(dev) if self.cb else None
+        xa = R.pack_blocked(self.x[:, : self.ca], dt)
+        xb = R.pack_blocked(self.x[:, self.ca:], dt) if self.cb else None
+        if src_poison is not None:
+            R.poison_blocked(xa, src_poison)
+            if xb is not None:
+                R.poison_blocked(xb, src_poison)
+        xa = xa.to(dev)
+        xb = xb.to(dev) if xb is not None else None
         wt = encode_conv_weights(self.w.numpy(), dt).to(dev)
         bt = self.b.to(torch.float32).to(dev)
         dst = torch.zeros((n, self.cout // k, d, h, w, k), dtype=R.STORAGE[dt], device=dev)
@@ -358,6 +366,26 @@ def test_region(probe, dt, case):
                                                                  dst_fill=SENTINEL)
     assert _tile(L.params) == tile, L.params
     _check_region(L, region)
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", REGIONS, ids=lambda c: f"thin{c[0]}-" + "-".join(map(str, c[6])))
+def test_region_reads_only_its_grown_box(probe, dt, case):
+    """The engine's contract for a region launch: outputs in [org, org + ext) depend on source voxels of
+    that box grown by one voxel only. Everything else of the source is NaN here, and the region still
+    passes the float64 check, has the bits of the launch on the clean source, and holds no NaN."""
+    thin, ca, cout, d, h, w, region, tile = case
+    kw = dict(region=region, thin=bool(thin), dst_fill=SENTINEL)
+    clean = Layer(dt, ca, 0, cout, 2, d, h, w, seed=sum(region)).run(probe, **kw)
+    L = Layer(dt, ca, 0, cout, 2, d, h, w, seed=sum(region)).run(probe, src_poison=region, **kw)
+    assert _tile(L.params) == tile and L.config == clean.config, L.params
+    _check_region(L, region)
+    m = _region_mask((2, cout, d, h, w), region)
+    k = R.kc(dt)
+    mb = m.reshape(2, cout // k, k, d, h, w).permute(0, 1, 3, 4, 5, 2)
+    assert not torch.isnan(R.unpack_blocked(L.dst)[m]).any(), "NaN inside the region"
+    differ = R.bits(L.dst)[mb] != R.bits(clean.dst)[mb]
+    assert not differ.any(), f"{int(differ.sum())} of {int(mb.sum())} outputs of the region changed with the poison"
 
 
 # ---- persistent tile walk ---------------------------------------------------------------

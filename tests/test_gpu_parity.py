@@ -21,6 +21,9 @@ from aind_exaspim_neuron_segmentation_amd.utils import synthetic
 
 pytestmark = pytest.mark.gpu
 
+PROB_TOL_FP32 = 5e-6                              # probabilities of the fp32 path (max abs)
+PROB_TOL_16BIT = [("bf16", 4e-3), ("fp16", 1e-3)]   # ... and of the 16-bit storage modes
+
 
 @pytest.fixture(scope="module")
 def dev():
@@ -76,10 +79,10 @@ def test_unet_single_96_patch_vs_reference_golden(dev, oracle, golden):
     print(f"fp32 96^3 logits vs reference: {err:.3e} / {err2:.3e}")
     assert err < 3e-5 and err2 < 3e-5
     sig = torch.sigmoid(logits).cpu().numpy()[0, :, ::8, ::8, ::8]
-    assert np.abs(sig - g["sigmoid_sub"]).max() < 5e-6
+    assert np.abs(sig - g["sigmoid_sub"]).max() < PROB_TOL_FP32
 
 
-@pytest.mark.parametrize("cdt,tol", [("bf16", 4e-3), ("fp16", 1e-3)])
+@pytest.mark.parametrize("cdt,tol", PROB_TOL_16BIT)
 def test_unet_16bit_paths_vs_oracle(dev, oracle, cdt, tol):
     # 16-bit storage of activations/weights, fp32 accumulate: tolerance on the
     # probabilities (max abs): fp16 = north_star's 1e-3; bf16 has 8 significant bits.
@@ -115,7 +118,7 @@ def test_conv_transpose_variant_vs_reference_golden_and_oracle(dev, oracle, gold
     assert e_pred < 5e-6
 
 
-@pytest.mark.parametrize("cdt,tol", [("bf16", 4e-3), ("fp16", 1e-3)])
+@pytest.mark.parametrize("cdt,tol", PROB_TOL_16BIT)
 def test_conv_transpose_variant_16bit(dev, oracle, cdt, tol):
     model, sd = make_model(dev, seed=8, compute_dtype=cdt, trilinear=False)
     x = normalized_input(oracle, (32, 32, 32), seed=62, n=3)

@@ -147,3 +147,52 @@ def test_checker_rejects_kernel_defects(dt):
     nan_acc[0, 0, 1, 1, 1] = float("nan")
     with pytest.raises(AssertionError):
         R.check_conv(store(acc), nan_acc, s, cin, dt, cout_real=cout_real)
+
+
+# (d, h, w, org + ext): interior, touching faces (the grown box is clipped), a thin tile, the whole patch
+FOOTPRINTS = [
+    (8, 12, 20, (1, 2, 3, 6, 9, 14)),
+    (6, 12, 16, (2, 0, 5, 3, 12, 11)),
+    (12, 16, 16, (2, 13, 8, 8, 2, 8)),
+    (6, 8, 16, (1, 0, 14, 4, 8, 2)),
+    (4, 6, 8, (0, 0, 0, 4, 6, 8)),
+]
+
+
+@pytest.mark.parametrize("case", FOOTPRINTS, ids=lambda c: "-".join(map(str, c[3])))
+def test_poison_mask_is_the_read_footprint_of_a_region(case):
+    """The mask the GPU layer tests poison with (src_poison): in the float64 reference, NaN everywhere
+    outside the region grown by one voxel leaves every output of the region as it was, and a NaN in any
+    single voxel of the grown box's shell (inside the box, outside the region) reaches the region."""
+    d, h, w, region = case
+    (oz, oy, ox), (ez, ey, ex) = region[:3], region[3:]
+    gen = torch.Generator().manual_seed(sum(region))
+    cin, cout = 8, 4
+    x = _uniform_pm((2, cin, d, h, w), gen)
+    wt = _uniform_pm((cout, cin, 27), gen)
+    b = _uniform_pm((cout,), gen)
+    inside = (Ellipsis, slice(oz, oz + ez), slice(oy, oy + ey), slice(ox, ox + ex))
+    acc, _ = R.conv_ref(x, wt, b)
+    box = R.grown_box((d, h, w), region)
+    want = torch.zeros((d, h, w), dtype=torch.bool)
+    want[max(0, oz - 1): oz + ez + 1, max(0, oy - 1): oy + ey + 1, max(0, ox - 1): ox + ex + 1] = True
+    assert torch.equal(box, want)
+    xp = R.poison_outside(x, region)
+    assert torch.equal(torch.isnan(xp), (~box).expand(2, cin, d, h, w)) and torch.equal(xp[:, :, box], x[:, :, box])
+    acc_p, _ = R.conv_ref(xp, wt, b)
+    assert not torch.isnan(acc_p[inside]).any()
+    assert torch.equal(acc_p[inside], acc[inside])
+    # every voxel of the shell is read: one NaN there, in one channel of one patch, changes the region
+    shell = box.clone()
+    shell[oz: oz + ez, oy: oy + ey, ox: ox + ex] = False
+    for z, y, xx in shell.nonzero().tolist():
+        one = xp.clone()
+        one[1, 3, z, y, xx] = float("nan")
+        hit = torch.isnan(R.conv_ref(one[1:], wt, b)[0][inside])
+        assert hit.any(), (z, y, xx)
+    # the blocked helper poisons the same voxels, every channel, in every storage type
+    for dt in ("f32", "bf16", "f16"):
+        k = R.kc(dt)
+        t = R.poison_blocked(R.pack_blocked(x[:, :1].expand(2, 2 * k, d, h, w), dt), region)
+        assert torch.equal(torch.isnan(R.unpack_blocked(t)), (~box).expand(2, 2 * k, d, h, w))
+        assert bool((R.bits(t)[:, :, ~box] == -1).all())
