@@ -20,6 +20,7 @@ OPT_SEPARATE_POOL, OPT_SEPARATE_DEEP_POOLS, OPT_PLAIN_UPSAMPLE, OPT_FIRST_PER_GR
 OPT_UPSAMPLE_PER_THREAD = 16
 OPT_PER_PATCH_ENCODER = 32
 OPT_SEPARATE_HEAD = 64   # the head as its own launch, nothing trimmed (bf16x3: same bits)
+OPT_ROW_SEPARATE_BORDERS = 256   # row mode: border faces as two thin launches + a column max-pool (same bits)
 AFF_F32, AFF_F16 = 0, 1   # EXASPIM_AFF_*: element type of exaspim_components' input
 
 DTYPE_CODES = {
@@ -95,6 +96,8 @@ SIGNATURES = {
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "exaspim_unet_forward_prepared_row": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "exaspim_unet_forward_prepared_clipped": (
+        _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, _vp, _sz, _vp]),
     "exaspim_unet_forward_absmax": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_unet_set_options": (_i32, [_vp, ctypes.c_uint32]),

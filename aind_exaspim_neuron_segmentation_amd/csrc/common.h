@@ -312,6 +312,12 @@ bool conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, bool fu
 // the tests' layer probe looks at what each one leaves behind).
 constexpr int kRowStageMain = 1, kRowStageThin = 2, kRowStagePool = 4;
 constexpr int kRowStagesAll = kRowStageMain | kRowStageThin | kRowStagePool;
+// kRowStageBorders: what Thin and Pool do, in one launch after them -- the thin-along-x tiles of both faces
+// as two jobs of one grid, each tile writing the pooled column it holds (conv3x3x3_t14 with ZORD and POOL).
+// The convolution has launch_conv3x3x3_thin's bits, the pooled columns launch_maxpool2_xcols's. The engine
+// runs Main | Borders (EXASPIM_OPT_ROW_SEPARATE_BORDERS: Main | Thin | Pool).
+constexpr int kRowStageBorders = 8;
+constexpr int kRowStagesFused = kRowStageMain | kRowStageBorders;
 int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats
@@ -329,8 +335,12 @@ int launch_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, 
 int launch_maxpool2_xcols(int dtype, const void* src, void* dst, int n, int d, int h, int w,
                           int c, int ox0, int ox1, hipStream_t stream);
 // d,h,w = INPUT size; output voxels within "margin" of a face are not computed
+// margin_hi (optional, int[3]): output voxels within margin_hi[axis] >= margin of an axis' HIGH face are not
+// needed either. The row-strip kernel skips them (along z down to a whole number of its runs); every other
+// variant computes the symmetric superset. The voxels that are computed have the same bits either way.
 int launch_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, int w,
-                     int c, int margin, hipStream_t stream, bool plain_kernel = false, bool per_thread = false);
+                     int c, int margin, hipStream_t stream, bool plain_kernel = false, bool per_thread = false,
+                     const int* margin_hi = nullptr);
 // *out = max(*out, largest |value| in the tensor) as float bits (out zeroed by the caller)
 int launch_absmax(int dtype, const void* src, size_t bytes, float* out, hipStream_t stream);
 int launch_head(int dtype, const void* src, const float* w, const float* bias,

@@ -489,6 +489,36 @@ int launch_conv3x3x3_thin(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     return EXASPIM_E_INVALID;
 }
 
+// Row mode, both border faces in one launch (kRowStageBorders): 2-voxel-thick tiles along x like
+// launch_thin_typed's, tiles_x = the two jobs of conv3x3x3_t14's ZORD + POOL instantiation
+template <typename Tag, int TZ, int MT>
+static int launch_row_borders_cfg(const ConvArgs& a, hipStream_t stream) {
+    const int tz = cdiv(a.d, TZ), ty = cdiv(a.h, 16);
+    const long long blocks = (long long)tz * ty * 2 * (a.n - 1);
+    if (blocks <= 0 || blocks > 0x7fffffffLL) {
+        set_error("conv: grid of %lld blocks out of range", blocks);
+        return EXASPIM_E_INVALID;
+    }
+    last_conv_launch() = {__PRETTY_FUNCTION__, 1};
+    conv3x3x3_t14<Tag, TZ, 16, 2, 4, 1, MT, 1, 4, 3, true, true>
+        <<<dim3((unsigned)blocks, a.cout / 32, 1), 256, 0, stream>>>(a, tz, ty, 2);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+// (a: whole patches, row arguments checked)
+template <typename Tag>
+static int launch_row_borders(const ConvArgs& a_in, hipStream_t stream) {
+    ConvArgs a = a_in;
+    a.partial = nullptr;   // no split-K
+    a.ksplit = 1;
+    a.row_stride = 0;
+    // the tile depth launch_thin_typed picks for tiles thin along x
+    auto planes = [&](int tz) { return (a.d + tz - 1) / tz * tz; };
+    if (planes(8) * 0.78f <= planes(4) * 1.00f) return launch_row_borders_cfg<Tag, 8, 2>(a, stream);
+    return launch_row_borders_cfg<Tag, 4, 1>(a, stream);
+}
+
 int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream) {
     ConvArgs b = a;
     if (int rc = check_conv_args(dtype, a, kCheckEmpty)) return rc;   // (the main stage checks the rest)
@@ -516,6 +546,14 @@ int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t s
     }
     if (r == EXASPIM_OK && (stages & kRowStagePool))
         r = launch_maxpool2_xcols(dtype, a.dst, a.pool_dst, a.n, a.d, a.h, a.w, a.cout, 0, a.w / 2 - 1, stream);
+    if (r == EXASPIM_OK && (stages & kRowStageBorders)) {
+        r = check_conv_args(dtype, a, kCheckPadded);
+        ConvArgs c = a;
+        for (int i = 0; i < 3; ++i) { c.org[i] = b.org[i]; c.ext[i] = b.ext[i]; }   // (resolved: whole patches)
+        c.org[2] = 0;
+        if (r == EXASPIM_OK)    // (check_row_args: a 16-bit type)
+            r = dtype == EXASPIM_DT_F16 ? launch_row_borders<F16Tag>(c, stream) : launch_row_borders<BF16Tag>(c, stream);
+    }
     return r;
 }
 

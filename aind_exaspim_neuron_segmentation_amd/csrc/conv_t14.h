@@ -26,6 +26,10 @@ namespace exaspim {
 // workgroup barrier any thread can take the maximum over a 2 x 2 x 2 block of the tile (planes z
 // and z + 1 belong to different waves). The skip tensor is not read again and the separate
 // max-pool launch disappears. Same bits as maxpool2_kernel: the maximum of stored values.
+// ZORD and POOL together are the border launch of inc.3's row mode (launch_conv3x3x3_row, kRowStageBorders;
+// TX = 2): tiles_x counts two jobs instead of tiles along x -- job 0 is x in [0, 2) of patches 1 .. n-1, job 1
+// x in [w - 2, w) of patches 0 .. n-2, each in the patch's own frame -- and org / ext of the x axis are not
+// read. The 2-wide tile holds exactly one pooled column, 0 respectively w/2 - 1, which the epilogue writes.
 template <typename Tag, int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD,
           bool ZORD = false, bool POOL = false>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_t14(
@@ -84,9 +88,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_t14(
     const int tx = bid % tiles_x; bid /= tiles_x;
     const int ty = bid % tiles_y; bid /= tiles_y;
     const int tz = bid % tiles_z; bid /= tiles_z;
-    const int nb = bid;
-    const int z0 = a.org[0] + tz * TZ, y0 = a.org[1] + ty * TY, x0 = a.org[2] + tx * TX;
-    const int zend = a.org[0] + a.ext[0], yend = a.org[1] + a.ext[1], xend = a.org[2] + a.ext[2];
+    constexpr bool BORDERS = ZORD && POOL;
+    const int nb = BORDERS && tx == 0 ? bid + 1 : bid;
+    const int z0 = a.org[0] + tz * TZ, y0 = a.org[1] + ty * TY;
+    const int x0 = BORDERS ? (tx == 0 ? 0 : a.w - TX) : a.org[2] + tx * TX;
+    const int zend = a.org[0] + a.ext[0], yend = a.org[1] + a.ext[1];
+    const int xend = BORDERS ? x0 + TX : a.org[2] + a.ext[2];
 
     const int ntiles = a.cout >> 5;
     const int ntile0 = (blockIdx.y * WAVES_N + wn) * NT;

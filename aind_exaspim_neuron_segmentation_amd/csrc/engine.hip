@@ -86,10 +86,13 @@ static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
 // absmax (optional): float[1 + kNumMfmaConvs + 4], the largest |activation| inc.0, every MFMA
 // convolution and every ConvTranspose3d stored (range probe: nothing is fused away, nothing trimmed)
 // row_stride > 0: the caller says the n patches are one row along x, row_stride voxels apart
+// keep_hi (optional, int32[3]): of the trimmed outputs the caller keeps local [trim, keep_hi[axis]) only -- a
+// patch that ends beyond the volume, whose far part the stitch drops. Checked by the entry point; plans
+// that do not trim ignore it.
 static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, int h, int w,
                    int apply_sigmoid, int trim, void* workspace, size_t workspace_bytes,
                    hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr,
-                   int row_stride = 0) {
+                   int row_stride = 0, const int32_t* keep_hi = nullptr) {
     const UNetPlan& p = e->plan;
     const Workspace ws = make_workspace(p, n, d, h, w);
     if (workspace_bytes < ws.bytes) {
@@ -115,6 +118,10 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     // With the head fused, voxels within "trim" of a patch face are never read again:
     // up4.3 skips them, and up4.0 everything its 3x3x3 consumer does not reach.
     const bool trimmed = fuse_head && trim > 0 && 2 * trim < d && 2 * trim < h && 2 * trim < w;
+    // ... and voxels from khi on (clipped forward: the patch reaches beyond the volume there) neither
+    int khi[3] = {d - trim, h - trim, w - trim};
+    if (trimmed && keep_hi)
+        for (int i = 0; i < 3; ++i) khi[i] = keep_hi[i];
     // conv 2l (inc.3, down1.3, down2.3, down3.3) can write its own max-pool, the input of level l + 1
     // (EXASPIM_OPT_SEPARATE_POOL, set per handle: run the stand-alone max-pool launches instead -- the
     // tests hold the two to each other bit for bit)
@@ -125,8 +132,8 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         fuse_pool[l] = !separate_pool && !(separate_deep && l > 0) && conv_can_fuse_pool(p.dtype, p.conv[2 * l].cout, d >> l, h >> l, w >> l);
     // Row mode of inc.3 (ConvArgs::row_stride): a column two neighbours share is computed once, the
     // two outermost x of every patch face that borders a neighbour and their pooled column are
-    // recomputed in the patch's own frame by the thin-tile and column max-pool launches that follow
-    // (launch_conv3x3x3_row). Same
+    // recomputed in the patch's own frame by the border launch that follows (launch_conv3x3x3_row;
+    // EXASPIM_OPT_ROW_SEPARATE_BORDERS: by two thin-tile launches and a column max-pool). Same
     // bits: a voxel's products are summed in the same order on every tile shape.
     // (EXASPIM_OPT_PER_PATCH_ENCODER: every patch on its own, as without a row.)
     const bool row = !absmax && !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) &&
@@ -139,12 +146,13 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         a.partial = reinterpret_cast<float*>(base + ws.xpad);
         a.partial_patch_bytes = (size_t)(d + 2) * (h + 2) * (w + 2) * sizeof(float);
         if (idx <= 6 && idx % 2 == 0 && fuse_pool[idx / 2]) a.pool_dst = A(idx / 2 + 1);
-        // up4.3 produces [trim, size - trim), up4.0 one voxel more on every face
-        const int margin = !trimmed ? 0 : idx == kNumMfmaConvs - 1 ? trim : idx == kNumMfmaConvs - 2 ? trim - 1 : 0;
+        // up4.3 produces [trim, khi) (khi = size - trim unless clipped), up4.0 one voxel more on every face
+        const bool last = idx == kNumMfmaConvs - 1, last_but_one = idx == kNumMfmaConvs - 2;
+        const int margin = !trimmed ? 0 : last ? trim : last_but_one ? trim - 1 : 0;
         const int full[3] = {d >> l, h >> l, w >> l};
         for (int i = 0; i < 3; ++i) {
             a.org[i] = margin;
-            a.ext[i] = full[i] - 2 * margin;
+            a.ext[i] = trimmed && (last || last_but_one) ? khi[i] + (last ? 0 : 1) - margin : full[i];
         }
         // When the region is a few voxels more than whole z-column tiles along y or x (82 =
         // 10 x 8 + 2 = 5 x 16 + 2 for the default patch), the z-column kernel covers the whole
@@ -179,9 +187,9 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
             slot = t->next;
             EXA_CHECK_HIP(hipEventRecord(t->start[slot], stream));
         }
-        // (row mode: the row launch, then the thin-tile and column max-pool launches that finish it)
+        // (row mode: the row launch, then the border launch that finishes it)
         int r = x3 && has_head      ? launch_conv3x3x3_x3_head(a, stream)
-                : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, kRowStagesAll, stream)
+                : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, (e->options & EXASPIM_OPT_ROW_SEPARATE_BORDERS) ? kRowStagesAll : kRowStagesFused, stream)
                                    : launch_conv3x3x3(dt, a, stream);
         if (timed && r == EXASPIM_OK) {
             EXA_CHECK_HIP(hipEventRecord(t->stop[slot], stream));
@@ -239,10 +247,12 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                                   absmax + 1 + kNumMfmaConvs + (3 - l), stream));
         } else {
             // up4.0 reads the upsampled tensor one voxel beyond its own trimmed output
+            const bool ups_trimmed = trimmed && l == 0 && trim > 2;
+            const int ups_hi[3] = {std::max(d - khi[0] - 2, 0), std::max(h - khi[1] - 2, 0), std::max(w - khi[2] - 2, 0)};
             RUN(launch_upsample2(dt, prev, A(l), n, d >> (l + 1), h >> (l + 1), w >> (l + 1), L0.cb,
-                                 trimmed && l == 0 && trim > 2 ? trim - 2 : 0, stream,
+                                 ups_trimmed ? trim - 2 : 0, stream,
                                  (e->options & EXASPIM_OPT_PLAIN_UPSAMPLE) != 0,
-                                 (e->options & EXASPIM_OPT_UPSAMPLE_PER_THREAD) != 0));
+                                 (e->options & EXASPIM_OPT_UPSAMPLE_PER_THREAD) != 0, ups_trimmed ? ups_hi : nullptr));
         }
         RUN(conv(i0, skip(l), A(l), B(l), l));
         RUN(conv(i0 + 1, B(l), nullptr, A(l), l));
@@ -435,6 +445,27 @@ extern "C" int exaspim_unet_forward_prepared_row(exaspim_unet* h, const void* x_
                    workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride);
 }
 
+extern "C" int exaspim_unet_forward_prepared_clipped(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                                     int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                                     int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                                     const int32_t keep_hi[3], void* workspace_dev,
+                                                     size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(h && x_prepared_dev && out_dev && workspace_dev && keep_hi, "forward: NULL pointer");
+    EXA_CHECK_ARG(n > 0, "forward: empty batch");
+    EXA_CHECK_ARG(trim >= 0, "forward: negative trim %d", trim);
+    EXA_CHECK_ARG(row_stride >= 0, "forward: negative row stride %d", row_stride);
+    EXA_CHECK_ARG(level_dims_ok(d, hgt, w),
+                  "forward: patch %dx%dx%d: every dimension must be a positive multiple of 16",
+                  d, hgt, w);
+    const int size[3] = {d, hgt, w};
+    for (int i = 0; i < 3; ++i)
+        EXA_CHECK_ARG(keep_hi[i] > trim && keep_hi[i] <= size[i] - trim,
+                      "forward: keep_hi[%d] = %d outside (%d, %d] (trim %d of %d voxels)", i, keep_hi[i], trim,
+                      size[i] - trim, trim, size[i]);
+    return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
+                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi);
+}
+
 extern "C" int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out_dev,
                                             int32_t n, int32_t d, int32_t hgt, int32_t w,
                                             int32_t apply_sigmoid, int32_t trim,
@@ -467,7 +498,7 @@ extern "C" int exaspim_unet_set_options(exaspim_unet* h, uint32_t options) {
     EXA_CHECK_ARG(h != nullptr, "set_options: NULL handle");
     EXA_CHECK_ARG((options & ~(uint32_t)(EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS | EXASPIM_OPT_PLAIN_UPSAMPLE | EXASPIM_OPT_FIRST_PER_GROUP |
                                           EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER |
-                                          EXASPIM_OPT_SEPARATE_HEAD)) == 0,
+                                          EXASPIM_OPT_SEPARATE_HEAD | EXASPIM_OPT_ROW_SEPARATE_BORDERS)) == 0,
                   "set_options: unknown option bits 0x%x", options);
     h->options = options;
     return EXASPIM_OK;

@@ -1180,7 +1180,9 @@ template <typename T, int RUN>
 __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __restrict__ src,
                                                        uint4* __restrict__ dst, int d, int h,
                                                        int w, float sz, float sy, float sx,
-                                                       int margin) {
+                                                       int margin, int hz, int hy, int hx) {
+    // (hz, hy, hx: the margin at the high face of each axis, >= margin -- a caller that keeps less of the
+    // patch's far end, engine.hip's keep_hi)
     constexpr int cg = 2;
     constexpr int NP = T::kG / 2;
     constexpr int A = kUpsAhead;
@@ -1188,7 +1190,7 @@ __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __res
     typedef float f2 __attribute__((ext_vector_type(2)));
     __shared__ uint4 slots[4][kUpsSlotPieces];
     const int od = d * 2, oh = h * 2, ow = w * 2;
-    const int nz = od - 2 * margin, ny = oh - 2 * margin, nx = ow - 2 * margin;
+    const int nz = od - margin - hz, ny = oh - margin - hy, nx = ow - margin - hx;
     const int nzp = (nz + 1) >> 1, nyp = (ny + 1) >> 1;
     const int nruns = nzp / RUN;                 // (the launcher checks nzp % RUN == 0)
     const int nb = blockIdx.x / nruns, run = blockIdx.x - nb * nruns;
@@ -1257,7 +1259,7 @@ __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __res
     const int g = it & 1;
     const int yp = (int)(it >> 1) / nx, x = margin + (int)(it >> 1) - yp * nx;
     const int ya = margin + 2 * yp;
-    const bool has_yb = ya + 1 < oh - margin;
+    const bool has_yb = ya + 1 < oh - hy;
     const LerpPair py = lerp_pair(ya, has_yb, h, sy);
     int x0, x1;
     float lx;
@@ -1296,7 +1298,7 @@ __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __res
         }
     };
     auto emit_pair = [&](int za, const LerpPair& pz, const f2 (*v0)[NP], const f2 (*v1)[NP], const f2 (*v2)[NP]) {
-        const bool has_zb = za + 1 < od - margin;
+        const bool has_zb = za + 1 < od - hz;
 #pragma unroll
         for (int zz = 0; zz < 2; ++zz) {
             const __amdgpu_buffer_rsrc_t ors =
@@ -1333,7 +1335,7 @@ __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __res
         }
         if (t >= 4) {
             const int za = margin + 2 * (pr0 + t - 4);
-            const LerpPair pz = lerp_pair(za, za + 1 < od - margin, d, sz);
+            const LerpPair pz = lerp_pair(za, za + 1 < od - hz, d, sz);
             emit_pair(za, pz, q0, q1, q2);
         }
         step_barrier();
@@ -1342,8 +1344,8 @@ __global__ __launch_bounds__(320) void upsample2_strip_kernel(const uint4* __res
 
 // rows of source a workgroup of upsample2_strip_kernel shares, over all its workgroups (host copy of the
 // kernel's float arithmetic)
-static int upsample_strip_rows(int h, int w, int margin, float sy) {
-    const int oh = 2 * h, ny = oh - 2 * margin, nx = 2 * w - 2 * margin;
+static int upsample_strip_rows(int h, int w, int margin, int hy, int hx, float sy) {
+    const int oh = 2 * h, ny = oh - margin - hy, nx = 2 * w - margin - hx;
     const int nyp = (ny + 1) / 2, nitems = nyp * nx * 2;
     auto i0 = [&](int o) { const int v = (int)floorf(sy * (float)o); return v < h - 1 ? v : h - 1; };
     int rows = 0;
@@ -1560,7 +1562,8 @@ int launch_maxpool2_xcols(int dtype, const void* src, void* dst, int n, int d, i
 }
 
 int launch_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, int w,
-                     int c, int margin, hipStream_t stream, bool plain_kernel, bool per_thread) {
+                     int c, int margin, hipStream_t stream, bool plain_kernel, bool per_thread,
+                     const int* margin_hi) {
     if (margin < 0 || margin >= d || margin >= h || margin >= w) margin = 0;
     const int nv = n * (c * dtype_size(dtype) / 32);   // chunk planes = independent volumes
     // items of one pair of output planes: (row pair, column, 16-byte group)
@@ -1580,13 +1583,28 @@ int launch_upsample2(int dtype, const void* src, void* dst, int n, int d, int h,
     // ... and with the workgroup's source rows shared through LDS when, on top of that, no pair of the launch
     // is one of the two that do not advance, the pairs are a whole number of runs and the rows fit a slot
     // ("per_thread", EXASPIM_OPT_UPSAMPLE_PER_THREAD: the per-thread pipeline instead, for the tests)
-    if (pipe && !per_thread && margin >= 4 && upsample_strip_rows(h, w, margin, scale(h)) * w * 2 <= kUpsSlotPieces) {
-        const int run = nzp % 14 == 0 ? 14 : nzp % 12 == 0 ? 12 : 0;
-        if (run) {
-            dim3 sgrid((unsigned)(nv * (nzp / run)), (unsigned)((items + 255) / 256));
+    if (pipe && !per_thread && margin >= 4) {
+        // margin_hi: a wider margin at the high faces. Only this kernel honours it -- first as given (along z
+        // widened to the next whole number of runs), then, like every other variant, the symmetric superset.
+        const int dims2[3] = {2 * d, 2 * h, 2 * w};
+        int hi[3] = {margin, margin, margin};
+        bool clipped = false;
+        for (int i = 0; margin_hi && i < 3; ++i)
+            if (margin_hi[i] > margin && margin_hi[i] < dims2[i] - margin) { hi[i] = margin_hi[i]; clipped = true; }
+        for (int attempt = clipped ? 0 : 1; attempt < 2; ++attempt) {
+            if (attempt == 1) hi[0] = hi[1] = hi[2] = margin;
+            int run = 0, hz = hi[0] + 1, zp = 0;
+            while (!run && hz > margin) {
+                --hz;
+                zp = (dims2[0] - margin - hz + 1) / 2;
+                run = zp % 14 == 0 ? 14 : zp % 12 == 0 ? 12 : 0;
+            }
+            if (!run || upsample_strip_rows(h, w, margin, hi[1], hi[2], scale(h)) * w * 2 > kUpsSlotPieces) continue;
+            const long long sitems = (long long)((dims2[1] - margin - hi[1] + 1) / 2) * (dims2[2] - margin - hi[2]) * 2;
+            dim3 sgrid((unsigned)(nv * (zp / run)), (unsigned)((sitems + 255) / 256));
 #define UPS_STRIP(RR) DISPATCH_T(dtype, (upsample2_strip_kernel<T, RR><<<sgrid, 320, 0, stream>>>(   \
                           static_cast<const uint4*>(src), static_cast<uint4*>(dst), d, h, w, scale(d), \
-                          scale(h), scale(w), margin)))
+                          scale(h), scale(w), margin, hz, hi[1], hi[2])))
             if (run == 14) { UPS_STRIP(14); } else { UPS_STRIP(12); }
 #undef UPS_STRIP
             last_layer_kernel() = run == 14 ? "upsample2_strip14" : "upsample2_strip12";

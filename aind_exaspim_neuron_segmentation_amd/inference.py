@@ -51,6 +51,7 @@ DEFAULT_STREAMS = 3
 # outside the calling code can flip them.
 PLAIN_GATHER = False    # True: gather float32 patches and let the engine pad them, instead of the prepared layout
 FULL_PATCHES = False    # True: compute the margin predict() discards as well (exaspim_unet_forward untrimmed)
+CLIP_TO_VOLUME = True   # False: also compute the trimmed outputs beyond the volume's high faces, which the stitch drops
 
 _VOX_CODES = {
     np.dtype(np.uint8): _native.VOX_U8,
@@ -667,6 +668,27 @@ def batch_row_stride(starts, patch_shape, overlap):
     return stride
 
 
+def batch_keep_hi(starts, patch_shape, trim, global_shape):
+    """
+    Per axis, the end of the trimmed outputs a batch of patch starts (global coordinates)
+    contributes to a volume of global_shape: the stitch places patch[trim:trim + e - s] with
+    s = start + trim, e = min(s + patch - 2 trim, dim) (inference.py:101-116), so a patch keeps
+    local [trim, min(patch - trim, dim - start)); the batch keeps the largest of its patches'.
+    None when that is everything (UNet3D.run_prepared's keep_hi). Host-side, no device sync.
+    """
+    trim = int(trim)
+    keep = []
+    for axis in range(3):
+        full = int(patch_shape[axis]) - trim
+        hi = min(full, max(int(global_shape[axis]) - int(s[axis]) for s in starts))
+        if hi <= trim:      # nothing of the batch is kept on this axis: nothing to gain from a clip
+            hi = full
+        keep.append(hi)
+    if trim <= 0 or all(k == int(p) - trim for k, p in zip(keep, patch_shape)):
+        return None
+    return tuple(keep)
+
+
 def _start_ranges(dims, patch_shape, overlap):
     """range(0, d - patch + stride, stride) per axis (inference.py:361-364)."""
     return [
@@ -996,6 +1018,9 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
     for bi, i in enumerate(range(0, len(starts), batch_size)):
         batch = starts_dev[i:i + batch_size]
         row_stride = batch_row_stride(starts[i:i + batch_size], plan.patch_shape, plan.overlap)
+        keep_hi = None
+        if CLIP_TO_VOLUME and not FULL_PATCHES:
+            keep_hi = batch_keep_hi(starts[i:i + batch_size], plan.patch_shape, plan.trim, plan.shape)
         worker = workers[bi % n_streams]
         with torch.cuda.stream(worker):
             if prepared_layout is not None:
@@ -1004,7 +1029,7 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                                            mn=mn, mx=mx, layout=prepared_layout)
                 pred = model.run_prepared(
                     inputs, (int(batch.shape[0]),) + tuple(plan.patch_shape), apply_sigmoid=True,
-                    trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride)
+                    trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride, keep_hi=keep_hi)
             else:
                 inputs = _get_batch_inputs(volume, batch, plan.patch_shape, device, clip=clip,
                                            mn=mn, mx=mx)

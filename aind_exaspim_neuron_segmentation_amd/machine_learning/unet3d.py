@@ -430,7 +430,7 @@ class UNet3D(nn.Module):
             raise RuntimeError("exaspim_unet_input_layout failed")
         return int(code)
 
-    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0, row_stride=0):
+    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0, row_stride=0, keep_hi=None):
         """
         run() from a batch the gather kernel has already written in the first
         convolution's operand layout (inference._get_batch_inputs(..., layout=
@@ -447,6 +447,10 @@ class UNet3D(nn.Module):
             > 0 when the B patches are one row along x, each starting row_stride voxels
             after the previous one (inference.batch_row_stride): the engine then computes
             the columns neighbours share once in the first level. Same bits.
+        keep_hi : Tuple[int], optional
+            Per axis, the caller keeps the trimmed outputs [trim, keep_hi) only
+            (inference.batch_keep_hi: patches that reach beyond the volume). The rest is
+            left unwritten like the trimmed margin; kept voxels have the same bits.
         """
         if self.training:
             raise RuntimeError(
@@ -472,7 +476,16 @@ class UNet3D(nn.Module):
                 out = torch.empty(
                     (n, self.output_channels, d, h, w), dtype=torch.float32, device=device
                 )
-            if row_stride > 0:
+            if keep_hi is not None:
+                _native.check(
+                    _native.lib().exaspim_unet_forward_prepared_clipped(
+                        self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
+                        1 if apply_sigmoid else 0, int(trim), int(row_stride), _native.int3(keep_hi),
+                        ws.data_ptr(), ws.numel(), stream,
+                    ),
+                    "exaspim_unet_forward_prepared_clipped",
+                )
+            elif row_stride > 0:
                 _native.check(
                     _native.lib().exaspim_unet_forward_prepared_row(
                         self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,

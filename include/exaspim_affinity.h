@@ -40,7 +40,8 @@ extern "C" {
  *    later within 5: exaspim_unet_forward_prepared_row, EXASPIM_OPT_PER_PATCH_ENCODER;
  *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point);
  *    later within 5: exaspim_synth_volume_neurite_u16;
- *    later within 5: exaspim_components, exaspim_components_workspace_bytes (EXASPIM_AFF_*) */
+ *    later within 5: exaspim_components, exaspim_components_workspace_bytes (EXASPIM_AFF_*)
+ *    later within 5: exaspim_unet_forward_prepared_clipped, EXASPIM_OPT_ROW_SEPARATE_BORDERS */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -194,6 +195,18 @@ int exaspim_unet_forward_prepared_row(exaspim_unet* h, const void* x_prepared_de
                                       int32_t n, int32_t d, int32_t hgt, int32_t w,
                                       int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
                                       void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The same, for a batch whose patches reach beyond the volume's high faces: of the trimmed outputs
+ * the caller keeps local [trim, keep_hi[axis]) per axis (z, y, x) only, as the stitch does with
+ * e = min(s + out, dim) (inference.py:101-116). trim < keep_hi[axis] <= size - trim, anything else is
+ * EXASPIM_E_INVALID; keep_hi = size - trim is exaspim_unet_forward_prepared_row. The level-0 decoder skips
+ * the work only the dropped voxels would have needed: they are left untouched in out_dev like the
+ * trimmed margin, every kept voxel has the same bits. Plans that do not trim (trim = 0 or too large,
+ * EXASPIM_OPT_SEPARATE_HEAD, shapes whose head cannot be fused) ignore keep_hi. row_stride = 0: no row. */
+int exaspim_unet_forward_prepared_clipped(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                          int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                          int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                          const int32_t keep_hi[3], void* workspace_dev,
+                                          size_t workspace_bytes, void* stream);
 
 /* Range probe for the 16-bit storage modes. The reference loads ANY trained state_dict
  * (inference.py:400-424) and runs it in float32; IEEE-half storage holds |v| <= 65504 (stores
@@ -225,6 +238,9 @@ int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, float* out_
  * sums in a different order, and the 16-bit modes fuse on unrounded accumulators, so the values
  * differ within rounding. For the bit-identity tests and A/B timing. */
 #define EXASPIM_OPT_SEPARATE_HEAD 64u
+/* row mode of the first level: the patch faces that border a neighbour as two thin-tile launches and a
+ * column max-pool instead of one launch that does both (same bits). (Bit 128 is not assigned.) */
+#define EXASPIM_OPT_ROW_SEPARATE_BORDERS 256u
 int exaspim_unet_set_options(exaspim_unet* h, uint32_t options);
 
 /* Measurement hooks (bench.py's roofline leg). timing_begin arms HIP-event
