@@ -69,6 +69,26 @@ class Window(ctypes.Structure):
         return w
 
 
+class ComponentsStreamDesc(ctypes.Structure):
+    """exaspim_components_stream: the caller-owned state of a slab-by-slab labelling."""
+
+    _fields_ = [
+        ("dims", ctypes.c_int32 * 3),
+        ("channels", ctypes.c_int32),
+        ("threshold", ctypes.c_float),
+        ("capacity", ctypes.c_int32),
+        ("min_size", ctypes.c_int64),
+        ("next_z", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("id_parent_dev", ctypes.c_void_p),
+        ("id_count_dev", ctypes.c_void_p),
+        ("table_dev", ctypes.c_void_p),
+        ("state_dev", ctypes.c_void_p),
+        ("seam_ids_dev", ctypes.c_void_p),
+        ("seam_bits_dev", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 _I32x5 = ctypes.c_int32 * 5
@@ -118,6 +138,12 @@ SIGNATURES = {
     "exaspim_components_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_components": (_i32, [_vp, _i32, _i32, _I32x3, ctypes.c_float, ctypes.c_int64, _vp, _vp, _vp,
                                   _sz, _vp]),
+    "exaspim_components_stream_slab_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_components_stream_finish_workspace_bytes": (_sz, [_i32]),
+    "exaspim_components_stream_slab": (_i32, [ctypes.POINTER(ComponentsStreamDesc), _vp, _i32, _I32x3, _i32, _vp,
+                                              _vp, _sz, _vp]),
+    "exaspim_components_stream_finish": (_i32, [ctypes.POINTER(ComponentsStreamDesc), _vp, _sz, _vp]),
+    "exaspim_components_stream_apply": (_i32, [ctypes.POINTER(ComponentsStreamDesc), _vp, _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

@@ -17,6 +17,13 @@
 // Every retry loop is a lock-free union whose larger root strictly decreases per iteration; a stale
 // read of parent[] only yields an older ancestor of the same set, and the value atomicMin returns
 // decides, so no loop depends on when another workgroup's stores become visible.
+//
+// The streamed form (exaspim_components_stream_*) labels a volume that arrives in z slabs.
+// A slab runs passes (a) to (e) as they are; instead of (f)/(g)'s final numbering every slab-local root
+// that can still matter gets a provisional id (slab_ids: the same three-pass scan, offset by the
+// running id count on the device), seam_union joins ids across the plane between two slabs in a
+// second union-find over ids, and after the last slab table_* turn the id forest into
+// table[provisional id] -> final label, which apply_table writes over the slabs.
 #include "common.h"
 
 namespace exaspim {
@@ -55,7 +62,7 @@ __device__ __forceinline__ float widen<_Float16>(_Float16 v) { return (float)v; 
 template <typename T, int VEC>
 __global__ __launch_bounds__(kThreads) void edge_mask_affinity(const T* __restrict__ aff,
                                                               unsigned char* __restrict__ mask, Dims dm,
-                                                              float thr) {
+                                                              float thr, unsigned char* __restrict__ seam) {
     struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
     struct alignas(VEC) Bytes { unsigned char b[VEC]; };
     const size_t groups = (size_t)dm.n / VEC;
@@ -78,6 +85,12 @@ __global__ __launch_bounds__(kThreads) void edge_mask_affinity(const T* __restri
             out.b[k] = (unsigned char)m;
         }
         *reinterpret_cast<Bytes*>(mask + i) = out;
+        if (seam && !zin) {   // streamed slabs: the z edges that leave the slab, one byte per (y, x)
+            Bytes sb;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) sb.b[k] = widen<T>(az.v[k]) >= thr ? 1 : 0;
+            *reinterpret_cast<Bytes*>(seam + (i - ((unsigned)dm.n - (unsigned)dm.h * (unsigned)dm.w))) = sb;
+        }
     }
 }
 
@@ -85,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void edge_mask_affinity(const T* __restri
 template <typename T>
 __global__ __launch_bounds__(kThreads) void edge_mask_foreground(const T* __restrict__ p,
                                                                 unsigned char* __restrict__ mask, Dims dm,
-                                                                float thr) {
+                                                                float thr, unsigned char* __restrict__ seam) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const unsigned hw = (unsigned)dm.h * (unsigned)dm.w;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < (size_t)dm.n; g += stride) {
@@ -100,6 +113,8 @@ __global__ __launch_bounds__(kThreads) void edge_mask_foreground(const T* __rest
             if ((int)x < dm.w - 1 && widen<T>(p[i + 1]) >= thr) m |= kBitX;
         }
         mask[i] = (unsigned char)m;
+        // streamed slabs: the last plane's on bits, the half of a seam edge this slab knows
+        if (seam && (int)z == dm.d - 1) seam[i - ((unsigned)dm.n - hw)] = m ? 1 : 0;
     }
 }
 
@@ -249,12 +264,68 @@ __global__ __launch_bounds__(kThreads) void sizes(const int* __restrict__ parent
 }
 
 // ---- (f) renumbering -------------------------------------------------------------------------
-// scan_count and scan_assign run one workgroup per block of kScanBlock voxels: n <= 2^31 - 1 gives
-// at most 2^20 of them, which one launch holds.
-__device__ __forceinline__ bool kept_root(const int* parent, const unsigned char* mask, const int* aux,
-                                          size_t v, int min_size) {
-    return parent[v] == (int)v && (mask[v] & kBitOn) && aux[v] >= min_size;   // size = aux + 1 > min_size
-}
+// scan_count and scan_assign run one workgroup per block of kScanBlock items: n <= 2^31 - 1 gives
+// at most 2^20 of them, which one launch holds. PRED(v) says whether item v is numbered, SINK(v,
+// flag, rank) takes its 0-based rank among the numbered ones; the whole-volume call, the streamed
+// slabs and the streamed table share the three passes and differ in these two.
+constexpr int kSeamMark = (int)0x80000000;   // streamed slabs: aux bit "this root has a seam edge"
+
+// the whole volume: kept roots, aux[v] = new id (1 ...) of a kept root, 0 for everything else
+struct KeptRoot {
+    const int* parent;
+    const unsigned char* mask;
+    int* aux;
+    int min_size;
+    __device__ __forceinline__ bool operator()(size_t v) const {
+        return parent[v] == (int)v && (mask[v] & kBitOn) && aux[v] >= min_size;   // size = aux + 1 > min_size
+    }
+    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const { aux[v] = flag ? rank + 1 : 0; }
+};
+
+// a slab: roots that are large enough on their own or have an edge across a seam (the
+// singleton rule). aux[v] = provisional id = *ids_used + rank + 1, with its size and itself as parent
+// in the id table; an id beyond the capacity is not written anywhere and becomes 0 (slab_advance
+// raises the overflow flag).
+struct SlabRoot {
+    const int* parent;
+    const unsigned char* mask;
+    int* aux;
+    int min_size;
+    const int* ids_used;
+    int capacity;
+    int* id_parent;
+    long long* id_count;
+    __device__ __forceinline__ bool operator()(size_t v) const {
+        if (parent[v] != (int)v || !(mask[v] & kBitOn)) return false;
+        const int a = aux[v];
+        return a < 0 || a >= min_size;
+    }
+    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const {
+        int out = 0;
+        if (flag) {
+            const long long id = (long long)*ids_used + rank + 1;
+            if (id <= capacity) {
+                out = (int)id;
+                id_parent[id] = out;
+                id_count[id] = (long long)(aux[v] & ~kSeamMark) + 1;
+            }
+        }
+        aux[v] = out;
+    }
+};
+
+// the id table after the last slab: roots whose summed size passes the filter, ids 1 .. *ids_used
+struct TableRoot {
+    const int* id_parent;
+    const long long* id_count;
+    const int* ids_used;
+    long long min_size;
+    int* table;
+    __device__ __forceinline__ bool operator()(size_t v) const {
+        return v >= 1 && v <= (size_t)*ids_used && id_parent[v] == (int)v && id_count[v] > min_size;
+    }
+    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const { table[v] = flag ? rank + 1 : 0; }
+};
 
 // exclusive prefix of "flag" over the block's threads, and the block's total
 __device__ __forceinline__ int block_exclusive(bool flag, int* wave_sums, int* total) {
@@ -274,16 +345,14 @@ __device__ __forceinline__ int block_exclusive(bool flag, int* wave_sums, int* t
     return before + below;
 }
 
-__global__ __launch_bounds__(kThreads) void scan_count(const int* __restrict__ parent,
-                                                      const unsigned char* __restrict__ mask,
-                                                      const int* __restrict__ aux, int* __restrict__ block_sums,
-                                                      int n, int min_size) {
+template <typename PRED>
+__global__ __launch_bounds__(kThreads) void scan_count(PRED pred, int* __restrict__ block_sums, size_t n) {
     __shared__ int wave_sums[kThreads / 64];
     const size_t b = blockIdx.x;
     int count = 0;
     for (int r = 0; r < kScanRounds; ++r) {
         const size_t v = b * kScanBlock + r * kThreads + threadIdx.x;
-        const bool flag = v < (size_t)n && kept_root(parent, mask, aux, v, min_size);
+        const bool flag = v < n && pred(v);
         int total;
         block_exclusive(flag, wave_sums, &total);
         count += total;
@@ -331,19 +400,17 @@ __global__ __launch_bounds__(kSumThreads) void scan_block_sums(int* block_sums, 
     if (threadIdx.x == 0) *n_segments = carry;
 }
 
-// aux[v] = new id (1 ...) of a kept root, 0 for everything else
-__global__ __launch_bounds__(kThreads) void scan_assign(const int* __restrict__ parent,
-                                                       const unsigned char* __restrict__ mask, int* aux,
-                                                       const int* __restrict__ block_sums, int n, int min_size) {
+template <typename PRED>
+__global__ __launch_bounds__(kThreads) void scan_assign(PRED pred, const int* __restrict__ block_sums, size_t n) {
     __shared__ int wave_sums[kThreads / 64];
     const size_t b = blockIdx.x;
     int offset = block_sums[b];
     for (int r = 0; r < kScanRounds; ++r) {
         const size_t v = b * kScanBlock + r * kThreads + threadIdx.x;
-        const bool flag = v < (size_t)n && kept_root(parent, mask, aux, v, min_size);
+        const bool flag = v < n && pred(v);
         int total;
         const int rank = block_exclusive(flag, wave_sums, &total);
-        if (v < (size_t)n) aux[v] = flag ? offset + rank + 1 : 0;
+        if (v < n) pred(v, flag, offset + rank);
         offset += total;
     }
 }
@@ -354,6 +421,117 @@ __global__ __launch_bounds__(kThreads) void relabel(int* labels, const int* __re
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < (size_t)n; g += stride)
         labels[g] = aux[labels[g]];
+}
+
+// ---- streamed slabs -----------------------------------------------------------------
+// state words on the device
+constexpr int kIdsUsed = 0, kOverflow = 1, kSegments = 2, kSlabIds = 3;
+
+// After sizes: aux[root] |= kSeamMark for every root with an edge across a seam of this slab. carry
+// (the previous slab's last plane: z-edge bits, in foreground mode on bits) is NULL for the volume's
+// first slab, seam (this slab's last plane, the same) for its last one. parent is flattened.
+__global__ __launch_bounds__(kThreads) void seam_mark(const int* __restrict__ parent,
+                                                     const unsigned char* __restrict__ mask, int* aux, Dims dm,
+                                                     const unsigned char* __restrict__ carry,
+                                                     const unsigned char* __restrict__ seam) {
+    const size_t hw = (size_t)dm.h * dm.w, last = (size_t)dm.n - hw;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += stride) {
+        if (carry && carry[p] && (mask[p] & kBitOn)) atomicOr(aux + parent[p], kSeamMark);
+        if (seam && seam[p]) atomicOr(aux + parent[last + p], kSeamMark);
+    }
+}
+
+// labels holds provisional ids. Joins, in the union-find over ids, the two ends of every on edge
+// between the previous slab's last plane (carry_ids, carry) and this slab's first one. An id of 0
+// only occurs after an overflow, which finish reports.
+__global__ __launch_bounds__(kThreads) void seam_union(const int* __restrict__ labels,
+                                                      const unsigned char* __restrict__ mask,
+                                                      const int* __restrict__ carry_ids,
+                                                      const unsigned char* __restrict__ carry, int* id_parent,
+                                                      size_t hw) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += stride) {
+        if (!carry[p] || !(mask[p] & kBitOn)) continue;
+        const int a = carry_ids[p], b = labels[p];
+        if (a > 0 && b > 0) unite<GlobalLoad>(id_parent, a, b);
+    }
+}
+
+// What the next slab needs of this one: its last plane of ids and of seam bits; and the running id
+// count moves on by this slab's ids, saturating at the capacity with the overflow flag raised.
+__global__ __launch_bounds__(kThreads) void slab_advance(const int* __restrict__ last_plane,
+                                                        const unsigned char* __restrict__ seam,
+                                                        int* __restrict__ carry_ids,
+                                                        unsigned char* __restrict__ carry, size_t hw, int* state,
+                                                        int capacity) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        long long used = (long long)state[kIdsUsed] + state[kSlabIds];
+        if (used > capacity) {
+            used = capacity;
+            state[kOverflow] = 1;
+        }
+        state[kIdsUsed] = (int)used;
+    }
+    if (!seam) return;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += stride) {
+        carry_ids[p] = last_plane[p];
+        carry[p] = seam[p];
+    }
+}
+
+// ---- the id table after the last slab ----
+// id_parent[id] = root(id) for ids 1 .. *ids_used (flatten over ids: no union runs any more)
+__global__ __launch_bounds__(kThreads) void table_flatten(int* id_parent, const int* __restrict__ state) {
+    const size_t n = (size_t)state[kIdsUsed] + 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x + 1; g < n; g += stride) {
+        const int p = id_parent[g];
+        if (p == (int)g) continue;
+        const int r = find_root<GlobalLoad>(id_parent, p);
+        if (r != p) id_parent[g] = r;
+    }
+}
+
+// id_count[root] += id_count[id] for every id that is not a root: 64-bit integer adds, any order
+__global__ __launch_bounds__(kThreads) void table_sum(const int* __restrict__ id_parent, long long* id_count,
+                                                     const int* __restrict__ state) {
+    const size_t n = (size_t)state[kIdsUsed] + 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x + 1; g < n; g += stride) {
+        const int r = id_parent[g];
+        if (r != (int)g)
+            atomicAdd(reinterpret_cast<unsigned long long*>(id_count + r), (unsigned long long)id_count[g]);
+    }
+}
+
+// table[id] = table[root(id)] for the ids that are not roots (scan_assign gave the roots theirs)
+__global__ __launch_bounds__(kThreads) void table_spread(const int* __restrict__ id_parent, int* table,
+                                                        const int* __restrict__ state) {
+    const size_t n = (size_t)state[kIdsUsed] + 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x + 1; g < n; g += stride) {
+        const int r = id_parent[g];
+        if (r != (int)g) table[g] = table[r];
+    }
+}
+
+// labels[v] = table[labels[v]] in place, four voxels per thread where the pointer allows; a value
+// that is no id (negative, beyond the capacity) becomes 0 instead of an index
+__global__ __launch_bounds__(kThreads) void apply_table(int* labels, const int* __restrict__ table, int capacity,
+                                                       size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    auto map = [&](int id) { return (unsigned)id <= (unsigned)capacity ? table[id] : 0; };
+    const size_t quads = ((uintptr_t)labels & 15) == 0 ? n / 4 : 0;
+    int4* l4 = reinterpret_cast<int4*>(labels);
+    for (size_t g = first; g < quads; g += stride) {
+        int4 v = l4[g];
+        v.x = map(v.x); v.y = map(v.y); v.z = map(v.z); v.w = map(v.w);
+        l4[g] = v;
+    }
+    for (size_t g = quads * 4 + first; g < n; g += stride) labels[g] = map(labels[g]);
 }
 
 // ---- workspace -------------------------------------------------------------------------------
@@ -384,17 +562,59 @@ Layout layout_of(const Dims& dm) {
     return l;
 }
 
+// a streamed slab: the whole-volume layout of its dims, then the plane of seam bits it hands on
+struct SlabLayout {
+    Layout base;
+    size_t seam_off, bytes;
+};
+
+SlabLayout slab_layout_of(const Dims& dm) {
+    SlabLayout l;
+    l.base = layout_of(dm);
+    l.seam_off = l.base.bytes;
+    l.bytes = l.seam_off + align_up((size_t)dm.h * dm.w, 256);
+    return l;
+}
+
+constexpr int kMaxCapacity = 2147483646;   // ids 1 .. capacity, capacity + 1 table entries
+
+long long table_scan_blocks(int capacity) { return ((long long)capacity + 1 + kScanBlock - 1) / kScanBlock; }
+
+// what every streamed entry point checks of the descriptor; NULL if it is sound, else what is wrong
+const char* stream_fault(const exaspim_components_stream* st) {
+    if (!st) return "NULL stream descriptor";
+    if (st->channels != 3 && st->channels != 1) return "channels must be 3 or 1";
+    if (st->dims[0] <= 0 || st->dims[1] <= 0 || st->dims[2] <= 0 ||
+        (long long)st->dims[1] * st->dims[2] > 2147483647ll)
+        return "dims must be positive with dims[1] * dims[2] of at most 2^31 - 1";
+    if (st->capacity < 1 || st->capacity > kMaxCapacity) return "capacity must be 1 .. 2^31 - 2";
+    if (!st->id_parent_dev || !st->id_count_dev || !st->table_dev || !st->state_dev || !st->seam_ids_dev ||
+        !st->seam_bits_dev)
+        return "NULL device buffer in the stream descriptor";
+    if (((uintptr_t)st->id_parent_dev & 3) || ((uintptr_t)st->id_count_dev & 7) || ((uintptr_t)st->table_dev & 3) ||
+        ((uintptr_t)st->state_dev & 3) || ((uintptr_t)st->seam_ids_dev & 3))
+        return "misaligned device buffer in the stream descriptor";
+    if (st->next_z < 0 || st->next_z > st->dims[0]) return "next_z outside the volume";
+    return nullptr;
+}
+
+// the size filter's floor (see exaspim_components)
+int64_t floored_min_size(int channels, int64_t min_size) {
+    const int64_t floor_size = channels == 3 ? 1 : 0;
+    return min_size < floor_size ? floor_size : min_size;
+}
+
 template <typename T>
 void launch_edge_mask(const void* src, int channels, unsigned char* mask, const Dims& dm, float thr,
-                      hipStream_t stream) {
+                      hipStream_t stream, unsigned char* seam = nullptr) {
     constexpr int VEC = 16 / (int)sizeof(T);
     const T* p = static_cast<const T*>(src);
     if (channels == 1) {
-        edge_mask_foreground<T><<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr);
+        edge_mask_foreground<T><<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr, seam);
     } else if (dm.w % VEC == 0 && ((uintptr_t)src & 15) == 0) {
-        edge_mask_affinity<T, VEC><<<capped_grid((size_t)dm.n / VEC, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr);
+        edge_mask_affinity<T, VEC><<<capped_grid((size_t)dm.n / VEC, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr, seam);
     } else {
-        edge_mask_affinity<T, 1><<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr);
+        edge_mask_affinity<T, 1><<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr, seam);
     }
 }
 
@@ -457,10 +677,147 @@ extern "C" int exaspim_components(const void* aff_dev, int32_t aff_dtype, int32_
     flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
     sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
     const unsigned scan_grid = (unsigned)l.n_scan_blocks;
-    scan_count<<<scan_grid, kThreads, 0, s>>>(parent, mask, aux, sums, dm.n, min_eff);
+    const KeptRoot kept{parent, mask, aux, min_eff};
+    scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
     scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, n_segments_dev);
-    scan_assign<<<scan_grid, kThreads, 0, s>>>(parent, mask, aux, sums, dm.n, min_eff);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
     relabel<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+// ---- the streamed form ---------------------------------------------------------------------------
+extern "C" size_t exaspim_components_stream_slab_workspace_bytes(const int32_t slab_dims[3]) {
+    Dims dm;
+    if (!valid_dims(slab_dims, &dm)) {
+        set_error("components_stream_slab_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return slab_layout_of(dm).bytes;
+}
+
+extern "C" size_t exaspim_components_stream_finish_workspace_bytes(int32_t capacity) {
+    if (capacity < 1 || capacity > kMaxCapacity) {
+        set_error("components_stream_finish_workspace_bytes: capacity must be 1 .. 2^31 - 2");
+        return 0;
+    }
+    return align_up((size_t)table_scan_blocks(capacity) * 4, 256);
+}
+
+extern "C" int exaspim_components_stream_slab(exaspim_components_stream* st, const void* aff_dev,
+                                              int32_t aff_dtype, const int32_t slab_dims[3], int32_t z0,
+                                              int32_t* labels_dev, void* workspace_dev, size_t workspace_bytes,
+                                              void* stream) {
+    const char* fault = stream_fault(st);
+    EXA_CHECK_ARG(!fault, "components_stream_slab: %s", fault);
+    EXA_CHECK_ARG(aff_dev && labels_dev && workspace_dev && slab_dims, "components_stream_slab: NULL argument");
+    EXA_CHECK_ARG(aff_dtype == EXASPIM_AFF_F32 || aff_dtype == EXASPIM_AFF_F16,
+                  "components_stream_slab: aff_dtype %d is neither EXASPIM_AFF_F32 nor EXASPIM_AFF_F16", aff_dtype);
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(slab_dims, &dm),
+                  "components_stream_slab: slab dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(dm.h == st->dims[1] && dm.w == st->dims[2],
+                  "components_stream_slab: the slab is %d x %d in (y, x), the volume %d x %d", dm.h, dm.w,
+                  st->dims[1], st->dims[2]);
+    EXA_CHECK_ARG(z0 == st->next_z, "components_stream_slab: slabs go in z order, the next one starts at %d, not %d",
+                  st->next_z, z0);
+    EXA_CHECK_ARG((long long)z0 + dm.d <= st->dims[0],
+                  "components_stream_slab: planes [%d, %lld) leave the volume of depth %d", z0, (long long)z0 + dm.d,
+                  st->dims[0]);
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && ((uintptr_t)labels_dev & 3) == 0 &&
+                      ((uintptr_t)aff_dev & (aff_dtype == EXASPIM_AFF_F32 ? 3 : 1)) == 0,
+                  "components_stream_slab: misaligned buffer");
+    const SlabLayout l = slab_layout_of(dm);
+    if (workspace_bytes < l.bytes) {
+        set_error("components_stream_slab: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+        return EXASPIM_E_WORKSPACE;
+    }
+    const int64_t ms = floored_min_size(st->channels, st->min_size);
+    const int min_eff = ms > 2147483647ll ? 2147483647 : (int)ms;
+    const bool first = z0 == 0, last = z0 + dm.d == st->dims[0];
+
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace_dev);
+    int* aux = reinterpret_cast<int*>(ws + l.base.aux_off);
+    unsigned char* mask = reinterpret_cast<unsigned char*>(ws + l.base.mask_off);
+    int* sums = reinterpret_cast<int*>(ws + l.base.sums_off);
+    unsigned char* seam = last ? nullptr : reinterpret_cast<unsigned char*>(ws + l.seam_off);
+    const unsigned char* carry = first ? nullptr : st->seam_bits_dev;
+    int* parent = labels_dev;
+    const size_t hw = (size_t)dm.h * dm.w;
+
+    if (first) {   // a new volume: no ids yet, id 0 is the background's
+        EXA_CHECK_HIP(hipMemsetAsync(st->state_dev, 0, 4 * sizeof(int32_t), s));
+        EXA_CHECK_HIP(hipMemsetAsync(st->id_parent_dev, 0, sizeof(int32_t), s));
+        EXA_CHECK_HIP(hipMemsetAsync(st->id_count_dev, 0, sizeof(int64_t), s));
+    }
+    EXA_CHECK_HIP(hipMemsetAsync(aux, 0, (size_t)dm.n * 4, s));
+    if (aff_dtype == EXASPIM_AFF_F32)
+        launch_edge_mask<float>(aff_dev, st->channels, mask, dm, st->threshold, s, seam);
+    else
+        launch_edge_mask<_Float16>(aff_dev, st->channels, mask, dm, st->threshold, s, seam);
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(mask, parent, dm, tiles_x, tiles_y, n_tiles);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads), plane_grid = capped_grid(hw, kThreads);
+    face_merge<<<grid, kThreads, 0, s>>>(mask, parent, dm);
+    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+    sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    if (carry || seam) seam_mark<<<plane_grid, kThreads, 0, s>>>(parent, mask, aux, dm, carry, seam);
+    const SlabRoot ids{parent, mask, aux, min_eff, st->state_dev + kIdsUsed, st->capacity, st->id_parent_dev,
+                       reinterpret_cast<long long*>(st->id_count_dev)};
+    const unsigned scan_grid = (unsigned)l.base.n_scan_blocks;
+    scan_count<<<scan_grid, kThreads, 0, s>>>(ids, sums, (size_t)dm.n);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.base.n_scan_blocks, st->state_dev + kSlabIds);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(ids, sums, (size_t)dm.n);
+    relabel<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    if (carry) seam_union<<<plane_grid, kThreads, 0, s>>>(parent, mask, st->seam_ids_dev, carry, st->id_parent_dev, hw);
+    slab_advance<<<seam ? plane_grid : 1, kThreads, 0, s>>>(parent + ((size_t)dm.n - hw), seam, st->seam_ids_dev,
+                                                           st->seam_bits_dev, hw, st->state_dev, st->capacity);
+    EXA_CHECK_HIP(hipGetLastError());
+    st->next_z = z0 + dm.d;
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_components_stream_finish(const exaspim_components_stream* st, void* workspace_dev,
+                                                size_t workspace_bytes, void* stream) {
+    const char* fault = stream_fault(st);
+    EXA_CHECK_ARG(!fault, "components_stream_finish: %s", fault);
+    EXA_CHECK_ARG(st->next_z == st->dims[0], "components_stream_finish: %d of %d planes have been pushed",
+                  st->next_z, st->dims[0]);
+    EXA_CHECK_ARG(workspace_dev && ((uintptr_t)workspace_dev & 15) == 0,
+                  "components_stream_finish: NULL or misaligned workspace");
+    const long long n_blocks = table_scan_blocks(st->capacity);
+    const size_t need = align_up((size_t)n_blocks * 4, 256);
+    if (workspace_bytes < need) {
+        set_error("components_stream_finish: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return EXASPIM_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* sums = static_cast<int*>(workspace_dev);
+    long long* counts = reinterpret_cast<long long*>(st->id_count_dev);
+    const size_t entries = (size_t)st->capacity + 1;
+    const unsigned grid = capped_grid(entries, kThreads);
+    table_flatten<<<grid, kThreads, 0, s>>>(st->id_parent_dev, st->state_dev);
+    table_sum<<<grid, kThreads, 0, s>>>(st->id_parent_dev, counts, st->state_dev);
+    const TableRoot roots{st->id_parent_dev, counts, st->state_dev + kIdsUsed,
+                          (long long)floored_min_size(st->channels, st->min_size), st->table_dev};
+    scan_count<<<(unsigned)n_blocks, kThreads, 0, s>>>(roots, sums, entries);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, n_blocks, st->state_dev + kSegments);
+    scan_assign<<<(unsigned)n_blocks, kThreads, 0, s>>>(roots, sums, entries);
+    table_spread<<<grid, kThreads, 0, s>>>(st->id_parent_dev, st->table_dev, st->state_dev);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_components_stream_apply(const exaspim_components_stream* st, int32_t* labels_dev, size_t n,
+                                               void* stream) {
+    const char* fault = stream_fault(st);
+    EXA_CHECK_ARG(!fault, "components_stream_apply: %s", fault);
+    EXA_CHECK_ARG(labels_dev && ((uintptr_t)labels_dev & 3) == 0, "components_stream_apply: NULL or misaligned labels");
+    if (n == 0) return EXASPIM_OK;
+    apply_table<<<capped_grid((n + 3) / 4, kThreads), kThreads, 0, (hipStream_t)stream>>>(labels_dev, st->table_dev,
+                                                                                        st->capacity, n);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
 }

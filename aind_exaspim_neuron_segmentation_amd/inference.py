@@ -24,6 +24,7 @@ options are trailing keyword arguments. What differs is where the work runs:
 There is no CPU fallback: a model on a CPU device raises.
 """
 
+import ctypes
 import itertools
 import threading
 import time
@@ -330,6 +331,303 @@ def affinities_to_components(affinities, threshold=0.5, min_segment_size=100, *,
     if return_device_tensor:
         return labels
     return labels.cpu().numpy()
+
+
+# Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes
+# of device memory each, so 256 MiB at most; a volume with fewer voxels gets as many ids as voxels.
+DEFAULT_ID_CAPACITY = 1 << 24
+
+
+class ComponentsStream:
+    """
+    affinities_to_components for a volume that arrives in z slabs:
+    every slab is labelled while it sits on the device, components are joined
+    across the seams between slabs, and the final labels equal, bit for bit,
+    those of the whole volume -- which may have more than 2^31 - 1 voxels and
+    never has to be anywhere in one piece.
+
+        cs = ComponentsStream((D, H, W), threshold, min_segment_size)
+        for slab in slabs_in_z_order:          # (3, d, H, W) device tensors
+            provisional = cs.push(slab)        # int32 (d, H, W), provisional ids
+            ...keep or download provisional...
+        table, k = cs.finish()                 # provisional id -> final label
+        cs.apply(provisional)                  # in place, any run of voxels
+
+    Parameters
+    ----------
+    shape : Tuple[int]
+        (D, H, W) of the whole volume; H * W and every slab must stay within
+        2^31 - 1 voxels, D * H * W need not.
+    threshold, min_segment_size
+        As in affinities_to_components.
+    foreground : bool, optional
+        Slabs are (d, H, W) foreground probabilities instead of (3, d, H, W)
+        affinities. Default is False.
+    device : torch.device, optional
+        Default is cuda:0.
+    id_capacity : int, optional
+        Most provisional ids the volume may use (1 .. 2^31 - 2). An id goes
+        to every slab-local component with more than min_segment_size voxels
+        and to every one with an edge across a seam, so shallow slabs of noisy
+        affinities need more. The id count stays on the device while slabs are
+        pushed; finish() raises if it went past the capacity. 16 bytes of
+        device memory per id. Default: DEFAULT_ID_CAPACITY (2^24), or the
+        number of voxels if that is less.
+    """
+
+    def __init__(self, shape, threshold=0.5, min_segment_size=100, *, foreground=False, device=None,
+                 id_capacity=None):
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"shape must be a non-empty (D, H, W), got {shape}")
+        if shape[1] * shape[2] > 2**31 - 1:
+            raise ValueError(f"a plane of {shape[1]} x {shape[2]} voxels exceeds 2^31 - 1")
+        device = torch.device("cuda:0" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError(f"ComponentsStream (MI355X) has no CPU path: it needs a HIP device, got {device}")
+        if id_capacity is None:
+            id_capacity = min(DEFAULT_ID_CAPACITY, shape[0] * shape[1] * shape[2])
+        id_capacity = int(id_capacity)
+        if not 1 <= id_capacity <= 2**31 - 2:
+            raise ValueError(f"id_capacity must be 1 .. 2^31 - 2, got {id_capacity}")
+        self.shape, self.device, self.foreground, self.id_capacity = shape, device, bool(foreground), id_capacity
+        self.finished = False
+        plane = shape[1] * shape[2]
+        with torch.cuda.device(device):
+            self.id_parent = torch.empty(id_capacity + 1, dtype=torch.int32, device=device)
+            self.id_count = torch.empty(id_capacity + 1, dtype=torch.int64, device=device)
+            self.table = torch.empty(id_capacity + 1, dtype=torch.int32, device=device)
+            self.state = torch.zeros(4, dtype=torch.int32, device=device)
+            self.seam_ids = torch.empty(plane, dtype=torch.int32, device=device)
+            self.seam_bits = torch.empty(plane, dtype=torch.uint8, device=device)
+        self.workspace = None
+        d = self.desc = _native.ComponentsStreamDesc()
+        d.dims[:] = shape
+        d.channels = 1 if foreground else 3
+        d.threshold = float(np.float32(threshold))
+        d.capacity = id_capacity
+        d.min_size = int(min_segment_size)
+        d.next_z = 0
+        d.id_parent_dev, d.id_count_dev = self.id_parent.data_ptr(), self.id_count.data_ptr()
+        d.table_dev, d.state_dev = self.table.data_ptr(), self.state.data_ptr()
+        d.seam_ids_dev, d.seam_bits_dev = self.seam_ids.data_ptr(), self.seam_bits.data_ptr()
+
+    @property
+    def next_z(self):
+        """Planes pushed so far."""
+        return int(self.desc.next_z)
+
+    def _scratch(self, need):
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.workspace
+
+    def push(self, slab, z0=None, out=None):
+        """
+        Labels the next slab. Nothing is synchronised.
+
+        Parameters
+        ----------
+        slab : torch.Tensor
+            float32 or float16 on the stream's device: (3, d, H, W), or
+            (d, H, W) in foreground mode, planes [next_z, next_z + d).
+        z0 : int, optional
+            The slab's first plane, checked against next_z. Default: next_z.
+        out : torch.Tensor, optional
+            Contiguous int32 (d, H, W) device tensor to write into.
+
+        Returns
+        -------
+        torch.Tensor
+            int32 (d, H, W) provisional ids (0: certainly background).
+        """
+        if self.finished:
+            raise RuntimeError("ComponentsStream: push() after finish()")
+        if not isinstance(slab, torch.Tensor):
+            raise TypeError(f"push needs a torch tensor, got {type(slab).__name__}")
+        if slab.dtype not in _AFF_CODES:
+            raise TypeError(f"slab must be float32 or float16, got {slab.dtype}")
+        if slab.device != self.device:
+            raise RuntimeError(f"slab is on {slab.device}, the stream on {self.device}")
+        want_dims = 3 if self.foreground else 4
+        if slab.dim() != want_dims or (not self.foreground and slab.shape[0] != 3):
+            raise ValueError("slab must be " + ("(d, H, W)" if self.foreground else "(3, d, H, W)") +
+                             f", got {tuple(slab.shape)}")
+        dims = tuple(int(v) for v in slab.shape[-3:])
+        if min(dims) < 1:
+            raise ValueError(f"empty slab {dims}")
+        slab = slab.contiguous()
+        lib = _native.lib()
+        need = lib.exaspim_components_stream_slab_workspace_bytes(_native.int3(dims))
+        if need == 0:
+            raise ValueError(_native.last_error())
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(dims, dtype=torch.int32, device=self.device)
+            elif (out.dtype != torch.int32 or tuple(out.shape) != dims or not out.is_contiguous()
+                  or out.device != self.device):
+                raise ValueError(f"out must be a contiguous int32 {dims} tensor on {self.device}")
+            ws = self._scratch(need)
+            _native.check(
+                lib.exaspim_components_stream_slab(
+                    ctypes.byref(self.desc), slab.data_ptr(), _AFF_CODES[slab.dtype], _native.int3(dims),
+                    self.next_z if z0 is None else int(z0), out.data_ptr(), ws.data_ptr(), need,
+                    _stream(self.device)),
+                "exaspim_components_stream_slab",
+            )
+        return out
+
+    def finish(self):
+        """
+        After the last slab: the table from provisional ids to final labels.
+        Reads the device's id count and overflow flag, once (this synchronises).
+
+        Returns
+        -------
+        table : torch.Tensor
+            int32 (id_capacity + 1,) on the device, table[0] = 0.
+        count : int
+            K, the number of kept components.
+
+        Raises
+        ------
+        RuntimeError
+            If the volume needed more provisional ids than id_capacity.
+        """
+        if self.finished:
+            raise RuntimeError("ComponentsStream: finish() called twice")
+        lib = _native.lib()
+        need = lib.exaspim_components_stream_finish_workspace_bytes(self.id_capacity)
+        with torch.cuda.device(self.device):
+            ws = self._scratch(need)
+            _native.check(
+                lib.exaspim_components_stream_finish(ctypes.byref(self.desc), ws.data_ptr(), need,
+                                                     _stream(self.device)),
+                "exaspim_components_stream_finish",
+            )
+            self.finished = True
+            used, overflow, count, _ = (int(v) for v in self.state.cpu())
+        if overflow:
+            raise RuntimeError(
+                f"ComponentsStream: the volume needs more than id_capacity={self.id_capacity} provisional ids; "
+                "the labels handed out are unusable. Label it again with a larger id_capacity (or deeper slabs)")
+        self.ids_used = used
+        return self.table, count
+
+    def apply(self, labels):
+        """Provisional ids -> final labels, in place, on a contiguous int32 device tensor of any shape."""
+        if not self.finished:
+            raise RuntimeError("ComponentsStream: apply() before finish()")
+        if (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.device != self.device
+                or not labels.is_contiguous()):
+            raise ValueError(f"apply needs a contiguous int32 tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            _native.check(
+                _native.lib().exaspim_components_stream_apply(ctypes.byref(self.desc), labels.data_ptr(),
+                                                              labels.numel(), _stream(self.device)),
+                "exaspim_components_stream_apply",
+            )
+        return labels
+
+
+def _labels_fit_on_device(device, shape):
+    """The provisional labels of the whole volume stay in HBM if they take under a quarter of what is free."""
+    free, _ = torch.cuda.mem_get_info(device)
+    return int(np.prod(shape, dtype=np.int64)) * 4 <= free // 4
+
+
+def _relabel_host_array(cs, result, planes):
+    """The second pass when the provisional labels did not stay on the device: "planes" at a time they
+    go up, through the table and back into the same host array."""
+    for z0 in range(0, result.shape[0], planes):
+        part = torch.from_numpy(result[z0:z0 + planes]).to(cs.device)
+        result[z0:z0 + planes] = cs.apply(part).cpu().numpy()
+
+
+def affinities_to_components_streaming(source, threshold=0.5, min_segment_size=100, *, slab_depth,
+                                       write_block=None, id_capacity=None, device=None,
+                                       keep_labels_resident=None):
+    """
+    affinities_to_components for affinities that sit in a host array, a
+    memmap or a zarr-like array too large for the device (or for 2^31 - 1
+    voxels): z slabs of "slab_depth" planes are uploaded and labelled one
+    after the other (ComponentsStream), and the result is the whole volume's.
+
+    Parameters
+    ----------
+    source : array-like
+        float32 or float16, (3, D, H, W) affinities or a (D, H, W) foreground
+        map; only source[..., z0:z1, :, :] is ever read.
+    threshold, min_segment_size
+        As in affinities_to_components.
+    slab_depth : int
+        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
+    write_block : Callable[[int, int, numpy.ndarray], None], optional
+        The two-pass contract of chunked segmentation: receives every slab
+        once, in z order, as write_block(z0, z1, block) with block int32
+        (z1 - z0, H, W) of PROVISIONAL ids; the function then returns the
+        table that maps them to final labels instead of the labels.
+    id_capacity : int, optional
+        See ComponentsStream.
+    device : torch.device, optional
+        Default is cuda:0.
+    keep_labels_resident : bool, optional
+        Keep the provisional labels in HBM and relabel them there. Default:
+        True if they take less than a quarter of the free device memory;
+        otherwise they are relabelled slab by slab in a second device pass
+        over the downloaded array.
+
+    Returns
+    -------
+    numpy.ndarray
+        int32 (D, H, W) final labels; or, with "write_block", the tuple
+        (table, K): table int32 with final = table[provisional], K kept
+        components.
+    """
+    if not hasattr(source, "shape") or not hasattr(source, "dtype"):
+        source = np.asarray(source)
+    if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise TypeError(f"affinities must be float32 or float16, got {source.dtype}")
+    shape = tuple(int(v) for v in source.shape)
+    if len(shape) == 4 and shape[0] == 3:
+        foreground = False
+    elif len(shape) == 3:
+        foreground = True
+    else:
+        raise ValueError(f"affinities must be (3, D, H, W) or a (D, H, W) foreground map, got shape {shape}")
+    vshape = shape[-3:]
+    slab_depth = int(slab_depth)
+    if slab_depth < 1:
+        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("affinities_to_components_streaming (MI355X) has no CPU path and no HIP device is present")
+    cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=foreground, device=device,
+                          id_capacity=id_capacity)
+    device = cs.device
+    with torch.cuda.device(device):
+        if keep_labels_resident is None:
+            keep_labels_resident = _labels_fit_on_device(device, vshape)
+        resident = result = None
+        if write_block is None:
+            if keep_labels_resident:
+                resident = torch.empty(vshape, dtype=torch.int32, device=device)
+            else:
+                result = np.empty(vshape, dtype=np.int32)
+        for z0 in range(0, vshape[0], slab_depth):
+            z1 = min(z0 + slab_depth, vshape[0])
+            block = np.asarray(source[..., z0:z1, :, :])
+            labels = cs.push(_carrier(block).to(device), z0, None if resident is None else resident[z0:z1])
+            if write_block is not None:
+                write_block(z0, z1, labels.cpu().numpy())
+            elif result is not None:
+                result[z0:z1] = labels.cpu().numpy()
+        table, count = cs.finish()
+        if write_block is not None:
+            return table[: cs.ids_used + 1].cpu().numpy(), count
+        if resident is not None:
+            return cs.apply(resident).cpu().numpy()
+        _relabel_host_array(cs, result, slab_depth)
+    return result
 
 
 def _predict_batch(img, model, starts, patch_shape, trim=8, *, clip=None, mn=0.0, mx=1.0):
@@ -1117,31 +1415,39 @@ class _SlabDrain:
         Round slabs to IEEE half on the device before they leave it.
     threads : int
         Host threads that consume downloaded slabs.
+    label_elems : int, optional
+        Not 0: slabs leave the device as int32 labels (emit's "label"), at most this many
+        elements each, and the staging memory is int32.
     """
 
     N_SLOTS = 3
 
-    def __init__(self, device, slot_elems, half_out, threads):
+    def __init__(self, device, slot_elems, half_out, threads, label_elems=0):
         self.device = device
         self.half_out = half_out
         self.main = torch.cuda.current_stream(device)
         self.copy_stream = _copy_stream(device)
-        self.host_dtype = torch.float16 if half_out else torch.float32
+        self.host_dtype = torch.int32 if label_elems else torch.float16 if half_out else torch.float32
         n = self.N_SLOTS
+        self.dev_labels = [torch.empty(label_elems, dtype=torch.int32, device=device) for _ in range(n)
+                           if label_elems]
         self.dev_out = [torch.empty(slot_elems, dtype=torch.float32, device=device) for _ in range(n)]
         self.dev_half = ([torch.empty(slot_elems, dtype=torch.float16, device=device) for _ in range(n)]
                          if half_out else None)
-        self.host = _checkout_pinned(device, n, slot_elems, self.host_dtype)
+        self.host = _checkout_pinned(device, n, label_elems or slot_elems, self.host_dtype)
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(threads)))
         self.pending = [[] for _ in range(n)]
         self.n_emitted = 0
 
-    def emit(self, shape, fill, consumers):
+    def emit(self, shape, fill, consumers, label=None):
         """
         Queues one slab: "fill(out)" writes the final values into the zeroed float32 device
         tensor "out" of "shape"; "consumers(view)" returns the host jobs (callables) that read
         the downloaded numpy "view" of the same shape -- each runs on a pool thread once the
         download has finished, and the staging slot is reused only after all of them returned.
+        "label(out, slot)", if given, turns the filled slab into the int32 tensor that travels
+        instead (in the flat int32 device buffer "slot", whose previous slab has left it), or
+        returns None when nothing is to leave the device; "view" then has that tensor's shape.
         """
         slot = self.n_emitted % self.N_SLOTS
         self.n_emitted += 1
@@ -1151,7 +1457,13 @@ class _SlabDrain:
         out = self.dev_out[slot][:count].view(shape)
         out.zero_()                      # planes no patch covers stay 0 (inference.py:120-125)
         fill(out)
-        if self.half_out:
+        if label is not None:
+            out = label(out, self.dev_labels[slot])
+            if out is None:
+                self.pending[slot] = []
+                return
+            shape, count = tuple(out.shape), out.numel()
+        elif self.half_out:
             out = export_half(out, self.dev_half[slot][:count]).view(shape)
         ready, done = torch.cuda.Event(), torch.cuda.Event()
         ready.record(self.main)
@@ -1334,6 +1646,24 @@ def predict_streaming(
     numpy.ndarray or None
         The prediction (see predict), or None when "write_block" is given.
     """
+    return _predict_streaming_impl(
+        source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles, patch_shape,
+        overlap, trim, verbose, shape, dtype, write_block, keep_input_resident, n_streams, copy_threads,
+        timings, out_dtype)
+
+
+def _predict_streaming_impl(source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
+                            patch_shape, overlap, trim, verbose, shape, dtype, write_block, keep_input_resident,
+                            n_streams, copy_threads, timings, out_dtype, components=None):
+    """
+    predict_streaming's two passes. "components": None, or the sink that replaces the download of
+    the affinities (predict_components_streaming): a function (vshape, device) -> (label, result)
+    called once the geometry is known; label(z0, z1, out, slot) labels the finished, divided
+    (C, z1 - z0, H, W) slab "out" where it lies and returns the int32 (1, z1 - z0, H, W) tensor
+    that leaves the device in its place (or None: nothing leaves), "result" is the int32
+    (D, H, W) host array the slabs are copied into (or None). Everything else is the same code
+    for both, so the affinities a labelling sees are predict_streaming's, bit for bit.
+    """
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError(
@@ -1370,8 +1700,12 @@ def predict_streaming(
     torch_dtype = _TORCH_VOXELS[vdtype]
     plane = H * W
 
-    result = res4 = None
-    if write_block is None:
+    result = res4 = label = None
+    if components is not None:
+        label, result = components(vshape, device)
+        if result is not None:
+            res4 = result.reshape((1,) + vshape)
+    elif write_block is None:
         result = np.empty(((n_channels,) if affinity_mode else ()) + vshape, dtype=out_dtype)
         res4 = result.reshape((n_channels,) + vshape)
 
@@ -1428,7 +1762,8 @@ def predict_streaming(
         # a sink is called from ONE thread, so the slabs arrive in z order, one at a time;
         # copies into the result array are split over several threads
         drain = _SlabDrain(device, n_channels * max_out * plane, half_out,
-                           1 if write_block is not None else max(1, int(copy_threads)))
+                           1 if write_block is not None else max(1, int(copy_threads)),
+                           label_elems=max_out * plane if label is not None else 0)
         acc_flat = [torch.empty(n_channels * slab_d * plane, dtype=torch.float32, device=device)
                     for _ in range(2)]
         in_slab = None
@@ -1447,7 +1782,7 @@ def predict_streaming(
             """Host jobs for output planes [z0, z1) once they sit in staging memory."""
             def make(view):
                 if write_block is not None:
-                    return [lambda: write_block(z0, z1, view if affinity_mode else view[0])]
+                    return [lambda: write_block(z0, z1, view if affinity_mode and label is None else view[0])]
                 # the copy into the pageable result is split over the threads
                 pieces = max(1, min(int(copy_threads), z1 - z0))
                 jobs = []
@@ -1461,7 +1796,8 @@ def predict_streaming(
         def emit(z0, z1, fill):
             """Planes [z0, z1) are final: "fill(out)" writes the divided sums into the
             zeroed (C, z1 - z0, H, W) device slab, which then travels to the host."""
-            drain.emit((n_channels, z1 - z0, H, W), fill, consumers(z0, z1))
+            drain.emit((n_channels, z1 - z0, H, W), fill, consumers(z0, z1),
+                       None if label is None else lambda out, slot: label(z0, z1, out, slot))
 
         try:
             final_lo = 0
@@ -1522,3 +1858,116 @@ def predict_streaming(
             if pbar is not None:
                 pbar.close()
     return result
+
+
+def predict_components_streaming(
+    source,
+    model,
+    threshold=0.5,
+    min_segment_size=100,
+    affinity_mode=True,
+    batch_size=16,
+    brightness_clip=1000,
+    normalization_percentiles=(1, 99.9),
+    patch_shape=(96, 96, 96),
+    overlap=(32, 32, 32),
+    trim=8,
+    verbose=True,
+    *,
+    shape=None,
+    dtype=None,
+    write_block=None,
+    keep_input_resident=None,
+    n_streams=DEFAULT_STREAMS,
+    copy_threads=4,
+    timings=None,
+    id_capacity=None,
+    keep_labels_resident=None,
+):
+    """
+    predict_streaming followed by affinities_to_components without the
+    affinities ever leaving the device: every finished, divided slab is
+    labelled right where predict_streaming would have started its download
+    (ComponentsStream), and only int32 labels travel -- 4 bytes
+    per voxel instead of 12. The result equals, bit for bit,
+    affinities_to_components(predict_streaming(...), threshold,
+    min_segment_size) on the whole volume, which neither the device nor this
+    function ever holds as affinities.
+
+    Parameters
+    ----------
+    source, model
+        As in predict_streaming.
+    threshold, min_segment_size
+        As in affinities_to_components. With affinity_mode=False the model's
+        output is a foreground map and is labelled as one.
+    affinity_mode, batch_size, brightness_clip, normalization_percentiles,
+    patch_shape, overlap, trim, verbose, shape, dtype, keep_input_resident,
+    n_streams, copy_threads, timings
+        As in predict_streaming; "timings" also gets "components_finish", the
+        wall seconds from the last slab to the final labels.
+    write_block : Callable[[int, int, numpy.ndarray], None], optional
+        Receives every slab once, in z order, as write_block(z0, z1, block)
+        with block int32 (z1 - z0, H, W) of PROVISIONAL ids, valid during the
+        call only; the function then returns the table that maps them to
+        final labels (the two-pass contract of chunked segmentation).
+    id_capacity : int, optional
+        See ComponentsStream.
+    keep_labels_resident : bool, optional
+        Without "write_block": keep the provisional labels in HBM (4 B/voxel),
+        relabel them there and download them once. Default: True if they take
+        less than a quarter of the free device memory. Otherwise every slab
+        is downloaded with its provisional ids while later layers compute and
+        relabelled in a second device pass over the downloaded array.
+
+    Returns
+    -------
+    numpy.ndarray
+        int32 (D, H, W) final labels; or, with "write_block", the tuple
+        (table, K): table int32 with final = table[provisional], K kept
+        components.
+    """
+    state = {}
+
+    def components(vshape, device):
+        cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=not affinity_mode, device=device,
+                              id_capacity=id_capacity)
+        keep = keep_labels_resident
+        if write_block is not None:
+            keep = False
+        elif keep is None:
+            keep = _labels_fit_on_device(device, vshape)
+        resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
+        result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
+        state.update(cs=cs, resident=resident, result=result)
+        plane = vshape[1] * vshape[2]
+
+        def label(z0, z1, out, slot):
+            aff = out if affinity_mode else out[0]
+            if resident is not None:
+                cs.push(aff, z0, resident[z0:z1])
+                return None
+            labels = slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2])
+            return cs.push(aff, z0, labels).view((1,) + tuple(labels.shape))
+
+        return label, result
+
+    _predict_streaming_impl(
+        source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles, patch_shape,
+        overlap, trim, verbose, shape, dtype, write_block, keep_input_resident, n_streams, copy_threads,
+        timings, np.float32, components=components)
+    cs, resident, result = state["cs"], state["resident"], state["result"]
+    t0 = time.perf_counter()
+    with torch.cuda.device(cs.device):
+        table, count = cs.finish()
+        if write_block is not None:
+            out = table[: cs.ids_used + 1].cpu().numpy(), count
+        elif resident is not None:
+            out = cs.apply(resident).cpu().numpy()
+        else:
+            planes = max(1, PINNED_SLOT_BYTES // (4 * cs.shape[1] * cs.shape[2]))
+            _relabel_host_array(cs, result, planes)
+            out = result
+    if timings is not None:
+        timings["components_finish"] = time.perf_counter() - t0
+    return out

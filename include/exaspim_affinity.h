@@ -41,7 +41,9 @@ extern "C" {
  *    later within 5: EXASPIM_DT_BF16X3 (a value every "dtype" argument accepts; no new entry point);
  *    later within 5: exaspim_synth_volume_neurite_u16;
  *    later within 5: exaspim_components, exaspim_components_workspace_bytes (EXASPIM_AFF_*)
- *    later within 5: exaspim_unet_forward_prepared_clipped, EXASPIM_OPT_ROW_SEPARATE_BORDERS */
+ *    later within 5: exaspim_unet_forward_prepared_clipped, EXASPIM_OPT_ROW_SEPARATE_BORDERS;
+ *    later within 5: exaspim_components_stream_slab / _finish / _apply and their workspace queries
+ *    (struct exaspim_components_stream): the components of a volume that arrives in z slabs */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -376,6 +378,86 @@ int exaspim_components(const void* aff_dev, int32_t aff_dtype, int32_t channels,
                        const int32_t dims[3], float threshold, int64_t min_size,
                        int32_t* labels_dev, int32_t* n_segments_dev, void* workspace_dev,
                        size_t workspace_bytes, void* stream);
+
+/* ---- the same components for a volume that arrives in z slabs ----------------
+ *      (DESIGN 6d). The slabs [z0, z1) of a dims[0] x dims[1] x dims[2] volume are pushed in z order,
+ *      each while it sits on the device; the final labels equal, bit for bit, what exaspim_components
+ *      gives on the whole volume, which may have more than 2^31 - 1 voxels (a slab may not).
+ *      Semantics (edge convention, threshold rule, background, foreground mode, size filter,
+ *      numbering, purity) are exaspim_components' own.
+ *
+ *      slab    labels the slab on its own and writes PROVISIONAL ids: 0, or an id in 1 .. capacity
+ *              that is dense, grows in raster order of each slab-local component's first voxel and
+ *              continues the previous slab's count. An id goes to every slab-local component that is
+ *              larger than min_size on its own or has an on edge across a seam (so a voxel whose
+ *              only on edge crosses a seam gets one although it is background within its slab);
+ *              ids joined by an on edge between the previous slab's last plane and this slab's
+ *              first one are united in a union-find over ids (atomicMin on the larger root);
+ *      finish  after the last slab: sums the sizes per set of ids in 64 bits, keeps the sets with
+ *              size > min_size and numbers them 1 .. K in the order of their smallest id, which is
+ *              the raster order of the components' first voxels: table[id] = final label;
+ *      apply   labels[v] = table[labels[v]] in place on any run of provisional labels.
+ *
+ *      All state is the caller's: this descriptor (host memory) and the device buffers it points to.
+ *      Fill every field, next_z = 0, and keep them until the last apply. */
+typedef struct exaspim_components_stream {
+    int32_t dims[3];         /* the whole volume (z, y, x); dims[1] * dims[2] <= 2^31 - 1           */
+    int32_t channels;        /* 3: affinities, 1: a foreground map                                  */
+    float threshold;         /* on iff float32(value) >= threshold                                  */
+    int32_t capacity;        /* most provisional ids the volume may use, 1 .. 2^31 - 2              */
+    int64_t min_size;        /* a component is kept iff size > min_size; the same for every call    */
+    int32_t next_z;          /* planes pushed so far: 0 to start, advanced by slab                  */
+    int32_t reserved;        /* 0                                                                   */
+    int32_t* id_parent_dev;  /* int32[capacity + 1]: the union-find over ids                        */
+    int64_t* id_count_dev;   /* int64[capacity + 1]: voxels per id; after finish, per root, of its set */
+    int32_t* table_dev;      /* int32[capacity + 1]: written by finish, table[0] = 0                */
+    int32_t* state_dev;      /* int32[4]: ids used so far, overflow flag, K (after finish), scratch */
+    int32_t* seam_ids_dev;   /* int32[dims[1] * dims[2]]: the last pushed plane's provisional ids   */
+    uint8_t* seam_bits_dev;  /* uint8[dims[1] * dims[2]]: its z-edge bits (channels = 1: on bits)   */
+} exaspim_components_stream;
+
+/* Scratch bytes of one slab call for a slab_dims[0] x slab_dims[1] x slab_dims[2] slab: what
+ * exaspim_components needs for a volume of that shape plus one byte per voxel of a plane. 0 (and a
+ * message) if a dim is not positive or the slab has more than 2^31 - 1 voxels. */
+size_t exaspim_components_stream_slab_workspace_bytes(const int32_t slab_dims[3]);
+
+/* Scratch bytes of the finish call: 4 bytes per 2048 table entries. 0 (and a message) for a capacity
+ * outside 1 .. 2^31 - 2. */
+size_t exaspim_components_stream_finish_workspace_bytes(int32_t capacity);
+
+/* Pushes planes [z0, z0 + slab_dims[0]) of the volume: aff_dev is the contiguous (channels, slab_dims)
+ * tensor of aff_dtype (EXASPIM_AFF_*), labels_dev (int32, slab_dims) receives the provisional ids and
+ * doubles as the slab's parent array while the passes run. z0 = 0 starts a new volume (the device
+ * state is reset on the stream). The z edges of the slab's last plane are ignored only when that
+ * plane is the volume's last. Needs z0 == st->next_z (slabs in z order, none twice), slab_dims[1:]
+ * equal to st->dims[1:], z0 + slab_dims[0] <= st->dims[0]; then advances st->next_z.
+ * More ids than st->capacity: the ids beyond it are written nowhere, their voxels get 0, and
+ * state_dev[1] becomes 1, which the caller reads once after finish; the labels are then unusable.
+ * Launches on "stream" only: nothing is allocated or synchronised, so the id count never visits the
+ * host. Alignment: workspace_dev 16 bytes, labels_dev 4, aff_dev its element (16 for the wide
+ * loads), the descriptor's int32 buffers 4 and id_count_dev 8. EXASPIM_E_WORKSPACE for fewer bytes
+ * than exaspim_components_stream_slab_workspace_bytes(slab_dims), EXASPIM_E_INVALID for a NULL or
+ * misaligned pointer, an unknown aff_dtype, a descriptor with channels other than 3 or 1, a dim that
+ * is not positive, a plane or a slab of more than 2^31 - 1 voxels, a capacity outside 1 .. 2^31 - 2,
+ * a slab out of order, of another (y, x) shape or beyond the volume: all before anything is launched
+ * and with st unchanged. */
+int exaspim_components_stream_slab(exaspim_components_stream* st, const void* aff_dev, int32_t aff_dtype,
+                                   const int32_t slab_dims[3], int32_t z0, int32_t* labels_dev,
+                                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Once, after the last slab (st->next_z == st->dims[0], else EXASPIM_E_INVALID): writes table_dev and
+ * state_dev[2] = K. Sizes are summed in 64 bits, so a component may have more than 2^31 voxels.
+ * workspace_dev: 16-byte aligned, exaspim_components_stream_finish_workspace_bytes(st->capacity)
+ * bytes (EXASPIM_E_WORKSPACE below that). Launches only; read state_dev[1] (overflow) and
+ * state_dev[2] after synchronising the stream. */
+int exaspim_components_stream_finish(const exaspim_components_stream* st, void* workspace_dev,
+                                     size_t workspace_bytes, void* stream);
+
+/* labels_dev[i] = table_dev[labels_dev[i]] for i < n, in place: provisional ids to final labels, on a
+ * slab, a part of one or several at once (n is not limited to 2^31). A value outside 0 .. capacity
+ * becomes 0. labels_dev 4-byte aligned (16 for the wide form). One launch on "stream". */
+int exaspim_components_stream_apply(const exaspim_components_stream* st, int32_t* labels_dev, size_t n,
+                                    void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 

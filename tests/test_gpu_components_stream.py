@@ -1,0 +1,493 @@
+"""
+The slab-by-slab components on the GPU (-m gpu): inference.ComponentsStream (exaspim_components_stream_*,
+DESIGN 6d) against the whole-volume CPU oracle (tests/components_ref.py), labels and K bit for bit --
+random affinities near percolation under tile-aligned, ragged and one-plane slabs, a serpentine that
+crosses every seam, the singleton rule, numbering, float16, foreground mode, degenerate shapes, purity,
+the capacity guard, refused arguments, 64-bit sizes -- and predict_components_streaming /
+affinities_to_components_streaming end to end against predict_streaming's own affinities.
+"""
+
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import components_ref
+from aind_exaspim_neuron_segmentation_amd import _native
+from aind_exaspim_neuron_segmentation_amd.utils import synthetic
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch.device("cuda:0")
+
+
+def bounds_of(cuts, depth):
+    return list(zip([0] + list(cuts), list(cuts) + [depth]))
+
+
+def every_plane(depth):
+    return list(range(1, depth))
+
+
+def stream(dev, aff, threshold, min_size, cuts, **kw):
+    """(labels, K, provisional, table) of a ComponentsStream fed the slabs that "cuts" make of aff."""
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    aff = np.asarray(aff)
+    vshape = aff.shape[-3:]
+    cs = inference.ComponentsStream(vshape, threshold, min_size, foreground=aff.ndim == 3, device=dev, **kw)
+    t = torch.from_numpy(np.array(aff, order="C")).to(dev)
+    parts = [cs.push(t[..., z0:z1, :, :]) for z0, z1 in bounds_of(cuts, vshape[0])]
+    assert cs.next_z == vshape[0]
+    table, k = cs.finish()
+    provisional = torch.cat(parts).cpu().numpy()
+    final = torch.cat([cs.apply(p) for p in parts]).cpu().numpy()
+    table = table[: cs.ids_used + 1].cpu().numpy()
+    assert provisional.max(initial=0) <= cs.ids_used
+    np.testing.assert_array_equal(table[provisional], final)
+    return final, k, provisional, table
+
+
+_ORACLE = {}
+
+
+def oracle(key, aff, threshold, min_size):
+    k = (key, float(threshold), int(min_size))
+    if k not in _ORACLE:
+        _ORACLE[k] = components_ref.components(aff, threshold, min_size)
+    return _ORACLE[k]
+
+
+def check(dev, aff, threshold, min_size, cuts, key=None, **kw):
+    want, k = oracle(key, aff, threshold, min_size) if key else components_ref.components(aff, threshold, min_size)
+    got, got_k, _, table = stream(dev, aff, threshold, min_size, cuts, **kw)
+    assert got.dtype == np.int32 and got.shape == want.shape
+    assert got_k == k == int(got.max(initial=0)) == int(table.max(initial=0))
+    np.testing.assert_array_equal(got, want)
+    return want, k
+
+
+# ---- 1. random affinities near bond percolation ----------------------------------------------------
+_RANDOM = {}
+
+
+def random_affinities(shape):
+    if shape not in _RANDOM:
+        a = np.random.default_rng(5).random((3,) + shape).astype(np.float32)
+        a.setflags(write=False)
+        _RANDOM[shape] = a
+    return _RANDOM[shape]
+
+
+def crossing(labels, z):
+    """Kept components with voxels on both sides of the seam between planes z - 1 and z."""
+    both = np.intersect1d(np.unique(labels[:z]), np.unique(labels[z:]))
+    return both[both > 0]
+
+
+def test_the_random_case_exercises_seams():
+    """
+    From the oracle alone, (23, 37, 71) at 0.75 / 100: 40 kept components, of which 14, 17, 22, 24 and
+    18 have voxels on both sides of z = 1, 5, 8, 16 and 22. "Rescued" at seam 8: the kept components
+    across it that lose voxels when [0, 8) and [8, 23) are labelled on their own with the same filter
+    -- pieces of at most 100 voxels that count only because they join the rest: all 22. (Under the
+    strictest reading, no voxel of the component survives on either side, there are 4.)
+    """
+    aff = random_affinities((23, 37, 71))
+    want, k = oracle("r23", aff, 0.75, 100)
+    assert k == 40
+    counts = [len(crossing(want, z)) for z in (1, 5, 8, 16, 22)]
+    assert counts == [14, 17, 22, 24, 18] and min(counts) >= 10
+    for z in every_plane(23):
+        assert len(crossing(want, z)) >= 10
+    alone = np.concatenate([components_ref.components(aff[:, :8], 0.75, 100)[0],
+                            components_ref.components(aff[:, 8:], 0.75, 100)[0]])
+    across = crossing(want, 8)
+    rescued = [c for c in across if not alone[want == c].all()]
+    lost = [c for c in across if not alone[want == c].any()]
+    print("rescued at seam 8:", len(rescued), "of", len(across), "; wholly dropped on both sides:", len(lost))
+    assert len(rescued) >= 10 and len(lost) >= 1
+
+
+CUTS = {"aligned": lambda d: [8, 16], "ragged": lambda d: [1, 2, 3, 9, 20, 22], "planes": every_plane}
+
+
+@pytest.mark.parametrize("cuts", sorted(CUTS))
+@pytest.mark.parametrize("threshold", [0.6, 0.75, 0.8])
+@pytest.mark.parametrize("shape", [(23, 37, 71), (24, 40, 72)])
+def test_random_affinities_near_percolation(dev, shape, threshold, cuts):
+    aff = random_affinities(shape)
+    for min_size in (0, 100):
+        _, k = check(dev, aff, threshold, min_size, CUTS[cuts](shape[0]), key=f"r{shape[0]}")
+        assert k >= 1
+
+
+# ---- 2. a serpentine ---------------------------------------------------------------------------------
+def serpentine_yz(shape):
+    """One path through every voxel whose rows run along x, whose planes of rows stand upright
+    (constant y) and follow one another along y: it climbs or descends through z in every plane, so
+    it crosses every z seam h times."""
+    d, h, w = shape
+    path = []
+    row = 0
+    for y in range(h):
+        for z in (range(d) if y % 2 == 0 else range(d - 1, -1, -1)):
+            for x in (range(w) if row % 2 == 0 else range(w - 1, -1, -1)):
+                path.append((z, y, x))
+            row += 1
+    path = np.array(path)
+    a, b = path[:-1], path[1:]
+    step = b - a
+    assert len(path) == d * h * w and (np.abs(step).sum(axis=1) == 1).all()
+    axis = np.abs(step).argmax(axis=1)
+    low = np.minimum(a, b)
+    aff = np.zeros((3,) + shape, np.float32)
+    aff[axis, low[:, 0], low[:, 1], low[:, 2]] = 1.0
+    return aff
+
+
+@pytest.mark.parametrize("cuts", [[8], [3, 8, 9, 13], every_plane(16)])
+def test_serpentine_crosses_every_seam(dev, cuts):
+    shape = (16, 12, 40)
+    aff = serpentine_yz(shape)
+    n = int(np.prod(shape))
+    for z in cuts:
+        assert np.count_nonzero(aff[0, z - 1]) == shape[1]      # one crossing per plane of rows
+    want, k = check(dev, aff, 0.5, n - 1, cuts)
+    assert k == 1 and (want == 1).all()
+    want, k = check(dev, aff, 0.5, n, cuts)
+    assert k == 0 and not want.any()
+
+
+# ---- 3. the singleton rule ----------------------------------------------------------------------------
+def test_columns_of_slab_local_singletons(dev):
+    shape = (7, 5, 9)
+    aff = np.zeros((3,) + shape, np.float32)
+    aff[0, 0:6, 1, 2] = 1.0     # a column through all 7 planes
+    aff[0, 2:5, 3, 8] = 1.0     # planes 2 .. 5
+    aff[0, 5:6, 4, 0] = 1.0     # planes 5, 6
+    aff[0, 6] = 1.0             # leaves the volume
+    for min_size, k in ((0, 3), (2, 2), (4, 1), (7, 0)):
+        want, got_k = check(dev, aff, 0.5, min_size, every_plane(7))
+        assert got_k == k
+    _, _, provisional, _ = stream(dev, aff, 0.5, 0, every_plane(7))
+    assert np.count_nonzero(provisional) == 7 + 4 + 2    # nothing but the columns took an id
+
+
+def test_two_voxels_joined_only_by_a_seam_edge(dev):
+    aff = np.zeros((3, 4, 3, 5), np.float32)
+    aff[0, 1, 2, 4] = 1.0
+    want, k = check(dev, aff, 0.5, 1, [2])
+    assert k == 1 and want[1, 2, 4] == want[2, 2, 4] == 1 and np.count_nonzero(want) == 2
+    want, k = check(dev, aff, 0.5, 2, [2])
+    assert k == 0
+    want, k = check(dev, aff, 0.5, 1, [1, 3])      # the edge inside a slab
+    assert k == 1
+
+
+def test_foreground_lone_voxels_at_a_seam(dev):
+    p = np.zeros((4, 3, 6), np.float32)
+    p[1, 1, 1] = p[2, 1, 1] = 0.9      # adjacent across the seam at z = 2
+    p[1, 2, 4] = 0.9                   # lone, next to an off voxel across the seam
+    p[2, 0, 5] = 0.9                   # lone on the other side
+    for min_size, k in ((0, 3), (1, 1), (2, 0)):
+        want, got_k = check(dev, p, 0.5, min_size, [2])
+        assert got_k == k
+    want, _ = check(dev, p, 0.5, 0, [2])
+    assert want[1, 1, 1] == want[2, 1, 1] == 1 and want[1, 2, 4] == 2 and want[2, 0, 5] == 3
+    check(dev, p, 0.5, 0, every_plane(4))
+
+
+# ---- 4. numbering ---------------------------------------------------------------------------------------
+def test_numbering_follows_the_first_voxel_of_the_whole_component(dev):
+    aff = np.zeros((3, 2, 2, 8), np.float32)
+    aff[2, 0, 0, 0] = 1.0      # B: (0,0,0)-(0,0,1), slab 0
+    aff[0, 0, 1, 6] = 1.0      # A: (0,1,6) - (1,1,6) across the seam ...
+    aff[2, 1, 1, 6] = 1.0      #    ... - (1,1,7)
+    aff[2, 1, 0, 0] = 1.0      # C: (1,0,0)-(1,0,1), slab 1: its local root precedes A's piece there
+    want, k = check(dev, aff, 0.5, 0, [1])
+    assert k == 3
+    assert want[0, 0, 0] == 1 and want[0, 1, 6] == want[1, 1, 6] == want[1, 1, 7] == 2 and want[1, 0, 0] == 3
+    _, _, provisional, table = stream(dev, aff, 0.5, 0, [1])
+    assert provisional[0, 0, 0] == 1 and provisional[0, 1, 6] == 2 and provisional[1, 0, 0] == 3
+    assert provisional[1, 1, 6] == 4 and list(table) == [0, 1, 2, 3, 2]
+
+
+# ---- 5. float16, foreground mode, degenerate shapes, purity ------------------------------------------------
+def test_float16_equals_the_rounded_float32(dev):
+    half = np.random.default_rng(13).random((3, 12, 20, 40)).astype(np.float16)
+    got16 = stream(dev, half, 0.7, 2, [5])
+    got32 = stream(dev, half.astype(np.float32), 0.7, 2, [5])
+    np.testing.assert_array_equal(got16[0], got32[0])
+    assert got16[1] == got32[1]
+    check(dev, half, 0.7, 2, [5])
+
+
+def test_foreground_mode(dev):
+    p = np.random.default_rng(17).random((12, 20, 40)).astype(np.float32)
+    for thr in (0.55, 0.75):
+        for min_size in (0, 1, 10):
+            check(dev, p, thr, min_size, [5])
+    check(dev, p.astype(np.float16), 0.6, 0, [5])
+
+
+@pytest.mark.parametrize("shape", [(9, 1, 1), (1, 33, 65), (5, 1, 9)])
+def test_degenerate_shapes_in_one_plane_slabs(dev, shape):
+    rng = np.random.default_rng(7)
+    cuts = every_plane(shape[0])
+    check(dev, rng.random((3,) + shape).astype(np.float32), 0.4, 0, cuts)
+    check(dev, np.ones((3,) + shape, np.float32), 0.5, 0, cuts)
+    want, k = check(dev, np.zeros((3,) + shape, np.float32), 0.5, 0, cuts)
+    assert k == 0 and not want.any()
+    check(dev, rng.random(shape).astype(np.float32), 0.4, 0, cuts)
+
+
+def test_purity(dev):
+    aff = random_affinities((23, 37, 71))
+    a = stream(dev, aff, 0.75, 100, [8, 16])
+    b = stream(dev, aff, 0.75, 100, [1, 2, 3, 9, 20, 22])
+    c = stream(dev, aff, 0.75, 100, [8, 16])
+    assert a[0].tobytes() == b[0].tobytes() == c[0].tobytes() and a[1] == b[1] == c[1]
+    assert a[2].tobytes() == c[2].tobytes() and a[3].tobytes() == c[3].tobytes()
+
+
+# ---- 6. capacity ---------------------------------------------------------------------------------------------
+def test_capacity_overflow_is_flagged_not_written(dev):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    shape = (24, 40, 72)
+    aff = random_affinities(shape)
+    t = torch.from_numpy(aff.copy()).to(dev)
+    capacity, guard = 4, 64
+    cs = inference.ComponentsStream(shape, 0.8, 0, device=dev, id_capacity=capacity)
+    # the id table and the label slab with guard words behind them
+    bufs = {"id_parent": (torch.int32, -1234567), "id_count": (torch.int64, -7654321), "table": (torch.int32, -2345678)}
+    for name, (dtype, fillv) in bufs.items():
+        buf = torch.full((capacity + 1 + guard,), fillv, dtype=dtype, device=dev)
+        setattr(cs, name, buf)
+        setattr(cs.desc, name + "_dev", buf.data_ptr())
+    outs = []
+    for z0, z1 in bounds_of([8, 16], 24):
+        n = (z1 - z0) * 40 * 72
+        lab = torch.full((n + guard,), -1234567, dtype=torch.int32, device=dev)
+        cs.push(t[:, z0:z1], out=lab[:n].view(z1 - z0, 40, 72))
+        outs.append((lab, n))
+    with pytest.raises(RuntimeError, match="id_capacity"):
+        cs.finish()
+    torch.cuda.synchronize()
+    for name, (dtype, fillv) in bufs.items():
+        assert (getattr(cs, name)[capacity + 1:] == fillv).all(), name
+    for lab, n in outs:
+        assert (lab[n:] == -1234567).all()
+        assert int(lab[:n].min()) >= 0 and int(lab[:n].max()) <= capacity
+    used, overflow = (int(v) for v in cs.state.cpu()[:2])
+    assert (used, overflow) == (capacity, 1)
+    # the device is fine: a correct run right after it
+    check(dev, aff, 0.8, 0, [8, 16], key="r24")
+
+
+# ---- 7. refused arguments ----------------------------------------------------------------------------------------
+def test_bad_arguments_are_refused_before_any_launch(dev):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    shape = (24, 40, 72)
+    t = torch.from_numpy(random_affinities(shape).copy()).to(dev)
+    cs = inference.ComponentsStream(shape, 0.75, 0, device=dev)
+    lib = _native.lib()
+    poison = -1234567
+
+    def fresh(n):
+        return torch.full((n,), poison, dtype=torch.int32, device=dev)
+
+    def untouched(lab):
+        torch.cuda.synchronize()
+        return bool((lab == poison).all()) and int(cs.state.cpu()[0]) == 0
+
+    lab = fresh(8 * 40 * 72)
+    with pytest.raises(ValueError, match="z order"):          # the first slab must start at 0
+        cs.push(t[:, 8:16], z0=8, out=lab.view(8, 40, 72))
+    assert cs.next_z == 0 and untouched(lab)
+    cs.push(t[:, 0:8])
+    ids_after_one = int(cs.state.cpu()[0])
+    assert ids_after_one > 0
+    with pytest.raises(ValueError, match="z order"):          # one skipped, one repeated
+        cs.push(t[:, 16:24], z0=16, out=lab.view(8, 40, 72))
+    with pytest.raises(ValueError, match="z order"):
+        cs.push(t[:, 0:8], z0=0, out=lab.view(8, 40, 72))
+    with pytest.raises(ValueError, match="leave the volume"):
+        cs.push(torch.cat([t[:, 8:24], t[:, 0:8]], dim=1), out=None)
+    narrow = fresh(8 * 40 * 71)
+    with pytest.raises(ValueError, match=r"\(y, x\)"):       # a changed W, a changed H
+        cs.push(t[:, 8:16, :, :71], out=narrow.view(8, 40, 71))
+    with pytest.raises(ValueError, match=r"\(y, x\)"):
+        cs.push(t[:, 8:16, :39], out=narrow[: 8 * 39 * 72].view(8, 39, 72))
+    torch.cuda.synchronize()
+    assert cs.next_z == 8 and (lab == poison).all() and (narrow == poison).all()
+    assert int(cs.state.cpu()[0]) == ids_after_one
+
+    # a short workspace and misaligned pointers, at the ABI
+    dims = _native.int3((8, 40, 72))
+    need = lib.exaspim_components_stream_slab_workspace_bytes(dims)
+    assert need >= 5 * 8 * 40 * 72 + 40 * 72
+    ws = torch.full((need + 16,), 0xA5, dtype=torch.uint8, device=dev)
+    slab = t[:, 8:16].contiguous()
+    desc = ctypes.byref(cs.desc)
+    rc = lib.exaspim_components_stream_slab(desc, slab.data_ptr(), _native.AFF_F32, dims, 8, lab.data_ptr(),
+                                            ws.data_ptr(), need - 1, None)
+    assert rc == -3 and "workspace" in _native.last_error()
+    for bad in ((slab.data_ptr(), lab.data_ptr(), ws.data_ptr() + 4), (slab.data_ptr(), lab.data_ptr() + 2, ws.data_ptr()),
+                (slab.data_ptr() + 2, lab.data_ptr(), ws.data_ptr())):
+        rc = lib.exaspim_components_stream_slab(desc, bad[0], _native.AFF_F32, dims, 8, bad[1], bad[2], need, None)
+        assert rc == -1 and "misaligned" in _native.last_error()
+    rc = lib.exaspim_components_stream_finish(desc, ws.data_ptr(), need, None)     # two slabs are missing
+    assert rc == -1 and "planes have been pushed" in _native.last_error()
+    torch.cuda.synchronize()
+    assert cs.next_z == 8 and (lab == poison).all() and (ws == 0xA5).all()
+    assert int(cs.state.cpu()[0]) == ids_after_one
+    with pytest.raises(ValueError):
+        inference.ComponentsStream(shape, device=dev, id_capacity=2**31 - 1)
+    with pytest.raises(RuntimeError, match="before finish"):
+        cs.apply(lab)
+
+    # and the stream still goes on from where it was
+    rest = [cs.push(t[:, 8:16]), cs.push(t[:, 16:24])]
+    _, k = cs.finish()
+    assert k == oracle("r24", random_affinities(shape), 0.75, 0)[1]
+    for r in rest:
+        cs.apply(r)
+    np.testing.assert_array_equal(torch.cat(rest).cpu().numpy(), oracle("r24", random_affinities(shape), 0.75, 0)[0][8:])
+
+
+# ---- 8. sizes beyond int32 --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("min_size,k", [(2**31, 1), (3 * 10**9, 0)])
+def test_sizes_are_summed_in_64_bits(dev, min_size, k):
+    """Two ids of 1.5e9 voxels each, joined by one seam: the id table's counts are the caller's buffer
+    (exaspim_components_stream.id_count_dev), so they are planted there between the slabs and finish."""
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    aff = np.zeros((3, 2, 1, 2), np.float32)
+    aff[0, 0, 0, 0] = 1.0
+    t = torch.from_numpy(aff).to(dev)
+    cs = inference.ComponentsStream((2, 1, 2), 0.5, min_size, device=dev)
+    parts = [cs.push(t[:, 0:1]), cs.push(t[:, 1:2])]
+    assert torch.cat(parts).cpu().numpy().ravel().tolist() == [1, 0, 2, 0]
+    assert cs.id_count[1:3].cpu().tolist() == [1, 1]
+    cs.id_count[1:3] = 1_500_000_000
+    table, got_k = cs.finish()
+    assert got_k == k
+    assert table[:3].cpu().tolist() == [0, k, k]
+    assert int(cs.id_count[1].cpu()) == 3_000_000_000
+
+
+# ---- 9. end to end -------------------------------------------------------------------------------------------------
+SEAM = 28
+GEOMETRY = dict(batch_size=3, patch_shape=(32, 32, 32), overlap=(8, 8, 8), trim=4, verbose=False)
+
+
+def seam_threshold(aff, min_size):
+    """
+    A threshold, taken from the data as a quantile of its non-zero values, at which the oracle keeps
+    K >= 2 components of which at least one has voxels on both sides of z = 28: the median if it does,
+    else the quantile found by bisection. This model's three channels sit in three narrow clusters of
+    values with the z channel lowest (on the CPU restatement of the same path: z 0.445 .. 0.491, x 0.469 ..
+    0.493, y 0.541 .. 0.557), so as the threshold rises the volume goes from one component (everything
+    on) to many without one across the seam (no z edge on) within a narrow band of quantiles around
+    1/3; bisection between "one component, across" (too low) and "none across" (too high) finds the
+    band where both hold. Returns (threshold, labels, K, what was tried); threshold None if none is found.
+    """
+    nonzero = aff[aff != 0]
+    tried = []
+
+    def look(q):
+        threshold = float(np.quantile(nonzero, q))
+        want, k = components_ref.components(aff, threshold, min_size)
+        across = len(crossing(want, SEAM))
+        tried.append((q, threshold, k, across))
+        return threshold, want, k, across
+
+    lo, hi = 0.0, 1.0
+    q = 0.5
+    for _ in range(24):
+        threshold, want, k, across = look(q)
+        if k >= 2 and across >= 1:
+            return threshold, want, k, tried
+        if across >= 1:
+            lo = q      # still one component: raise the threshold
+        else:
+            hi = q      # nothing kept across the seam: lower it
+        q = (lo + hi) / 2
+    return None, None, 0, tried
+
+
+@pytest.fixture(scope="module")
+def e2e(dev):
+    """The tiny model, its volume, predict_streaming's affinities and a threshold and oracle that have
+    a kept component across the one seam (z = 28) between the two slabs that geometry finishes."""
+    from aind_exaspim_neuron_segmentation_amd import inference
+    from aind_exaspim_neuron_segmentation_amd.machine_learning.unet3d import UNet3D
+
+    sd = synthetic.synth_state_dict(3, 0.125, seed=1)
+    model = UNet3D(output_channels=3, width_multiplier=0.125)
+    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+    model.to(dev).eval()
+    vol = synthetic.synth_volume((40, 48, 56), seed=21)
+    aff = inference.predict_streaming(vol, model, **GEOMETRY)
+    assert aff.dtype == np.float32 and aff.shape == (3, 40, 48, 56)
+    threshold, want, k, tried = seam_threshold(aff, 20)
+    print("quantile, threshold, K, kept components across z = 28:", tried)
+    assert threshold is not None, tried
+    chosen, min_size = (threshold, want, k), 20
+    return dict(model=model, vol=vol, aff=aff, threshold=chosen[0], min_size=min_size, want=chosen[1], k=chosen[2])
+
+
+@pytest.mark.parametrize("resident", [True, False])
+def test_predict_components_streaming_equals_the_oracle(dev, e2e, resident):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    got = inference.predict_components_streaming(e2e["vol"], e2e["model"], e2e["threshold"], e2e["min_size"],
+                                                 keep_labels_resident=resident, **GEOMETRY)
+    assert isinstance(got, np.ndarray) and got.dtype == np.int32
+    np.testing.assert_array_equal(got, e2e["want"])
+    assert int(got.max()) == e2e["k"]
+
+
+def test_predict_components_streaming_write_block(dev, e2e):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    blocks = []
+
+    def write_block(z0, z1, block):
+        blocks.append((z0, z1, block.dtype, block.shape, block.copy()))
+
+    table, k = inference.predict_components_streaming(e2e["vol"], e2e["model"], e2e["threshold"], e2e["min_size"],
+                                                      write_block=write_block, **GEOMETRY)
+    assert [(b[0], b[1]) for b in blocks] == [(0, SEAM), (SEAM, 40)]       # two slabs, one seam
+    assert all(b[2] == np.int32 and b[3] == (b[1] - b[0], 48, 56) for b in blocks)   # int32 and nothing else left
+    provisional = np.concatenate([b[4] for b in blocks])
+    assert table.dtype == np.int32 and table[0] == 0 and provisional.max() < table.size
+    np.testing.assert_array_equal(table[provisional], e2e["want"])
+    assert k == e2e["k"]
+
+
+def test_affinities_to_components_streaming_on_the_same_affinities(dev, e2e):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    for resident in (True, False):
+        got = inference.affinities_to_components_streaming(e2e["aff"], e2e["threshold"], e2e["min_size"],
+                                                           slab_depth=7, keep_labels_resident=resident)
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, e2e["want"])
+    blocks = []
+    table, k = inference.affinities_to_components_streaming(
+        e2e["aff"], e2e["threshold"], e2e["min_size"], slab_depth=7,
+        write_block=lambda z0, z1, b: blocks.append((z0, z1, b.copy())))
+    assert [(b[0], b[1]) for b in blocks] == [(z, min(z + 7, 40)) for z in range(0, 40, 7)]
+    assert all(b[2].dtype == np.int32 for b in blocks)
+    np.testing.assert_array_equal(table[np.concatenate([b[2] for b in blocks])], e2e["want"])
+    assert k == e2e["k"]
