@@ -139,12 +139,7 @@ def predict(
         (3, D, H, W), or (D, H, W) if "affinity_mode" is False.
     """
     out_dtype = _checked_out_dtype(out_dtype)
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        raise RuntimeError(
-            "predict (MI355X) has no CPU path: the model must be on a HIP device, "
-            f"got {device}"
-        )
+    device = _hip_device(model)
     if not return_device_tensor and not isinstance(img, (DeviceVolume, torch.Tensor)):
         # host array in, host array out: slab pipeline with overlapped transfers
         return predict_streaming(
@@ -1495,7 +1490,7 @@ class _SlabDrain:
 
 
 class _ArraySource:
-    """read_block over anything that slices like a numpy array (ndarray, memmap,
+    """read_box(lo, hi) over anything that slices like a 3-D numpy array (ndarray, memmap,
     a zarr / N5 / TIFF-backed array as img_util.read returns, img_util.py:25-121)."""
 
     def __init__(self, arr):
@@ -1509,8 +1504,18 @@ class _ArraySource:
         self.shape = tuple(int(v) for v in arr.shape)
         self.dtype = np.dtype(arr.dtype)
 
-    def __call__(self, z0, z1):
-        return np.asarray(self.arr[z0:z1])
+    def __call__(self, lo, hi):
+        return np.asarray(self.arr[tuple(slice(a, b) for a, b in zip(lo, hi))])
+
+
+def _plane_reader(read_block, shape):
+    """read_box(lo, hi) over a read_block(z0, z1) function, which hands out whole planes."""
+    def read_box(lo, hi):
+        block = read_block(lo[0], hi[0])
+        if tuple(block.shape) != (hi[0] - lo[0],) + tuple(shape[1:]):
+            raise ValueError(f"read_block({lo[0]}, {hi[0]}) returned shape {tuple(block.shape)}")
+        return block[:, lo[1]:hi[1], lo[2]:hi[2]]
+    return read_box
 
 
 def _device_voxel_dtype(np_dtype, whole=None, clip=None):
@@ -1560,6 +1565,387 @@ def _carrier(block):
     return torch.from_numpy(block)
 
 
+class DeviceShardOps:
+    """
+    What run_slab_pipeline does on the device, as overridable steps (the CPU tests replace the
+    kernels by their numpy restatements and keep the schedule, the band bookkeeping and the
+    exchanges).
+    """
+
+    def __init__(self, model, plan, n_channels, batch_size, brightness_clip, n_streams, half_out,
+                 copy_threads):
+        self.model, self.plan = model, plan
+        self.n_channels, self.batch_size = n_channels, batch_size
+        self.brightness_clip, self.n_streams = brightness_clip, n_streams
+        self.half_out, self.copy_threads = half_out, copy_threads
+        self.device = _hip_device(model)
+
+    # -- voxels
+    def storage(self, src_dtype, whole=None):
+        """(voxel dtype in device memory, host conversion) for an image dtype; "whole": the entire
+        image where it is an in-memory array (it can show that float32 carries it exactly)."""
+        vdtype, convert = _device_voxel_dtype(src_dtype, whole=whole, clip=self.brightness_clip)
+        if vdtype not in _VOX_CODES:
+            raise TypeError(_unsupported(src_dtype))
+        return vdtype, convert
+
+    def upload(self, block, convert):
+        """The host side of an upload: a block the reader returned as the tensor the pipeline
+        copies, once, to its place in device memory."""
+        return _carrier(convert(block))
+
+    def empty_voxels(self, dims, vdtype):
+        return torch.empty(tuple(dims), dtype=_TORCH_VOXELS[np.dtype(vdtype)], device=self.device)
+
+    def effective_clip(self, src_dtype, vdtype):
+        return _effective_clip(src_dtype, self.brightness_clip, vdtype)
+
+    def histogram_into(self, hist, voxels, vdtype, clip, pass_index, prefix):
+        _histogram_into(hist, voxels.contiguous(), _VOX_CODES[np.dtype(vdtype)], clip, pass_index, prefix)
+
+    def percentiles(self, histogram, vdtype, percentiles, value_dtype, clip):
+        return _percentiles_from_histograms(histogram, vdtype, percentiles, value_dtype, clip)
+
+    # -- one patch layer: gather -> network -> sigmoid -> trimmed overlap-add into "accum"
+    def run_layer(self, voxels, vox_origin, src_dtype, vdtype, starts, accum, accum_origin, mn, mx, pbar=None):
+        gshape = self.plan.shape
+        volume = DeviceVolume(voxels, src_dtype, vox_origin, gshape, storage_dtype=vdtype)
+        blk = _native.Block.make(tuple(accum.shape[1:]), accum_origin, gshape)
+        run_sliding_window(volume, self.model, self.plan, self.n_channels, self.batch_size,
+                           self.brightness_clip, mn, mx, starts=starts, accum=accum,
+                           accum_block=blk, n_streams=self.n_streams, pbar=pbar)
+
+    def finalize(self, out, origin):
+        """Divides the sums of the box at global "origin" by the per-voxel patch count."""
+        stitch_finalize(out, self.plan, _native.Block.make(tuple(out.shape[1:]), origin, self.plan.shape))
+
+    def zeros(self, shape):
+        return torch.zeros(tuple(shape), dtype=torch.float32, device=self.device)
+
+    def empty(self, shape):
+        return torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+
+    def slab_bytes_cap(self):
+        return PINNED_SLOT_BYTES
+
+    def make_drain(self, slot_elems, threads, label_elems=0):
+        return _SlabDrain(self.device, slot_elems, self.half_out, threads, label_elems=label_elems)
+
+    def synchronize(self):
+        torch.cuda.synchronize(self.device)
+
+
+class _WholeVolume:
+    """
+    The one rank of a 1 x 1 grid: the fields of sharding.Shard that run_slab_pipeline reads, for
+    a device that has the volume to itself. Unlike Shard it also describes a volume no patch fits
+    into (a dimension <= overlap): no starts, every plane still owned.
+    """
+
+    def __init__(self, plan):
+        self.plan = plan
+        ranges = _start_ranges(plan.shape, plan.patch_shape, plan.overlap)
+        self.yx_starts = list(itertools.product(*ranges[1:]))
+        self.z_starts = list(ranges[0]) if self.yx_starts else []
+        self.input_origin = self.core_origin = self.accum_origin = self.own_lo = (0, 0, 0)
+        self.input_dims = self.core_dims = self.accum_dims = self.own_hi = plan.shape
+
+
+def run_slab_pipeline(ops, shard, read_box, src_dtype, storage, normalization_percentiles, *,
+                      affinity_mode=True, write_block=None, result=None, label=None, copy_threads=4,
+                      keep_input_resident=None, exchanges=None, progress=None, timings=None):
+    """
+    The out-of-core sliding window: one rank's share of predict() with the image READ and the
+    result WRITTEN in pieces, behind predict_streaming, predict_components_streaming (the 1 x 1
+    grid) and sharding.predict_shard_streaming. The device never holds more than one patch layer
+    of input, two one-layer accumulators and three output slabs, whatever the depth of the block.
+
+    pass 1  z-chunks of the rank's disjoint sub-volume are read once, uploaded and added to the
+            device histogram ("exchanges" sums it over the ranks); np.percentile of the clipped
+            volume follows from it exactly. With "keep_input_resident" the rank's whole input
+            block is uploaded here and stays; pass 2 then reads nothing.
+    pass 2  per patch layer k (the rank's patches with z-start z_k; the reference's order is
+            z-major, inference.py:368-397):
+            * the planes the layer adds go, with one copy from the host, into one of two rolling
+              input slabs; the planes it shares with layer k - 1 move there on the device;
+            * gather -> U-Net -> sigmoid -> trimmed overlap-add run into a one-layer accumulator
+              that starts from the partial sums layer k - 1 left in the overlap band;
+            * planes up to min(z_{k+1} + trim, end of the region) -- after the last layer, up to
+              the end -- get no further addition from this rank. A 1 x 1 grid has no other rank,
+              so the owned rows go from the accumulator into an output slot in cuts of at most
+              min(D, max(stride + trim, patch depth), slab_bytes_cap() // bytes of a global plane)
+              planes, are divided by the patch count there and leave: device -> pinned memory
+              on a copy stream -> "write_block" or "result" on host threads, while the next
+              layer computes. Between ranks, "exchanges" takes the finished planes first and
+              calls emit() on the sums it has completed.
+    Planes no patch reaches are emitted as zeros (inference.py:120-125), also when no patch fits
+    into the volume at all.
+
+    Parameters
+    ----------
+    ops : DeviceShardOps
+        The device steps.
+    shard : sharding.Shard or _WholeVolume
+        The rank's part of the window (shard.plan) over the global volume.
+    read_box : Callable[[Tuple[int], Tuple[int]], numpy.ndarray]
+        Returns voxels [lo, hi) of the global image; only boxes inside the rank's input block
+        are requested.
+    src_dtype : numpy.dtype
+        Voxel dtype of the image.
+    storage : Tuple[numpy.dtype, Callable]
+        ops.storage(src_dtype): the voxel dtype in device memory and the host conversion to it.
+    write_block : Callable[[Tuple[int], Tuple[int], numpy.ndarray], None], optional
+        Receives every finished box of the rank's region once, from one thread, as
+        write_block(lo, hi, block); the block is valid during the call only.
+    result : numpy.ndarray, optional
+        Without "write_block": the array of the rank's region, (C, *own dims) or (*own dims),
+        the slabs are copied into by "copy_threads" threads.
+    label : Callable, optional
+        label(z0, z1, out, slot) turns the finished, divided (C, z1 - z0, h, w) device slab "out"
+        into the int32 (1, z1 - z0, h, w) tensor that leaves the device in its place (it may use
+        the flat int32 device buffer "slot"), or returns None: nothing leaves.
+    exchanges : object, optional
+        What the ranks of a larger grid add (sharding._RankExchanges): reduce_histogram(hist),
+        finished(cur, zs, hi, z0, z1, emit) for planes [z0, z1) of the layer accumulator "cur"
+        (planes [zs, hi)), last_layer_done(cur, zs, hi, emit). emit(z0, z1, sums, s0, s1) hands
+        over planes [z0, z1) out of "sums", which holds all accumulator rows of planes [s0, s1).
+    progress : str, optional
+        Description of a tqdm bar over the patches.
+    timings : dict, optional
+        Filled with the wall seconds of "upload_histogram", "layers" (ends with a device
+        synchronisation) and "drain".
+    """
+    plan = shard.plan
+    vdtype, convert = storage
+    n_channels = 3 if affinity_mode else 1
+    D, H, W = plan.shape
+    pz, trim = plan.patch_shape[0], plan.trim
+    stride = pz - plan.overlap[0]
+    z_starts, yx_starts = shard.z_starts, shard.yx_starts
+    in_lo = shard.input_origin
+    in_hi = tuple(o + d for o, d in zip(in_lo, shard.input_dims))
+    core_lo = shard.core_origin
+    core_hi = tuple(o + d for o, d in zip(core_lo, shard.core_dims))
+    acc_lo = shard.accum_origin
+    AH, AW = shard.accum_dims[1], shard.accum_dims[2]
+    own_lo, own_hi = shard.own_lo, shard.own_hi
+    own_dims = tuple(h - l for l, h in zip(own_lo, own_hi))
+    res4 = None if result is None else result.reshape((-1,) + own_dims)
+
+    def read(lo, hi):
+        block = read_box(tuple(lo), tuple(hi))
+        if tuple(block.shape) != tuple(h - l for l, h in zip(lo, hi)):
+            raise ValueError(f"read_box({tuple(lo)}, {tuple(hi)}) returned shape {tuple(block.shape)}")
+        return ops.upload(block, convert)
+
+    # ---- pass 1: histogram of the rank's disjoint sub-volume (inference.py:79, img_util.py:526) ----
+    in_plane_bytes = shard.input_dims[1] * shard.input_dims[2] * np.dtype(vdtype).itemsize
+    if keep_input_resident is None:
+        keep_input_resident = False
+        if ops.device.type == "cuda":
+            free, _ = torch.cuda.mem_get_info(ops.device)
+            keep_input_resident = shard.input_dims[0] * in_plane_bytes <= free // 4
+    chunk = max(1, min(shard.input_dims[0], max(stride, (256 << 20) // max(in_plane_bytes, 1))))
+    resident = ops.empty_voxels(shard.input_dims, vdtype) if keep_input_resident else None
+    clip, value_dtype = ops.effective_clip(src_dtype, vdtype)
+    loaded = [False]
+
+    def core_chunks():
+        """The rank's sub-volume in z-chunks (device tensors); fills "resident" on the first walk."""
+        z_lo, z_hi = (in_lo[0], in_hi[0]) if resident is not None else (core_lo[0], core_hi[0])
+        for z0 in range(z_lo, z_hi, chunk):
+            z1 = min(z0 + chunk, z_hi)
+            if resident is None:
+                yield read((z0, core_lo[1], core_lo[2]), (z1, core_hi[1], core_hi[2])).to(ops.device, non_blocking=True)
+                continue
+            if not loaded[0]:
+                resident[z0 - in_lo[0]:z1 - in_lo[0]].copy_(read((z0, in_lo[1], in_lo[2]), (z1, in_hi[1], in_hi[2])),
+                                                            non_blocking=True)
+            a, b = max(z0, core_lo[0]), min(z1, core_hi[0])
+            if b > a:
+                yield resident[(slice(a - in_lo[0], b - in_lo[0]),
+                                slice(core_lo[1] - in_lo[1], core_hi[1] - in_lo[1]),
+                                slice(core_lo[2] - in_lo[2], core_hi[2] - in_lo[2]))]
+        loaded[0] = True
+
+    def histogram(pass_index=0, prefix=0):
+        hist = torch.zeros(65536, dtype=torch.int64, device=ops.device)
+        for part in core_chunks():
+            ops.histogram_into(hist, part, vdtype, clip, pass_index, prefix)
+        if exchanges is not None:
+            exchanges.reduce_histogram(hist)
+        return hist.cpu().numpy()
+
+    t_phase = time.perf_counter()
+    mn, mx = ops.percentiles(histogram, vdtype, normalization_percentiles, value_dtype, clip)
+    if timings is not None:
+        timings["upload_histogram"] = time.perf_counter() - t_phase
+        t_phase = time.perf_counter()
+
+    # ---- pass 2: the rank's patch layers ------------------------------------------------------------
+    band = pz - 2 * trim - stride            # partial sums a layer hands to the next one
+    slab_d = min(pz, D)
+    # deepest slab handed over at once: a layer finishes stride planes (the first one stride + trim,
+    # the last one the patch depth - trim); anything deeper is cut, and so is anything that would
+    # make a staging slot larger than the cap. The rule depends on the GLOBAL plane only: the ranks
+    # of a grid row cut alike (their y exchange pairs the slabs up)
+    max_out = max(1, min(D, max(stride + trim, pz), ops.slab_bytes_cap() // (n_channels * H * W * 4)))
+    # a sink is called from ONE thread, so the slabs arrive one at a time; copies into the result
+    # array are split over several threads
+    # (the label arguments are passed only with a label function: device steps written without them stay valid)
+    drain = ops.make_drain(n_channels * max_out * own_dims[1] * own_dims[2],
+                           1 if write_block is not None else max(1, int(copy_threads)),
+                           **({} if label is None else {"label_elems": max_out * own_dims[1] * own_dims[2]}))
+    acc_flat = [ops.empty((n_channels * slab_d * AH * AW,)) for _ in range(2)]
+    in_slab = None
+    if resident is None:
+        in_slab = [ops.empty_voxels((slab_d,) + tuple(shard.input_dims[1:]), vdtype) for _ in range(2)]
+    pbar = None
+    if progress is not None and tqdm is not None:
+        pbar = tqdm(total=len(z_starts) * len(yx_starts), desc=progress)
+
+    def acc_view(k):
+        zs = z_starts[k]
+        depth = min(zs + pz, D) - zs
+        return acc_flat[k % 2][: n_channels * depth * AH * AW].view(n_channels, depth, AH, AW)
+
+    own_rows = (slice(None), slice(None), slice(own_lo[1] - acc_lo[1], own_hi[1] - acc_lo[1]),
+                slice(own_lo[2] - acc_lo[2], own_hi[2] - acc_lo[2]))
+
+    def consumers(z0, z1):
+        """Host jobs for output planes [z0, z1) once they sit in staging memory."""
+        lo, hi = (z0, own_lo[1], own_lo[2]), (z1, own_hi[1], own_hi[2])
+
+        def make(view):
+            if write_block is not None:
+                return [lambda: write_block(lo, hi, view if affinity_mode and label is None else view[0])]
+            # the copy into the pageable result is split over the threads
+            pieces = max(1, min(int(copy_threads), z1 - z0))
+            jobs = []
+            for i in range(pieces):
+                a = z0 + (z1 - z0) * i // pieces
+                b = z0 + (z1 - z0) * (i + 1) // pieces
+                jobs.append(lambda a=a, b=b: np.copyto(res4[:, a - own_lo[0]:b - own_lo[0]],
+                                                       view[:, a - z0:b - z0]))
+            return jobs
+        return make
+
+    def emit(z0, z1, sums=None, s0=0, s1=0):
+        """Planes [z0, z1) are final once divided: in cuts of max_out planes, the owned rows of
+        "sums" (all accumulator rows of planes [s0, s1); planes outside stay 0, and so does
+        everything without "sums") go into a zeroed output slab, are divided and handed over."""
+        for a in range(z0, z1, max_out):
+            b = min(a + max_out, z1)
+
+            def fill(out, a=a, b=b):
+                if sums is None:
+                    return
+                lo, hi = max(a, s0), min(b, s1)
+                if hi > lo:
+                    out[:, lo - a:hi - a].copy_(sums[:, lo - s0:hi - s0][own_rows])
+                ops.finalize(out, (a, own_lo[1], own_lo[2]))
+
+            drain.emit((n_channels, b - a, own_dims[1], own_dims[2]), fill, consumers(a, b),
+                       **({} if label is None else {"label": lambda out, slot, a=a, b=b: label(a, b, out, slot)}))
+
+    try:
+        final_lo = own_lo[0]
+        cur = zs = hi = None
+        for k, zs in enumerate(z_starts):
+            hi = min(zs + pz, D)
+            cur = acc_view(k)
+            # -- input planes [zs, hi) of the rank's block
+            if resident is not None:
+                voxels, vox_origin = resident, in_lo
+            else:
+                slab, old = in_slab[k % 2], in_slab[(k + 1) % 2]
+                have = 0
+                if k > 0:    # planes shared with the previous layer move on the device
+                    zp = z_starts[k - 1]
+                    have = max(0, min(zp + pz, D) - zs)
+                    if have > 0:
+                        slab[:have].copy_(old[zs - zp: zs - zp + have])
+                if hi - zs > have:
+                    slab[have:hi - zs].copy_(read((zs + have, in_lo[1], in_lo[2]), (hi, in_hi[1], in_hi[2])),
+                                             non_blocking=True)
+                voxels, vox_origin = slab[: hi - zs], (zs, in_lo[1], in_lo[2])
+            # -- this layer's accumulator continues the previous layer's overlap band
+            cur.zero_()
+            if k > 0 and band > 0:
+                zp = z_starts[k - 1]
+                b0 = zs + trim
+                b1 = min(b0 + band, D, zp + pz)
+                if b1 > b0:
+                    cur[:, b0 - zs:b1 - zs].copy_(acc_view(k - 1)[:, b0 - zp:b1 - zp])
+            ops.run_layer(voxels, vox_origin, src_dtype, vdtype, [(zs, y, x) for y, x in yx_starts], cur,
+                          (zs, acc_lo[1], acc_lo[2]), mn, mx, pbar=pbar)
+            # -- planes of the rank's region no later layer of it touches
+            last = k + 1 == len(z_starts)
+            final_hi = own_hi[0] if last else min(z_starts[k + 1] + trim, own_hi[0])
+            if final_hi > final_lo:
+                if exchanges is None:
+                    emit(final_lo, final_hi, cur, zs, hi)
+                else:
+                    exchanges.finished(cur, zs, hi, final_lo, final_hi, emit)
+                final_lo = final_hi
+        if cur is None:      # no patch fits (a dimension <= overlap): zeros, like the reference
+            emit(final_lo, own_hi[0])
+        elif exchanges is not None:
+            exchanges.last_layer_done(cur, zs, hi, emit)
+        if timings is not None:
+            ops.synchronize()
+            timings["layers"] = time.perf_counter() - t_phase
+            t_phase = time.perf_counter()
+        drain.drain()
+        if timings is not None:
+            timings["drain"] = time.perf_counter() - t_phase
+    finally:
+        drain.close()
+        if pbar is not None:
+            pbar.close()
+
+
+def _open_volume(source, shape, dtype):
+    """predict_streaming's "source" as (read_box, (D, H, W), voxel dtype, whole): "whole" is the
+    image itself where it is an in-memory array, else None."""
+    if callable(source) and not hasattr(source, "shape"):
+        if shape is None or dtype is None:
+            raise ValueError("a read_block function needs shape= and dtype=")
+        vshape = tuple(int(v) for v in shape)
+        if len(vshape) != 3:
+            raise ValueError(f"expected a 3-D shape, got {vshape}")
+        return _plane_reader(source, vshape), vshape, np.dtype(dtype), None
+    src = _ArraySource(source if hasattr(source, "shape") else np.asarray(source))
+    in_memory = isinstance(src.arr, np.ndarray) and not isinstance(src.arr, np.memmap)
+    return src, src.shape, src.dtype, src.arr if in_memory else None
+
+
+def _hip_device(model):
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError(
+            "predict (MI355X) has no CPU path: the model must be on a HIP device, "
+            f"got {device}"
+        )
+    return device
+
+
+def _stream_whole_volume(volume, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
+                         patch_shape, overlap, trim, verbose, n_streams, out_dtype, write_block, **sink):
+    """run_slab_pipeline for a device that has the volume "volume" (from _open_volume) to itself:
+    the 1 x 1 grid, z-slab sinks. "sink": further keyword arguments of run_slab_pipeline."""
+    read_box, vshape, src_dtype, whole = volume
+    plan = SlidingWindow(vshape, patch_shape, overlap, trim)
+    ops = DeviceShardOps(model, plan, 3 if affinity_mode else 1, batch_size, brightness_clip, n_streams,
+                         out_dtype == np.float16, sink["copy_threads"])
+    if write_block is not None:
+        sink["write_block"] = lambda lo, hi, block: write_block(lo[0], hi[0], block)
+    with torch.cuda.device(ops.device):
+        run_slab_pipeline(ops, _WholeVolume(plan), read_box, src_dtype, ops.storage(src_dtype, whole=whole),
+                          normalization_percentiles, affinity_mode=affinity_mode,
+                          progress="Predict" if verbose else None, **sink)
+
+
 def predict_streaming(
     source,
     model,
@@ -1591,19 +1977,10 @@ def predict_streaming(
     keeps a float64 normalised copy plus the float32 accumulators in host
     memory (22 B/voxel); its readers (img_util.py:25-121) hand out lazily
     chunked zarr / N5 / TIFF arrays that are sliced on demand. This function
-    consumes exactly that interface:
-
-    pass 1  every z-chunk is read once, uploaded and added to the device
-            histogram (np.percentile of the clipped volume, exactly);
-    pass 2  per patch layer k (all patches with z-start k * stride, the
-            reference's z-major order, inference.py:368-397): upload the planes
-            the layer adds to the rolling input slab, run gather -> U-Net ->
-            sigmoid -> trimmed overlap-add into a one-layer accumulator that
-            starts from the partial sums the previous layer left in the
-            overlap band, then divide and emit the z-range no later layer
-            touches. Finished slabs go device -> pinned memory on a copy stream
-            and from there into the result (or to "write_block") on a few host
-            threads while the next layer computes.
+    consumes exactly that interface and runs run_slab_pipeline (the two
+    passes are described there) on the 1 x 1 rank grid: every z-chunk is read
+    once for the percentiles and once for its patch layer, and finished slabs
+    leave the device while the next layer computes.
 
     Parameters
     ----------
@@ -1646,217 +2023,15 @@ def predict_streaming(
     numpy.ndarray or None
         The prediction (see predict), or None when "write_block" is given.
     """
-    return _predict_streaming_impl(
-        source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles, patch_shape,
-        overlap, trim, verbose, shape, dtype, write_block, keep_input_resident, n_streams, copy_threads,
-        timings, out_dtype)
-
-
-def _predict_streaming_impl(source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
-                            patch_shape, overlap, trim, verbose, shape, dtype, write_block, keep_input_resident,
-                            n_streams, copy_threads, timings, out_dtype, components=None):
-    """
-    predict_streaming's two passes. "components": None, or the sink that replaces the download of
-    the affinities (predict_components_streaming): a function (vshape, device) -> (label, result)
-    called once the geometry is known; label(z0, z1, out, slot) labels the finished, divided
-    (C, z1 - z0, H, W) slab "out" where it lies and returns the int32 (1, z1 - z0, H, W) tensor
-    that leaves the device in its place (or None: nothing leaves), "result" is the int32
-    (D, H, W) host array the slabs are copied into (or None). Everything else is the same code
-    for both, so the affinities a labelling sees are predict_streaming's, bit for bit.
-    """
-    device = next(model.parameters()).device
-    if device.type != "cuda":
-        raise RuntimeError(
-            "predict (MI355X) has no CPU path: the model must be on a HIP device, "
-            f"got {device}"
-        )
+    _hip_device(model)
     out_dtype = _checked_out_dtype(out_dtype)
-    half_out = out_dtype == np.float16
-    if callable(source) and not hasattr(source, "shape"):
-        if shape is None or dtype is None:
-            raise ValueError("a read_block function needs shape= and dtype=")
-        read_block, vshape, src_dtype = source, tuple(int(v) for v in shape), np.dtype(dtype)
-        if len(vshape) != 3:
-            raise ValueError(f"expected a 3-D shape, got {vshape}")
-    else:
-        src = _ArraySource(source if hasattr(source, "shape") else np.asarray(source))
-        read_block, vshape, src_dtype = src, src.shape, src.dtype
-    whole = None
-    if not callable(source) or hasattr(source, "shape"):
-        arr = read_block.arr
-        if isinstance(arr, np.ndarray) and not isinstance(arr, np.memmap):
-            whole = arr      # an in-memory array can show that float32 carries it exactly
-    vdtype, convert = _device_voxel_dtype(src_dtype, whole=whole, clip=brightness_clip)   # dtype in device memory
-    if vdtype not in _VOX_CODES:
-        raise TypeError(_unsupported(src_dtype))
-    plan = SlidingWindow(vshape, patch_shape, overlap, trim)
-    n_channels = 3 if affinity_mode else 1
-    D, H, W = vshape
-    pz = plan.patch_shape[0]
-    stride = pz - plan.overlap[0]
-    ranges = _start_ranges(vshape, plan.patch_shape, plan.overlap)
-    yx_starts = list(itertools.product(*ranges[1:]))
-    z_starts = list(ranges[0]) if yx_starts else []
-    torch_dtype = _TORCH_VOXELS[vdtype]
-    plane = H * W
-
-    result = res4 = label = None
-    if components is not None:
-        label, result = components(vshape, device)
-        if result is not None:
-            res4 = result.reshape((1,) + vshape)
-    elif write_block is None:
-        result = np.empty(((n_channels,) if affinity_mode else ()) + vshape, dtype=out_dtype)
-        res4 = result.reshape((n_channels,) + vshape)
-
-    def read(z0, z1):
-        block = read_block(z0, z1)
-        if tuple(block.shape) != (z1 - z0, H, W):
-            raise ValueError(f"read_block({z0}, {z1}) returned shape {tuple(block.shape)}")
-        return _carrier(convert(block))
-
-    with torch.cuda.device(device):
-        plane_bytes = plane * vdtype.itemsize
-        if keep_input_resident is None:
-            free, _ = torch.cuda.mem_get_info(device)
-            keep_input_resident = D * plane_bytes <= free // 4
-        chunk = max(1, min(D, max(stride, (256 << 20) // max(plane_bytes, 1))))
-
-        # ---- pass 1: histogram of the clipped volume (inference.py:79, img_util.py:526) ----
-        resident = None
-        if keep_input_resident:
-            resident = torch.empty((D, H, W), dtype=torch_dtype, device=device)
-        clip, value_dtype = _effective_clip(src_dtype, brightness_clip, vdtype)
-        loaded = [False]
-
-        def chunks():
-            for z0 in range(0, D, chunk):
-                z1 = min(z0 + chunk, D)
-                if resident is None:
-                    yield read(z0, z1).to(device, non_blocking=True)
-                else:
-                    if not loaded[0]:
-                        resident[z0:z1].copy_(read(z0, z1), non_blocking=True)
-                    yield resident[z0:z1]
-            loaded[0] = True
-
-        def histogram(pass_index=0, prefix=0):
-            hist = torch.zeros(65536, dtype=torch.int64, device=device)
-            for part in chunks():
-                _histogram_into(hist, part, _VOX_CODES[vdtype], clip, pass_index, prefix)
-            return hist.cpu().numpy()
-
-        t_phase = time.perf_counter()
-        mn, mx = _percentiles_from_histograms(histogram, vdtype, normalization_percentiles, value_dtype, clip)
-        if timings is not None:
-            timings["upload_histogram"] = time.perf_counter() - t_phase
-            t_phase = time.perf_counter()
-
-        # ---- pass 2: patch layers ------------------------------------------------------
-        band = pz - 2 * plan.trim - stride          # partial sums the next layer continues
-        slab_d = min(pz, D)
-        # deepest slab handed over at once: a layer finishes stride planes (the first one
-        # stride + trim, the last one the patch depth - trim); anything deeper is cut, and so is
-        # anything that would make a staging slot larger than PINNED_SLOT_BYTES
-        max_out = min(D, max(stride + plan.trim, pz), max(1, PINNED_SLOT_BYTES // (n_channels * plane * 4)))
-        # a sink is called from ONE thread, so the slabs arrive in z order, one at a time;
-        # copies into the result array are split over several threads
-        drain = _SlabDrain(device, n_channels * max_out * plane, half_out,
-                           1 if write_block is not None else max(1, int(copy_threads)),
-                           label_elems=max_out * plane if label is not None else 0)
-        acc_flat = [torch.empty(n_channels * slab_d * plane, dtype=torch.float32, device=device)
-                    for _ in range(2)]
-        in_slab = None
-        if resident is None:
-            in_slab = [torch.empty((slab_d, H, W), dtype=torch_dtype, device=device) for _ in range(2)]
-        pbar = None
-        if verbose and tqdm is not None:
-            pbar = tqdm(total=len(z_starts) * len(yx_starts), desc="Predict")
-
-        def acc_view(k):
-            zs = z_starts[k]
-            depth = min(zs + pz, D) - zs
-            return acc_flat[k % 2][: n_channels * depth * plane].view(n_channels, depth, H, W)
-
-        def consumers(z0, z1):
-            """Host jobs for output planes [z0, z1) once they sit in staging memory."""
-            def make(view):
-                if write_block is not None:
-                    return [lambda: write_block(z0, z1, view if affinity_mode and label is None else view[0])]
-                # the copy into the pageable result is split over the threads
-                pieces = max(1, min(int(copy_threads), z1 - z0))
-                jobs = []
-                for i in range(pieces):
-                    a = z0 + (z1 - z0) * i // pieces
-                    b = z0 + (z1 - z0) * (i + 1) // pieces
-                    jobs.append(lambda a=a, b=b: np.copyto(res4[:, a:b], view[:, a - z0:b - z0]))
-                return jobs
-            return make
-
-        def emit(z0, z1, fill):
-            """Planes [z0, z1) are final: "fill(out)" writes the divided sums into the
-            zeroed (C, z1 - z0, H, W) device slab, which then travels to the host."""
-            drain.emit((n_channels, z1 - z0, H, W), fill, consumers(z0, z1),
-                       None if label is None else lambda out, slot: label(z0, z1, out, slot))
-
-        try:
-            final_lo = 0
-            for k, zs in enumerate(z_starts):
-                hi = min(zs + pz, D)
-                cur = acc_view(k)
-                # -- input planes [zs, hi)
-                if resident is not None:
-                    volume = DeviceVolume(resident, src_dtype, storage_dtype=vdtype)
-                else:
-                    slab, old = in_slab[k % 2], in_slab[(k + 1) % 2]
-                    have = 0
-                    if k > 0:    # planes shared with the previous layer move on the device
-                        zp = z_starts[k - 1]
-                        have = max(0, min(zp + pz, D) - zs)
-                        if have > 0:
-                            slab[:have].copy_(old[zs - zp: zs - zp + have])
-                    if hi - zs > have:
-                        slab[have:hi - zs].copy_(read(zs + have, hi), non_blocking=True)
-                    volume = DeviceVolume(slab[: hi - zs], src_dtype, (zs, 0, 0), vshape, storage_dtype=vdtype)
-                # -- this layer's accumulator continues the previous layer's overlap band
-                cur.zero_()
-                if k > 0 and band > 0:
-                    zp = z_starts[k - 1]
-                    b0 = zs + plan.trim
-                    b1 = min(b0 + band, D, zp + pz)
-                    if b1 > b0:
-                        cur[:, b0 - zs:b1 - zs].copy_(acc_view(k - 1)[:, b0 - zp:b1 - zp])
-                blk = _native.Block.make((hi - zs, H, W), (zs, 0, 0), vshape)
-                run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_clip,
-                                   mn, mx, starts=[(zs, y, x) for y, x in yx_starts], accum=cur,
-                                   accum_block=blk, n_streams=n_streams, pbar=pbar)
-                # -- planes no later layer touches
-                final_hi = D if k + 1 == len(z_starts) else min(z_starts[k + 1] + plan.trim, D)
-                for z0 in range(final_lo, final_hi, max_out):
-                    z1 = min(z0 + max_out, final_hi)
-
-                    def fill(out, z0=z0, z1=z1):
-                        a, b = max(z0, zs), min(z1, hi)
-                        if b > a:
-                            out[:, a - z0:b - z0].copy_(cur[:, a - zs:b - zs])
-                        stitch_finalize(out, plan, _native.Block.make((z1 - z0, H, W), (z0, 0, 0), vshape))
-
-                    emit(z0, z1, fill)
-                final_lo = max(final_lo, final_hi)
-            # no patch fits (a dimension <= overlap): zeros, like the reference
-            for z0 in range(final_lo, D, max_out):
-                emit(z0, min(z0 + max_out, D), lambda out: None)
-            if timings is not None:
-                torch.cuda.synchronize(device)
-                timings["layers"] = time.perf_counter() - t_phase
-                t_phase = time.perf_counter()
-            drain.drain()
-            if timings is not None:
-                timings["drain"] = time.perf_counter() - t_phase
-        finally:
-            drain.close()
-            if pbar is not None:
-                pbar.close()
+    volume = _open_volume(source, shape, dtype)
+    result = None
+    if write_block is None:
+        result = np.empty(((3,) if affinity_mode else ()) + volume[1], dtype=out_dtype)
+    _stream_whole_volume(volume, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
+                         patch_shape, overlap, trim, verbose, n_streams, out_dtype, write_block, result=result,
+                         copy_threads=copy_threads, keep_input_resident=keep_input_resident, timings=timings)
     return result
 
 
@@ -1927,38 +2102,34 @@ def predict_components_streaming(
         (table, K): table int32 with final = table[provisional], K kept
         components.
     """
-    state = {}
+    device = _hip_device(model)
+    volume = _open_volume(source, shape, dtype)
+    vshape = volume[1]
+    cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=not affinity_mode, device=device,
+                          id_capacity=id_capacity)
+    keep = keep_labels_resident
+    if write_block is not None:
+        keep = False
+    elif keep is None:
+        keep = _labels_fit_on_device(device, vshape)
+    resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
+    result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
+    plane = vshape[1] * vshape[2]
 
-    def components(vshape, device):
-        cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=not affinity_mode, device=device,
-                              id_capacity=id_capacity)
-        keep = keep_labels_resident
-        if write_block is not None:
-            keep = False
-        elif keep is None:
-            keep = _labels_fit_on_device(device, vshape)
-        resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
-        result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
-        state.update(cs=cs, resident=resident, result=result)
-        plane = vshape[1] * vshape[2]
+    def label(z0, z1, out, slot):
+        aff = out if affinity_mode else out[0]
+        if resident is not None:
+            cs.push(aff, z0, resident[z0:z1])
+            return None
+        labels = slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2])
+        return cs.push(aff, z0, labels).view((1,) + tuple(labels.shape))
 
-        def label(z0, z1, out, slot):
-            aff = out if affinity_mode else out[0]
-            if resident is not None:
-                cs.push(aff, z0, resident[z0:z1])
-                return None
-            labels = slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2])
-            return cs.push(aff, z0, labels).view((1,) + tuple(labels.shape))
-
-        return label, result
-
-    _predict_streaming_impl(
-        source, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles, patch_shape,
-        overlap, trim, verbose, shape, dtype, write_block, keep_input_resident, n_streams, copy_threads,
-        timings, np.float32, components=components)
-    cs, resident, result = state["cs"], state["resident"], state["result"]
+    _stream_whole_volume(volume, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
+                         patch_shape, overlap, trim, verbose, n_streams, np.float32, write_block, result=result,
+                         label=label, copy_threads=copy_threads, keep_input_resident=keep_input_resident,
+                         timings=timings)
     t0 = time.perf_counter()
-    with torch.cuda.device(cs.device):
+    with torch.cuda.device(device):
         table, count = cs.finish()
         if write_block is not None:
             out = table[: cs.ids_used + 1].cpu().numpy(), count

@@ -9,6 +9,10 @@ z-band planes, the per-slab y exchange, the z exchange at the end, the boxes han
 The assembled result must equal predict_shard's whole-accumulator route (accumulate everything,
 exchange_output_bands, divide) BIT FOR BIT, with float patch outputs whose sums depend on the
 order of the additions.
+
+The loop is inference.run_slab_pipeline, the one predict_streaming and predict_components_streaming
+run on the 1 x 1 grid of a whole volume; the cases at the end drive it the way they do: the slab
+cuts a sink sees, the label sink, a volume no patch fits into, the read_block(z0, z1) adapter.
 """
 
 import os
@@ -65,9 +69,16 @@ def weights(plan):
 class SyncDrain:
     """The download pipeline without a device: fill, then run the consumers at once."""
 
-    def emit(self, shape, fill, consumers):
+    def __init__(self, label_elems=0):
+        self.label_slot = torch.empty(label_elems, dtype=torch.int32)
+
+    def emit(self, shape, fill, consumers, label=None):
         out = torch.zeros(shape, dtype=torch.float32)
         fill(out)
+        if label is not None:
+            out = label(out, self.label_slot)
+            if out is None:
+                return
         for job in consumers(out.numpy()):
             job()
 
@@ -139,8 +150,8 @@ class NumpyShardOps:
         g = self.plan.shape
         return self.slab_planes * CHANNELS * g[1] * g[2] * 4
 
-    def make_drain(self, slot_elems, threads):
-        return SyncDrain()
+    def make_drain(self, slot_elems, threads, label_elems=0):
+        return SyncDrain(label_elems)
 
     def synchronize(self):
         pass
@@ -265,3 +276,165 @@ def test_streamed_shards_equal_the_whole_accumulator_route(world, geometry, resi
 def test_single_rank_streaming_needs_no_group(geometry):
     """World size 1: no neighbours, nothing parked, no exchange; the same code path as the ranks'."""
     run_rank(0, 1, geometry, False, 3)
+
+
+# --- the same loop on the 1 x 1 grid of a device that has the volume to itself: what -----------
+# --- predict_streaming and predict_components_streaming hand to inference.run_slab_pipeline -----
+WHOLE_GEOMETRIES = dict(GEOMETRIES, nofit=((40, 88, 12), (16, 16, 16)))   # nofit: x <= overlap, no patch fits
+# the (z0, z1) a sink sees when the slot cap (100 planes) cuts nothing: layer k finishes planes up
+# to z_{k+1} + trim, the last layer the rest
+UNCUT = {
+    "bands": [(0, 20), (20, 36), (36, 52), (52, 68), (68, 84), (84, 104)],
+    "tiling": [(0, 28), (28, 52), (52, 76), (76, 104)],
+    "deep": [(0, 12)] + [(z, z + 8) for z in range(12, 108, 8)] + [(108, 136)],
+}
+
+
+def run_whole(geometry, cap_planes, resident=False, read_box=None, **sink):
+    gshape, overlap = WHOLE_GEOMETRIES[geometry]
+    plan = inference.SlidingWindow(gshape, PATCH, overlap, TRIM)
+    whole = inference._WholeVolume(plan)
+    gvol = synthetic.synth_volume(gshape, seed=3)
+    ops = NumpyShardOps(plan, whole, gvol, cap_planes)
+    if read_box is None:
+        read_box = inference._ArraySource(gvol)
+    inference.run_slab_pipeline(ops, whole, read_box, np.dtype(np.uint16), ops.storage(np.uint16), (1, 99.9),
+                                keep_input_resident=resident, **sink)
+    return plan, ops
+
+
+def expected_cuts(plan, cap_planes):
+    """The cut rule, restated: finished ranges in pieces of min(D, max(stride + trim, patch_z), cap)."""
+    D, pz = plan.shape[0], PATCH[0]
+    stride = pz - plan.overlap[0]
+    z = list(range(0, D - plan.overlap[0], stride))
+    piece = min(D, max(stride + TRIM, pz), cap_planes)
+    cuts, lo = [], 0
+    for k in range(len(z)):
+        hi = D if k + 1 == len(z) else min(z[k + 1] + TRIM, D)
+        cuts += [(a, min(a + piece, hi)) for a in range(lo, hi, piece)]
+        lo = hi
+    return cuts
+
+
+@pytest.fixture(scope="module")
+def whole_reference():
+    """reference_route of the 1 x 1 shard per geometry, computed once and never written to."""
+    cache = {}
+
+    def get(geometry):
+        if geometry not in cache:
+            gshape, overlap = GEOMETRIES[geometry]
+            plan = inference.SlidingWindow(gshape, PATCH, overlap, TRIM)
+            want = reference_route(plan, sharding.Shard(plan, (1, 1), 0), None)
+            want.flags.writeable = False
+            cache[geometry] = want
+        return cache[geometry]
+    return get
+
+
+@pytest.mark.parametrize("geometry", ["bands", "tiling", "deep"])
+@pytest.mark.parametrize("cap_planes", [3, 100])
+def test_whole_volume_slabs_follow_the_cut_rule(geometry, cap_planes, whole_reference):
+    gshape = GEOMETRIES[geometry][0]
+    seen = []
+    parts = np.full((CHANNELS,) + gshape, np.nan, np.float32)
+
+    def sink(lo, hi, block):
+        assert (lo[1:], hi[1:]) == ((0, 0), gshape[1:])
+        seen.append((lo[0], hi[0]))
+        parts[:, lo[0]:hi[0]] = block
+
+    plan, _ = run_whole(geometry, cap_planes, write_block=sink)
+    assert seen == expected_cuts(plan, cap_planes)
+    if cap_planes == 100:
+        assert seen == UNCUT[geometry]
+    else:
+        assert max(b - a for a, b in seen) == 3
+    np.testing.assert_array_equal(parts, whole_reference(geometry))
+
+
+@pytest.mark.parametrize("geometry,cap_planes", [("bands", 3), ("tiling", 100), ("deep", 5)])
+def test_whole_volume_label_sink(geometry, cap_planes, whole_reference):
+    gshape = GEOMETRIES[geometry][0]
+    D, H, W = gshape
+    calls = []
+    divided = np.full((CHANNELS,) + gshape, np.nan, np.float32)
+
+    def label(z0, z1, out, slot):
+        assert tuple(out.shape) == (CHANNELS, z1 - z0, H, W)
+        calls.append((z0, z1))
+        divided[:, z0:z1] = out.numpy()
+        ids = slot[: (z1 - z0) * H * W].view(1, z1 - z0, H, W)
+        ids.copy_(torch.arange(ids.numel(), dtype=torch.int32).view(ids.shape) + z0 * H * W)   # = the voxel's index
+        return ids
+
+    voxel_index = np.arange(D * H * W, dtype=np.int32).reshape(gshape)
+    handed = []
+    got = np.full(gshape, -1, np.int32)
+
+    def sink(lo, hi, block):
+        handed.append((lo[0], hi[0]))
+        assert block.dtype == np.int32 and block.shape == (hi[0] - lo[0], H, W)
+        got[lo[0]:hi[0]] = block
+
+    plan, _ = run_whole(geometry, cap_planes, write_block=sink, label=label)
+    # once per slab, in z order, contiguous over [0, D): the cuts a float sink sees
+    assert calls == expected_cuts(plan, cap_planes) and handed == calls
+    assert calls[0][0] == 0 and calls[-1][1] == D and all(a[1] == b[0] for a, b in zip(calls, calls[1:]))
+    np.testing.assert_array_equal(divided, whole_reference(geometry))      # it saw the divided values
+    np.testing.assert_array_equal(got, voxel_index)                        # the sink got what it returned
+    # ... and so does a result array
+    result = np.full(gshape, -1, np.int32)
+    run_whole(geometry, cap_planes, result=result, label=label)
+    np.testing.assert_array_equal(result, voxel_index)
+    assert calls == 2 * expected_cuts(plan, cap_planes)
+    # a label function that keeps its labels (returns None) is called as often, and nothing is handed over
+    kept = []
+    untouched = np.full(gshape, -1, np.int32)
+    run_whole(geometry, cap_planes, result=untouched, label=lambda z0, z1, out, slot: kept.append((z0, z1)))
+    assert kept == expected_cuts(plan, cap_planes) and (untouched == -1).all()
+    run_whole(geometry, cap_planes, write_block=lambda lo, hi, block: pytest.fail("handed over"),
+              label=lambda z0, z1, out, slot: None)
+
+
+@pytest.mark.parametrize("cap_planes", [3, 100])
+def test_whole_volume_no_patch_fits(cap_planes, monkeypatch):
+    gshape = WHOLE_GEOMETRIES["nofit"][0]
+    monkeypatch.setattr(NumpyShardOps, "run_layer", lambda self, *a, **k: pytest.fail("run_layer without a patch"))
+    seen = []
+    cover = np.zeros(gshape[0], np.int32)
+
+    def sink(lo, hi, block):
+        assert (lo[1:], hi[1:]) == ((0, 0), gshape[1:]) and block.shape == (CHANNELS, hi[0] - lo[0]) + gshape[1:]
+        assert not block.any()
+        seen.append((lo[0], hi[0]))
+        cover[lo[0]:hi[0]] += 1
+
+    run_whole("nofit", cap_planes, write_block=sink)
+    assert (cover == 1).all()
+    piece = min(32, cap_planes)      # min(D, max(stride + trim, patch_z), cap) with D = 40
+    assert seen == [(a, min(a + piece, 40)) for a in range(0, 40, piece)]
+    result = np.full((CHANNELS,) + gshape, np.nan, np.float32)
+    run_whole("nofit", cap_planes, result=result)
+    assert not result.any()
+    with pytest.raises(ValueError):      # (the rank geometry of a larger grid has no such case)
+        sharding.Shard(inference.SlidingWindow(gshape, PATCH, WHOLE_GEOMETRIES["nofit"][1], TRIM), (1, 1), 0)
+
+
+@pytest.mark.parametrize("geometry", ["bands", "tiling", "deep"])
+@pytest.mark.parametrize("resident", [False, True])
+def test_read_block_adapter_requests(geometry, resident, whole_reference):
+    gshape = GEOMETRIES[geometry][0]
+    gvol = synthetic.synth_volume(gshape, seed=3)
+    requests = np.zeros(gshape[0], np.int32)
+
+    def read_block(z0, z1):
+        assert 0 <= z0 < z1 <= gshape[0], (z0, z1)
+        requests[z0:z1] += 1
+        return gvol[z0:z1]
+
+    result = np.full((CHANNELS,) + gshape, np.nan, np.float32)
+    run_whole(geometry, 100, resident=resident, read_box=inference._plane_reader(read_block, gshape), result=result)
+    assert requests.min() >= 1 and requests.max() <= (1 if resident else 2), requests
+    np.testing.assert_array_equal(result, whole_reference(geometry))
