@@ -144,6 +144,12 @@ SIGNATURES = {
                                               _vp, _sz, _vp]),
     "exaspim_components_stream_finish": (_i32, [ctypes.POINTER(ComponentsStreamDesc), _vp, _sz, _vp]),
     "exaspim_components_stream_apply": (_i32, [ctypes.POINTER(ComponentsStreamDesc), _vp, _sz, _vp]),
+    "exaspim_region_graph_workspace_bytes": (_sz, [_I32x3, _i32, ctypes.c_int64]),
+    "exaspim_region_graph": (_i32, [_vp, _vp, _i32, _I32x3, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _sz, _vp]),
+    "exaspim_agglomerate": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, ctypes.c_float, ctypes.c_int64,
+                                   _vp, _vp]),
+    "exaspim_apply_label_table": (_i32, [_vp, _sz, _vp, _i32, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

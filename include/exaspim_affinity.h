@@ -43,7 +43,9 @@ extern "C" {
  *    later within 5: exaspim_components, exaspim_components_workspace_bytes (EXASPIM_AFF_*)
  *    later within 5: exaspim_unet_forward_prepared_clipped, EXASPIM_OPT_ROW_SEPARATE_BORDERS;
  *    later within 5: exaspim_components_stream_slab / _finish / _apply and their workspace queries
- *    (struct exaspim_components_stream): the components of a volume that arrives in z slabs */
+ *    (struct exaspim_components_stream): the components of a volume that arrives in z slabs;
+ *    later within 5: exaspim_region_graph (and its workspace query), exaspim_agglomerate,
+ *    exaspim_apply_label_table: mean-affinity agglomeration of components */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -458,6 +460,75 @@ int exaspim_components_stream_finish(const exaspim_components_stream* st, void* 
  * becomes 0. labels_dev 4-byte aligned (16 for the wide form). One launch on "stream". */
 int exaspim_components_stream_apply(const exaspim_components_stream* st, int32_t* labels_dev, size_t n,
                                     void* stream);
+
+/* ---- mean-affinity agglomeration of components: the region graph ------------
+ *      (later within ABI 5). The order of operations of the reference's
+ *      affinities_to_segmentation (inference.py:196-237): over-segment into fragments, merge fragments
+ *      whose contact has a high mean affinity, only then remove small segments. Fragments are
+ *      exaspim_components at a threshold with min_size 0, the score is waterz's default (1 - mean
+ *      affinity of the contact, merged greedily in order of score). It is NOT waterz: the fragments are
+ *      connected components, not watershed basins, so the labels are not comparable with the
+ *      reference's. */
+
+/* Scratch bytes of exaspim_region_graph: 24 bytes per slot of the accumulator (a 64-bit key, count and
+ * sum) plus 4 bytes per 2048 slots. 0 (and a message) if a dim is not positive, the volume has more than
+ * 2^31 - 1 voxels, n_labels is negative or edge_capacity is not a power of two in 1 .. 2^30. */
+size_t exaspim_region_graph_workspace_bytes(const int32_t dims[3], int32_t n_labels, int64_t edge_capacity);
+
+/* The region graph of labels_dev (int32, dims) under aff_dev ((3, dims) of aff_dtype, EXASPIM_AFF_*, in
+ * exaspim_components' edge convention: channel c at voxel v is the edge v -- v + e_c, the entries at the
+ * last index along axis c are ignored whatever they hold). For every in-volume voxel edge with
+ * la = labels[v], lb = labels[v + e_c], both in 1 .. n_labels and la != lb:
+ *     key = (min(la, lb), max(la, lb)),  count[key] += 1,  sum[key] += q(a),
+ *     q(a) = (uint32) rint(clamp(float32(a), 0, 1) * 2^24), a NaN gives 0, ties round to even.
+ * count and sum are 64-bit integers: integer adds commute, so the result is a pure function of the input
+ * whatever order the atomics land in. sizes_dev[l] (int64, n_labels + 1 entries) = the number of voxels
+ * with label l, l = 0 (background) .. n_labels. A label outside 0 .. n_labels is counted nowhere, forms
+ * no edge and never becomes an address.
+ *  - Output: the E distinct keys in an UNSPECIFIED order (sort them after the download): row i of
+ *    edges_dev (int32, edge_capacity x 2) = (lo, hi), count_dev[i] (int64), sum_dev[i] (uint64); all
+ *    three must hold edge_capacity entries, the first E are written. n_edges_dev is int32[2]:
+ *    n_edges_dev[0] = E, n_edges_dev[1] = the overflow flag.
+ *  - The accumulator is an open-addressing table of edge_capacity slots (a power of two, the caller's
+ *    choice) in the workspace. More distinct keys than slots: the contributions that find none are
+ *    dropped and n_edges_dev[1] becomes 1, which the caller reads once, together with E; the output is
+ *    then unusable. Every probe sequence is bounded by the capacity.
+ * Separate launches on "stream"; no lock, no inter-workgroup waiting, nothing allocated, nothing
+ * synchronised. EXASPIM_E_INVALID for a NULL pointer, an unknown aff_dtype, a dim that is not positive, a
+ * volume of more than 2^31 - 1 voxels, a negative n_labels, an edge_capacity that is not a power of two
+ * in 1 .. 2^30 or a misaligned buffer (workspace_dev 16 bytes, count_dev / sum_dev / sizes_dev 8, labels_dev
+ * / edges_dev / n_edges_dev 4, aff_dev its element); EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_region_graph_workspace_bytes(dims, n_labels, edge_capacity): all before anything is launched. */
+int exaspim_region_graph(const int32_t* labels_dev, const void* aff_dev, int32_t aff_dtype,
+                         const int32_t dims[3], int32_t n_labels, int64_t edge_capacity,
+                         int32_t* edges_dev, int64_t* count_dev, uint64_t* sum_dev, int64_t* sizes_dev,
+                         int32_t* n_edges_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Host only (no device is touched). Merges the fragments 1 .. n_labels of a region graph and numbers
+ * what is left: table[0 .. n_labels] (int32), table[0] = 0, *n_segments = S.
+ *  - Input: n_edges rows (lo, hi) of "edges" sorted by (lo, hi) without repeats, 1 <= lo < hi <= n_labels,
+ *    with counts[i] >= 1 and sums[i] <= counts[i] * 2^24; sizes[0 .. n_labels] voxels per fragment.
+ *  - Rule, exact in integers: m = rint((1 - (double)threshold) * 2^24). Among the CURRENT edges take the
+ *    one with the largest mean sum / count (means compared by cross-multiplication in 128 bits; ties by
+ *    the smaller lo, then the smaller hi, of the current root ids); merge it iff sum > m * count, else
+ *    stop. Merging puts the larger root under the smaller; parallel edges to a common neighbour add their
+ *    count and sum. The rule is a total order, so the result does not depend on the implementation.
+ *  - A segment's size is the sum of its fragments' sizes; it is kept iff size > min_size
+ *    (img_util.py:555-558), AFTER merging. Kept segments are numbered 1 .. S in the order of their root
+ *    (smallest) id; with fragments numbered in raster order of their first voxel that is the raster order
+ *    of the segments' first voxels. A dropped segment's fragments map to 0.
+ * EXASPIM_E_INVALID for a NULL pointer, a negative n_labels or n_edges, a NaN threshold, or an edge list
+ * that breaks the input rules above. */
+int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, const uint64_t* sums, int64_t n_edges,
+                        const int64_t* sizes, int32_t n_labels, float threshold, int64_t min_size,
+                        int32_t* table, int32_t* n_segments);
+
+/* labels_dev[i] = table_dev[labels_dev[i]] for i < n, in place (exaspim_components_stream_apply's kernel
+ * without a stream descriptor). A value outside 0 .. table_len - 1 becomes 0 rather than an address.
+ * labels_dev and table_dev 4-byte aligned (labels_dev 16 for the wide form), table_len >= 1. One launch
+ * on "stream". */
+int exaspim_apply_label_table(int32_t* labels_dev, size_t n, const int32_t* table_dev, int32_t table_len,
+                              void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
