@@ -89,6 +89,22 @@ class ComponentsStreamDesc(ctypes.Structure):
     ]
 
 
+class UNetCarry(ctypes.Structure):
+    """exaspim_unet_carry: the caller's buffers for the first level's skip tensor and its max-pool, the
+    plane range already present in them and the range to store for the batch further down z."""
+
+    _fields_ = [
+        ("own_skip", ctypes.c_void_p),
+        ("own_pool", ctypes.c_void_p),
+        ("in_z", ctypes.c_int32 * 2),
+        ("out_skip", ctypes.c_void_p),
+        ("out_pool", ctypes.c_void_p),
+        ("out_z", ctypes.c_int32 * 2),
+        ("out_shift", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 _I32x5 = ctypes.c_int32 * 5
@@ -118,6 +134,10 @@ SIGNATURES = {
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "exaspim_unet_forward_prepared_clipped": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, _vp, _sz, _vp]),
+    "exaspim_unet_carry_planes": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_int32 * 2]),
+    "exaspim_unet_forward_prepared_carry": (
+        _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, ctypes.POINTER(UNetCarry), _vp,
+               _sz, _vp]),
     "exaspim_unet_forward_absmax": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_unet_set_options": (_i32, [_vp, ctypes.c_uint32]),

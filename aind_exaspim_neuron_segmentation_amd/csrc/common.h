@@ -218,12 +218,14 @@ struct ConvArgs {
     const void* src_b;
     int ca, cb;          // padded channel counts of the two sources (cb may be 0)
     const void* weights; // packed fragments
-    // Unused: they fed kernels that were removed. They stay for now because they hold 16 bytes of the
-    // kernel-argument block: without them every later field moves, and hipcc then allocates the scalar
-    // registers of every convolution kernel differently (profiles/conv_prune_kernel_identity.txt, step
-    // B). To go with the next change that recompiles and re-measures those kernels anyway.
-    const void* weights_paired = nullptr;
-    const void* weights_k32 = nullptr;
+    // Carry out (row mode, conv3x3x3_zpipe_rowz): planes [out_z0, out_z1) of this launch's output, as the
+    // row launch stores them (own frame and x neighbour), go to carry_dst as well, at plane - out_shift of
+    // the same per-patch layout, and their pooled planes to carry_pool_dst at pooled plane - out_shift / 2:
+    // the later batch whose patches start out_shift planes further down z finds them where it would have
+    // written them itself. Null: off. (These two take the place of two pointers that fed removed kernels:
+    // the kernel-argument block of every other convolution kernel keeps its layout and hence its code.)
+    void* carry_dst = nullptr;
+    void* carry_pool_dst = nullptr;
     const float* bias;
     void* dst;
     int cout;            // padded
@@ -256,12 +258,20 @@ struct ConvArgs {
     // neighbour's two outermost x (and pooled x) whose inputs reach its zero padding. Those are left
     // for launch_conv3x3x3_thin and launch_maxpool2_xcols. 0: off.
     int row_stride = 0;
+    // Carry in (row mode): planes [in_z0, in_z1) of dst and their pooled planes of pool_dst are already
+    // there (an earlier launch's carry out). Whole z tiles of the depth the launcher picks, even bounds;
+    // the tile walk leaves them out and nothing is written for them. Empty: off.
+    unsigned short in_z0 = 0, in_z1 = 0;
     // Optional scratch for split-K (t14 kernel): launches with too few workgroups to fill
     // the device cut the input-channel chunks into up to 4 ranges, every range writes its
     // float32 partial sums here and a second kernel adds them in a fixed order.
     float* partial = nullptr;
     size_t partial_patch_bytes = 0;   // scratch bytes per patch of the batch
     int ksplit = 1;      // set by the launcher
+    // carry out: even bounds, any alignment to the tiles (narrow types: the carry fields fill what was
+    // padding, so the argument block of every kernel keeps its size; planes up to 254 are plenty)
+    unsigned char out_z0 = 0, out_z1 = 0;
+    unsigned short out_shift = 0;
 #ifdef EXASPIM_TRACE
     // tools/conv_trace.hip only: 16 x 64-bit cycle stamps per wave (never in the library build)
     unsigned long long* trace = nullptr;
@@ -274,7 +284,8 @@ struct ConvArgs {
 struct ConvLaunchRecord {
     const char* config = "";
     int ksplit = 0;
-    bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride)
+    bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride) ...
+    bool carry = false;  // ... or conv3x3x3_zpipe_rowz (a carry field of ConvArgs set)
 };
 ConvLaunchRecord& last_conv_launch();
 // The same for the inc.0 and upsampling launchers (layers.hip): the name of the kernel variant
@@ -319,6 +330,11 @@ constexpr int kRowStagesAll = kRowStageMain | kRowStageThin | kRowStagePool;
 constexpr int kRowStageBorders = 8;
 constexpr int kRowStagesFused = kRowStageMain | kRowStageBorders;
 int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
+// Tile depth of the z-column kernel on a 32-cout slice of depth d without a fused head (launch_typed)
+int conv_zcol_tile_depth(int d);
+#ifndef EXASPIM_TRACE
+static_assert(sizeof(ConvArgs) == 184, "ConvArgs: the carry fields fill padding, the argument block keeps its size");
+#endif
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats
 // first_no_strips: keep the per-group kernel (the tests hold it to the row-strip kernel bit for bit)

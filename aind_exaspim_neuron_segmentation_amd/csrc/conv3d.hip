@@ -111,6 +111,11 @@ static int choose_ksplit(const ConvArgs& a, const TileGrid& g, int slices, int u
     return ks;
 }
 
+// a carry field of ConvArgs is set
+static bool conv_has_carry(const ConvArgs& a) {
+    return a.carry_dst || a.carry_pool_dst || a.in_z0 || a.in_z1 || a.out_z0 || a.out_z1;
+}
+
 template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD = 0, bool POOL = false>
 static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     // (row mode: the strip columns of the row, which the 16-wide tiles divide: launch_conv3x3x3
@@ -120,6 +125,12 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     if (int rc = row ? tile_grid(a, TZ, TY, TX, a.n * a.row_stride + a.w - a.row_stride, 1, g)
                      : tile_grid(a, TZ, TY, TX, a.ext[2], a.n, g))
         return rc;
+    // carry in (ConvArgs::in_z0): the z tiles already present are left out of the walk
+    const bool carry = row && conv_has_carry(a);
+    if (carry) {
+        g.tz -= (a.in_z1 - a.in_z0) / TZ;
+        g.blocks = (long long)g.tz * g.ty * g.tx;
+    }
     const int tz = g.tz, ty = g.ty, tx = g.tx;
     const long long blocks = g.blocks;
     // persistent workgroups: as many as the device holds at once (a multiple of the 8
@@ -136,6 +147,12 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     dim3 grid((unsigned)wgs, slices);
     last_conv_launch() = {__PRETTY_FUNCTION__, 1};
     if constexpr (POOL && HEAD == 0 && Tag::kG == 8) {
+        if (carry) {
+            last_conv_launch().carry = true;
+            conv3x3x3_zpipe_rowz<Tag, TZ, TY, TX, MINW, D><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
+            EXA_CHECK_HIP(hipGetLastError());
+            return EXASPIM_OK;
+        }
         if (row) {
             last_conv_launch().row = true;
             conv3x3x3_zpipe_row<Tag, TZ, TY, TX, MINW, D><<<grid, TY * TX * 2, 0, stream>>>(a, tz, ty, tx);
@@ -248,7 +265,7 @@ static int launch_typed(const ConvArgs& a, hipStream_t stream) {
                 }
             }
             // 6-plane tiles when the depth divides (96, 48, 24): more dz reuse per LDS read
-            if (a.d % 6 == 0) return launch_zpipe_d<Tag, 6>(a, stream);
+            if (conv_zcol_tile_depth(a.d) == 6) return launch_zpipe_d<Tag, 6>(a, stream);
             return launch_zpipe_d<Tag, 4>(a, stream);
         }
         if (a.pool_dst) return launch_cfg_pool<Tag, 4, 8, 16, 4, 1, 4, 2, 2>(a, stream);
@@ -369,6 +386,8 @@ static int resolve_region(ConvArgs& a) {
     return EXASPIM_OK;
 }
 
+int conv_zcol_tile_depth(int d) { return d % 6 == 0 ? 6 : 4; }
+
 int conv_zcol_main_extent(int ext, int axis) {
     const int tile = axis == 1 ? 8 : 16;   // the z-column kernel's TY / TX
     const int rem = ext % tile;
@@ -392,6 +411,18 @@ static int check_row_args(int dtype, const ConvArgs& a) {
                   "conv: row mode needs a 16-bit fused-pool z-column layer, whole patches, n >= 2 and "
                   "an overlap that is a multiple of 32 and at most the stride (w %d, stride %d, n %d)",
                   a.w, a.row_stride, a.n);
+    // carry: planes whose inputs stay clear of the zero padding along z, [2, d - 2), in whole plane pairs
+    const int tzd = conv_zcol_tile_depth(a.d);
+    EXA_CHECK_ARG(a.in_z0 <= a.in_z1 && a.in_z0 % 2 == 0 && a.in_z1 % 2 == 0 && a.in_z0 % tzd == 0 && a.in_z1 % tzd == 0 &&
+                      (a.in_z0 == a.in_z1 || (a.in_z0 >= 2 && a.in_z1 <= a.d - 2)),
+                  "conv: carry in [%d, %d) must be whole %d-plane tiles with even bounds inside [2, %d)", (int)a.in_z0,
+                  (int)a.in_z1, tzd, a.d - 2);
+    const bool out = a.carry_dst || a.carry_pool_dst || a.out_z0 || a.out_z1;
+    EXA_CHECK_ARG(!out || (a.carry_dst && a.carry_pool_dst && a.out_z0 < a.out_z1 && a.out_z0 % 2 == 0 && a.out_z1 % 2 == 0 &&
+                           a.out_z0 >= 2 && a.out_z1 <= a.d - 2 && a.out_shift > 0 && a.out_shift % 2 == 0 &&
+                           (int)a.out_z0 - a.out_shift >= 2),
+                  "conv: carry out [%d, %d) shifted by %d needs both targets, even bounds and source and target planes "
+                  "inside [2, %d)", (int)a.out_z0, (int)a.out_z1, a.out_shift, a.d - 2);
     return EXASPIM_OK;
 }
 
@@ -421,6 +452,7 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
                   "float32: a 32-cout-slice layer)");
     EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc, dtype),
                   "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs (and not bf16x3)");
+    EXA_CHECK_ARG(a.row_stride > 0 || !conv_has_carry(a), "conv: carried planes need row mode");
     if (a.row_stride > 0)
         if (int rc = check_row_args(dtype, a)) return rc;
     switch (dtype) {
@@ -476,7 +508,8 @@ static int launch_thin_typed(const ConvArgs& a, hipStream_t stream) {
 int launch_conv3x3x3_thin(int dtype, const ConvArgs& a_in, hipStream_t stream) {
     ConvArgs a = a_in;
     if (int rc = check_conv_args(dtype, a, kCheckPadded | kCheckEmpty)) return rc;   // (as ever: no slope or size check here)
-    EXA_CHECK_ARG(!a.pool_dst && !a.head_out && a.row_stride == 0, "conv: thin tiles have no fused pool, head or row mode");
+    EXA_CHECK_ARG(!a.pool_dst && !a.head_out && a.row_stride == 0 && !conv_has_carry(a),
+                  "conv: thin tiles have no fused pool, head, row mode or carried planes");
     if (int rc = resolve_region(a)) return rc;
     a.partial = nullptr;   // no split-K on a partial region
     switch (dtype) {
@@ -530,6 +563,9 @@ int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t s
     // w/2 - 1 of every patch
     b.pool_dst = nullptr;
     b.row_stride = 0;
+    b.carry_dst = b.carry_pool_dst = nullptr;   // (the border launches write every plane, and only dst / pool_dst)
+    b.in_z0 = b.in_z1 = b.out_z0 = b.out_z1 = 0;
+    b.out_shift = 0;
     b.n = a.n - 1;
     b.ext[2] = 2;
     if (r == EXASPIM_OK && (stages & kRowStageThin)) {
@@ -550,6 +586,9 @@ int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t s
         r = check_conv_args(dtype, a, kCheckPadded);
         ConvArgs c = a;
         for (int i = 0; i < 3; ++i) { c.org[i] = b.org[i]; c.ext[i] = b.ext[i]; }   // (resolved: whole patches)
+        c.carry_dst = c.carry_pool_dst = nullptr;
+        c.in_z0 = c.in_z1 = c.out_z0 = c.out_z1 = 0;
+        c.out_shift = 0;
         c.org[2] = 0;
         if (r == EXASPIM_OK)    // (check_row_args: a 16-bit type)
             r = dtype == EXASPIM_DT_F16 ? launch_row_borders<F16Tag>(c, stream) : launch_row_borders<BF16Tag>(c, stream);

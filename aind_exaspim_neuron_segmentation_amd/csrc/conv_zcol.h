@@ -27,7 +27,7 @@ namespace exaspim {
 //    layout a load instruction covers whole halo rows of contiguous bytes (the
 //    texture addresser works per 64-byte segment: 16 cycles per instruction
 //    instead of 64 with one voxel record per lane).
-template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD, bool POOL, bool ROW>
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD, bool POOL, bool ROW, bool CARRY = false>
 __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int tiles_y, int tiles_x) {
     constexpr int G = Tag::kG;
     constexpr int KC = 2 * G;
@@ -82,6 +82,8 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
     // row mode (ConvArgs::row_stride): tiles_x counts the strip columns of the whole row
     constexpr bool row = ROW;
     static_assert(!ROW || (POOL && ES == 2 && HEAD == 0), "row mode: 16-bit fused-pool epilogue");
+    // carry (ConvArgs::in_z0 .. out_shift): tiles_z counts the z tiles that are left
+    static_assert(!CARRY || ROW, "carry: row mode only");
     const int total = tiles_z * tiles_y * tiles_x * (row ? 1 : a.n);
     int t_first, t_count, t_step;
     {
@@ -106,7 +108,9 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
         const int nb = min(max(rx - ho, 0) / s, a.n - 1);
         t.x0 = __builtin_amdgcn_readfirstlane(rx - nb * s);
         t.y0 = __builtin_amdgcn_readfirstlane((id % tiles_y) * TY); id /= tiles_y;
-        t.z0 = __builtin_amdgcn_readfirstlane((id % tiles_z) * TZ);
+        int tz = id % tiles_z;
+        if (CARRY && tz >= a.in_z0 / TZ) tz += (a.in_z1 - a.in_z0) / TZ;   // (the z tiles already present)
+        t.z0 = __builtin_amdgcn_readfirstlane(tz * TZ);
         t.nb = __builtin_amdgcn_readfirstlane(nb);
         return t;
     };
@@ -150,7 +154,14 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
         s_slot[k] = q < REM * HZ ? kg * GS + hz * PLANE + (c / HX) * HXP + c % HX : -1;
     }
     auto set_offsets = [&](const Tile& t) {
-        {
+        if constexpr (CARRY) {
+            // (the carry stores' scalars take the registers the hoisted p_hy / p_hx / p_kg lived in: the
+            // pair is derived again per tile from an opaque lane index, see fresh_lane())
+            const int ft = wave * 64 + fresh_lane();
+            const int gy = t.y0 + (ft >> 1) / HX - 1, gx = t.x0 + (ft >> 1) % HX - 1;
+            const bool in = ft < NPAIR && (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
+            p_voff = in ? (unsigned)(gy * a.w + gx) * 32u + (ft & 1) * 16u : kOutOfRange;
+        } else {
             const int gy = t.y0 + p_hy - 1, gx = t.x0 + p_hx - 1;
             const bool in = p_ok && (unsigned)gy < (unsigned)a.h && (unsigned)gx < (unsigned)a.w;
             p_voff = in ? (unsigned)(gy * a.w + gx) * 32u + p_kg * 16u : kOutOfRange;
@@ -476,6 +487,14 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
             char* const nplane = static_cast<char*>(a.dst) + nbase +
                                  ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
             const size_t nbytes = (size_t)((long long)2 * patch_vox * 32 - nbase);
+            // carry out: the same records once more, to carry_dst at plane - out_shift (the shift rides in
+            // the descriptors' bases too; a plane outside [out_z0, out_z1) gets zero records)
+            const bool cout_on = CARRY && a.carry_dst != nullptr;
+            const long long cshift = (long long)a.out_shift * plane_vox * 32;
+            char* const cplane = static_cast<char*>(a.carry_dst) - cshift +
+                                 ((size_t)cur.nb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+            char* const cnplane = static_cast<char*>(a.carry_dst) - cshift + nbase +
+                                  ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
 #pragma unroll
             for (int zp = 0; zp < TZ / 2; ++zp) {
                 uint2 grp[2][4];
@@ -505,6 +524,14 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                         buf_store16(rec, orsrc, ovoff, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
                         if (shared)
                             buf_store16(rec, nrsrc, nlane ? ovoff : kOutOfRange, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                        if (CARRY && cout_on) {
+                            const bool cz = gz >= a.out_z0 && gz < a.out_z1;
+                            buf_store16(rec, make_rsrc(cplane, cz ? (size_t)2 * patch_vox * 32 : (size_t)0), ovoff,
+                                        ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                            if (shared)
+                                buf_store16(rec, make_rsrc(cnplane, cz ? nbytes : (size_t)0), nlane ? ovoff : kOutOfRange,
+                                            ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                        }
                     }
                 }
             }
@@ -522,6 +549,12 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                 char* const npplane = static_cast<char*>(a.pool_dst) + nbase / 2 +
                                       ((size_t)nnb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
                 const __amdgpu_buffer_rsrc_t nprsrc = make_rsrc(npplane, (size_t)((long long)CPT * pvox * 32 - nbase / 2));
+                // carry out of the pooled planes [out_z0 / 2, out_z1 / 2), at pooled plane - out_shift / 2
+                const long long cpshift = (long long)(a.out_shift >> 1) * ph * pw2 * 32;
+                char* const cpplane = static_cast<char*>(a.carry_pool_dst) - cpshift +
+                                      ((size_t)cur.nb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
+                char* const cnpplane = static_cast<char*>(a.carry_pool_dst) - cpshift + nbase / 2 +
+                                       ((size_t)nnb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
 #pragma unroll
                 for (int p0 = 0; p0 < NP; p0 += 64) {
                     const int p = p0 + lane_e;
@@ -543,6 +576,15 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                     if (shared) {   // (pooled x 0 and w / 2 - 1 of the neighbour: from its own outermost x)
                         const int nqx = qx + nshift / 2;
                         buf_store16(m, nprsrc, nqx >= 1 && nqx < pw2 - 1 ? pvoff : kOutOfRange, 0u);
+                    }
+                    if (CARRY && cout_on) {   // (the plane pair is per lane here)
+                        const unsigned cpvoff = 2 * qz >= a.out_z0 && 2 * qz < a.out_z1 ? pvoff : kOutOfRange;
+                        buf_store16(m, make_rsrc(cpplane, (size_t)CPT * pvox * 32), cpvoff, 0u);
+                        if (shared) {
+                            const int nqx = qx + nshift / 2;
+                            buf_store16(m, make_rsrc(cnpplane, (size_t)((long long)CPT * pvox * 32 - nbase / 2)),
+                                        nqx >= 1 && nqx < pw2 - 1 ? cpvoff : kOutOfRange, 0u);
+                        }
                     }
                 }
             }
@@ -666,6 +708,15 @@ template <typename Tag, int TZ, int TY, int TX, int MINW, int D>
 __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe_row(
     ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
     zpipe_body<Tag, TZ, TY, TX, MINW, D, 0, true, true>(a, tiles_z, tiles_y, tiles_x);
+}
+
+// Row mode with planes carried along z (ConvArgs::in_z0 .. out_shift): z tiles an earlier launch left in
+// dst are not computed, and a plane range of this launch's stores goes to a second tensor as well. A symbol
+// of its own again: conv3x3x3_zpipe_row keeps its code.
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D>
+__global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe_rowz(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    zpipe_body<Tag, TZ, TY, TX, MINW, D, 0, true, true, true>(a, tiles_z, tiles_y, tiles_x);
 }
 
 }  // namespace exaspim

@@ -57,6 +57,19 @@ static int conv_level(int i) {
     return 3 - (i - 9) / 2;                  // up1..up4 -> 3..0
 }
 
+// Planes [out[0], out[1]) of a forward's own frame that hold what a forward shift_z planes earlier computed at
+// its planes + shift_z: the whole tiles (of the depth inc.3's launcher picks) inside [2, d - shift_z - 2),
+// even bounds. Empty: {0, 0}.
+static void carry_span(int d, int shift_z, int32_t out[2]) {
+    out[0] = out[1] = 0;
+    if (shift_z <= 0 || shift_z % 2 != 0 || shift_z >= d) return;
+    const int tz = conv_zcol_tile_depth(d);
+    const int step = tz % 2 == 0 ? tz : 2 * tz;
+    const int lo = (2 + step - 1) / step * step, hi = (d - shift_z - 2) / step * step;
+    // (a whole number of tiles whichever way: bounds are multiples of the tile depth and even)
+    if (lo < hi && hi + shift_z <= 254) { out[0] = lo; out[1] = hi; }
+}
+
 static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
     // widest tensor stored at each level: every input and output of its convs
     // (the pooled / upsampled tensors are inputs of the level's first conv)
@@ -92,7 +105,7 @@ static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
 static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, int h, int w,
                    int apply_sigmoid, int trim, void* workspace, size_t workspace_bytes,
                    hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr,
-                   int row_stride = 0, const int32_t* keep_hi = nullptr) {
+                   int row_stride = 0, const int32_t* keep_hi = nullptr, const exaspim_unet_carry* carry = nullptr) {
     const UNetPlan& p = e->plan;
     const Workspace ws = make_workspace(p, n, d, h, w);
     if (workspace_bytes < ws.bytes) {
@@ -138,6 +151,33 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     // (EXASPIM_OPT_PER_PATCH_ENCODER: every patch on its own, as without a row.)
     const bool row = !absmax && !(e->options & EXASPIM_OPT_PER_PATCH_ENCODER) &&
                      conv_row_mode_ok(dt, p.conv[0].cout, n, w, row_stride, fuse_pool[0]);
+    // carried planes (exaspim_unet_forward_prepared_carry): x1 and its max-pool live in the caller's buffers
+    if (carry) {
+        int32_t span[2];
+        const int shift = carry->out_skip ? carry->out_shift : 0;
+        const bool in = carry->in_z[0] != 0 || carry->in_z[1] != 0;
+        EXA_CHECK_ARG(row && carry->own_skip && carry->own_pool && carry->reserved == 0,
+                      "forward: carried planes need row mode at this geometry and both own buffers");
+        EXA_CHECK_ARG(!carry->out_skip == !carry->out_pool, "forward: carry out needs both targets or neither");
+        const int tzd = conv_zcol_tile_depth(d);
+        // the range a successor may take over is what exaspim_unet_carry_planes gives for its shift; a range
+        // carried in must be whole tiles with even bounds inside [2, d - 2)
+        if (in)
+            EXA_CHECK_ARG(carry->in_z[0] >= 2 && carry->in_z[0] < carry->in_z[1] && carry->in_z[1] <= d - 2 &&
+                              carry->in_z[0] % tzd == 0 && carry->in_z[1] % tzd == 0 && carry->in_z[0] % 2 == 0 &&
+                              carry->in_z[1] % 2 == 0,
+                          "forward: carry in [%d, %d) is not whole %d-plane tiles with even bounds inside [2, %d)",
+                          carry->in_z[0], carry->in_z[1], tzd, d - 2);
+        if (shift || carry->out_skip) {
+            carry_span(d, shift, span);
+            EXA_CHECK_ARG(shift > 0 && span[0] < span[1] && carry->out_z[0] == span[0] + shift &&
+                              carry->out_z[1] == span[1] + shift && carry->out_z[1] <= 254,
+                          "forward: carry out [%d, %d) shifted by %d is not the range a forward %d planes down takes over",
+                          carry->out_z[0], carry->out_z[1], shift, shift);
+        }
+    }
+    void* const x1 = carry ? carry->own_skip : skip(0);
+    void* const x1_pool = carry ? carry->own_pool : A(1);
     auto conv = [&](int idx, const void* sa, const void* sb, void* dst, int l) -> int {
         const ConvLayer& L = p.conv[idx];
         ConvArgs a;
@@ -145,7 +185,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         // split-K scratch: the zero-bordered input copy is dead once inc.0 has run
         a.partial = reinterpret_cast<float*>(base + ws.xpad);
         a.partial_patch_bytes = (size_t)(d + 2) * (h + 2) * (w + 2) * sizeof(float);
-        if (idx <= 6 && idx % 2 == 0 && fuse_pool[idx / 2]) a.pool_dst = A(idx / 2 + 1);
+        if (idx <= 6 && idx % 2 == 0 && fuse_pool[idx / 2]) a.pool_dst = idx == 0 ? x1_pool : A(idx / 2 + 1);
         // up4.3 produces [trim, khi) (khi = size - trim unless clipped), up4.0 one voxel more on every face
         const bool last = idx == kNumMfmaConvs - 1, last_but_one = idx == kNumMfmaConvs - 2;
         const int margin = !trimmed ? 0 : last ? trim : last_but_one ? trim - 1 : 0;
@@ -180,6 +220,17 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         a.n = n; a.d = d >> l; a.h = h >> l; a.w = w >> l;
         a.slope = kLeakySlope;
         if (idx == 0 && row) a.row_stride = row_stride;
+        if (idx == 0 && carry) {
+            a.in_z0 = (unsigned short)carry->in_z[0];
+            a.in_z1 = (unsigned short)carry->in_z[1];
+            if (carry->out_skip) {
+                a.carry_dst = carry->out_skip;
+                a.carry_pool_dst = carry->out_pool;
+                a.out_z0 = (unsigned char)carry->out_z[0];
+                a.out_z1 = (unsigned char)carry->out_z[1];
+                a.out_shift = (unsigned short)carry->out_shift;
+            }
+        }
         LayerTimer* t = e->timer;
         const bool timed = t && (t->mask >> idx & 1u) && t->used < LayerTimer::kRing;
         int slot = 0;
@@ -222,14 +273,14 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                           reinterpret_cast<const float*>(e->packed + p.first_b_off), A(0), n, d,
                           h, w, p.c0p, kLeakySlope, stream, (e->options & EXASPIM_OPT_FIRST_PER_GROUP) != 0));
     if (absmax) RUN(launch_absmax(dt, A(0), (size_t)n * d * h * w * p.c0p * dtype_size(dt), absmax, stream));
-    RUN(conv(0, A(0), nullptr, skip(0), 0));                      // x1
+    RUN(conv(0, A(0), nullptr, x1, 0));                           // x1
     for (int l = 1; l <= 4; ++l) {
         const ConvLayer& L0 = p.conv[2 * l - 1];
-        const void* prev = skip(l - 1);
+        const void* prev = l == 1 ? x1 : skip(l - 1);
         if (!fuse_pool[l - 1])
             RUN(launch_maxpool2(dt, prev, A(l), n, d >> (l - 1), h >> (l - 1), w >> (l - 1), L0.ca,
                                 stream));
-        RUN(conv(2 * l - 1, A(l), nullptr, B(l), l));
+        RUN(conv(2 * l - 1, l == 1 ? x1_pool : A(l), nullptr, B(l), l));
         RUN(conv(2 * l, B(l), nullptr, l < 4 ? skip(l) : A(l), l));  // x2..x4, x5 in A(4)
     }
     // decoder (unet3d.py:100-103): y = DoubleConv(cat[skip, up(prev)])
@@ -254,7 +305,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                                  (e->options & EXASPIM_OPT_PLAIN_UPSAMPLE) != 0,
                                  (e->options & EXASPIM_OPT_UPSAMPLE_PER_THREAD) != 0, ups_trimmed ? ups_hi : nullptr));
         }
-        RUN(conv(i0, skip(l), A(l), B(l), l));
+        RUN(conv(i0, l == 0 ? x1 : skip(l), A(l), B(l), l));
         RUN(conv(i0 + 1, B(l), nullptr, A(l), l));
         prev = A(l);
     }
@@ -464,6 +515,43 @@ extern "C" int exaspim_unet_forward_prepared_clipped(exaspim_unet* h, const void
                       size[i] - trim, trim, size[i]);
     return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
                    workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi);
+}
+
+extern "C" int exaspim_unet_carry_planes(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                         int32_t row_stride, int32_t shift_z, int32_t out[2]) {
+    EXA_CHECK_ARG(h && out, "carry_planes: NULL pointer");
+    out[0] = out[1] = 0;
+    EXA_CHECK_ARG(n > 0 && level_dims_ok(d, hgt, w) && row_stride >= 0 && shift_z > 0,
+                  "carry_planes: bad arguments (n %d, patch %dx%dx%d, row stride %d, shift %d)", n, d, hgt, w,
+                  row_stride, shift_z);
+    // the conditions under which forward() runs inc.3 in row mode
+    const UNetPlan& p = h->plan;
+    const bool fused = !(h->options & EXASPIM_OPT_SEPARATE_POOL) && conv_can_fuse_pool(p.dtype, p.conv[0].cout, d, hgt, w);
+    if ((h->options & EXASPIM_OPT_PER_PATCH_ENCODER) || !conv_row_mode_ok(p.dtype, p.conv[0].cout, n, w, row_stride, fused))
+        return EXASPIM_OK;
+    carry_span(d, shift_z, out);
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_unet_forward_prepared_carry(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                                   int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                                   int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                                   const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                                   void* workspace_dev, size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(h && x_prepared_dev && out_dev && workspace_dev && keep_hi && carry, "forward: NULL pointer");
+    EXA_CHECK_ARG(n > 0, "forward: empty batch");
+    EXA_CHECK_ARG(trim >= 0, "forward: negative trim %d", trim);
+    EXA_CHECK_ARG(row_stride >= 0, "forward: negative row stride %d", row_stride);
+    EXA_CHECK_ARG(level_dims_ok(d, hgt, w),
+                  "forward: patch %dx%dx%d: every dimension must be a positive multiple of 16",
+                  d, hgt, w);
+    const int size[3] = {d, hgt, w};
+    for (int i = 0; i < 3; ++i)
+        EXA_CHECK_ARG(keep_hi[i] > trim && keep_hi[i] <= size[i] - trim,
+                      "forward: keep_hi[%d] = %d outside (%d, %d] (trim %d of %d voxels)", i, keep_hi[i], trim,
+                      size[i] - trim, trim, size[i]);
+    return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
+                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi, carry);
 }
 
 extern "C" int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out_dev,

@@ -120,6 +120,40 @@ int probe_conv3x3x3_row(int dtype, const void* src, int ca, const void* weights,
     return launch_conv3x3x3_row(dtype, a, stages, stream);
 }
 
+// probe_conv3x3x3_row with planes carried along z (ConvArgs::in_z0 .. out_shift); carry[0..4] = in_z0, in_z1,
+// out_z0, out_z1, out_shift. 1 from probe_last_carry if the main launch ran conv3x3x3_zpipe_rowz.
+int probe_conv3x3x3_row_carry(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,
+                              int cout, int n, int d, int h, int w, float slope, int row_stride, void* pool_dst,
+                              const int32_t* carry, void* carry_dst, void* carry_pool_dst, int stages,
+                              hipStream_t stream) {
+    EXA_CHECK_ARG(carry != nullptr, "probe: NULL carry");
+    for (int i = 0; i < 5; ++i)   // (what ConvArgs' narrow fields hold)
+        EXA_CHECK_ARG(carry[i] >= 0 && carry[i] <= (i == 2 || i == 3 ? 254 : 65534), "probe: carry[%d] = %d out of range", i, carry[i]);
+    ConvArgs a{};
+    a.src_a = src;
+    a.ca = ca;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    a.row_stride = row_stride;
+    a.pool_dst = pool_dst;
+    a.in_z0 = (unsigned short)carry[0];
+    a.in_z1 = (unsigned short)carry[1];
+    a.out_z0 = (unsigned char)carry[2];
+    a.out_z1 = (unsigned char)carry[3];
+    a.out_shift = (unsigned short)carry[4];
+    a.carry_dst = carry_dst;
+    a.carry_pool_dst = carry_pool_dst;
+    return launch_conv3x3x3_row(dtype, a, stages, stream);
+}
+int probe_last_carry(void) { return last_conv_launch().carry ? 1 : 0; }
+
 int probe_conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, int fused_pool_whole_patch) {
     return conv_row_mode_ok(dtype, cout, n, w, row_stride, fused_pool_whole_patch != 0) ? 1 : 0;
 }

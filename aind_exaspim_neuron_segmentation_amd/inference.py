@@ -24,6 +24,7 @@ options are trailing keyword arguments. What differs is where the work runs:
 There is no CPU fallback: a model on a CPU device raises.
 """
 
+import collections
 import ctypes
 import itertools
 import threading
@@ -52,6 +53,8 @@ DEFAULT_STREAMS = 3
 # outside the calling code can flip them.
 PLAIN_GATHER = False    # True: gather float32 patches and let the engine pad them, instead of the prepared layout
 FULL_PATCHES = False    # True: compute the margin predict() discards as well (exaspim_unet_forward untrimmed)
+CARRY_Z = True          # False: every batch computes its whole first level (no planes carried from the z slab above)
+CARRY_POOL_BYTES = 24 << 30   # most device memory one run_sliding_window call may hold in carry buffers
 CLIP_TO_VOLUME = True   # False: also compute the trimmed outputs beyond the volume's high faces, which the stitch drops
 
 _VOX_CODES = {
@@ -1249,6 +1252,77 @@ def batch_row_stride(starts, patch_shape, overlap):
     return stride
 
 
+def carry_plan(starts, batch_size, patch_shape, overlap):
+    """
+    For every batch of the sliding window (starts cut into runs of batch_size), the index of the later
+    batch that can take first-level planes over from it, or None: the nearest later batch whose starts are
+    this batch's shifted by one positive z amount below the patch depth, with the same number of patches,
+    both of them rows along x of the same stride (batch_row_stride). Host-side, no device sync.
+    """
+    batch_size = int(batch_size)
+    batches = [starts[i:i + batch_size] for i in range(0, len(starts), batch_size)]
+    chains = {}     # (row stride, the row's (y, x) starts) -> [(z, batch index)]
+    for bi, b in enumerate(batches):
+        stride = batch_row_stride(b, patch_shape, overlap)
+        if stride > 0:
+            key = (stride, tuple((int(s[1]), int(s[2])) for s in b))
+            chains.setdefault(key, []).append((int(b[0][0]), bi))
+    succ = [None] * len(batches)
+    depth = int(patch_shape[0])
+    for members in chains.values():
+        for z, bi in members:
+            later = [(z2 - z, bj) for z2, bj in members if bj > bi and 0 < z2 - z < depth]
+            if later:
+                succ[bi] = min(later)[1]
+    return succ
+
+
+def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_streams, device):
+    """
+    The carry links run_sliding_window can use and the buffer pairs they need: (links, peak) with
+    links[bi] = (successor, shift, the successor's plane range) or None and peak = the pairs to allocate, or
+    (None, 0) when nothing can be carried or the buffers would not fit. peak is the most pairs alive at once
+    plus, with several streams, one per stream: pairs are handed out oldest first, so the pair a batch takes
+    was last read by the batch n_streams earlier -- the previous one on its own stream -- and the batches in
+    flight never wait for each other over a buffer.
+    """
+    links = [None] * len(succ)
+    spans = {}
+    for bi, bj in enumerate(succ):
+        if bj is None:
+            continue
+        own = starts[bi * batch_size:(bi + 1) * batch_size]
+        shift = int(starts[bj * batch_size][0]) - int(own[0][0])
+        stride = batch_row_stride(own, patch_shape, overlap)
+        key = (len(own), stride, shift)
+        if key not in spans:
+            spans[key] = model.carry_planes((len(own),) + tuple(patch_shape), stride, shift, device)
+        if spans[key][1] > spans[key][0]:
+            links[bi] = (bj, shift, spans[key])
+    if not any(links):
+        return None, 0
+    # pairs alive at once: a batch's pair lives from its predecessor's (or its own) forward to its own
+    has_pair, alive, peak = set(), 0, 0
+    for bi, link in enumerate(links):
+        if bi not in has_pair and link is not None:
+            has_pair.add(bi)
+            alive += 1
+        if link is not None:
+            has_pair.add(link[0])
+            alive += 1
+        peak = max(peak, alive)
+        if bi in has_pair:
+            alive -= 1
+    if n_streams > 1:
+        peak += int(n_streams)
+    skip_elems, pool_elems = model.carry_pair_elems((int(batch_size),) + tuple(patch_shape))
+    need = peak * 2 * (skip_elems + pool_elems)
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > CARRY_POOL_BYTES or need > free // 2:
+        return None, 0
+    return links, peak
+
+
 def batch_keep_hi(starts, patch_shape, trim, global_shape):
     """
     Per axis, the end of the trimmed outputs a batch of patch starts (global coordinates)
@@ -1596,6 +1670,26 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
     prepared_layout = None
     if isinstance(model, UNet3D) and not PLAIN_GATHER:
         prepared_layout = model.input_layout(device)    # (PLAIN_GATHER: tests hold the two paths to each other)
+    # first-level planes carried from one z slab of patches to the next
+    links, free_pairs = None, collections.deque()
+    if CARRY_Z and prepared_layout is not None and not model.needs_resolution():
+        links, peak = _carry_schedule(model, carry_plan(starts, batch_size, plan.patch_shape, plan.overlap), starts,
+                                      batch_size, plan.patch_shape, plan.overlap, n_streams, device)
+        if links is not None:
+            elems = model.carry_pair_elems((batch_size,) + tuple(plan.patch_shape))
+            # (allocated before the workers branch off the caller's stream; alive until the call returns)
+            free_pairs.extend([tuple(torch.empty(e, dtype=torch.int16, device=device) for e in elems), None]
+                              for _ in range(peak))
+            for s in workers:
+                s.wait_stream(main)
+    pending = {}     # batch index -> [its pair, the planes already there, its predecessor's event]
+
+    def take_pair(worker):
+        pair = free_pairs.popleft()     # (the one released longest ago)
+        if pair[1] is not None:     # the forward that read it last, maybe on another stream
+            worker.wait_event(pair[1])
+        return pair
+
     for bi, i in enumerate(range(0, len(starts), batch_size)):
         batch = starts_dev[i:i + batch_size]
         row_stride = batch_row_stride(starts[i:i + batch_size], plan.patch_shape, plan.overlap)
@@ -1608,9 +1702,29 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                 # the gather kernel writes the first convolution's operand layout directly
                 inputs = _get_batch_inputs(volume, batch, plan.patch_shape, device, clip=clip,
                                            mn=mn, mx=mx, layout=prepared_layout)
+                carry, own = None, None
+                if links is not None and (bi in pending or links[bi] is not None):
+                    own, in_z, before = pending.pop(bi, None) or (take_pair(worker), (0, 0), None)
+                    carry = {"own": own[0], "in_z": in_z}
+                    if before is not None:
+                        worker.wait_event(before)      # the planes carried in are there
+                    if links[bi] is not None:
+                        nxt, shift, span = links[bi]
+                        out_pair = take_pair(worker)
+                        carry.update(out=out_pair[0], out_z=(span[0] + shift, span[1] + shift), out_shift=shift)
+                        pending[nxt] = [out_pair, span, None]
                 pred = model.run_prepared(
                     inputs, (int(batch.shape[0]),) + tuple(plan.patch_shape), apply_sigmoid=True,
-                    trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride, keep_hi=keep_hi)
+                    trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride, keep_hi=keep_hi, carry=carry)
+                if own is not None:
+                    done = None
+                    if n_streams > 1:
+                        done = torch.cuda.Event()
+                        done.record(worker)
+                    if links[bi] is not None:
+                        pending[links[bi][0]][2] = done
+                    own[1] = done
+                    free_pairs.append(own)
             else:
                 inputs = _get_batch_inputs(volume, batch, plan.patch_shape, device, clip=clip,
                                            mn=mn, mx=mx)

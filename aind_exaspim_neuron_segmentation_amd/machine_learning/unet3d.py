@@ -430,7 +430,32 @@ class UNet3D(nn.Module):
             raise RuntimeError("exaspim_unet_input_layout failed")
         return int(code)
 
-    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0, row_stride=0, keep_hi=None):
+    def carry_planes(self, shape, row_stride, shift_z, device=None):
+        """
+        (z0, z1): the planes of its own frame that a row batch of patches "shape" = (B, D, H, W) can take
+        over from the same row shift_z planes up the volume (exaspim_unet_carry_planes: the first level's
+        skip tensor and its max-pool, whole z tiles away from the zero padding). (0, 0): none -- no row mode
+        at this geometry, compute dtype or option set.
+        """
+        device = next(self.parameters()).device if device is None else device
+        n, d, h, w = (int(v) for v in shape)
+        with torch.cuda.device(device):
+            self._ensure_engine(device)
+        span = (ctypes.c_int32 * 2)()
+        _native.check(
+            _native.lib().exaspim_unet_carry_planes(self._engine, n, d, h, w, int(row_stride), int(shift_z), span),
+            "exaspim_unet_carry_planes")
+        return int(span[0]), int(span[1])
+
+    def carry_pair_elems(self, shape):
+        """Elements (16-bit) of the two buffers a carrying forward of patches "shape" keeps its first-level
+        skip tensor and its max-pool in (run_prepared's carry["own"] / carry["out"])."""
+        n, d, h, w = (int(v) for v in shape)
+        c0p = -(-int(self.channels[0]) // 32) * 32
+        return n * d * h * w * c0p, n * (d // 2) * (h // 2) * (w // 2) * c0p
+
+    def run_prepared(self, prepared, shape, apply_sigmoid=False, out=None, trim=0, row_stride=0, keep_hi=None,
+                     carry=None):
         """
         run() from a batch the gather kernel has already written in the first
         convolution's operand layout (inference._get_batch_inputs(..., layout=
@@ -451,6 +476,12 @@ class UNet3D(nn.Module):
             Per axis, the caller keeps the trimmed outputs [trim, keep_hi) only
             (inference.batch_keep_hi: patches that reach beyond the volume). The rest is
             left unwritten like the trimmed margin; kept voxels have the same bits.
+        carry : dict, optional
+            Planes of the first level carried along z (exaspim_unet_forward_prepared_carry; same bits):
+            "own" = (skip, pool) device tensors of carry_pair_elems(shape) 16-bit elements this forward keeps
+            its first-level skip tensor and max-pool in, "in_z" = the plane range an earlier forward already
+            left there, and optionally "out" = the (skip, pool) of the batch "out_shift" planes further down
+            with "out_z", this forward's planes to store there. Raises where the engine cannot honour it.
         """
         if self.training:
             raise RuntimeError(
@@ -476,7 +507,31 @@ class UNet3D(nn.Module):
                 out = torch.empty(
                     (n, self.output_channels, d, h, w), dtype=torch.float32, device=device
                 )
-            if keep_hi is not None:
+            if carry is not None:
+                desc = _native.UNetCarry()
+                need = self.carry_pair_elems(shape)
+                pairs = [carry["own"]] + ([carry["out"]] if carry.get("out") is not None else [])
+                for pair in pairs:
+                    for t, elems in zip(pair, need):
+                        if not t.is_cuda or t.element_size() != 2 or t.numel() < elems or not t.is_contiguous():
+                            raise RuntimeError("carry buffers must be contiguous 16-bit device tensors of "
+                                               f"{need} elements")
+                desc.own_skip, desc.own_pool = carry["own"][0].data_ptr(), carry["own"][1].data_ptr()
+                desc.in_z[:] = [int(v) for v in carry.get("in_z", (0, 0))]
+                if carry.get("out") is not None:
+                    desc.out_skip, desc.out_pool = carry["out"][0].data_ptr(), carry["out"][1].data_ptr()
+                    desc.out_z[:] = [int(v) for v in carry["out_z"]]
+                    desc.out_shift = int(carry["out_shift"])
+                hi = keep_hi if keep_hi is not None else (d - int(trim), h - int(trim), w - int(trim))
+                _native.check(
+                    _native.lib().exaspim_unet_forward_prepared_carry(
+                        self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
+                        1 if apply_sigmoid else 0, int(trim), int(row_stride), _native.int3(hi),
+                        ctypes.byref(desc), ws.data_ptr(), ws.numel(), stream,
+                    ),
+                    "exaspim_unet_forward_prepared_carry",
+                )
+            elif keep_hi is not None:
                 _native.check(
                     _native.lib().exaspim_unet_forward_prepared_clipped(
                         self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,

@@ -45,7 +45,9 @@ extern "C" {
  *    later within 5: exaspim_components_stream_slab / _finish / _apply and their workspace queries
  *    (struct exaspim_components_stream): the components of a volume that arrives in z slabs;
  *    later within 5: exaspim_region_graph (and its workspace query), exaspim_agglomerate,
- *    exaspim_apply_label_table: mean-affinity agglomeration of components */
+ *    exaspim_apply_label_table: mean-affinity agglomeration of components;
+ *    later within 5: exaspim_unet_carry_planes, exaspim_unet_forward_prepared_carry (struct
+ *    exaspim_unet_carry): first-level planes carried from one z slab of patches to the next */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -211,6 +213,44 @@ int exaspim_unet_forward_prepared_clipped(exaspim_unet* h, const void* x_prepare
                                           int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
                                           const int32_t keep_hi[3], void* workspace_dev,
                                           size_t workspace_bytes, void* stream);
+
+/* Planes of the first level carried along z. A row batch whose patches start shift_z planes below an
+ * earlier row batch (same x and y starts, same n and row_stride) computes, away from its own zero
+ * padding, the bits that batch computed for x1 (inc.3's output) and its max-pool: its planes
+ * [2, d - shift_z - 2) are the earlier batch's [2 + shift_z, d - 2).
+ * exaspim_unet_carry_planes: out[0..1] = the plane range [z0, z1) of the LATER batch's frame that a forward
+ * at this geometry can take over: the whole tiles of the depth inc.3's launcher picks inside that span,
+ * even bounds. Empty (z0 = z1 = 0) when the engine has no row mode here (dtype, geometry, options, no
+ * fused max-pool) or nothing fits. EXASPIM_E_INVALID for bad arguments. For d = 96, shift_z = 64: [6, 30). */
+int exaspim_unet_carry_planes(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                              int32_t row_stride, int32_t shift_z, int32_t out[2]);
+/* own_skip / own_pool: where x1 (n, c0p, d, hgt, w) and its max-pool (n, c0p, d/2, hgt/2, w/2) live for
+ * this forward, in the workspace's channels-last chunk layout and storage type, instead of inside the
+ * workspace. Both required; sizes n * d * hgt * w * c0p * (2 bytes) and an eighth of it, 256-byte aligned.
+ * in_z: the plane range already present in both (an earlier forward's carry out); {0, 0}: none.
+ * out_skip / out_pool (both or neither), out_z, out_shift: planes out_z of this forward's x1 are stored to
+ * out_skip too, at plane - out_shift, and their pooled planes to out_pool at pooled plane - out_shift / 2:
+ * the own_skip / own_pool of the batch out_shift planes further down, with in_z = out_z - out_shift. */
+typedef struct exaspim_unet_carry {
+    void* own_skip;
+    void* own_pool;
+    int32_t in_z[2];
+    void* out_skip;
+    void* out_pool;
+    int32_t out_z[2];
+    int32_t out_shift;
+    int32_t reserved;   /* 0 */
+} exaspim_unet_carry;
+/* exaspim_unet_forward_prepared_clipped with the first level's skip tensor and its max-pool in caller
+ * buffers and planes carried in and / or out; out_dev gets the same bits. A request the engine cannot
+ * honour (no row mode at this geometry, a range that exaspim_unet_carry_planes would not give, a missing
+ * buffer) is EXASPIM_E_INVALID before anything is launched: a silent fall-back would leave the successor
+ * reading planes nobody wrote. */
+int exaspim_unet_forward_prepared_carry(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                        int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                        int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                        const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Range probe for the 16-bit storage modes. The reference loads ANY trained state_dict
  * (inference.py:400-424) and runs it in float32; IEEE-half storage holds |v| <= 65504 (stores
