@@ -89,6 +89,25 @@ class ComponentsStreamDesc(ctypes.Structure):
     ]
 
 
+class RegionGraphStreamDesc(ctypes.Structure):
+    """exaspim_region_graph_stream: the caller-owned state of a slab-by-slab region graph."""
+
+    _fields_ = [
+        ("dims", ctypes.c_int32 * 3),
+        ("id_capacity", ctypes.c_int32),
+        ("edge_capacity", ctypes.c_int64),
+        ("next_z", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("keys_dev", ctypes.c_void_p),
+        ("counts_dev", ctypes.c_void_p),
+        ("sums_dev", ctypes.c_void_p),
+        ("sizes_by_id_dev", ctypes.c_void_p),
+        ("seam_ids_dev", ctypes.c_void_p),
+        ("seam_q_dev", ctypes.c_void_p),
+        ("state_dev", ctypes.c_void_p),
+    ]
+
+
 class UNetCarry(ctypes.Structure):
     """exaspim_unet_carry: the caller's buffers for the first level's skip tensor and its max-pool, the
     plane range already present in them and the range to store for the batch further down z."""
@@ -167,6 +186,11 @@ SIGNATURES = {
     "exaspim_region_graph_workspace_bytes": (_sz, [_I32x3, _i32, ctypes.c_int64]),
     "exaspim_region_graph": (_i32, [_vp, _vp, _i32, _I32x3, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _sz, _vp]),
+    "exaspim_region_graph_stream_slab": (_i32, [ctypes.POINTER(RegionGraphStreamDesc), _vp, _vp, _i32, _I32x3, _i32,
+                                                _vp]),
+    "exaspim_region_graph_stream_finish_workspace_bytes": (_sz, [ctypes.c_int64]),
+    "exaspim_region_graph_stream_finish": (_i32, [ctypes.POINTER(RegionGraphStreamDesc), _vp, _i32, _i32, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_agglomerate": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, ctypes.c_float, ctypes.c_int64,
                                    _vp, _vp]),
     "exaspim_apply_label_table": (_i32, [_vp, _sz, _vp, _i32, _vp]),

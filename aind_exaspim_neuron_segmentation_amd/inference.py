@@ -916,6 +916,334 @@ def affinities_to_components_streaming(source, threshold=0.5, min_segment_size=1
     return result
 
 
+class RegionGraphStream:
+    """
+    region_graph for a volume that arrives in z slabs: every slab
+    is pushed with its labels -- provisional ids, e.g. ComponentsStream's --
+    and its affinities while both sit on the device; finish() maps the ids
+    through a table and returns the region graph of the final labels, bit for
+    bit what region_graph gives on table[labels] of the whole volume, which
+    may have more than 2^31 - 1 voxels and never has to be anywhere in one
+    piece.
+
+        cs = ComponentsStream((D, H, W), fragment_threshold, 0)
+        rgs = RegionGraphStream((D, H, W))
+        for slab in slabs_in_z_order:              # (3, d, H, W) device tensors
+            rgs.push(cs.push(slab), slab)
+        table, k = cs.finish()
+        edges, counts, sums, sizes = rgs.finish(table, k)
+
+    Two planes are carried from slab to slab, the last plane's ids and its
+    quantised z affinities: ComponentsStream's own seam plane has already
+    moved on to the current slab when the graph sees it.
+
+    Parameters
+    ----------
+    shape : Tuple[int]
+        (D, H, W) of the whole volume; H * W and every slab must stay within
+        2^31 - 1 voxels, D * H * W need not.
+    device : torch.device, optional
+        Default is cuda:0.
+    id_capacity : int, optional
+        The largest id that counts (1 .. 2^31 - 2): labels beyond it are
+        counted nowhere. 8 bytes of device memory per id. Default:
+        DEFAULT_ID_CAPACITY (2^24), or the number of voxels if that is less,
+        as in ComponentsStream.
+    edge_capacity : int, optional
+        Slots of the accumulator, a power of two; 24 bytes each, and as many
+        again while finish() runs. It holds pairs of PROVISIONAL ids: a slab
+        cannot know that two of its ids belong to one fragment, so shallow
+        slabs need more slots than the final graph has edges. Default is the
+        smaller of 2^22 and the next power of two >= 6 * D * H * W.
+    """
+
+    def __init__(self, shape, *, device=None, id_capacity=None, edge_capacity=None):
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"shape must be a non-empty (D, H, W), got {shape}")
+        if shape[1] * shape[2] > 2**31 - 1:
+            raise ValueError(f"a plane of {shape[1]} x {shape[2]} voxels exceeds 2^31 - 1")
+        device = torch.device("cuda:0" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError(f"RegionGraphStream (MI355X) has no CPU path: it needs a HIP device, got {device}")
+        voxels = shape[0] * shape[1] * shape[2]
+        if id_capacity is None:
+            id_capacity = min(DEFAULT_ID_CAPACITY, voxels)
+        id_capacity = int(id_capacity)
+        if not 1 <= id_capacity <= 2**31 - 2:
+            raise ValueError(f"id_capacity must be 1 .. 2^31 - 2, got {id_capacity}")
+        edge_capacity = _default_edge_capacity(voxels) if edge_capacity is None else int(edge_capacity)
+        if not 1 <= edge_capacity <= 1 << 30 or edge_capacity & (edge_capacity - 1):
+            raise ValueError(f"edge_capacity must be a power of two in 1 .. 2^30, got {edge_capacity}")
+        self.shape, self.device = shape, device
+        self.id_capacity, self.edge_capacity = id_capacity, edge_capacity
+        plane = shape[1] * shape[2]
+        with torch.cuda.device(device):
+            self.keys = torch.empty(edge_capacity, dtype=torch.int64, device=device)     # uint64 bits
+            self.counts = torch.empty(edge_capacity, dtype=torch.int64, device=device)
+            self.sums = torch.empty(edge_capacity, dtype=torch.int64, device=device)
+            self.sizes_by_id = torch.empty(id_capacity + 1, dtype=torch.int64, device=device)
+            self.seam_ids = torch.empty(plane, dtype=torch.int32, device=device)
+            self.seam_q = torch.empty(plane, dtype=torch.int32, device=device)            # uint32 bits
+            self.state = torch.zeros(2, dtype=torch.int32, device=device)
+        d = self.desc = _native.RegionGraphStreamDesc()
+        d.dims[:] = shape
+        d.id_capacity, d.edge_capacity, d.next_z = id_capacity, edge_capacity, 0
+        d.keys_dev, d.counts_dev, d.sums_dev = self.keys.data_ptr(), self.counts.data_ptr(), self.sums.data_ptr()
+        d.sizes_by_id_dev = self.sizes_by_id.data_ptr()
+        d.seam_ids_dev, d.seam_q_dev = self.seam_ids.data_ptr(), self.seam_q.data_ptr()
+        d.state_dev = self.state.data_ptr()
+
+    @property
+    def next_z(self):
+        """Planes pushed so far."""
+        return int(self.desc.next_z)
+
+    def push(self, labels, slab, z0=None):
+        """
+        Adds the next slab to the graph. Nothing is synchronised.
+
+        Parameters
+        ----------
+        labels : torch.Tensor
+            int32 (d, H, W) on the stream's device: the slab's ids.
+        slab : torch.Tensor
+            float32 or float16 (3, d, H, W) on the same device, planes
+            [next_z, next_z + d).
+        z0 : int, optional
+            The slab's first plane, checked against next_z. Default: next_z.
+        """
+        if not isinstance(labels, torch.Tensor) or not isinstance(slab, torch.Tensor):
+            raise TypeError(f"push needs torch tensors, got {type(labels).__name__} and {type(slab).__name__}")
+        if labels.dtype != torch.int32:
+            raise TypeError(f"labels must be int32, got {labels.dtype}")
+        if slab.dtype not in _AFF_CODES:
+            raise TypeError(f"slab must be float32 or float16, got {slab.dtype}")
+        if labels.device != self.device or slab.device != self.device:
+            raise RuntimeError(f"labels are on {labels.device} and the slab on {slab.device}, the stream on "
+                               f"{self.device}")
+        if slab.dim() != 4 or slab.shape[0] != 3:
+            raise ValueError(f"slab must be (3, d, H, W), got {tuple(slab.shape)}; "
+                             "a foreground map has no affinities to score")
+        dims = tuple(int(v) for v in slab.shape[-3:])
+        if tuple(labels.shape) != dims:
+            raise ValueError(f"labels must be (d, H, W) = {dims}, got {tuple(labels.shape)}")
+        if min(dims) < 1:
+            raise ValueError(f"empty slab {dims}")
+        labels, slab = labels.contiguous(), slab.contiguous()
+        with torch.cuda.device(self.device):
+            _native.check(
+                _native.lib().exaspim_region_graph_stream_slab(
+                    ctypes.byref(self.desc), labels.data_ptr(), slab.data_ptr(), _AFF_CODES[slab.dtype],
+                    _native.int3(dims), self.next_z if z0 is None else int(z0), _stream(self.device)),
+                "exaspim_region_graph_stream_slab",
+            )
+
+    def finish(self, table, n_labels):
+        """
+        After the last slab: the region graph of table[ids]. Reads the edge
+        count and the overflow flag, once (this synchronises). The accumulated
+        graph of ids is left as it is, so finish may be called again with
+        another table.
+
+        Parameters
+        ----------
+        table : torch.Tensor or numpy.ndarray
+            int32 (n,): id -> final label; ids at or beyond n are background.
+        n_labels : int
+            Final labels are 1 .. n_labels; what the table maps elsewhere
+            forms no edge and counts as background.
+
+        Returns
+        -------
+        edges, counts, sums, sizes
+            As region_graph returns them, sorted by (lo, hi).
+
+        Raises
+        ------
+        RuntimeError
+            If the slabs had more distinct pairs of adjacent ids than
+            edge_capacity.
+        """
+        if isinstance(table, np.ndarray):
+            if table.dtype != np.dtype(np.int32):
+                raise TypeError(f"table must be int32, got {table.dtype}")
+            table = torch.from_numpy(np.ascontiguousarray(table)).to(self.device)
+        if not isinstance(table, torch.Tensor):
+            raise TypeError(f"table must be a torch tensor or a numpy array, got {type(table).__name__}")
+        if table.dtype != torch.int32 or table.dim() != 1 or table.numel() < 1:
+            raise TypeError(f"table must be a non-empty 1-D int32 tensor, got {table.dtype} {tuple(table.shape)}")
+        if table.device != self.device:
+            raise RuntimeError(f"table is on {table.device}, the stream on {self.device}")
+        n_labels = int(n_labels)
+        if n_labels < 0:
+            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+        if self.next_z != self.shape[0]:
+            raise RuntimeError(f"RegionGraphStream: finish() after {self.next_z} of {self.shape[0]} planes")
+        table = table.contiguous()
+        capacity = self.edge_capacity
+        lib = _native.lib()
+        need = lib.exaspim_region_graph_stream_finish_workspace_bytes(capacity)
+        if need == 0:
+            raise ValueError(_native.last_error())
+        with torch.cuda.device(self.device):
+            edges = torch.empty((capacity, 2), dtype=torch.int32, device=self.device)
+            counts = torch.empty(capacity, dtype=torch.int64, device=self.device)
+            sums = torch.empty(capacity, dtype=torch.int64, device=self.device)   # uint64 bits
+            sizes = torch.empty(n_labels + 1, dtype=torch.int64, device=self.device)
+            state = torch.empty(2, dtype=torch.int32, device=self.device)
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _native.check(
+                lib.exaspim_region_graph_stream_finish(
+                    ctypes.byref(self.desc), table.data_ptr(), min(table.numel(), 2**31 - 1), n_labels,
+                    edges.data_ptr(), counts.data_ptr(), sums.data_ptr(), sizes.data_ptr(), state.data_ptr(),
+                    workspace.data_ptr(), need, _stream(self.device)),
+                "exaspim_region_graph_stream_finish",
+            )
+            n_edges, overflow = (int(v) for v in state.cpu())   # the one read of the device state
+            if overflow:
+                raise RuntimeError(
+                    f"RegionGraphStream: the slabs have more pairs of adjacent provisional ids than "
+                    f"edge_capacity={capacity}. Shallow slabs need more slots than the final graph has edges: "
+                    "two ids of one fragment look like two fragments until finish. Run it again with a larger "
+                    "edge_capacity (a power of two) or deeper slabs")
+            edges_h = edges[:n_edges].cpu().numpy()
+            counts_h = counts[:n_edges].cpu().numpy()
+            sums_h = sums[:n_edges].cpu().numpy().view(np.uint64)
+            sizes_h = sizes.cpu().numpy()
+        order = np.lexsort((edges_h[:, 1], edges_h[:, 0]))   # slot order depends on arrival: sort by (lo, hi)
+        return (np.ascontiguousarray(edges_h[order]), np.ascontiguousarray(counts_h[order]),
+                np.ascontiguousarray(sums_h[order]), sizes_h)
+
+
+class _ComposedTable:
+    """What _relabel_host_array needs of a ComponentsStream, for the table segment[fragment[id]]."""
+
+    def __init__(self, device, table):
+        self.device, self.table = device, table
+
+    def apply(self, labels):
+        with torch.cuda.device(self.device):
+            _native.check(
+                _native.lib().exaspim_apply_label_table(labels.data_ptr(), labels.numel(), self.table.data_ptr(),
+                                                        self.table.numel(), _stream(self.device)),
+                "exaspim_apply_label_table",
+            )
+        return labels
+
+
+def _agglomerate_streams(cs, rgs, thresholds, min_segment_size):
+    """
+    After the last slab of both streams: the fragments' graph, its merging on
+    the host, and the table provisional id -> segment, composed on the device
+    by sending the fragment table itself through the segment table.
+
+    Returns
+    -------
+    composed : _ComposedTable
+        composed.table is int32 (ids_used + 1,) on the device.
+    count : int
+        S, the number of kept segments.
+    """
+    fragment_table, n_fragments = cs.finish()
+    edges, counts, sums, sizes = rgs.finish(fragment_table[: cs.ids_used + 1], n_fragments)
+    segment_table, n_segments = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
+    device = cs.device
+    with torch.cuda.device(device):
+        composed = _ComposedTable(device, torch.from_numpy(segment_table).to(device))
+        table = composed.apply(fragment_table[: cs.ids_used + 1].clone())
+    return _ComposedTable(device, table), n_segments
+
+
+def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
+                                     fragment_threshold=0.5, slab_depth, write_block=None, id_capacity=None,
+                                     edge_capacity=None, device=None, keep_labels_resident=None):
+    """
+    agglomerate_affinities for affinities that sit in a host array, a memmap
+    or a zarr-like array too large for the device (or for 2^31 - 1 voxels):
+    z slabs of "slab_depth" planes are uploaded one after the other, each is
+    labelled (ComponentsStream with no size filter) and added to the region
+    graph of provisional ids (RegionGraphStream) while it sits on the device;
+    at the end the graph of fragments is merged on the host and the
+    provisional labels go through the composed table segment[fragment[id]]
+    once. The result equals agglomerate_affinities on the whole volume, bit
+    for bit.
+
+    Parameters
+    ----------
+    source : array-like
+        float32 or float16 (3, D, H, W); only source[..., z0:z1, :, :] is ever
+        read. A foreground map has no affinities to score.
+    agglomeration_thresholds, min_segment_size, fragment_threshold
+        As in agglomerate_affinities.
+    slab_depth : int
+        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
+    write_block : Callable[[int, int, numpy.ndarray], None], optional
+        Receives every slab once, in z order, as write_block(z0, z1, block)
+        with block int32 (z1 - z0, H, W) of PROVISIONAL ids; the function then
+        returns the table that maps them to segment labels.
+    id_capacity : int, optional
+        See ComponentsStream.
+    edge_capacity : int, optional
+        See RegionGraphStream.
+    device : torch.device, optional
+        Default is cuda:0.
+    keep_labels_resident : bool, optional
+        As in affinities_to_components_streaming.
+
+    Returns
+    -------
+    numpy.ndarray
+        int32 (D, H, W) segment labels; or, with "write_block", the tuple
+        (table, S): table int32 with segment = table[provisional], S kept
+        segments.
+    """
+    thresholds = list(agglomeration_thresholds)
+    _last_threshold(thresholds)
+    if not hasattr(source, "shape") or not hasattr(source, "dtype"):
+        source = np.asarray(source)
+    if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise TypeError(f"affinities must be float32 or float16, got {source.dtype}")
+    shape = tuple(int(v) for v in source.shape)
+    if len(shape) != 4 or shape[0] != 3:
+        raise ValueError(f"agglomerate_affinities_streaming needs (3, D, H, W) affinities, got {shape}; "
+                         "a foreground map has no affinities to score")
+    vshape = shape[-3:]
+    slab_depth = int(slab_depth)
+    if slab_depth < 1:
+        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("agglomerate_affinities_streaming (MI355X) has no CPU path and no HIP device is present")
+    cs = ComponentsStream(vshape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
+    device = cs.device
+    rgs = RegionGraphStream(vshape, device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
+    with torch.cuda.device(device):
+        if keep_labels_resident is None:
+            keep_labels_resident = _labels_fit_on_device(device, vshape)
+        resident = result = None
+        if write_block is None:
+            if keep_labels_resident:
+                resident = torch.empty(vshape, dtype=torch.int32, device=device)
+            else:
+                result = np.empty(vshape, dtype=np.int32)
+        for z0 in range(0, vshape[0], slab_depth):
+            z1 = min(z0 + slab_depth, vshape[0])
+            slab = _carrier(np.asarray(source[..., z0:z1, :, :])).to(device)
+            labels = cs.push(slab, z0, None if resident is None else resident[z0:z1])
+            rgs.push(labels, slab, z0)
+            if write_block is not None:
+                write_block(z0, z1, labels.cpu().numpy())
+            elif result is not None:
+                result[z0:z1] = labels.cpu().numpy()
+        composed, count = _agglomerate_streams(cs, rgs, thresholds, min_segment_size)
+        if write_block is not None:
+            return composed.table.cpu().numpy(), count
+        if resident is not None:
+            return composed.apply(resident).cpu().numpy()
+        _relabel_host_array(composed, result, slab_depth)
+    return result
+
+
 def _predict_batch(img, model, starts, patch_shape, trim=8, *, clip=None, mn=0.0, mx=1.0):
     """
     Extracts a batch of 3D patches from a device-resident volume, runs them
@@ -2543,4 +2871,121 @@ def predict_components_streaming(
             out = result
     if timings is not None:
         timings["components_finish"] = time.perf_counter() - t0
+    return out
+
+
+def predict_agglomerate_streaming(
+    source,
+    model,
+    agglomeration_thresholds=[0.6, 0.8, 0.9],
+    min_segment_size=100,
+    batch_size=16,
+    brightness_clip=1000,
+    normalization_percentiles=(1, 99.9),
+    patch_shape=(96, 96, 96),
+    overlap=(32, 32, 32),
+    trim=8,
+    verbose=True,
+    *,
+    fragment_threshold=0.5,
+    affinity_mode=True,
+    shape=None,
+    dtype=None,
+    write_block=None,
+    keep_input_resident=None,
+    n_streams=DEFAULT_STREAMS,
+    copy_threads=4,
+    timings=None,
+    id_capacity=None,
+    edge_capacity=None,
+    keep_labels_resident=None,
+):
+    """
+    predict_streaming followed by agglomerate_affinities without the
+    affinities ever leaving the device: every finished, divided slab is
+    labelled (ComponentsStream with no size filter) and added to the region
+    graph of provisional ids (RegionGraphStream) right where
+    predict_streaming would have started its download, and only int32 labels
+    travel. The result equals, bit for bit,
+    agglomerate_affinities(predict_streaming(...), agglomeration_thresholds,
+    min_segment_size, fragment_threshold=fragment_threshold) on the whole
+    volume, which neither the device nor this function ever holds as
+    affinities.
+
+    Parameters
+    ----------
+    source, model
+        As in predict_streaming.
+    agglomeration_thresholds, min_segment_size, fragment_threshold
+        As in agglomerate_affinities.
+    batch_size, brightness_clip, normalization_percentiles, patch_shape,
+    overlap, trim, verbose, shape, dtype, keep_input_resident, n_streams,
+    copy_threads, timings
+        As in predict_streaming; "timings" also gets "agglomerate_finish", the
+        wall seconds from the last slab to the final labels.
+    affinity_mode : bool, optional
+        Must be True: a foreground map has no affinities to score.
+    write_block : Callable[[int, int, numpy.ndarray], None], optional
+        Receives every slab once, in z order, as write_block(z0, z1, block)
+        with block int32 (z1 - z0, H, W) of PROVISIONAL ids, valid during the
+        call only; the function then returns the table that maps them to
+        segment labels.
+    id_capacity : int, optional
+        See ComponentsStream.
+    edge_capacity : int, optional
+        See RegionGraphStream.
+    keep_labels_resident : bool, optional
+        As in predict_components_streaming.
+
+    Returns
+    -------
+    numpy.ndarray
+        int32 (D, H, W) segment labels; or, with "write_block", the tuple
+        (table, S): table int32 with segment = table[provisional], S kept
+        segments.
+    """
+    thresholds = list(agglomeration_thresholds)
+    _last_threshold(thresholds)
+    if not affinity_mode:
+        raise ValueError("predict_agglomerate_streaming needs affinity_mode=True: "
+                         "a foreground map has no affinities to score")
+    device = _hip_device(model)
+    volume = _open_volume(source, shape, dtype)
+    vshape = volume[1]
+    cs = ComponentsStream(vshape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
+    rgs = RegionGraphStream(vshape, device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
+    keep = keep_labels_resident
+    if write_block is not None:
+        keep = False
+    elif keep is None:
+        keep = _labels_fit_on_device(device, vshape)
+    resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
+    result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
+    plane = vshape[1] * vshape[2]
+
+    def label(z0, z1, out, slot):
+        if resident is not None:
+            rgs.push(cs.push(out, z0, resident[z0:z1]), out, z0)
+            return None
+        labels = cs.push(out, z0, slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2]))
+        rgs.push(labels, out, z0)
+        return labels.view((1,) + tuple(labels.shape))
+
+    _stream_whole_volume(volume, model, True, batch_size, brightness_clip, normalization_percentiles,
+                         patch_shape, overlap, trim, verbose, n_streams, np.float32, write_block, result=result,
+                         label=label, copy_threads=copy_threads, keep_input_resident=keep_input_resident,
+                         timings=timings)
+    t0 = time.perf_counter()
+    with torch.cuda.device(device):
+        composed, count = _agglomerate_streams(cs, rgs, thresholds, min_segment_size)
+        if write_block is not None:
+            out = composed.table.cpu().numpy(), count
+        elif resident is not None:
+            out = composed.apply(resident).cpu().numpy()
+        else:
+            planes = max(1, PINNED_SLOT_BYTES // (4 * vshape[1] * vshape[2]))
+            _relabel_host_array(composed, result, planes)
+            out = result
+    if timings is not None:
+        timings["agglomerate_finish"] = time.perf_counter() - t0
     return out

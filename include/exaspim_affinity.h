@@ -47,7 +47,9 @@ extern "C" {
  *    later within 5: exaspim_region_graph (and its workspace query), exaspim_agglomerate,
  *    exaspim_apply_label_table: mean-affinity agglomeration of components;
  *    later within 5: exaspim_unet_carry_planes, exaspim_unet_forward_prepared_carry (struct
- *    exaspim_unet_carry): first-level planes carried from one z slab of patches to the next */
+ *    exaspim_unet_carry): first-level planes carried from one z slab of patches to the next;
+ *    later within 5: exaspim_region_graph_stream_slab / _finish and the finish workspace query (struct
+ *    exaspim_region_graph_stream): the region graph of a volume that arrives in z slabs */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -543,6 +545,84 @@ int exaspim_region_graph(const int32_t* labels_dev, const void* aff_dev, int32_t
                          const int32_t dims[3], int32_t n_labels, int64_t edge_capacity,
                          int32_t* edges_dev, int64_t* count_dev, uint64_t* sum_dev, int64_t* sizes_dev,
                          int32_t* n_edges_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- the same region graph for a volume that arrives in z slabs ---------------
+ *      (later within ABI 5). The slabs [z0, z1) of a dims[0] x dims[1] x dims[2] volume are
+ *      pushed in z order, each with its int32 labels -- "provisional ids", any values, typically what
+ *      exaspim_components_stream_slab wrote -- and its (3, z1 - z0, dims[1], dims[2]) affinities, while
+ *      both sit on the device. The volume may have more than 2^31 - 1 voxels; a slab and a plane may not.
+ *
+ *      slab    every voxel edge inside the slab contributes under exaspim_region_graph's rule (both
+ *              labels in 1 .. id_capacity, la != lb: key = (min, max), count += 1, sum += q(a)); the z
+ *              entries of the slab's last plane form no edge inside the slab. For every (y, x) the edge
+ *              from plane z0 - 1 to plane z0 contributes under the same rule with the carried id of the
+ *              previous slab's last plane, this slab's first-plane id and the carried q of the previous
+ *              slab's channel-0 value there. Two planes are carried from slab to slab: int32 ids and
+ *              uint32 q. The volume's last plane carries nothing: its z entries are ignored whatever
+ *              they hold. The same pass adds to sizes_by_id[0 .. id_capacity], 64-bit voxel counts; a
+ *              label outside 0 .. id_capacity is counted nowhere and never becomes an address.
+ *      finish  given any int32 table[0 .. table_len - 1] from provisional id to final label and
+ *              n_labels: every accumulated key (a, b) becomes (table[a], table[b]); a key with an id at
+ *              or beyond table_len, with equal ends or with an end outside 1 .. n_labels is dropped;
+ *              equal final keys add their counts and sums; sizes[table[id]] += sizes_by_id[id] for ids
+ *              inside the table, ids outside it or mapped outside 0 .. n_labels go to sizes[0]. The
+ *              accumulator is only read, so finish may be called again with another table. Id 0 is the
+ *              background of every table: it forms no edge whatever table[0] holds (label tables have
+ *              table[0] = 0, and the equality below is stated for those).
+ *
+ *      After sorting by (lo, hi) the output equals exaspim_region_graph(table[labels], aff, n_labels) on
+ *      the whole volume bit for bit, for every list of cuts: a pure function of the volume and the table.
+ *      All state is the caller's: this descriptor (host memory) and the device buffers it points to.
+ *      Fill every field, next_z = 0, and keep them until the last finish. */
+typedef struct exaspim_region_graph_stream {
+    int32_t dims[3];           /* the whole volume (z, y, x); dims[1] * dims[2] <= 2^31 - 1          */
+    int32_t id_capacity;       /* the largest provisional id that counts, 1 .. 2^31 - 2              */
+    int64_t edge_capacity;     /* slots of the accumulator: a power of two in 1 .. 2^30              */
+    int32_t next_z;            /* planes pushed so far: 0 to start, advanced by slab                 */
+    int32_t reserved;          /* 0                                                                  */
+    uint64_t* keys_dev;        /* uint64[edge_capacity]: the accumulator's keys (provisional ids)    */
+    uint64_t* counts_dev;      /* uint64[edge_capacity]: its counts                                  */
+    uint64_t* sums_dev;        /* uint64[edge_capacity]: its sums                                    */
+    int64_t* sizes_by_id_dev;  /* int64[id_capacity + 1]: voxels per provisional id                  */
+    int32_t* seam_ids_dev;     /* int32[dims[1] * dims[2]]: the last pushed plane's ids              */
+    uint32_t* seam_q_dev;      /* uint32[dims[1] * dims[2]]: q of its z affinities                   */
+    int32_t* state_dev;        /* int32[2]: [1] = the accumulator's overflow flag                    */
+} exaspim_region_graph_stream;
+
+/* Pushes planes [z0, z0 + slab_dims[0]): labels_dev (int32, slab_dims) and aff_dev ((3, slab_dims) of
+ * aff_dtype, EXASPIM_AFF_*), both contiguous. z0 = 0 starts a new volume: the accumulator, sizes_by_id and
+ * the state are reset on the stream. Then, each a launch of its own: the seam above the slab, the slab's
+ * tiles (exaspim_region_graph's kernel), the carried planes. Needs z0 == st->next_z, slab_dims[1:] equal
+ * to st->dims[1:], z0 + slab_dims[0] <= st->dims[0]; then advances st->next_z. More distinct keys than
+ * edge_capacity: the contributions that find no slot are dropped and state_dev[1] becomes 1, which finish
+ * hands on. Shallow slabs need more slots than the final graph has edges: a slab cannot know that two of
+ * its ids belong to one fragment. Launches on "stream" only; no lock, no inter-workgroup waiting, nothing
+ * allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL or misaligned pointer (the descriptor's
+ * 64-bit buffers 8 bytes, its int32 buffers and labels_dev 4, aff_dev its element), an unknown aff_dtype,
+ * a dim that is not positive, a plane or a slab of more than 2^31 - 1 voxels, an id_capacity outside
+ * 1 .. 2^31 - 2, an edge_capacity that is not a power of two in 1 .. 2^30, a slab out of order, of another
+ * (y, x) shape or beyond the volume: all before anything is launched and with st unchanged. */
+int exaspim_region_graph_stream_slab(exaspim_region_graph_stream* st, const int32_t* labels_dev,
+                                     const void* aff_dev, int32_t aff_dtype, const int32_t slab_dims[3],
+                                     int32_t z0, void* stream);
+
+/* Scratch bytes of the finish call: a second table of edge_capacity slots, 24 bytes each, plus 4 bytes per
+ * 2048 slots. 0 (and a message) if edge_capacity is not a power of two in 1 .. 2^30. */
+size_t exaspim_region_graph_stream_finish_workspace_bytes(int64_t edge_capacity);
+
+/* After the last slab (st->next_z == st->dims[0], else EXASPIM_E_INVALID), any number of times: the region
+ * graph under table_dev (int32, table_len >= 1 entries) and n_labels >= 0, in exaspim_region_graph's output
+ * format: edges_dev / count_dev / sum_dev hold st->edge_capacity entries, the first E in an unspecified
+ * order are written, sizes_dev has n_labels + 1 entries, n_edges_dev[0] = E, n_edges_dev[1] = 1 if the
+ * accumulator or the second table overflowed (the output is then unusable). Launches on "stream" only.
+ * workspace_dev: 16-byte aligned, exaspim_region_graph_stream_finish_workspace_bytes(st->edge_capacity)
+ * bytes, EXASPIM_E_WORKSPACE below that; EXASPIM_E_INVALID for a NULL or misaligned pointer, a bad
+ * descriptor, table_len < 1 or a negative n_labels: all before anything is launched. */
+int exaspim_region_graph_stream_finish(const exaspim_region_graph_stream* st, const int32_t* table_dev,
+                                       int32_t table_len, int32_t n_labels, int32_t* edges_dev,
+                                       int64_t* count_dev, uint64_t* sum_dev, int64_t* sizes_dev,
+                                       int32_t* n_edges_dev, void* workspace_dev, size_t workspace_bytes,
+                                       void* stream);
 
 /* Host only (no device is touched). Merges the fragments 1 .. n_labels of a region graph and numbers
  * what is left: table[0 .. n_labels] (int32), table[0] = 0, *n_segments = S.
