@@ -124,6 +124,24 @@ class UNetCarry(ctypes.Structure):
     ]
 
 
+class UNetCarry1(ctypes.Structure):
+    """exaspim_unet_carry1: the same for the second level -- down1.0's output, the level's skip tensor and its
+    max-pool, plane ranges in level-1 planes."""
+
+    _fields_ = [
+        ("own_mid1", ctypes.c_void_p),
+        ("own_skip1", ctypes.c_void_p),
+        ("own_pool2", ctypes.c_void_p),
+        ("in_z", ctypes.c_int32 * 2),
+        ("out_mid1", ctypes.c_void_p),
+        ("out_skip1", ctypes.c_void_p),
+        ("out_pool2", ctypes.c_void_p),
+        ("out_z", ctypes.c_int32 * 2),
+        ("out_shift", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 _I32x5 = ctypes.c_int32 * 5
@@ -157,6 +175,10 @@ SIGNATURES = {
     "exaspim_unet_forward_prepared_carry": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, ctypes.POINTER(UNetCarry), _vp,
                _sz, _vp]),
+    "exaspim_unet_carry1_planes": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_int32 * 2]),
+    "exaspim_unet_forward_prepared_carry1": (
+        _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, ctypes.POINTER(UNetCarry),
+               ctypes.POINTER(UNetCarry1), _vp, _sz, _vp]),
     "exaspim_unet_forward_absmax": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_unet_set_options": (_i32, [_vp, ctypes.c_uint32]),

@@ -222,7 +222,8 @@ struct ConvArgs {
     // row launch stores them (own frame and x neighbour), go to carry_dst as well, at plane - out_shift of
     // the same per-patch layout, and their pooled planes to carry_pool_dst at pooled plane - out_shift / 2:
     // the later batch whose patches start out_shift planes further down z finds them where it would have
-    // written them itself. Null: off. (These two take the place of two pointers that fed removed kernels:
+    // written them itself. Null: off. Outside row mode (conv3x3x3_t14_carry, the 16-bit 64-cout layers of level
+    // 1): the same per patch, carry_pool_dst exactly when pool_dst is set. (These two take the place of two pointers that fed removed kernels:
     // the kernel-argument block of every other convolution kernel keeps its layout and hence its code.)
     void* carry_dst = nullptr;
     void* carry_pool_dst = nullptr;
@@ -258,7 +259,7 @@ struct ConvArgs {
     // neighbour's two outermost x (and pooled x) whose inputs reach its zero padding. Those are left
     // for launch_conv3x3x3_thin and launch_maxpool2_xcols. 0: off.
     int row_stride = 0;
-    // Carry in (row mode): planes [in_z0, in_z1) of dst and their pooled planes of pool_dst are already
+    // Carry in (row mode, or conv3x3x3_t14_carry): planes [in_z0, in_z1) of dst and their pooled planes of pool_dst are already
     // there (an earlier launch's carry out). Whole z tiles of the depth the launcher picks, even bounds;
     // the tile walk leaves them out and nothing is written for them. Empty: off.
     unsigned short in_z0 = 0, in_z1 = 0;
@@ -285,7 +286,7 @@ struct ConvLaunchRecord {
     const char* config = "";
     int ksplit = 0;
     bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride) ...
-    bool carry = false;  // ... or conv3x3x3_zpipe_rowz (a carry field of ConvArgs set)
+    bool carry = false;  // ... or conv3x3x3_zpipe_rowz / conv3x3x3_t14_carry (a carry field of ConvArgs set)
 };
 ConvLaunchRecord& last_conv_launch();
 // The same for the inc.0 and upsampling launchers (layers.hip): the name of the kernel variant
@@ -332,6 +333,13 @@ constexpr int kRowStagesFused = kRowStageMain | kRowStageBorders;
 int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
 // Tile depth of the z-column kernel on a 32-cout slice of depth d without a fused head (launch_typed)
 int conv_zcol_tile_depth(int d);
+// Carried planes outside row mode (conv3x3x3_t14_carry): the tile depth if launch_conv3x3x3 runs this launch
+// (dtype, shape, channels, split-K scratch of a) on the configuration that has a carry symbol, else 0
+constexpr int kCarryT14TZ = 4;
+int conv_carry_t14_tile_depth(int dtype, const ConvArgs& a);
+// (engine.hip) the level-1 plane range a forward of depth d takes over from the one shift_z planes up, for tiles
+// of tz planes; {0, 0}: none
+void carry1_span_of_tiles(int tz, int d, int shift_z, int32_t out[2]);
 #ifndef EXASPIM_TRACE
 static_assert(sizeof(ConvArgs) == 184, "ConvArgs: the carry fields fill padding, the argument block keeps its size");
 #endif

@@ -177,12 +177,32 @@ static int launch_cfg(const ConvArgs& a, hipStream_t stream) {
     }
     TileGrid g;
     if (int rc = tile_grid(a, TZ, TY, TX, a.ext[2], a.n, g)) return rc;
-    const int tz = g.tz, ty = g.ty, tx = g.tx;
     ConvArgs b = a;
     b.ksplit = a.head_out ? 1 : choose_ksplit(a, g, a.cout / NWG, (a.ca + a.cb) / (2 * Tag::kG));   // (chunks)
+    // carried planes (ConvArgs::in_z0 .. out_shift): the one configuration with a carry symbol, never split;
+    // the z tiles already present are left out of the grid
+    constexpr bool kCarryCfg = Tag::kG == 8 && TZ == kCarryT14TZ && TY == 8 && TX == 16 && WAVES_M == 4 && WAVES_N == 1 &&
+                               MT == 4 && NT == 2 && MINW == 2 && PD == 3 && !ZORD;
+    const bool carry = conv_has_carry(a);
+    if (carry) {
+        EXA_CHECK_ARG(kCarryCfg && b.ksplit == 1, "conv: this launch has no carried planes (tile configuration%s)",
+                      b.ksplit > 1 ? ", split-K" : "");
+        g.tz -= (a.in_z1 - a.in_z0) / TZ;
+        g.blocks = (long long)g.tz * g.ty * g.tx * a.n;
+    }
+    const int tz = g.tz, ty = g.ty, tx = g.tx;
     const size_t nvox_all = (size_t)a.n * a.d * a.h * a.w;
     dim3 grid((unsigned)g.blocks, a.cout / NWG, b.ksplit);
     last_conv_launch() = {__PRETTY_FUNCTION__, b.ksplit};
+    if constexpr (kCarryCfg) {
+        if (carry) {
+            last_conv_launch().carry = true;
+            conv3x3x3_t14_carry<Tag, TZ, TY, TX, WAVES_M, WAVES_N, MT, NT, MINW, PD, POOL>
+                <<<grid, WAVES_M * WAVES_N * 64, 0, stream>>>(b, tz, ty, tx);
+            EXA_CHECK_HIP(hipGetLastError());
+            return EXASPIM_OK;
+        }
+    }
     if (POOL && b.ksplit > 1) {
         // a split layer's output exists only after the reduction: its max-pool stays a launch of
         // its own (tiny layers; the split is a function of the layer, so is this choice)
@@ -388,6 +408,19 @@ static int resolve_region(ConvArgs& a) {
 
 int conv_zcol_tile_depth(int d) { return d % 6 == 0 ? 6 : 4; }
 
+int conv_carry_t14_tile_depth(int dtype, const ConvArgs& a) {
+    // launch_typed sends a 64-cout slice on 16-wide rows to the 4 x 8 x 16 configuration of conv3x3x3_t14, the
+    // one launch_cfg has a carry symbol for; launch_cfg refuses carried planes on any other and on a split launch
+    if (dtype_size(dtype) != 2 || dtype == EXASPIM_DT_BF16X3 || a.head_out || a.row_stride != 0) return 0;
+    if (!(a.w >= 16 && a.w % 16 == 0 && a.cout % 64 == 0 && a.d % kCarryT14TZ == 0)) return 0;
+    ConvArgs b = a;
+    for (int i = 0; i < 3; ++i) b.org[i] = b.ext[i] = 0;
+    if (resolve_region(b) != EXASPIM_OK) return 0;
+    TileGrid g;
+    if (tile_grid(b, kCarryT14TZ, 8, 16, b.ext[2], b.n, g) != EXASPIM_OK) return 0;
+    return choose_ksplit(b, g, b.cout / 64, (b.ca + b.cb) / 16) == 1 ? kCarryT14TZ : 0;
+}
+
 int conv_zcol_main_extent(int ext, int axis) {
     const int tile = axis == 1 ? 8 : 16;   // the z-column kernel's TY / TX
     const int rem = ext % tile;
@@ -426,6 +459,27 @@ static int check_row_args(int dtype, const ConvArgs& a) {
     return EXASPIM_OK;
 }
 
+// Carried planes without row mode (conv3x3x3_t14_carry; a: region resolved): planes whose inputs stay clear of
+// the zero padding along z, [2, d - 2), in whole tiles and whole plane pairs
+static int check_carry_args(int dtype, const ConvArgs& a, bool whole) {
+    const int tzd = conv_carry_t14_tile_depth(dtype, a);
+    EXA_CHECK_ARG(tzd > 0 && whole,
+                  "conv: carried planes need row mode or a whole-patch 16-bit 64-cout-slice layer on 16-wide rows "
+                  "that is not split (%dx%dx%d, cout %d)", a.d, a.h, a.w, a.cout);
+    EXA_CHECK_ARG(a.in_z0 <= a.in_z1 && a.in_z0 % 2 == 0 && a.in_z1 % 2 == 0 && a.in_z0 % tzd == 0 && a.in_z1 % tzd == 0 &&
+                      (a.in_z0 == a.in_z1 || (a.in_z0 >= 2 && a.in_z1 <= a.d - 2)),
+                  "conv: carry in [%d, %d) must be whole %d-plane tiles with even bounds inside [2, %d)", (int)a.in_z0,
+                  (int)a.in_z1, tzd, a.d - 2);
+    const bool out = a.carry_dst || a.carry_pool_dst || a.out_z0 || a.out_z1;
+    EXA_CHECK_ARG(!out || (a.carry_dst && !a.carry_pool_dst == !a.pool_dst && a.out_z0 < a.out_z1 && a.out_z0 % 2 == 0 &&
+                           a.out_z1 % 2 == 0 && a.out_z0 >= 2 && a.out_z1 <= a.d - 2 && a.out_shift > 0 &&
+                           a.out_shift % 2 == 0 && (int)a.out_z0 - a.out_shift >= 2),
+                  "conv: carry out [%d, %d) shifted by %d needs a target (a pooled one exactly with a fused max-pool), "
+                  "even bounds and source and target planes inside [2, %d)", (int)a.out_z0, (int)a.out_z1, a.out_shift,
+                  a.d - 2);
+    return EXASPIM_OK;
+}
+
 // The argument checks the public launchers share; `checks` names the ones a launcher makes.
 enum : unsigned { kCheckPadded = 1, kCheckEmpty = 2, kCheckSlope = 4, kCheckPatchBytes = 8, kCheckAll = 15 };
 static int check_conv_args(int dtype, const ConvArgs& a, unsigned checks) {
@@ -452,9 +506,11 @@ int launch_conv3x3x3(int dtype, const ConvArgs& a_in, hipStream_t stream) {
                   "float32: a 32-cout-slice layer)");
     EXA_CHECK_ARG(!a.head_out || conv_can_fuse_head(a.cout, a.w, a.head_oc, dtype),
                   "conv: fused head needs cout 32, w %% 16 == 0, 1..4 outputs (and not bf16x3)");
-    EXA_CHECK_ARG(a.row_stride > 0 || !conv_has_carry(a), "conv: carried planes need row mode");
-    if (a.row_stride > 0)
+    if (a.row_stride > 0) {
         if (int rc = check_row_args(dtype, a)) return rc;
+    } else if (conv_has_carry(a)) {
+        if (int rc = check_carry_args(dtype, a, whole)) return rc;
+    }
     switch (dtype) {
         case EXASPIM_DT_F32: return launch_typed<F32Tag>(a, stream);
         case EXASPIM_DT_BF16: return launch_typed<BF16Tag>(a, stream);

@@ -70,6 +70,45 @@ static void carry_span(int d, int shift_z, int32_t out[2]) {
     if (lo < hi && hi + shift_z <= 254) { out[0] = lo; out[1] = hi; }
 }
 
+// Tile depth of down1.0 and down1.3 if the launcher runs both on the configuration that can carry planes and
+// down1.3 writes its own max-pool (the forward of a batch of n patches d x h x w), else 0
+static int carry1_tile_depth(const exaspim_unet* e, int n, int d, int h, int w) {
+    const UNetPlan& p = e->plan;
+    if ((e->options & (EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS)) ||
+        !conv_can_fuse_pool(p.dtype, p.conv[2].cout, d >> 1, h >> 1, w >> 1))
+        return 0;
+    int tz = 0;
+    for (int idx = 1; idx <= 2; ++idx) {
+        static float scratch;   // (forward() offers split-K scratch of this size; only its presence is read here)
+        ConvArgs a{};
+        a.ca = p.conv[idx].ca; a.cb = p.conv[idx].cb; a.cout = p.conv[idx].cout;
+        a.n = n; a.d = d >> 1; a.h = h >> 1; a.w = w >> 1;
+        a.partial = &scratch;
+        a.partial_patch_bytes = (size_t)(d + 2) * (h + 2) * (w + 2) * sizeof(float);
+        const int t = conv_carry_t14_tile_depth(p.dtype, a);
+        if (t == 0 || (tz != 0 && t != tz)) return 0;
+        tz = t;
+    }
+    return tz;
+}
+
+// carry_span for the second level, in level-1 planes: the whole tiles inside [3, d/2 - shift_z/2 - 3) -- down1.3
+// is clear of the zero padding along z on planes [3, d/2 - 3), down1.0 on one more either side, and the pooled
+// planes pair up only for an even level-1 shift. Empty unless the first level carries too. tz: the tile depth of
+// the two layers (even).
+void carry1_span_of_tiles(int tz, int d, int shift_z, int32_t out[2]) {
+    out[0] = out[1] = 0;
+    int32_t l0[2];
+    carry_span(d, shift_z, l0);
+    if (l0[0] >= l0[1] || shift_z % 4 != 0 || tz <= 0 || tz % 2 != 0) return;
+    const int d1 = d / 2, s1 = shift_z / 2;
+    const int lo = (3 + tz - 1) / tz * tz, hi = (d1 - s1 - 3) / tz * tz;
+    if (lo < hi && hi + s1 <= 254) { out[0] = lo; out[1] = hi; }
+}
+static void carry1_span(const exaspim_unet* e, int n, int d, int h, int w, int shift_z, int32_t out[2]) {
+    carry1_span_of_tiles(carry1_tile_depth(e, n, d, h, w), d, shift_z, out);   // (no configuration that carries: depth 0)
+}
+
 static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
     // widest tensor stored at each level: every input and output of its convs
     // (the pooled / upsampled tensors are inputs of the level's first conv)
@@ -105,7 +144,8 @@ static Workspace make_workspace(const UNetPlan& p, int n, int d, int h, int w) {
 static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, int h, int w,
                    int apply_sigmoid, int trim, void* workspace, size_t workspace_bytes,
                    hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr,
-                   int row_stride = 0, const int32_t* keep_hi = nullptr, const exaspim_unet_carry* carry = nullptr) {
+                   int row_stride = 0, const int32_t* keep_hi = nullptr, const exaspim_unet_carry* carry = nullptr,
+                   const exaspim_unet_carry1* carry1 = nullptr) {
     const UNetPlan& p = e->plan;
     const Workspace ws = make_workspace(p, n, d, h, w);
     if (workspace_bytes < ws.bytes) {
@@ -174,10 +214,45 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                               carry->out_z[1] == span[1] + shift && carry->out_z[1] <= 254,
                           "forward: carry out [%d, %d) shifted by %d is not the range a forward %d planes down takes over",
                           carry->out_z[0], carry->out_z[1], shift, shift);
+            // (the planes carried in are not computed here: their tiles run no epilogue that could store them again)
+            EXA_CHECK_ARG(!in || carry->out_z[0] >= carry->in_z[1] || carry->out_z[1] <= carry->in_z[0],
+                          "forward: carry out [%d, %d) overlaps the planes carried in, [%d, %d)", carry->out_z[0],
+                          carry->out_z[1], carry->in_z[0], carry->in_z[1]);
         }
     }
     void* const x1 = carry ? carry->own_skip : skip(0);
     void* const x1_pool = carry ? carry->own_pool : A(1);
+    // ... and (exaspim_unet_forward_prepared_carry1) down1.0's output, x2 and its max-pool
+    if (carry1) {
+        EXA_CHECK_ARG(carry && carry1->own_mid1 && carry1->own_skip1 && carry1->own_pool2 && carry1->reserved == 0,
+                      "forward: carried planes of the second level need those of the first and all three own buffers");
+        EXA_CHECK_ARG(!carry1->out_mid1 == !carry1->out_skip1 && !carry1->out_mid1 == !carry1->out_pool2,
+                      "forward: second-level carry out needs all three targets or none");
+        const int tz1 = carry1_tile_depth(e, n, d, h, w);
+        EXA_CHECK_ARG(tz1 > 0, "forward: down1.0 and down1.3 cannot carry planes at this geometry, dtype or option set");
+        if (carry1->in_z[0] != 0 || carry1->in_z[1] != 0)
+            EXA_CHECK_ARG((carry->in_z[0] != 0 || carry->in_z[1] != 0) && carry1->in_z[0] >= 3 &&
+                              carry1->in_z[0] < carry1->in_z[1] && carry1->in_z[1] <= d / 2 - 3 &&
+                              carry1->in_z[0] % tz1 == 0 && carry1->in_z[1] % tz1 == 0,
+                          "forward: second-level carry in [%d, %d) needs a first-level carry in and whole %d-plane tiles "
+                          "inside [3, %d)", carry1->in_z[0], carry1->in_z[1], tz1, d / 2 - 3);
+        if (carry1->out_mid1 || carry1->out_shift) {
+            int32_t span[2];
+            const int shift1 = carry1->out_mid1 ? carry1->out_shift : 0;
+            carry1_span(e, n, d, h, w, 2 * shift1, span);
+            EXA_CHECK_ARG(shift1 > 0 && carry->out_skip && carry->out_shift == 2 * shift1 && span[0] < span[1] &&
+                              carry1->out_z[0] == span[0] + shift1 && carry1->out_z[1] == span[1] + shift1,
+                          "forward: second-level carry out [%d, %d) shifted by %d is not the range a forward %d planes down "
+                          "takes over, or the first level does not carry out by twice the shift",
+                          carry1->out_z[0], carry1->out_z[1], shift1, 2 * shift1);
+            EXA_CHECK_ARG(carry1->out_z[0] >= carry1->in_z[1] || carry1->out_z[1] <= carry1->in_z[0],
+                          "forward: second-level carry out [%d, %d) overlaps the planes carried in, [%d, %d)",
+                          carry1->out_z[0], carry1->out_z[1], carry1->in_z[0], carry1->in_z[1]);
+        }
+    }
+    void* const mid1 = carry1 ? carry1->own_mid1 : B(1);
+    void* const skip1 = carry1 ? carry1->own_skip1 : skip(1);
+    void* const pool2 = carry1 ? carry1->own_pool2 : A(2);
     auto conv = [&](int idx, const void* sa, const void* sb, void* dst, int l) -> int {
         const ConvLayer& L = p.conv[idx];
         ConvArgs a;
@@ -185,7 +260,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         // split-K scratch: the zero-bordered input copy is dead once inc.0 has run
         a.partial = reinterpret_cast<float*>(base + ws.xpad);
         a.partial_patch_bytes = (size_t)(d + 2) * (h + 2) * (w + 2) * sizeof(float);
-        if (idx <= 6 && idx % 2 == 0 && fuse_pool[idx / 2]) a.pool_dst = idx == 0 ? x1_pool : A(idx / 2 + 1);
+        if (idx <= 6 && idx % 2 == 0 && fuse_pool[idx / 2]) a.pool_dst = idx == 0 ? x1_pool : idx == 2 ? pool2 : A(idx / 2 + 1);
         // up4.3 produces [trim, khi) (khi = size - trim unless clipped), up4.0 one voxel more on every face
         const bool last = idx == kNumMfmaConvs - 1, last_but_one = idx == kNumMfmaConvs - 2;
         const int margin = !trimmed ? 0 : last ? trim : last_but_one ? trim - 1 : 0;
@@ -229,6 +304,17 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                 a.out_z0 = (unsigned char)carry->out_z[0];
                 a.out_z1 = (unsigned char)carry->out_z[1];
                 a.out_shift = (unsigned short)carry->out_shift;
+            }
+        }
+        if ((idx == 1 || idx == 2) && carry1) {
+            a.in_z0 = (unsigned short)carry1->in_z[0];
+            a.in_z1 = (unsigned short)carry1->in_z[1];
+            if (carry1->out_mid1) {
+                a.carry_dst = idx == 1 ? carry1->out_mid1 : carry1->out_skip1;
+                a.carry_pool_dst = idx == 1 ? nullptr : carry1->out_pool2;
+                a.out_z0 = (unsigned char)carry1->out_z[0];
+                a.out_z1 = (unsigned char)carry1->out_z[1];
+                a.out_shift = (unsigned short)carry1->out_shift;
             }
         }
         LayerTimer* t = e->timer;
@@ -276,12 +362,13 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
     RUN(conv(0, A(0), nullptr, x1, 0));                           // x1
     for (int l = 1; l <= 4; ++l) {
         const ConvLayer& L0 = p.conv[2 * l - 1];
-        const void* prev = l == 1 ? x1 : skip(l - 1);
+        const void* prev = l == 1 ? x1 : l == 2 ? skip1 : skip(l - 1);
         if (!fuse_pool[l - 1])
             RUN(launch_maxpool2(dt, prev, A(l), n, d >> (l - 1), h >> (l - 1), w >> (l - 1), L0.ca,
                                 stream));
-        RUN(conv(2 * l - 1, l == 1 ? x1_pool : A(l), nullptr, B(l), l));
-        RUN(conv(2 * l, B(l), nullptr, l < 4 ? skip(l) : A(l), l));  // x2..x4, x5 in A(4)
+        void* const mid = l == 1 ? mid1 : B(l);
+        RUN(conv(2 * l - 1, l == 1 ? x1_pool : l == 2 ? pool2 : A(l), nullptr, mid, l));
+        RUN(conv(2 * l, mid, nullptr, l == 1 ? skip1 : l < 4 ? skip(l) : A(l), l));  // x2..x4, x5 in A(4)
     }
     // decoder (unet3d.py:100-103): y = DoubleConv(cat[skip, up(prev)])
     const void* prev = A(4);
@@ -305,7 +392,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                                  (e->options & EXASPIM_OPT_PLAIN_UPSAMPLE) != 0,
                                  (e->options & EXASPIM_OPT_UPSAMPLE_PER_THREAD) != 0, ups_trimmed ? ups_hi : nullptr));
         }
-        RUN(conv(i0, l == 0 ? x1 : skip(l), A(l), B(l), l));
+        RUN(conv(i0, l == 0 ? x1 : l == 1 ? skip1 : skip(l), A(l), B(l), l));
         RUN(conv(i0 + 1, B(l), nullptr, A(l), l));
         prev = A(l);
     }
@@ -533,11 +620,32 @@ extern "C" int exaspim_unet_carry_planes(const exaspim_unet* h, int32_t n, int32
     return EXASPIM_OK;
 }
 
+extern "C" int exaspim_unet_carry1_planes(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                          int32_t row_stride, int32_t shift_z, int32_t out[2]) {
+    int32_t l0[2];
+    EXA_CHECK_ARG(out, "carry_planes: NULL pointer");
+    out[0] = out[1] = 0;
+    // (the argument checks and the conditions of the first level's row mode)
+    if (int rc = exaspim_unet_carry_planes(h, n, d, hgt, w, row_stride, shift_z, l0)) return rc;
+    if (l0[0] < l0[1]) carry1_span(h, n, d, hgt, w, shift_z, out);
+    return EXASPIM_OK;
+}
+
 extern "C" int exaspim_unet_forward_prepared_carry(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
                                                    int32_t n, int32_t d, int32_t hgt, int32_t w,
                                                    int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
                                                    const int32_t keep_hi[3], const exaspim_unet_carry* carry,
                                                    void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return exaspim_unet_forward_prepared_carry1(h, x_prepared_dev, out_dev, n, d, hgt, w, apply_sigmoid, trim, row_stride,
+                                                keep_hi, carry, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int exaspim_unet_forward_prepared_carry1(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                                    int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                                    int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                                    const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                                    const exaspim_unet_carry1* carry1, void* workspace_dev,
+                                                    size_t workspace_bytes, void* stream) {
     EXA_CHECK_ARG(h && x_prepared_dev && out_dev && workspace_dev && keep_hi && carry, "forward: NULL pointer");
     EXA_CHECK_ARG(n > 0, "forward: empty batch");
     EXA_CHECK_ARG(trim >= 0, "forward: negative trim %d", trim);
@@ -551,7 +659,7 @@ extern "C" int exaspim_unet_forward_prepared_carry(exaspim_unet* h, const void* 
                       "forward: keep_hi[%d] = %d outside (%d, %d] (trim %d of %d voxels)", i, keep_hi[i], trim,
                       size[i] - trim, trim, size[i]);
     return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
-                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi, carry);
+                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi, carry, carry1);
 }
 
 extern "C" int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out_dev,

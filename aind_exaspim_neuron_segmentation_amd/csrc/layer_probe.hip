@@ -154,6 +154,55 @@ int probe_conv3x3x3_row_carry(int dtype, const void* src, int ca, const void* we
 }
 int probe_last_carry(void) { return last_conv_launch().carry ? 1 : 0; }
 
+// One whole-patch convolution through launch_conv3x3x3 with planes carried along z outside row mode
+// (conv3x3x3_t14_carry); carry[0..4] as above, partial may be null (with scratch the launcher may split).
+int probe_conv3x3x3_carry(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,
+                          int cout, int n, int d, int h, int w, float slope, void* pool_dst, float* partial,
+                          size_t partial_patch_bytes, const int32_t* carry, void* carry_dst, void* carry_pool_dst,
+                          hipStream_t stream) {
+    EXA_CHECK_ARG(carry != nullptr, "probe: NULL carry");
+    for (int i = 0; i < 5; ++i)   // (what ConvArgs' narrow fields hold)
+        EXA_CHECK_ARG(carry[i] >= 0 && carry[i] <= (i == 2 || i == 3 ? 254 : 65534), "probe: carry[%d] = %d out of range", i, carry[i]);
+    ConvArgs a{};
+    a.src_a = src;
+    a.ca = ca;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    a.pool_dst = pool_dst;
+    a.partial = partial;
+    a.partial_patch_bytes = partial_patch_bytes;
+    a.in_z0 = (unsigned short)carry[0];
+    a.in_z1 = (unsigned short)carry[1];
+    a.out_z0 = (unsigned char)carry[2];
+    a.out_z1 = (unsigned char)carry[3];
+    a.out_shift = (unsigned short)carry[4];
+    a.carry_dst = carry_dst;
+    a.carry_pool_dst = carry_pool_dst;
+    return launch_conv3x3x3(dtype, a, stream);
+}
+void probe_carry1_span(int tz, int d, int shift_z, int32_t* out) { carry1_span_of_tiles(tz, d, shift_z, out); }
+// conv_carry_t14_tile_depth for a whole-patch launch of this shape
+int probe_conv_carry_tile_depth(int dtype, int ca, int cout, int n, int d, int h, int w, size_t partial_patch_bytes) {
+    ConvArgs a{};
+    a.ca = ca;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    static float scratch;   // (only its presence is read)
+    a.partial = partial_patch_bytes ? &scratch : nullptr;
+    a.partial_patch_bytes = partial_patch_bytes;
+    return conv_carry_t14_tile_depth(dtype, a);
+}
+
 int probe_conv_row_mode_ok(int dtype, int cout, int n, int w, int row_stride, int fused_pool_whole_patch) {
     return conv_row_mode_ok(dtype, cout, n, w, row_stride, fused_pool_whole_patch != 0) ? 1 : 0;
 }

@@ -54,7 +54,8 @@ DEFAULT_STREAMS = 3
 PLAIN_GATHER = False    # True: gather float32 patches and let the engine pad them, instead of the prepared layout
 FULL_PATCHES = False    # True: compute the margin predict() discards as well (exaspim_unet_forward untrimmed)
 CARRY_Z = True          # False: every batch computes its whole first level (no planes carried from the z slab above)
-CARRY_POOL_BYTES = 24 << 30   # most device memory one run_sliding_window call may hold in carry buffers
+CARRY_Z1 = True         # False: only the first level carries planes (down1.0 and down1.3 are computed whole)
+CARRY_POOL_BYTES = 36 << 30   # most device memory one run_sliding_window call may hold in carry buffers
 CLIP_TO_VOLUME = True   # False: also compute the trimmed outputs beyond the volume's high faces, which the stitch drops
 
 _VOX_CODES = {
@@ -1605,17 +1606,34 @@ def carry_plan(starts, batch_size, patch_shape, overlap):
     return succ
 
 
-def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_streams, device):
+def _carry_budget(peak, pair_bytes, triple_bytes, free, cap):
     """
-    The carry links run_sliding_window can use and the buffer pairs they need: (links, peak) with
-    links[bi] = (successor, shift, the successor's plane range) or None and peak = the pairs to allocate, or
-    (None, 0) when nothing can be carried or the buffers would not fit. peak is the most pairs alive at once
-    plus, with several streams, one per stream: pairs are handed out oldest first, so the pair a batch takes
+    (level 0, level 1): which of the two levels' carry buffers fit, peak sets of each. The first level is
+    budgeted first, under the cap and half of the free memory; the second level (triple_bytes = 0: nothing to
+    carry there) is taken only with the first and only if what is left of both bounds holds it.
+    """
+    limit = min(int(cap), int(free) // 2)
+    need0 = peak * pair_bytes
+    if peak <= 0 or need0 > limit:
+        return False, False
+    return True, triple_bytes > 0 and need0 + peak * triple_bytes <= limit
+
+
+def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_streams, device, free=None):
+    """
+    The carry links run_sliding_window can use and the buffer sets they need: (links, peak, level1) with
+    links[bi] = (successor, shift, the successor's plane range, its second-level plane range) or None, peak =
+    the sets to allocate and level1 = whether a set holds the second level's triple next to the first level's
+    pair, or (None, 0, False) when nothing can be carried or the buffers would not fit (_carry_budget; free:
+    the device's free bytes, asked from the device if None). The second-level range of a link is (0, 0) where
+    the engine gives none (or CARRY_Z1 is off, or the triples do not fit). peak is the most sets alive at once
+    plus, with several streams, one per stream: sets are handed out oldest first, so the set a batch takes
     was last read by the batch n_streams earlier -- the previous one on its own stream -- and the batches in
     flight never wait for each other over a buffer.
     """
     links = [None] * len(succ)
     spans = {}
+    taken = {}      # batch index -> the plane ranges its predecessor leaves it (first level, second level)
     for bi, bj in enumerate(succ):
         if bj is None:
             continue
@@ -1624,11 +1642,25 @@ def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_str
         stride = batch_row_stride(own, patch_shape, overlap)
         key = (len(own), stride, shift)
         if key not in spans:
-            spans[key] = model.carry_planes((len(own),) + tuple(patch_shape), stride, shift, device)
-        if spans[key][1] > spans[key][0]:
-            links[bi] = (bj, shift, spans[key])
+            span = model.carry_planes((len(own),) + tuple(patch_shape), stride, shift, device)
+            span1 = (0, 0)
+            if CARRY_Z1 and span[1] > span[0]:
+                span1 = model.carry1_planes((len(own),) + tuple(patch_shape), stride, shift, device)
+            spans[key] = (span, span1)
+        span, span1 = spans[key]
+        # A batch stores again only planes it computes: where the range it would pass on reaches into the range
+        # it takes over itself (a z stride of less than a third of the depth or so), the chain is cut here and
+        # starts again with the successor -- or, if only the second level's ranges meet, that level's is.
+        got, got1 = taken.get(bi, ((0, 0), (0, 0)))
+        if span[0] + shift < got[1] and got[0] < span[1] + shift:
+            continue
+        if span1[0] + shift // 2 < got1[1] and got1[0] < span1[1] + shift // 2:
+            span1 = (0, 0)
+        if span[1] > span[0]:
+            links[bi] = (bj, shift, span, span1)
+            taken[bj] = (span, span1)
     if not any(links):
-        return None, 0
+        return None, 0, False
     # pairs alive at once: a batch's pair lives from its predecessor's (or its own) forward to its own
     has_pair, alive, peak = set(), 0, 0
     for bi, link in enumerate(links):
@@ -1643,12 +1675,18 @@ def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_str
             alive -= 1
     if n_streams > 1:
         peak += int(n_streams)
-    skip_elems, pool_elems = model.carry_pair_elems((int(batch_size),) + tuple(patch_shape))
-    need = peak * 2 * (skip_elems + pool_elems)
-    free, _ = torch.cuda.mem_get_info(device)
-    if need > CARRY_POOL_BYTES or need > free // 2:
-        return None, 0
-    return links, peak
+    shape = (int(batch_size),) + tuple(patch_shape)
+    triple_bytes = 0
+    if any(link is not None and link[3][1] > link[3][0] for link in links):
+        triple_bytes = 2 * sum(model.carry_triple_elems(shape))
+    if free is None:
+        free, _ = torch.cuda.mem_get_info(device)
+    level0, level1 = _carry_budget(peak, 2 * sum(model.carry_pair_elems(shape)), triple_bytes, free, CARRY_POOL_BYTES)
+    if not level0:
+        return None, 0, False
+    if not level1:     # (a second-level range that was cut for a predecessor's stays cut: no link is added here)
+        links = [None if link is None else link[:3] + ((0, 0),) for link in links]
+    return links, peak, level1
 
 
 def batch_keep_hi(starts, patch_shape, trim, global_shape):
@@ -2001,16 +2039,20 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
     # first-level planes carried from one z slab of patches to the next
     links, free_pairs = None, collections.deque()
     if CARRY_Z and prepared_layout is not None and not model.needs_resolution():
-        links, peak = _carry_schedule(model, carry_plan(starts, batch_size, plan.patch_shape, plan.overlap), starts,
-                                      batch_size, plan.patch_shape, plan.overlap, n_streams, device)
+        links, peak, level1 = _carry_schedule(model, carry_plan(starts, batch_size, plan.patch_shape, plan.overlap),
+                                              starts, batch_size, plan.patch_shape, plan.overlap, n_streams, device)
         if links is not None:
-            elems = model.carry_pair_elems((batch_size,) + tuple(plan.patch_shape))
+            shape = (batch_size,) + tuple(plan.patch_shape)
+            elems = model.carry_pair_elems(shape)
+            elems1 = model.carry_triple_elems(shape) if level1 else None     # (section 3e: a triple with every pair)
             # (allocated before the workers branch off the caller's stream; alive until the call returns)
-            free_pairs.extend([tuple(torch.empty(e, dtype=torch.int16, device=device) for e in elems), None]
+            free_pairs.extend([tuple(torch.empty(e, dtype=torch.int16, device=device) for e in elems), None,
+                               elems1 and tuple(torch.empty(e, dtype=torch.int16, device=device) for e in elems1)]
                               for _ in range(peak))
             for s in workers:
                 s.wait_stream(main)
-    pending = {}     # batch index -> [its pair, the planes already there, its predecessor's event]
+    # batch index -> [its pair (and triple), the planes already there, its predecessor's event, the level-1 planes]
+    pending = {}
 
     def take_pair(worker):
         pair = free_pairs.popleft()     # (the one released longest ago)
@@ -2032,15 +2074,20 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                                            mn=mn, mx=mx, layout=prepared_layout)
                 carry, own = None, None
                 if links is not None and (bi in pending or links[bi] is not None):
-                    own, in_z, before = pending.pop(bi, None) or (take_pair(worker), (0, 0), None)
+                    own, in_z, before, in_z1 = pending.pop(bi, None) or (take_pair(worker), (0, 0), None, (0, 0))
                     carry = {"own": own[0], "in_z": in_z}
+                    if own[2] is not None:
+                        carry.update(own1=own[2], in_z1=in_z1)
                     if before is not None:
                         worker.wait_event(before)      # the planes carried in are there
                     if links[bi] is not None:
-                        nxt, shift, span = links[bi]
+                        nxt, shift, span, span1 = links[bi]
                         out_pair = take_pair(worker)
                         carry.update(out=out_pair[0], out_z=(span[0] + shift, span[1] + shift), out_shift=shift)
-                        pending[nxt] = [out_pair, span, None]
+                        if span1[1] > span1[0]:
+                            carry.update(out1=out_pair[2], out_z1=(span1[0] + shift // 2, span1[1] + shift // 2),
+                                         out_shift1=shift // 2)
+                        pending[nxt] = [out_pair, span, None, span1]
                 pred = model.run_prepared(
                     inputs, (int(batch.shape[0]),) + tuple(plan.patch_shape), apply_sigmoid=True,
                     trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride, keep_hi=keep_hi, carry=carry)

@@ -447,6 +447,30 @@ class UNet3D(nn.Module):
             "exaspim_unet_carry_planes")
         return int(span[0]), int(span[1])
 
+    def carry1_planes(self, shape, row_stride, shift_z, device=None):
+        """
+        carry_planes for the second level (exaspim_unet_carry1_planes): the range, in level-1 planes of its own
+        frame, of down1.0's and down1.3's outputs that the batch can take over as well. (0, 0): none -- in
+        particular wherever carry_planes gives none.
+        """
+        device = next(self.parameters()).device if device is None else device
+        n, d, h, w = (int(v) for v in shape)
+        with torch.cuda.device(device):
+            self._ensure_engine(device)
+        span = (ctypes.c_int32 * 2)()
+        _native.check(
+            _native.lib().exaspim_unet_carry1_planes(self._engine, n, d, h, w, int(row_stride), int(shift_z), span),
+            "exaspim_unet_carry1_planes")
+        return int(span[0]), int(span[1])
+
+    def carry_triple_elems(self, shape):
+        """Elements (16-bit) of the three buffers a forward that carries second-level planes keeps down1.0's
+        output, the level's skip tensor and its max-pool in (run_prepared's carry["own1"] / carry["out1"])."""
+        n, d, h, w = (int(v) for v in shape)
+        c1p = -(-int(self.channels[1]) // 32) * 32
+        full = n * (d // 2) * (h // 2) * (w // 2) * c1p
+        return full, full, full // 8
+
     def carry_pair_elems(self, shape):
         """Elements (16-bit) of the two buffers a carrying forward of patches "shape" keeps its first-level
         skip tensor and its max-pool in (run_prepared's carry["own"] / carry["out"])."""
@@ -482,6 +506,9 @@ class UNet3D(nn.Module):
             its first-level skip tensor and max-pool in, "in_z" = the plane range an earlier forward already
             left there, and optionally "out" = the (skip, pool) of the batch "out_shift" planes further down
             with "out_z", this forward's planes to store there. Raises where the engine cannot honour it.
+            Second level as well (exaspim_unet_forward_prepared_carry1): "own1" = (mid, skip, pool) tensors of
+            carry_triple_elems(shape) elements, "in_z1", and with "out" optionally "out1", "out_z1",
+            "out_shift1", in level-1 planes.
         """
         if self.training:
             raise RuntimeError(
@@ -522,14 +549,31 @@ class UNet3D(nn.Module):
                     desc.out_skip, desc.out_pool = carry["out"][0].data_ptr(), carry["out"][1].data_ptr()
                     desc.out_z[:] = [int(v) for v in carry["out_z"]]
                     desc.out_shift = int(carry["out_shift"])
+                desc1 = None
+                if carry.get("own1") is not None:
+                    desc1 = _native.UNetCarry1()
+                    need1 = self.carry_triple_elems(shape)
+                    triples = [carry["own1"]] + ([carry["out1"]] if carry.get("out1") is not None else [])
+                    for triple in triples:
+                        for t, elems in zip(triple, need1):
+                            if not t.is_cuda or t.element_size() != 2 or t.numel() < elems or not t.is_contiguous():
+                                raise RuntimeError("carry buffers must be contiguous 16-bit device tensors of "
+                                                   f"{need1} elements")
+                    desc1.own_mid1, desc1.own_skip1, desc1.own_pool2 = (t.data_ptr() for t in carry["own1"])
+                    desc1.in_z[:] = [int(v) for v in carry.get("in_z1", (0, 0))]
+                    if carry.get("out1") is not None:
+                        desc1.out_mid1, desc1.out_skip1, desc1.out_pool2 = (t.data_ptr() for t in carry["out1"])
+                        desc1.out_z[:] = [int(v) for v in carry["out_z1"]]
+                        desc1.out_shift = int(carry["out_shift1"])
                 hi = keep_hi if keep_hi is not None else (d - int(trim), h - int(trim), w - int(trim))
                 _native.check(
-                    _native.lib().exaspim_unet_forward_prepared_carry(
+                    _native.lib().exaspim_unet_forward_prepared_carry1(
                         self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
                         1 if apply_sigmoid else 0, int(trim), int(row_stride), _native.int3(hi),
-                        ctypes.byref(desc), ws.data_ptr(), ws.numel(), stream,
+                        ctypes.byref(desc), ctypes.byref(desc1) if desc1 is not None else None,
+                        ws.data_ptr(), ws.numel(), stream,
                     ),
-                    "exaspim_unet_forward_prepared_carry",
+                    "exaspim_unet_forward_prepared_carry1",
                 )
             elif keep_hi is not None:
                 _native.check(

@@ -49,7 +49,9 @@ extern "C" {
  *    later within 5: exaspim_unet_carry_planes, exaspim_unet_forward_prepared_carry (struct
  *    exaspim_unet_carry): first-level planes carried from one z slab of patches to the next;
  *    later within 5: exaspim_region_graph_stream_slab / _finish and the finish workspace query (struct
- *    exaspim_region_graph_stream): the region graph of a volume that arrives in z slabs */
+ *    exaspim_region_graph_stream): the region graph of a volume that arrives in z slabs;
+ *    later within 5: exaspim_unet_carry1_planes, exaspim_unet_forward_prepared_carry1 (struct
+ *    exaspim_unet_carry1): second-level planes carried along z as well */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -253,6 +255,42 @@ int exaspim_unet_forward_prepared_carry(exaspim_unet* h, const void* x_prepared_
                                         int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
                                         const int32_t keep_hi[3], const exaspim_unet_carry* carry,
                                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The same for the second level (down1.0 and down1.3, at half resolution): the later batch's down1.3 planes
+ * [3, d/2 - shift_z/2 - 3) are the earlier batch's [3 + shift_z/2, d/2 - 3), its down1.0 planes one more on
+ * either side. exaspim_unet_carry1_planes: out[0..1] = the plane range [z0, z1), in level-1 planes of the LATER
+ * batch's frame, that a forward can take over for both layers: the whole tiles, of the depth the launcher
+ * picks for them, inside that span. Empty when exaspim_unet_carry_planes is empty, when shift_z is odd, when
+ * the two layers do not run the tile configuration that can carry (16-bit, 64-cout slices on rows that are a
+ * multiple of 16 wide, not split, fused max-pool) or nothing fits. For d = 96, shift_z = 64: [4, 12). */
+int exaspim_unet_carry1_planes(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                               int32_t row_stride, int32_t shift_z, int32_t out[2]);
+/* own_mid1: down1.0's output (n, c1p, d/2, hgt/2, w/2), own_skip1: down1.3's output x2 (same shape), own_pool2:
+ * its max-pool (n, c1p, d/4, hgt/4, w/4); workspace layout and storage type, 256-byte aligned. All required.
+ * in_z: the level-1 plane range already present in own_mid1 and own_skip1 (and its pooled planes in own_pool2).
+ * out_mid1 / out_skip1 / out_pool2 (all or none), out_z, out_shift (level-1 planes): as in exaspim_unet_carry. */
+typedef struct exaspim_unet_carry1 {
+    void* own_mid1;
+    void* own_skip1;
+    void* own_pool2;
+    int32_t in_z[2];
+    void* out_mid1;
+    void* out_skip1;
+    void* out_pool2;
+    int32_t out_z[2];
+    int32_t out_shift;
+    int32_t reserved;   /* 0 */
+} exaspim_unet_carry1;
+/* exaspim_unet_forward_prepared_carry with planes of the second level carried as well; out_dev gets the same
+ * bits. carry1 needs carry (the pooled input planes of the left-out tiles arrive with the first level's carry):
+ * in_z of carry1 non-empty needs in_z of carry non-empty, carry out of carry1 needs carry out of carry with
+ * out_shift half of it. A request the engine cannot honour is EXASPIM_E_INVALID before anything is launched. */
+int exaspim_unet_forward_prepared_carry1(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                         int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                         int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                         const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                         const exaspim_unet_carry1* carry1, void* workspace_dev,
+                                         size_t workspace_bytes, void* stream);
 
 /* Range probe for the 16-bit storage modes. The reference loads ANY trained state_dict
  * (inference.py:400-424) and runs it in float32; IEEE-half storage holds |v| <= 65504 (stores
