@@ -229,6 +229,14 @@ int probe_upsample2(int dtype, const void* src, void* dst, int n, int d, int h, 
                             per_thread != 0);
 }
 
+// ... with a per-axis margin at the high faces (margin_hi[3] as engine.hip derives it from keep_hi)
+int probe_upsample2_hi(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,
+                       int margin, const int margin_hi[3], int plain_kernel, int per_thread,
+                       hipStream_t stream) {
+    return launch_upsample2(dtype, src, dst, n, d, h, w, c, margin, stream, plain_kernel != 0,
+                            per_thread != 0, margin_hi);
+}
+
 int probe_convt2(int dtype, const void* src, const void* weights, const float* bias, void* dst, int n,
                  int d, int h, int w, int cin, int cout, hipStream_t stream) {
     return launch_convt2(dtype, src, weights, bias, dst, n, d, h, w, cin, cout, stream);

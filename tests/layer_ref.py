@@ -260,6 +260,7 @@ def load_probe():
         "probe_maxpool2_xcols": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "probe_maxpool2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
         "probe_upsample2": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "probe_upsample2_hi": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_int32 * 3, i32, i32, vp]),
         "probe_head": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "probe_plan_conv": (i32, [ctypes.c_int32 * 5, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]),
     }

@@ -7,6 +7,7 @@ import ctypes
 import pytest
 
 import layer_ref as R
+from carry_ref import _brute_force, _Model
 from aind_exaspim_neuron_segmentation_amd import _native, inference
 
 
@@ -22,30 +23,6 @@ def probe():
     lib.probe_conv_carry_tile_depth.restype = i32
     lib.probe_conv_carry_tile_depth.argtypes = [i32, i32, i32, i32, i32, i32, i32, ctypes.c_size_t]
     return lib
-
-
-def _level0_span(d, shift):
-    """exaspim_unet_carry_planes' rule: whole inc.3 tiles (6 planes where they divide d, else 4) with even bounds
-    inside [2, d - shift - 2)."""
-    if shift <= 0 or shift % 2 or shift >= d:
-        return []
-    tz = 6 if d % 6 == 0 else 4
-    tiles = [t for t in range(0, d, tz) if t >= 2 and t + tz <= d - shift - 2 and t % 2 == 0 and (t + tz) % 2 == 0]
-    return tiles if tiles and tiles[-1] + tz + shift <= 254 else []
-
-
-def _brute_force(tz, d, shift):
-    """The level-1 planes of the later frame that are whole tz-plane tiles inside [3, d/2 - shift/2 - 3): down1.3
-    is clear of both frames' zero padding there. None unless the first level carries, the shift is even and so
-    is the level-1 shift (a pooled plane of one frame is a pooled plane of the other)."""
-    if not _level0_span(d, shift) or shift % 2 or (shift // 2) % 2:
-        return (0, 0)
-    d1, s1 = d // 2, shift // 2
-    tiles = [t for t in range(0, d1, tz) if all(3 <= z < d1 - s1 - 3 for z in range(t, t + tz))]
-    if not tiles:
-        return (0, 0)
-    assert tiles == list(range(tiles[0], tiles[-1] + tz, tz))
-    return (tiles[0], tiles[-1] + tz)
 
 
 def test_plane_range_is_the_brute_force_rule(probe):
@@ -104,31 +81,6 @@ def test_budget_takes_the_first_level_first():
     assert budget(4, 10, 5, 1000, 60) == (True, True) and budget(4, 10, 5, 1000, 59) == (True, False)
     assert budget(4, 10, 5, 118, 1000) == (True, False) and budget(4, 10, 5, 120, 1000) == (True, True)
     assert budget(4, 10, 5, 79, 1000) == (False, False)
-
-
-class _Model:
-    """What _carry_schedule asks of a model, with the engine's plane ranges for 16-bit row batches."""
-
-    def __init__(self, level1=True):
-        self.level1 = level1
-
-    def carry_planes(self, shape, row_stride, shift_z, device=None):
-        tiles = _level0_span(shape[1], shift_z) if row_stride > 0 else []
-        tz = 6 if shape[1] % 6 == 0 else 4
-        return (tiles[0], tiles[-1] + tz) if tiles else (0, 0)
-
-    def carry1_planes(self, shape, row_stride, shift_z, device=None):
-        if not self.level1 or self.carry_planes(shape, row_stride, shift_z) == (0, 0):
-            return (0, 0)
-        return _brute_force(4, shape[1], shift_z)
-
-    def carry_pair_elems(self, shape):
-        n, d, h, w = shape
-        return n * d * h * w * 32, n * d * h * w * 4
-
-    def carry_triple_elems(self, shape):
-        n, d, h, w = shape
-        return n * d * h * w * 8, n * d * h * w * 8, n * d * h * w
 
 
 # (volume, patch, overlap, batch size, a link's level-1 range)

@@ -552,6 +552,99 @@ def test_upsample2(probe, dt, mode, d, margin):
         assert exact.double().mean() >= 0.99
 
 
+# The level-0 upsampling of the trimmed and clipped forward at shapes with more than one workgroup, two images and
+# the high-face margins engine.hip derives from keep_hi. Per case: (d, h, w) of the source, margin, margin_hi, the
+# kernel the launcher must pick when left to itself, and -- where that is the strip kernel -- per axis the first
+# output index it leaves alone (hy and hx as given; along z the widest margin <= margin_hi[0] with whole runs).
+UPS_HI_CASES = {
+    # 12 pairs of 24 x 24 columns x 2 groups = 576 items: three workgroups along y, the later ones with image0 > 0
+    "16x16x16 m4": ((16, 16, 16), 4, None, "upsample2_strip12", (28, 28, 28)),
+    "32x16x16 m4": ((32, 16, 16), 4, None, "upsample2_strip14", (60, 28, 28)),       # 28 pairs: two runs of 14
+    "24x16x16 m6": ((24, 16, 16), 6, None, "upsample2_pipe", None),                  # 18 pairs: no whole run
+    # z margin 20 leaves 22 planes, 11 pairs; 19 leaves 23 planes in 12 pairs, one run, the last pair of one plane
+    "24x16x16 m6 hi 20,14,10": ((24, 16, 16), 6, (20, 14, 10), "upsample2_strip12", (29, 18, 22)),
+    "24x16x16 m6 hi z": ((24, 16, 16), 6, (20, 0, 0), "upsample2_strip12", (29, 26, 26)),
+    # no z margin in [6, 6] gives whole runs, as given or symmetric: the superset on the per-thread pipeline
+    "24x16x16 m6 hi y": ((24, 16, 16), 6, (0, 14, 0), "upsample2_pipe", None),
+    # odd extents: the last row pair has one row (ny = 17), nx = 19; along z margin 5 leaves 23 planes in 12 pairs
+    "16x16x16 m4 hi y,x odd": ((16, 16, 16), 4, (0, 11, 9), "upsample2_strip12", (28, 21, 23)),
+    "16x16x16 m4 hi odd": ((16, 16, 16), 4, (9, 11, 9), "upsample2_strip12", (27, 21, 23)),
+    # a workgroup's 128 (row pair, column) items span two row pairs of 152 columns: four source rows of 80 x 2
+    # pieces = 640 > the 512 of an LDS slot
+    "16x8x80 m4": ((16, 8, 80), 4, None, "upsample2_pipe", None),
+}
+
+
+def _axis_mask(dims, lo, hi):
+    """bool (D, H, W): lo[i] <= index < hi[i] on every axis."""
+    m = torch.ones(dims, dtype=torch.bool)
+    for axis, (n, a, b) in enumerate(zip(dims, lo, hi)):
+        idx = torch.arange(n)
+        shape = [1, 1, 1]
+        shape[axis] = n
+        m &= ((idx >= a) & (idx < b)).reshape(shape)
+    return m
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", list(UPS_HI_CASES))
+def test_upsample2_many_workgroups_and_high_margins(probe, dt, case):
+    (d, h, w), margin, margin_hi, auto_kernel, skipped = UPS_HI_CASES[case]
+    gen = torch.Generator().manual_seed(d * h * w + margin)
+    k = R.kc(dt)
+    n = 2
+    x = R.quantize(_uniform_pm((n, 2 * k, d, h, w), gen), dt)      # two images of two channel chunks
+    src = R.pack_blocked(x, dt).cuda()
+    dims = (2 * d, 2 * h, 2 * w)
+    word = {4: 0x5A5A5A5A, 2: 0x5A5A}[R.es(dt)]
+    # test_upsample2's reference and bound
+    up64 = torch.einsum("ai,bj,ck,nqijk->nqabc", _lerp_matrix(d), _lerp_matrix(h), _lerp_matrix(w), x)
+    e = 8 * 2.0 ** -24 * x.abs().max()
+    lo, hi = R.quantize(up64 - e, dt), R.quantize(up64 + e, dt)
+    rounded = R.quantize(up64, dt)
+    mhi = [margin] * 3 if margin_hi is None else [max(margin, v) for v in margin_hi]
+    assert all(margin <= v < s - margin for v, s in zip(mhi, dims))
+    required = _axis_mask(dims, [margin] * 3, [s - v for s, v in zip(dims, mhi)])
+    box = _axis_mask(dims, [margin] * 3, [s - margin for s in dims])
+    assert int(required.sum()) > 0 and bool((required & ~box).sum() == 0)
+    results = {}
+    for mode in ("plain", "per_thread", "auto"):
+        dst = torch.empty((n, 2) + dims + (k,), dtype=R.STORAGE[dt], device="cuda")
+        R.bits(dst).fill_(word)
+        flags = (int(mode == "plain"), int(mode == "per_thread"))
+        if margin_hi is None:
+            rc = probe.probe_upsample2(R.DTYPES[dt], _ptr(src), _ptr(dst), n, d, h, w, 2 * k, margin, *flags, None)
+        else:
+            rc = probe.probe_upsample2_hi(R.DTYPES[dt], _ptr(src), _ptr(dst), n, d, h, w, 2 * k, margin,
+                                          (ctypes.c_int32 * 3)(*margin_hi), *flags, None)
+        assert rc == 0, (mode, probe.probe_last_error())
+        torch.cuda.synchronize()
+        kernel = probe.probe_last_layer_kernel().decode()
+        assert kernel == {"plain": "upsample2", "per_thread": "upsample2_pipe", "auto": auto_kernel}[mode], (mode, kernel)
+        host = dst.cpu()
+        got = R.unpack_blocked(host)
+        untouched = R.unpack_blocked(R.bits(host)) == word
+        results[mode] = R.unpack_blocked(R.bits(host))[:, :, required]
+        good = (got >= lo) & (got <= hi)
+        bad = ~good[:, :, required]
+        assert not bad.any(), (f"{mode}: {int(bad.sum())} of {bad.numel()} needed outputs outside the bound, max |diff| "
+                               f"{float((got - up64)[:, :, required].abs().max()):.3e}")
+        optional = box & ~required
+        bad = ~(good | untouched)[:, :, optional]
+        assert not bad.any(), f"{mode}: {int(bad.sum())} outputs beyond margin_hi neither left alone nor within the bound"
+        assert bool(untouched[:, :, ~box].all()), f"{mode}: outputs within the margin were written"
+        if mode == "auto" and skipped is not None:     # the strip kernel stops where it says it does
+            written = _axis_mask(dims, [margin] * 3, skipped)
+            assert bool(untouched[:, :, ~written].all()), "the strip kernel wrote beyond its high margins"
+            assert not bool(untouched[:, :, written].any()), "the strip kernel left outputs inside its margins alone"
+        if dt != "f32":   # the storage cast is the correctly rounded one for nearly all
+            exact = (got == rounded)[:, :, required]
+            assert exact.double().mean() >= 0.99, mode
+    for mode in ("per_thread", "auto"):
+        differ = results[mode] != results["plain"]
+        assert not differ.any(), f"{mode} and plain differ in {int(differ.sum())} of {differ.numel()} needed outputs"
+
+
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("oc", [1, 3, 4])
 def test_head_kernel(probe, dt, oc):
