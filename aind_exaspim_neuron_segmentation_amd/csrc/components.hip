@@ -24,6 +24,10 @@
 // running id count on the device), seam_union joins ids across the plane between two slabs in a
 // second union-find over ids, and after the last slab table_* turn the id forest into
 // table[provisional id] -> final label, which apply_table writes over the slabs.
+//
+// Watershed fragments (exaspim_watershed_fragments) differ in pass (a) alone:
+// edge_mask_watershed writes the same mask byte from each voxel's steepest edge and its neighbours',
+// and passes (b) to (g) run on it as they are.
 #include "label_scan.h"
 
 namespace exaspim {
@@ -91,6 +95,162 @@ __global__ __launch_bounds__(kThreads) void edge_mask_foreground(const T* __rest
         mask[i] = (unsigned char)m;
         // streamed slabs: the last plane's on bits, the half of a seam edge this slab knows
         if (seam && (int)z == dm.d - 1) seam[i - ((unsigned)dm.n - hw)] = m ? 1 : 0;
+    }
+}
+
+// ---- (a') watershed edge mask (exaspim_watershed_fragments) -------------------------------
+// A voxel's steepest edge as a code: 0 none, else 1 .. 6 = the edge to -z, -y, -x, +x, +y, +z, which
+// is the order of the other end's linear index. The candidates are offered in that order and replace
+// the best so far only when strictly larger, so the first of equal values stays; "best" starts at low,
+// which makes "eligible" (a > low, NaN never) and "larger than the best" one comparison. An edge that
+// leaves the volume is offered as low itself: never eligible.
+constexpr unsigned kToLowZ = 1, kToLowY = 2, kToLowX = 3, kToHighX = 4, kToHighY = 5, kToHighZ = 6;
+
+__device__ __forceinline__ unsigned steepest(float mz, float my, float mx, float px, float py, float pz,
+                                             float low) {
+    float best = low;
+    unsigned code = 0;
+    if (mz > best) { best = mz; code = kToLowZ; }
+    if (my > best) { best = my; code = kToLowY; }
+    if (mx > best) { best = mx; code = kToLowX; }
+    if (px > best) { best = px; code = kToHighX; }
+    if (py > best) { best = py; code = kToHighY; }
+    if (pz > best) { best = pz; code = kToHighZ; }
+    return code;
+}
+
+// the code of one in-volume voxel from six scalar loads: the halo, whose voxels belong to other tiles
+template <typename T>
+__device__ __forceinline__ unsigned steepest_at(const T* __restrict__ aff, const Dims& dm, int z, int y, int x,
+                                                float low) {
+    const size_t n = (size_t)dm.n, hw = (size_t)dm.h * dm.w;
+    const size_t i = ((size_t)z * dm.h + y) * dm.w + x;
+    const float mz = z > 0 ? widen<T>(aff[i - hw]) : low;
+    const float my = y > 0 ? widen<T>(aff[n + i - dm.w]) : low;
+    const float mx = x > 0 ? widen<T>(aff[2 * n + i - 1]) : low;
+    const float px = x < dm.w - 1 ? widen<T>(aff[2 * n + i]) : low;
+    const float py = y < dm.h - 1 ? widen<T>(aff[n + i]) : low;
+    const float pz = z < dm.d - 1 ? widen<T>(aff[i]) : low;
+    return steepest(mz, my, mx, px, py, pz, low);
+}
+
+// One 8 x 8 x 32 tile per round of a workgroup. Step 1: the steepest edge of every voxel of the tile
+// (VEC voxels along x per thread and load, as in edge_mask_affinity: w % VEC == 0, so a group is inside
+// the volume or outside it as a whole) and of the one-voxel halo on the three high faces, as one byte
+// per voxel in LDS. Step 2, after the barrier: an eligible edge v -- v + e is on iff its value is >= high
+// or it is the steepest edge of v or of v + e. Affinities are read through L1/L2: every value is needed
+// by its two ends, and both reads of it come from this workgroup except on the tile's faces.
+// kBitOn is set for every voxel, as edge_mask_affinity sets it: a voxel without an on edge stays a set
+// of one voxel, which the size floor of affinity mode removes.
+constexpr int kCodeRow = kTX + 8;                               // 33 codes per row, rows 8-byte aligned
+constexpr int kCodeBytes = (kTZ + 1) * (kTY + 1) * kCodeRow;    // 3240
+constexpr int kHaloZ = kTY * kTX, kHaloY = kTZ * kTX, kHaloX = kTZ * kTY;
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(kThreads) void edge_mask_watershed(const T* __restrict__ aff,
+                                                               unsigned char* __restrict__ mask, Dims dm,
+                                                               float low, float high, int tiles_x, int tiles_y,
+                                                               long long n_tiles) {
+    struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
+    struct alignas(VEC) Bytes { unsigned char b[VEC]; };
+    constexpr int kGroupsPerRow = kTX / VEC;
+    constexpr int kRounds = kTileVox / (kThreads * VEC);
+    __shared__ __attribute__((aligned(16))) unsigned char code[kCodeBytes];
+    const int t = threadIdx.x;
+    const size_t n = (size_t)dm.n, hw = (size_t)dm.h * dm.w;
+    // Neighbouring tiles read each other's face planes. Workgroups go round the 8 XCDs in turn, each with an
+    // L2 of its own, so workgroup b takes tile (b % 8) * (grid / 8) + b / 8: an XCD works on a contiguous
+    // run of tiles (a bijection on the first grid & ~7 workgroups, the rest keep their own; it decides
+    // speed only: 0.59 against 0.69 ms at 512^3).
+    const unsigned full = gridDim.x & ~7u;
+    const unsigned first = blockIdx.x < full ? (blockIdx.x & 7u) * (full >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    for (long long tile = first; tile < n_tiles; tile += gridDim.x) {
+        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y);
+        const int tz = (int)(tile / ((long long)tiles_x * tiles_y));
+        const int z0 = tz * kTZ, y0 = ty * kTY, x0 = tx * kTX;
+        // per voxel k of round r: bit k of elig = edge to +z/+y/+x eligible, of sure = eligible and
+        // (>= high or this voxel's steepest edge)
+        unsigned elig_z[kRounds], elig_y[kRounds], elig_x[kRounds];
+        unsigned sure_z[kRounds], sure_y[kRounds], sure_x[kRounds];
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int j = t + kThreads * r;
+            const int row = j / kGroupsPerRow, lx = (j - row * kGroupsPerRow) * VEC;
+            const int ly = row & (kTY - 1), lz = row >> 3;
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            Bytes c;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) c.b[k] = 0;
+            elig_z[r] = elig_y[r] = elig_x[r] = sure_z[r] = sure_y[r] = sure_x[r] = 0;
+            if (z < dm.d && y < dm.h && x < dm.w) {
+                const size_t i = ((size_t)z * dm.h + y) * dm.w + x;
+                const bool zin = z < dm.d - 1, yin = y < dm.h - 1;
+                const Pack az = *reinterpret_cast<const Pack*>(aff + i);
+                const Pack ay = *reinterpret_cast<const Pack*>(aff + n + i);
+                const Pack ax = *reinterpret_cast<const Pack*>(aff + 2 * n + i);
+                Pack bz = az, by = ay;   // overwritten where the lower neighbour exists
+                if (z > 0) bz = *reinterpret_cast<const Pack*>(aff + i - hw);
+                if (y > 0) by = *reinterpret_cast<const Pack*>(aff + n + i - dm.w);
+                float prev_x = x > 0 ? widen<T>(aff[2 * n + i - 1]) : low;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float pz = zin ? widen<T>(az.v[k]) : low;
+                    const float py = yin ? widen<T>(ay.v[k]) : low;
+                    const float px = x + k < dm.w - 1 ? widen<T>(ax.v[k]) : low;
+                    const float mz = z > 0 ? widen<T>(bz.v[k]) : low;
+                    const float my = y > 0 ? widen<T>(by.v[k]) : low;
+                    const unsigned cv = steepest(mz, my, prev_x, px, py, pz, low);
+                    prev_x = px;   // only read where x + k + 1 exists, and then px is the in-volume value
+                    c.b[k] = (unsigned char)cv;
+                    const unsigned ez = pz > low, ey = py > low, ex = px > low;
+                    elig_z[r] |= ez << k;
+                    elig_y[r] |= ey << k;
+                    elig_x[r] |= ex << k;
+                    sure_z[r] |= (ez & (unsigned)(pz >= high || cv == kToHighZ)) << k;
+                    sure_y[r] |= (ey & (unsigned)(py >= high || cv == kToHighY)) << k;
+                    sure_x[r] |= (ex & (unsigned)(px >= high || cv == kToHighX)) << k;
+                }
+            }
+            *reinterpret_cast<Bytes*>(code + (lz * (kTY + 1) + ly) * kCodeRow + lx) = c;
+        }
+        // the halo: plane z0 + 8, plane y0 + 8, column x0 + 32 (no corners: no edge of the tile ends there)
+        for (int j = t; j < kHaloZ + kHaloY + kHaloX; j += kThreads) {
+            int lz, ly, lx;
+            if (j < kHaloZ) {
+                lz = kTZ; ly = j >> 5; lx = j & (kTX - 1);
+            } else if (j < kHaloZ + kHaloY) {
+                lz = (j - kHaloZ) >> 5; ly = kTY; lx = j & (kTX - 1);
+            } else {
+                lz = (j - kHaloZ - kHaloY) >> 3; ly = j & (kTY - 1); lx = kTX;
+            }
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            unsigned cv = 0;
+            if (z < dm.d && y < dm.h && x < dm.w) cv = steepest_at<T>(aff, dm, z, y, x, low);
+            code[(lz * (kTY + 1) + ly) * kCodeRow + lx] = (unsigned char)cv;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int j = t + kThreads * r;
+            const int row = j / kGroupsPerRow, lx = (j - row * kGroupsPerRow) * VEC;
+            const int ly = row & (kTY - 1), lz = row >> 3;
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            if (z < dm.d && y < dm.h && x < dm.w) {
+                const unsigned char* here = code + (lz * (kTY + 1) + ly) * kCodeRow + lx;
+                Bytes out;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    unsigned m = kBitOn;
+                    const unsigned up_z = here[k + (kTY + 1) * kCodeRow], up_y = here[k + kCodeRow], up_x = here[k + 1];
+                    if (((sure_z[r] >> k) & 1u) | (((elig_z[r] >> k) & 1u) & (unsigned)(up_z == kToLowZ))) m |= kBitZ;
+                    if (((sure_y[r] >> k) & 1u) | (((elig_y[r] >> k) & 1u) & (unsigned)(up_y == kToLowY))) m |= kBitY;
+                    if (((sure_x[r] >> k) & 1u) | (((elig_x[r] >> k) & 1u) & (unsigned)(up_x == kToLowX))) m |= kBitX;
+                    out.b[k] = (unsigned char)m;
+                }
+                *reinterpret_cast<Bytes*>(mask + ((size_t)z * dm.h + y) * dm.w + x) = out;
+            }
+        }
+        __syncthreads();   // code is reused by the next tile
     }
 }
 
@@ -455,7 +615,9 @@ const char* stream_fault(const exaspim_components_stream* st) {
     return nullptr;
 }
 
-// the size filter's floor (see exaspim_components)
+// the size filter's floor: a one-voxel segment has no affinity (img_util.get_affinity_channels), so in
+// affinity mode it is background whatever min_size says; in foreground mode an on voxel alone is a
+// segment of size 1
 int64_t floored_min_size(int channels, int64_t min_size) {
     const int64_t floor_size = channels == 3 ? 1 : 0;
     return min_size < floor_size ? floor_size : min_size;
@@ -473,6 +635,43 @@ void launch_edge_mask(const void* src, int channels, unsigned char* mask, const 
     } else {
         edge_mask_affinity<T, 1><<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, stream>>>(p, mask, dm, thr, seam);
     }
+}
+
+template <typename T>
+void launch_watershed_mask(const void* src, unsigned char* mask, const Dims& dm, float low, float high,
+                           hipStream_t stream) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const T* p = static_cast<const T*>(src);
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    const unsigned grid = capped_grid((size_t)n_tiles, 1);
+    if (dm.w % VEC == 0 && ((uintptr_t)src & 15) == 0)
+        edge_mask_watershed<T, VEC><<<grid, kThreads, 0, stream>>>(p, mask, dm, low, high, tiles_x, tiles_y, n_tiles);
+    else
+        edge_mask_watershed<T, 1><<<grid, kThreads, 0, stream>>>(p, mask, dm, low, high, tiles_x, tiles_y, n_tiles);
+}
+
+int clamped_min_size(int64_t ms) { return ms > 2147483647ll ? 2147483647 : (int)ms; }
+
+// passes (b) to (g) of the whole-volume call: the mask (and the zeroed aux) are in the workspace
+void label_from_mask(const Dims& dm, const Layout& l, char* ws, int min_eff, int* parent, int* n_segments_dev,
+                     hipStream_t s) {
+    int* aux = reinterpret_cast<int*>(ws + l.aux_off);
+    const unsigned char* mask = reinterpret_cast<const unsigned char*>(ws + l.mask_off);
+    int* sums = reinterpret_cast<int*>(ws + l.sums_off);
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(mask, parent, dm, tiles_x, tiles_y, n_tiles);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads);
+    face_merge<<<grid, kThreads, 0, s>>>(mask, parent, dm);
+    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+    sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    const unsigned scan_grid = (unsigned)l.n_scan_blocks;
+    const KeptRoot kept{parent, mask, aux, min_eff};
+    scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, n_segments_dev);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    relabel<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
 }
 
 }  // namespace
@@ -508,37 +707,59 @@ extern "C" int exaspim_components(const void* aff_dev, int32_t aff_dtype, int32_
         set_error("components: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
         return EXASPIM_E_WORKSPACE;
     }
-    // a one-voxel segment has no affinity (img_util.get_affinity_channels): in affinity mode it is
-    // background whatever min_size says; in foreground mode an on voxel alone is a segment of size 1
-    const int64_t floor_size = channels == 3 ? 1 : 0;
-    const int64_t ms = min_size < floor_size ? floor_size : min_size;
-    const int min_eff = ms > 2147483647ll ? 2147483647 : (int)ms;
-
+    const int min_eff = clamped_min_size(floored_min_size(channels, min_size));
     hipStream_t s = (hipStream_t)stream;
     char* ws = static_cast<char*>(workspace_dev);
-    int* aux = reinterpret_cast<int*>(ws + l.aux_off);
+    EXA_CHECK_HIP(hipMemsetAsync(ws + l.aux_off, 0, (size_t)dm.n * 4, s));
     unsigned char* mask = reinterpret_cast<unsigned char*>(ws + l.mask_off);
-    int* sums = reinterpret_cast<int*>(ws + l.sums_off);
-    int* parent = labels_dev;
-
-    EXA_CHECK_HIP(hipMemsetAsync(aux, 0, (size_t)dm.n * 4, s));
     if (aff_dtype == EXASPIM_AFF_F32)
         launch_edge_mask<float>(aff_dev, channels, mask, dm, threshold, s);
     else
         launch_edge_mask<_Float16>(aff_dev, channels, mask, dm, threshold, s);
-    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
-    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
-    tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(mask, parent, dm, tiles_x, tiles_y, n_tiles);
-    const unsigned grid = capped_grid((size_t)dm.n, kThreads);
-    face_merge<<<grid, kThreads, 0, s>>>(mask, parent, dm);
-    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
-    sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
-    const unsigned scan_grid = (unsigned)l.n_scan_blocks;
-    const KeptRoot kept{parent, mask, aux, min_eff};
-    scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
-    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, n_segments_dev);
-    scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
-    relabel<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    label_from_mask(dm, l, ws, min_eff, labels_dev, n_segments_dev, s);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" size_t exaspim_watershed_workspace_bytes(const int32_t dims[3]) {
+    Dims dm;
+    if (!valid_dims(dims, &dm)) {
+        set_error("watershed_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return layout_of(dm).bytes;
+}
+
+extern "C" int exaspim_watershed_fragments(const void* aff_dev, int32_t aff_dtype, const int32_t dims[3],
+                                           float low, float high, int64_t min_size, int32_t* labels_dev,
+                                           int32_t* n_fragments_dev, void* workspace_dev,
+                                           size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(aff_dev && labels_dev && n_fragments_dev && workspace_dev && dims,
+                  "watershed_fragments: NULL argument");
+    EXA_CHECK_ARG(aff_dtype == EXASPIM_AFF_F32 || aff_dtype == EXASPIM_AFF_F16,
+                  "watershed_fragments: aff_dtype %d is neither EXASPIM_AFF_F32 nor EXASPIM_AFF_F16", aff_dtype);
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(dims, &dm),
+                  "watershed_fragments: dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(low == low && high == high, "watershed_fragments: low or high is a NaN");
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && ((uintptr_t)labels_dev & 3) == 0 &&
+                      ((uintptr_t)aff_dev & (aff_dtype == EXASPIM_AFF_F32 ? 3 : 1)) == 0,
+                  "watershed_fragments: misaligned buffer");
+    const Layout l = layout_of(dm);
+    if (workspace_bytes < l.bytes) {
+        set_error("watershed_fragments: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+        return EXASPIM_E_WORKSPACE;
+    }
+    const int min_eff = clamped_min_size(floored_min_size(3, min_size));
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace_dev);
+    EXA_CHECK_HIP(hipMemsetAsync(ws + l.aux_off, 0, (size_t)dm.n * 4, s));
+    unsigned char* mask = reinterpret_cast<unsigned char*>(ws + l.mask_off);
+    if (aff_dtype == EXASPIM_AFF_F32)
+        launch_watershed_mask<float>(aff_dev, mask, dm, low, high, s);
+    else
+        launch_watershed_mask<_Float16>(aff_dev, mask, dm, low, high, s);
+    label_from_mask(dm, l, ws, min_eff, labels_dev, n_fragments_dev, s);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
 }

@@ -332,6 +332,139 @@ def affinities_to_components(affinities, threshold=0.5, min_segment_size=100, *,
     return labels.cpu().numpy()
 
 
+# --- Watershed fragments ---
+def _watershed_on_device(affinities, low=0.1, high=0.9999, min_segment_size=0):
+    """
+    exaspim_watershed_fragments on a device tensor: the labels and the number
+    of kept fragments, both left on the device (nothing is synchronised).
+
+    Parameters
+    ----------
+    affinities : torch.Tensor
+        float32 or float16 (3, D, H, W) tensor on a HIP device.
+    low, high : float, optional
+        Rounded to float32; see watershed_fragments. Defaults are 0.1 and
+        0.9999.
+    min_segment_size : int, optional
+        Fragments are kept iff they have more voxels than this. Default is 0.
+
+    Returns
+    -------
+    labels : torch.Tensor
+        int32 (D, H, W): 0 for background, 1 ... K in raster order of each
+        fragment's first voxel.
+    count : torch.Tensor
+        int32 (1,): K.
+    """
+    if not isinstance(affinities, torch.Tensor):
+        raise TypeError(f"_watershed_on_device needs a torch tensor, got {type(affinities).__name__}")
+    if affinities.dtype not in _AFF_CODES:
+        raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
+    if affinities.dim() != 4 or affinities.shape[0] != 3:
+        raise ValueError(f"watershed_fragments needs (3, D, H, W) affinities, got {tuple(affinities.shape)}; "
+                         "a foreground map has no affinities")
+    low, high = float(np.float32(low)), float(np.float32(high))
+    if low != low or high != high:
+        raise ValueError(f"aff_threshold_low and aff_threshold_high must not be NaN, got {low} and {high}")
+    if affinities.device.type != "cuda":
+        raise RuntimeError(
+            "watershed_fragments (MI355X) has no CPU path: the tensor must be on a HIP device, "
+            f"got {affinities.device}"
+        )
+    dims = tuple(int(v) for v in affinities.shape[-3:])
+    if min(dims) < 1:
+        raise ValueError(f"empty volume {dims}")
+    affinities = affinities.contiguous()
+    device = affinities.device
+    lib = _native.lib()
+    need = lib.exaspim_watershed_workspace_bytes(_native.int3(dims))
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        labels = torch.empty(dims, dtype=torch.int32, device=device)
+        count = torch.empty(1, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_watershed_fragments(affinities.data_ptr(), _AFF_CODES[affinities.dtype],
+                                            _native.int3(dims), low, high, int(min_segment_size),
+                                            labels.data_ptr(), count.data_ptr(), workspace.data_ptr(), need,
+                                            _stream(device)),
+            "exaspim_watershed_fragments",
+        )
+    return labels, count
+
+
+def watershed_fragments(affinities, aff_threshold_low=0.1, aff_threshold_high=0.9999, min_segment_size=0, *,
+                        return_device_tensor=False):
+    """
+    Labels the basins of a steepest-ascent watershed on the affinity graph on
+    the device: the fragments the reference's affinities_to_segmentation
+    starts from (inference.py:224-229, waterz.agglomerate(...,
+    aff_threshold_low=0.1, aff_threshold_high=0.9999)).
+
+    What this is, exactly: in the project's edge convention (channel c at
+    voxel v is the edge between v and v + e_c, e = z, y, x; the entries at the
+    last index along axis c are ignored), (1) an edge is eligible iff
+    float32(a) > aff_threshold_low, strictly (NaN never, +inf always); (2) a
+    voxel's steepest edge is its eligible incident edge of largest value,
+    among equal values the one whose other end has the smallest C-order
+    linear index (the order -z, -y, -x, +x, +y, +z); (3) an eligible edge is
+    on iff a >= aff_threshold_high or it is the steepest edge of one of its
+    two ends; (4) fragments are the connected components of the on edges, a
+    voxel without an on edge is background, a fragment is kept iff it has
+    more than max(min_segment_size, 1) voxels, and kept fragments are
+    numbered 1 ... K in raster order of each fragment's first voxel. No
+    relation between the two thresholds is required: with high <= low every
+    eligible edge is on.
+
+    What equals what: this equals the serial steepest-ascent watershed
+    (direction bits, plateau corners, breadth-first plateau division, pointer
+    chasing with ids in raster order) label for label on tie-free input, i.e.
+    where no voxel has two equal maximal eligible edges below
+    aff_threshold_high, by the oracle in tests/ (watershed_ref.py). Where
+    such ties exist the serial algorithm depends on its visiting order and
+    the two differ; this definition depends on no order. It has not been
+    compared with waterz itself, which also reads the same array as the
+    edges v -- v - e_c; the project keeps the convention the network was
+    trained in.
+
+    Parameters
+    ----------
+    affinities : torch.Tensor or numpy.ndarray
+        float32 or float16 (3, D, H, W): a tensor on a HIP device (e.g. from
+        predict(..., return_device_tensor=True)), or a numpy array, which is
+        uploaded to cuda:0. D * H * W must not exceed 2^31 - 1. A 3-D
+        foreground map has no affinities and raises ValueError.
+    aff_threshold_low, aff_threshold_high : float, optional
+        Rounded to float32, not NaN. Defaults are 0.1 and 0.9999, the
+        reference's.
+    min_segment_size : int, optional
+        Default is 0: every fragment is kept (the reference filters after
+        the agglomeration).
+    return_device_tensor : bool, optional
+        Return the labels as a device tensor instead of a numpy array.
+        Default is False.
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W) labels.
+    """
+    if isinstance(affinities, np.ndarray):
+        if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+            raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
+        if affinities.ndim != 4 or affinities.shape[0] != 3:
+            raise ValueError(f"watershed_fragments needs (3, D, H, W) affinities, got {tuple(affinities.shape)}; "
+                             "a foreground map has no affinities")
+        if not torch.cuda.is_available():
+            raise RuntimeError("watershed_fragments (MI355X) has no CPU path and no HIP device is present")
+        affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
+    labels, _ = _watershed_on_device(affinities, aff_threshold_low, aff_threshold_high, min_segment_size)
+    if return_device_tensor:
+        return labels
+    return labels.cpu().numpy()
+
+
 # --- Mean-affinity agglomeration of components (DESIGN 6e) ---
 # Slots of the region graph's accumulator unless the caller says otherwise (edge_capacity): 48 bytes of
 # device memory each (24 in the table, 24 in the compacted list), so 192 MiB at most; a small volume
@@ -535,15 +668,20 @@ def agglomerate(edges, counts, sums, sizes, agglomeration_thresholds=(0.6, 0.8, 
 
 
 def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
-                           fragment_threshold=0.5, edge_capacity=None, return_device_tensor=False):
+                           fragment_threshold=0.5, edge_capacity=None, return_device_tensor=False,
+                           fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999):
     """
-    Segments affinities by mean-affinity agglomeration of connected
-    components, in the reference's order of operations.
+    Segments affinities by mean-affinity agglomeration of fragments, in the
+    reference's order of operations.
 
     What this is: the three steps of the reference's
     affinities_to_segmentation (inference.py:196-237) with exactly defined
-    parts. (1) Fragments: the connected components of the affinity graph cut
-    at fragment_threshold (affinities_to_components with no size filter).
+    parts. (1) Fragments: with fragments="components", the default, the
+    connected components of the affinity graph cut at fragment_threshold
+    (affinities_to_components with no size filter); with
+    fragments="watershed" the basins of a steepest-ascent watershed between
+    aff_threshold_low and aff_threshold_high (watershed_fragments with no
+    size filter), which is the kind of fragment the reference starts from.
     (2) Fragments whose contact surface has a high mean affinity are merged,
     greedily in order of the score waterz uses by default, 1 - mean affinity
     of the contact, while that score is below the last agglomeration
@@ -555,12 +693,19 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     order of each segment's first voxel. The positional arguments and their
     defaults are those of affinities_to_segmentation.
 
-    What this is not: waterz. The fragments are connected components at a
-    threshold, not waterz's watershed basins, so the labels are not
-    comparable with the reference's, and the name differs on purpose. Only
-    the segmentation of the last threshold is returned, as in the reference
-    (deque(maxlen=1)); greedy merging in score order makes it independent of
-    the intermediate stops.
+    What this is not: waterz. Connected components at a threshold are not
+    watershed basins: one voxel edge above fragment_threshold fuses two
+    neurites for good, and agglomeration only merges. The watershed
+    fragments equal the serial steepest-ascent watershed on tie-free input
+    (no voxel with two equal maximal eligible edges below
+    aff_threshold_high), label for label, by the oracle in tests/
+    (watershed_ref.py); where affinities tie, the serial algorithm depends
+    on its visiting order and the two differ. Neither kind has been compared
+    with waterz itself, which reads the same array as the edges v -- v - e_c
+    while the project keeps the convention the network was trained in, so
+    the name differs on purpose. Only the segmentation of the last threshold
+    is returned, as in the reference (deque(maxlen=1)); greedy merging in
+    score order makes it independent of the intermediate stops.
 
     Parameters
     ----------
@@ -573,12 +718,17 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     min_segment_size : int, optional
         Default is 100.
     fragment_threshold : float, optional
-        Default is 0.5.
+        Used with fragments="components". Default is 0.5.
     edge_capacity : int, optional
         See region_graph.
     return_device_tensor : bool, optional
         Return the labels as a device tensor instead of a numpy array.
         Default is False.
+    fragments : {"components", "watershed"}, optional
+        The kind of fragments. Default is "components".
+    aff_threshold_low, aff_threshold_high : float, optional
+        Used with fragments="watershed". Defaults are 0.1 and 0.9999, the
+        reference's.
 
     Returns
     -------
@@ -587,6 +737,8 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     """
     thresholds = list(agglomeration_thresholds)
     _last_threshold(thresholds)
+    if fragments not in ("components", "watershed"):
+        raise ValueError(f'fragments must be "components" or "watershed", got {fragments!r}')
     if isinstance(affinities, np.ndarray):
         if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
             raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
@@ -603,7 +755,10 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
             raise RuntimeError("agglomerate_affinities (MI355X) has no CPU path and no HIP device is present")
         affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
     affinities = affinities.contiguous()
-    labels, count = _components_on_device(affinities, fragment_threshold, 0)
+    if fragments == "watershed":
+        labels, count = _watershed_on_device(affinities, aff_threshold_low, aff_threshold_high, 0)
+    else:
+        labels, count = _components_on_device(affinities, fragment_threshold, 0)
     n_fragments = int(count.cpu()[0])
     edges, counts, sums, sizes = _region_graph_on_device(labels, affinities, n_fragments, edge_capacity)
     table, _ = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)

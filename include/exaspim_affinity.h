@@ -51,7 +51,9 @@ extern "C" {
  *    later within 5: exaspim_region_graph_stream_slab / _finish and the finish workspace query (struct
  *    exaspim_region_graph_stream): the region graph of a volume that arrives in z slabs;
  *    later within 5: exaspim_unet_carry1_planes, exaspim_unet_forward_prepared_carry1 (struct
- *    exaspim_unet_carry1): second-level planes carried along z as well */
+ *    exaspim_unet_carry1): second-level planes carried along z as well;
+ *    later within 5: exaspim_watershed_fragments, exaspim_watershed_workspace_bytes: steepest-ascent
+ *    watershed fragments for the agglomeration */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -687,6 +689,52 @@ int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, const uint6
  * on "stream". */
 int exaspim_apply_label_table(int32_t* labels_dev, size_t n, const int32_t* table_dev, int32_t table_len,
                               void* stream);
+
+/* ---- watershed fragments for the agglomeration -------------------------------
+ *      (later within ABI 5). The reference's affinities_to_segmentation calls
+ *      waterz.agglomerate(aff, thresholds, aff_threshold_low=0.1, aff_threshold_high=0.9999)
+ *      (inference.py:224-229), whose fragments are the basins of a steepest-ascent watershed on the
+ *      affinity graph. This is that first step with an exact, order-independent definition; everything
+ *      after the edge mask is exaspim_components' own code.
+ *
+ *      aff_dev is (3, dims) of aff_dtype (EXASPIM_AFF_*, float16 widened exactly) in exaspim_components'
+ *      edge convention: channel c at voxel v is the edge v -- v + e_c, e = z, y, x; the entries at the
+ *      last index along axis c are ignored whatever they hold. (waterz reads the same array as the edges
+ *      v -- v - e_c; the project keeps the convention the network was trained in.)
+ *       1. An edge is eligible iff float32(a) > low, strictly; a NaN is not eligible, +inf is.
+ *       2. A voxel's steepest edge is the eligible edge of largest value among its up to six incident
+ *          edges; among equal values the edge whose other end has the smallest C-order linear index,
+ *          i.e. the first in the order -z, -y, -x, +x, +y, +z. A voxel without an eligible edge has none.
+ *       3. An eligible edge is on iff a >= high, or it is the steepest edge of its lower end, or it is
+ *          the steepest edge of its upper end.
+ *       4. Fragments are the connected components of the graph of on edges; a voxel without an on edge
+ *          is background (0). A fragment is kept iff size > max(min_size, 1), and kept fragments are
+ *          numbered 1 .. K in raster order of each fragment's first voxel, as in exaspim_components.
+ *      No relation between low and high is required: with high <= low every eligible edge is on.
+ *
+ *      This equals the serial steepest-ascent watershed (direction bits for "is the maximum, or >= high",
+ *      plateau corners, breadth-first plateau division, pointer chasing with ids in raster order), label
+ *      for label, on input where no voxel has two equal maximal eligible edges below high -- by the oracle
+ *      in tests/, not by a run of waterz. Where such ties exist the serial algorithm depends on its
+ *      visiting order and the two differ; this definition does not depend on any order. */
+
+/* Scratch bytes of exaspim_watershed_fragments: exaspim_components_workspace_bytes' figure, about 5 bytes
+ * per voxel. 0 (and a message) if a dim is not positive or the volume has more than 2^31 - 1 voxels. */
+size_t exaspim_watershed_workspace_bytes(const int32_t dims[3]);
+
+/* labels_dev (int32, dims) = the fragments defined above, *n_fragments_dev = K. A pure function of the
+ * input. One launch for the edge mask (8 x 8 x 32 tiles with a one-voxel halo on the high faces, no
+ * atomics), then exaspim_components' passes; launches on "stream" only, no inter-workgroup waiting,
+ * nothing allocated, nothing synchronised. Buffers as for exaspim_components (aff_dev 16-byte aligned
+ * and dims[2] a multiple of 16 bytes' worth of elements to get the wide loads). EXASPIM_E_WORKSPACE if
+ * workspace_bytes is less than exaspim_watershed_workspace_bytes(dims); EXASPIM_E_INVALID for a NULL
+ * pointer, an unknown aff_dtype, a dim that is not positive, a volume of more than 2^31 - 1 voxels, a
+ * NaN low or high, or a misaligned buffer (workspace_dev not 16-byte aligned, labels_dev or aff_dev not
+ * aligned to its element): all before anything is launched. */
+int exaspim_watershed_fragments(const void* aff_dev, int32_t aff_dtype, const int32_t dims[3],
+                                float low, float high, int64_t min_size,
+                                int32_t* labels_dev, int32_t* n_fragments_dev,
+                                void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
