@@ -216,6 +216,10 @@ SIGNATURES = {
     "exaspim_agglomerate": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, ctypes.c_float, ctypes.c_int64,
                                    _vp, _vp]),
     "exaspim_apply_label_table": (_i32, [_vp, _sz, _vp, _i32, _vp]),
+    "exaspim_region_graph_premerge_workspace_bytes": (_sz, [_i32, ctypes.c_int64]),
+    "exaspim_region_graph_premerge": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, ctypes.c_float,
+                                             ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _sz, _vp]),
     "exaspim_watershed_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_watershed_fragments": (_i32, [_vp, _i32, _I32x3, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp,
                                            _vp, _vp, _sz, _vp]),

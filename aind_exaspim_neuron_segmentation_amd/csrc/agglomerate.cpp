@@ -77,11 +77,10 @@ extern "C" int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, 
     for (int32_t l = 0; l <= K; ++l)
         EXA_CHECK_ARG(sizes[l] >= 0, "agglomerate: sizes[%d] is negative", l);
 
-    // merge iff sum > m * count, m = rint((1 - T) * 2^24), i.e. iff 1 - mean affinity < T up to the grid of q;
-    // m <= 0 merges nothing that has sum 0 and everything else, m >= 2^24 nothing at all
-    const double md = __builtin_rint((1.0 - (double)threshold) * 16777216.0);
-    const bool merge_all = md < 0.0;
-    const uint64_t m = md < 0.0 ? 0 : md > 16777216.0 ? 16777216ull : (uint64_t)md;
+    // merge iff merge_all or sum > m * count (common.h)
+    const MergeBound bound = merge_bound(threshold);
+    const bool merge_all = bound.merge_all;
+    const uint64_t m = bound.m;
 
     std::vector<Edge> edge((size_t)n_edges);
     std::vector<std::vector<int32_t>> adj((size_t)K + 1);

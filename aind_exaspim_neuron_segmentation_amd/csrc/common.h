@@ -164,6 +164,17 @@ constexpr int kNumMfmaConvs = 17;  // every 3x3x3 conv except inc.0 (Cin = 1)
 
 inline int pad_channels(int c) { return (c + kChannelPad - 1) / kChannelPad * kChannelPad; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The merge test of the agglomeration and of the pre-merge: an edge merges iff merge_all or
+// sum > m * count, m = rint((1 - T) * 2^24), i.e. iff 1 - mean affinity < T up to the grid of q;
+// m <= 0 merges nothing that has sum 0 and everything else, m >= 2^24 nothing at all.
+struct MergeBound {
+    uint64_t m;
+    bool merge_all;
+};
+inline MergeBound merge_bound(float threshold) {
+    const double md = __builtin_rint((1.0 - (double)threshold) * 16777216.0);
+    return MergeBound{md < 0.0 ? 0 : md > 16777216.0 ? 16777216ull : (uint64_t)md, md < 0.0};
+}
 // Type the activations are stored in between kernels: EXASPIM_DT_BF16X3 keeps them float32 (only
 // its 3x3x3 MFMA convolutions are its own; every other layer runs the float32 kernel).
 inline int storage_dtype(int dtype) { return dtype == EXASPIM_DT_BF16X3 ? EXASPIM_DT_F32 : dtype; }

@@ -29,58 +29,21 @@
 // finish: retarget walks the provisional table, maps both ends of every key through the caller's table
 // and re-adds what is left into a second table, retarget_sizes does the same for the voxel counts, and
 // the scan turns the second table into the edge list. The provisional table is only read.
-#include "label_scan.h"
+#include "edge_table.h"
 
 namespace exaspim {
 namespace {
 
-constexpr unsigned long long kEmpty = ~0ull;   // no key: lo and hi are at most 2^31 - 1
 constexpr int kLdsSlots = 2048;                // LDS table of a tile: 20 B per slot
 constexpr int kLdsProbes = 16;
 constexpr int kHZ = kTZ + 1, kHY = kTY + 1, kHX = kTX + 1;   // the tile with its +1 halo
 constexpr int kHaloVox = kHZ * kHY * kHX;                    // 2673
-constexpr int kEdges = 0, kOverflow = 1;       // state words
-
-struct Table {
-    unsigned long long* keys;
-    unsigned long long* counts;
-    unsigned long long* sums;
-    unsigned mask;   // capacity - 1
-    int* state;
-};
-
-__device__ __forceinline__ unsigned long long mix(unsigned long long k) {
-    k *= 0x9E3779B97F4A7C15ull;
-    return k ^ (k >> 29);
-}
 
 // q(a): NaN and everything below 0 to 0, everything above 1 to 2^24; a * 2^24 is exact in float32
 __device__ __forceinline__ unsigned quantise(float a) {
     a = a > 0.f ? a : 0.f;
     a = a < 1.f ? a : 1.f;
     return __float2uint_rn(a * 16777216.f);
-}
-
-// count[key] += cnt, sum[key] += sum in the global table
-__device__ void global_add(const Table& g, unsigned long long key, unsigned long long cnt,
-                           unsigned long long sum) {
-    unsigned slot = (unsigned)(mix(key) >> 32) & g.mask;
-    for (unsigned p = 0; p <= g.mask; ++p, slot = (slot + 1) & g.mask) {
-        // a table that has overflowed is unusable: do not walk it again for every later key
-        if ((p & 63) == 0 && __hip_atomic_load(g.state + kOverflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        unsigned long long k = __hip_atomic_load(g.keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == kEmpty) {
-            k = atomicCAS(g.keys + slot, kEmpty, key);
-            if (k == kEmpty) k = key;
-        }
-        if (k == key) {
-            atomicAdd(g.counts + slot, cnt);
-            atomicAdd(g.sums + slot, sum);
-            return;
-        }
-    }
-    atomicExch(g.state + kOverflow, 1);
 }
 
 struct LdsTable {
@@ -105,11 +68,6 @@ __device__ __forceinline__ bool lds_add(const LdsTable& t, unsigned long long ke
         }
     }
     return false;
-}
-
-__device__ __forceinline__ unsigned long long edge_key(int a, int b) {
-    const unsigned lo = (unsigned)(a < b ? a : b), hi = (unsigned)(a < b ? b : a);
-    return (unsigned long long)lo << 32 | hi;
 }
 
 __device__ __forceinline__ void lds_clear(const LdsTable& t) {
@@ -204,25 +162,6 @@ __global__ __launch_bounds__(kThreads) void tile_graph(const int* __restrict__ l
     }
 }
 
-// the scan's predicate and sink: occupied slots, in slot order, become the edge list
-struct UsedSlot {
-    const unsigned long long* keys;
-    const unsigned long long* counts;
-    const unsigned long long* sums;
-    int* edges;
-    long long* count_out;
-    unsigned long long* sum_out;
-    __device__ __forceinline__ bool operator()(size_t v) const { return keys[v] != kEmpty; }
-    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const {
-        if (!flag) return;
-        const unsigned long long key = keys[v];
-        edges[2 * (size_t)rank] = (int)(key >> 32);
-        edges[2 * (size_t)rank + 1] = (int)(unsigned)key;
-        count_out[rank] = (long long)counts[v];
-        sum_out[rank] = sums[v];
-    }
-};
-
 // ---- the streamed form ---------------------------------------------------------------------------
 constexpr int kSeamPerBlock = 16 * kThreads;   // (y, x) positions a workgroup of seam_graph pools
 
@@ -316,26 +255,6 @@ __global__ __launch_bounds__(kThreads) void retarget_sizes(const unsigned long l
         if ((unsigned)l > (unsigned)n_labels) l = 0;
         atomicAdd(sizes + l, c);
     }
-}
-
-struct Layout {
-    size_t keys_off, counts_off, sums_off, blocks_off, bytes;
-    long long n_scan_blocks;
-};
-
-constexpr int64_t kMaxEdgeCapacity = 1ll << 30;
-
-bool valid_capacity(int64_t c) { return c >= 1 && c <= kMaxEdgeCapacity && (c & (c - 1)) == 0; }
-
-Layout layout_of(int64_t capacity) {
-    Layout l;
-    l.n_scan_blocks = (capacity + kScanBlock - 1) / kScanBlock;
-    l.keys_off = 0;
-    l.counts_off = align_up((size_t)capacity * 8, 256);
-    l.sums_off = 2 * l.counts_off;
-    l.blocks_off = 3 * l.counts_off;
-    l.bytes = l.blocks_off + align_up((size_t)l.n_scan_blocks * 4, 256);
-    return l;
 }
 
 }  // namespace

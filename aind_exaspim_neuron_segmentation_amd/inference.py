@@ -477,20 +477,20 @@ def _default_edge_capacity(voxels):
     return min(DEFAULT_EDGE_CAPACITY, 1 << max(want - 1, 0).bit_length())
 
 
-def _region_graph_on_device(labels, affinities, n_labels, edge_capacity=None):
+def _region_graph_device(labels, affinities, n_labels, edge_capacity=None):
     """
-    exaspim_region_graph on device tensors, then the one small download.
+    exaspim_region_graph on device tensors and the one read of its state: the
+    graph stays on the device.
 
     Returns
     -------
-    edges : numpy.ndarray
-        int32 (E, 2), rows (lo, hi) sorted by (lo, hi).
-    counts : numpy.ndarray
-        int64 (E,): voxel edges between the two labels.
-    sums : numpy.ndarray
-        uint64 (E,): the sum of q(affinity) over them, q in units of 2^-24.
-    sizes : numpy.ndarray
-        int64 (n_labels + 1,): voxels per label, index 0 the background.
+    edges, counts, sums : torch.Tensor
+        int32 (capacity, 2), int64 (capacity,), int64 (capacity,) holding
+        uint64 bits: the first n_edges rows in an unspecified order.
+    sizes : torch.Tensor
+        int64 (n_labels + 1,).
+    n_edges : int
+    capacity : int
 
     Raises
     ------
@@ -540,10 +540,41 @@ def _region_graph_on_device(labels, affinities, n_labels, edge_capacity=None):
             raise RuntimeError(
                 f"region_graph: the volume has more pairs of adjacent labels than edge_capacity={capacity}; "
                 "run it again with a larger edge_capacity (a power of two)")
-        edges_h = edges[:n_edges].cpu().numpy()
-        counts_h = counts[:n_edges].cpu().numpy()
-        sums_h = sums[:n_edges].cpu().numpy().view(np.uint64)
-        sizes_h = sizes.cpu().numpy()
+    return edges, counts, sums, sizes, n_edges, capacity
+
+
+def _region_graph_on_device(labels, affinities, n_labels, edge_capacity=None):
+    """
+    exaspim_region_graph on device tensors, then the one small download.
+
+    Returns
+    -------
+    edges : numpy.ndarray
+        int32 (E, 2), rows (lo, hi) sorted by (lo, hi).
+    counts : numpy.ndarray
+        int64 (E,): voxel edges between the two labels.
+    sums : numpy.ndarray
+        uint64 (E,): the sum of q(affinity) over them, q in units of 2^-24.
+    sizes : numpy.ndarray
+        int64 (n_labels + 1,): voxels per label, index 0 the background.
+
+    Raises
+    ------
+    RuntimeError
+        If the volume has more distinct pairs of adjacent labels than
+        edge_capacity.
+    """
+    edges, counts, sums, sizes, n_edges, _ = _region_graph_device(labels, affinities, n_labels, edge_capacity)
+    with torch.cuda.device(labels.device):
+        return _download_graph(edges, counts, sums, sizes, n_edges)
+
+
+def _download_graph(edges, counts, sums, sizes, n_edges):
+    """The first n_edges rows of a device graph, and its sizes, as numpy arrays sorted by (lo, hi)."""
+    edges_h = edges[:n_edges].cpu().numpy().reshape(-1, 2)
+    counts_h = counts[:n_edges].cpu().numpy()
+    sums_h = sums[:n_edges].cpu().numpy().view(np.uint64)
+    sizes_h = sizes.cpu().numpy()
     order = np.lexsort((edges_h[:, 1], edges_h[:, 0]))   # slot order depends on arrival: sort by (lo, hi)
     return (np.ascontiguousarray(edges_h[order]), np.ascontiguousarray(counts_h[order]),
             np.ascontiguousarray(sums_h[order]), sizes_h)
@@ -667,9 +698,225 @@ def agglomerate(edges, counts, sums, sizes, agglomeration_thresholds=(0.6, 0.8, 
     return table, int(n_segments.value)
 
 
+def _checked_premerge(size_floor, rounds):
+    """(size_floor, rounds) as ints; ValueError for negatives and non-integers, before any device call."""
+    for what, v, least in (("the size floor", size_floor, 0), ("the number of rounds", rounds, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what} must be an integer, got {v!r}")
+        if v < least:
+            raise ValueError(f"{what} must be at least {least}, got {v}")
+    if size_floor >= 1 << 63:
+        raise ValueError(f"the size floor must fit in 63 bits, got {size_floor}")
+    return int(size_floor), int(rounds)
+
+
+def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity,
+                        timings=None):
+    """
+    Rounds of exaspim_region_graph_premerge on a graph that is on the device,
+    each on the previous one's output, until one merges nothing or "rounds"
+    have run. One 12-byte read of the state per round; the maps are composed
+    on the device (exaspim_apply_label_table on the composed map).
+
+    Parameters
+    ----------
+    edges, counts, sums, sizes : torch.Tensor
+        The graph in exaspim_region_graph's output format (sums holds uint64
+        bits); edges, counts and sums hold at least n_edges rows. Only read.
+    timings : list, optional
+        If given, HIP events time every round and the milliseconds are
+        appended (a measurement aid: it synchronises once at the end).
+
+    Returns
+    -------
+    edges, counts, sums, sizes : torch.Tensor
+        The reduced graph: n_edges rows in an unspecified order, K' + 1 sizes.
+    n_edges : int
+    composed : torch.Tensor
+        int32 (K + 1,): fragment id -> id in the reduced graph.
+    history : list of (int, int)
+        (K', E') after every round that ran.
+    """
+    device = sizes.device
+    n_labels = int(sizes.numel()) - 1
+    lib = _native.lib()
+    stream = _stream(device)
+    history, events = [], []
+    with torch.cuda.device(device):
+        composed = None
+        need = lib.exaspim_region_graph_premerge_workspace_bytes(n_labels, capacity)
+        if need == 0:
+            raise ValueError(_native.last_error())
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        state = torch.empty(3, dtype=torch.int32, device=device)
+        spare = None   # the buffers the round after next may write: never the caller's
+        for _ in range(rounds):
+            k = int(sizes.numel()) - 1
+            if spare is None:
+                out = (torch.empty((capacity, 2), dtype=torch.int32, device=device),
+                       torch.empty(capacity, dtype=torch.int64, device=device),
+                       torch.empty(capacity, dtype=torch.int64, device=device))
+            else:
+                out, spare = spare, None
+            sizes_out = torch.empty(k + 1, dtype=torch.int64, device=device)
+            mapping = torch.empty(k + 1, dtype=torch.int32, device=device)
+            if timings is not None:
+                events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                events[-1][0].record()
+            _native.check(
+                lib.exaspim_region_graph_premerge(edges.data_ptr(), counts.data_ptr(), sums.data_ptr(),
+                                                  sizes.data_ptr(), n_edges, k, float(np.float32(threshold)),
+                                                  size_floor, capacity, out[0].data_ptr(), out[1].data_ptr(),
+                                                  out[2].data_ptr(), sizes_out.data_ptr(), mapping.data_ptr(),
+                                                  state.data_ptr(), workspace.data_ptr(), need, stream),
+                "exaspim_region_graph_premerge",
+            )
+            if composed is None:
+                composed = mapping
+            else:
+                _native.check(
+                    lib.exaspim_apply_label_table(composed.data_ptr(), composed.numel(), mapping.data_ptr(),
+                                                  mapping.numel(), stream),
+                    "exaspim_apply_label_table",
+                )
+            if timings is not None:
+                events[-1][1].record()
+            k_new, e_new, overflow = (int(v) for v in state.cpu())   # the round's one read of the device
+            if overflow:
+                raise RuntimeError(
+                    f"premerge_region_graph: the contracted graph found no room in edge_capacity={capacity} "
+                    "slots; run it again with a larger edge_capacity (a power of two)")
+            if history:   # this round's input was an earlier round's output: free for the next one
+                spare = (edges, counts, sums)
+            edges, counts, sums = out
+            sizes, n_edges = sizes_out[:k_new + 1], e_new
+            history.append((k_new, e_new))
+            if k_new == k:
+                break
+        if timings is not None:
+            torch.cuda.synchronize(device)
+            timings.extend(a.elapsed_time(b) for a, b in events)
+    return edges, counts, sums, sizes, n_edges, composed, history
+
+
+def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, rounds=4, edge_capacity=None):
+    """
+    Merges the tiny fragments of a region graph into their best neighbours
+    on the device (exaspim_region_graph_premerge), so that
+    agglomerate starts from far fewer fragments.
+
+    One round: an edge is mergeable iff sum > rint((1 - T) * 2^24) * count
+    (agglomerate's test at threshold T); every fragment with fewer than
+    size_floor voxels that has a mergeable edge joins the neighbour across
+    its mergeable edge of largest mean (equal means: the smaller neighbour
+    id; of two fragments that choose each other the smaller id stays), whole
+    chains at once; the sets are numbered by their smallest member id, sizes
+    add up, edges inside a set vanish and parallel edges add their counts and
+    sums. Rounds run on their own output until one merges nothing or
+    "rounds" of them have run. All comparisons are exact integer ones.
+
+    This is not agglomerate's rule: a tiny fragment joins its best neighbour
+    at once, whatever that neighbour would have merged with first, so
+    agglomerating the reduced graph can give another segmentation than
+    agglomerating the input. size_floor 0 (and 1, when no fragment is empty)
+    returns the input.
+
+    Parameters
+    ----------
+    edges, counts, sums, sizes : numpy.ndarray or torch.Tensor
+        What region_graph returns, or the same on a HIP device (sums may be
+        int64 holding uint64 bits); numpy arrays are uploaded to cuda:0.
+    threshold : float
+        T of the mergeable test: the last agglomeration threshold.
+    size_floor : int
+        Fragments below this many voxels are merged. Not negative.
+    rounds : int, optional
+        The most rounds to run. Default is 4.
+    edge_capacity : int, optional
+        Slots of the device hash table, a power of two. Default is the next
+        power of two >= 2 * E.
+
+    Returns
+    -------
+    edges, counts, sums, sizes : numpy.ndarray
+        The reduced graph in region_graph's format, sorted by (lo, hi).
+    mapping : numpy.ndarray
+        int32 (K + 1,): fragment id -> id in the reduced graph, map[0] = 0.
+    history : list of int
+        The number of fragments after every round that ran.
+    """
+    size_floor, rounds = _checked_premerge(size_floor, rounds)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("the threshold is NaN")
+    given = (edges, counts, sums, sizes)
+    if all(isinstance(a, torch.Tensor) for a in given):
+        device = sizes.device
+        if device.type != "cuda" or any(a.device != device for a in given):
+            raise RuntimeError("premerge_region_graph (MI355X) has no CPU path: the graph must be on one HIP device")
+        edges, counts, sums, sizes = (a.contiguous() for a in given)
+    elif any(isinstance(a, torch.Tensor) for a in given):
+        raise TypeError("premerge_region_graph needs the four arrays all on the host or all on the device")
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("premerge_region_graph (MI355X) has no CPU path and no HIP device is present")
+        device = torch.device("cuda:0")
+        edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).to(device)
+        counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(device)
+        sums = torch.from_numpy(np.ascontiguousarray(sums, dtype=np.uint64).view(np.int64)).to(device)
+        sizes = torch.from_numpy(np.ascontiguousarray(sizes, dtype=np.int64)).to(device)
+    if (edges.dtype != torch.int32 or counts.dtype != torch.int64 or sums.dtype != torch.int64
+            or sizes.dtype != torch.int64):
+        raise TypeError("premerge_region_graph needs int32 edges and 64-bit counts, sums and sizes")
+    n_edges = int(counts.numel())
+    if (sizes.dim() != 1 or sizes.numel() < 1 or edges.numel() != 2 * n_edges or sums.numel() != n_edges):
+        raise ValueError("premerge_region_graph needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
+    capacity = 1 << max(2 * n_edges - 1, 0).bit_length() if edge_capacity is None else int(edge_capacity)
+    edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
+        edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity)
+    with torch.cuda.device(device):
+        graph = _download_graph(edges, counts, sums, sizes, n_edges)
+        mapping = composed.cpu().numpy()
+    return graph + (mapping, [k for k, _ in history])
+
+
+def _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity, premerge_size,
+                     premerge_rounds, stats=None):
+    """
+    The fragment -> segment table of agglomerate_affinities with a size
+    floor, as a device tensor: the region graph stays on the device, the
+    pre-merge rounds run there, only the reduced graph is downloaded and
+    agglomerated, and the final table is composed with the rounds' map on the
+    device. "stats", a dict, receives the rounds' history, their device
+    milliseconds, the host merging time and the number of segments.
+    """
+    device = labels.device
+    edges, counts, sums, sizes, n_edges, capacity = _region_graph_device(labels, affinities, n_fragments,
+                                                                         edge_capacity)
+    timings = None if stats is None else []
+    edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
+        edges, counts, sums, sizes, n_edges, thresholds[-1], premerge_size, premerge_rounds, capacity, timings)
+    with torch.cuda.device(device):
+        graph = _download_graph(edges, counts, sums, sizes, n_edges)
+        t0 = time.perf_counter()
+        table, n_segments = agglomerate(*graph, thresholds, min_segment_size)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        table_dev = torch.from_numpy(table).to(device)
+        _native.check(
+            _native.lib().exaspim_apply_label_table(composed.data_ptr(), composed.numel(), table_dev.data_ptr(),
+                                                    table.size, _stream(device)),
+            "exaspim_apply_label_table",
+        )
+    if stats is not None:
+        stats.update(fragments=n_fragments, history=history, round_ms=timings, host_ms=host_ms,
+                     segments=n_segments)
+    return composed
+
+
 def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
                            fragment_threshold=0.5, edge_capacity=None, return_device_tensor=False,
-                           fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999):
+                           fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999,
+                           premerge_size=0, premerge_rounds=4):
     """
     Segments affinities by mean-affinity agglomeration of fragments, in the
     reference's order of operations.
@@ -729,6 +976,21 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     aff_threshold_low, aff_threshold_high : float, optional
         Used with fragments="watershed". Defaults are 0.1 and 0.9999, the
         reference's.
+    premerge_size : int, optional
+        0, the default, is the path described above. A positive value
+        CHANGES THE SEGMENTATION: before the host merging, every fragment
+        with fewer than premerge_size voxels joins, on the device, the
+        neighbour across its contact of largest mean affinity among those
+        the last threshold would merge (premerge_region_graph), whole chains
+        at once and whatever that neighbour would itself have merged with
+        first; the greedy merging then starts from the reduced graph, which
+        is the only one downloaded. Watershed fragments of a large volume are
+        millions of tiny basins, and this is what makes the host step
+        affordable there. 1 gives the labels of 0 (no fragment is empty).
+        Negative values and non-integers raise ValueError.
+    premerge_rounds : int, optional
+        The most pre-merge rounds; they stop when one merges nothing.
+        Default is 4.
 
     Returns
     -------
@@ -737,6 +999,7 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     """
     thresholds = list(agglomeration_thresholds)
     _last_threshold(thresholds)
+    premerge_size, premerge_rounds = _checked_premerge(premerge_size, premerge_rounds)
     if fragments not in ("components", "watershed"):
         raise ValueError(f'fragments must be "components" or "watershed", got {fragments!r}')
     if isinstance(affinities, np.ndarray):
@@ -760,14 +1023,19 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     else:
         labels, count = _components_on_device(affinities, fragment_threshold, 0)
     n_fragments = int(count.cpu()[0])
-    edges, counts, sums, sizes = _region_graph_on_device(labels, affinities, n_fragments, edge_capacity)
-    table, _ = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
     device = labels.device
+    if premerge_size:
+        table_dev = _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity,
+                                     premerge_size, premerge_rounds)
+    else:
+        edges, counts, sums, sizes = _region_graph_on_device(labels, affinities, n_fragments, edge_capacity)
+        table, _ = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
+        with torch.cuda.device(device):
+            table_dev = torch.from_numpy(table).to(device)
     with torch.cuda.device(device):
-        table_dev = torch.from_numpy(table).to(device)
         _native.check(
             _native.lib().exaspim_apply_label_table(labels.data_ptr(), labels.numel(), table_dev.data_ptr(),
-                                                    table.size, _stream(device)),
+                                                    table_dev.numel(), _stream(device)),
             "exaspim_apply_label_table",
         )
     if return_device_tensor:

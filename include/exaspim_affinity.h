@@ -53,7 +53,9 @@ extern "C" {
  *    later within 5: exaspim_unet_carry1_planes, exaspim_unet_forward_prepared_carry1 (struct
  *    exaspim_unet_carry1): second-level planes carried along z as well;
  *    later within 5: exaspim_watershed_fragments, exaspim_watershed_workspace_bytes: steepest-ascent
- *    watershed fragments for the agglomeration */
+ *    watershed fragments for the agglomeration;
+ *    later within 5: exaspim_region_graph_premerge (and its workspace query): tiny fragments merged on
+ *    the device before the host agglomeration */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -735,6 +737,73 @@ int exaspim_watershed_fragments(const void* aff_dev, int32_t aff_dtype, const in
                                 float low, float high, int64_t min_size,
                                 int32_t* labels_dev, int32_t* n_fragments_dev,
                                 void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- size-floor pre-merge of a region graph -----------------------------------
+ *      (later within ABI 5). Watershed fragments of a large volume are millions of tiny basins,
+ *      and exaspim_agglomerate on that many is slow. One ROUND joins every fragment smaller than a floor
+ *      to the neighbour across its best mergeable contact and contracts the graph. It is NOT the
+ *      agglomeration's rule restricted: it changes the segmentation (a tiny fragment joins its best
+ *      neighbour at once, whatever that neighbour would have merged with first), so it is a named option.
+ *
+ *      Input: a region graph in exaspim_region_graph's format: K = n_labels fragments, E = n_edges rows
+ *      (lo, hi) with 1 <= lo < hi <= K without repeats in any order, count >= 1 and sum per row,
+ *      sizes[0 .. K]; a threshold T, from which m and merge_all are computed exactly as in
+ *      exaspim_agglomerate (m = rint((1 - (double)T) * 2^24) clamped to 0 .. 2^24, merge_all iff the
+ *      unclamped value is negative); a size floor S (int64). Everything in integers, a pure function of
+ *      the input:
+ *       1. An edge is mergeable iff merge_all or sum > m * count.
+ *       2. A fragment f in 1 .. K is tiny iff sizes[f] < S.
+ *       3. A tiny fragment with at least one mergeable edge chooses the neighbour across its mergeable
+ *          edge of largest mean sum / count, compared by cross-multiplication in 128 bits; among equal
+ *          means the smaller neighbour id. Other fragments choose nothing.
+ *       4. If f and g choose each other, the smaller id drops its choice. Longer cycles cannot occur
+ *          (means never decrease along choices, and ids strictly decrease around an all-equal cycle).
+ *       5. Following choices to their end gives each fragment a root; fragments with the same root form
+ *          a set.
+ *       6. Sets are numbered 1 .. K' in order of their smallest member id: with fragments numbered in
+ *          raster order of their first voxel so are the sets, and the order of any two sets' smallest ids
+ *          is kept, so exaspim_agglomerate's ties and numbering mean what they meant before.
+ *       7. map[0] = 0, map[f] = the number of f's set.
+ *       8. sizes'[j] = the sum of sizes[f] over the members of set j; sizes'[0] = sizes[0].
+ *       9. Every edge becomes (map[lo], map[hi]); edges inside a set vanish, edges between the same two
+ *          sets add their count and sum.
+ *      So: no set holds two fragments that are not tiny; the total size is kept; S <= 0 is the identity,
+ *      and so is S = 1 when no fragment is empty; E' <= E. Rounds are repeated by the caller on their own
+ *      output until one merges nothing (K' = K). An edge with an end outside 1 .. K or with equal ends is
+ *      ignored by every rule and never becomes an address. */
+
+/* Scratch bytes of exaspim_region_graph_premerge: a table of edge_capacity slots, 24 bytes each, plus 4
+ * bytes per 2048 slots, plus 16 bytes per fragment and 4 bytes per 2048 fragments. 0 (and a message) if
+ * n_labels is negative or edge_capacity is not a power of two in 1 .. 2^30. */
+size_t exaspim_region_graph_premerge_workspace_bytes(int32_t n_labels, int64_t edge_capacity);
+
+/* One round, on the device. In: edges_dev (int32, n_edges x 2), count_dev (int64), sum_dev (uint64),
+ * sizes_dev (int64, n_labels + 1); they are only read. Out: the contracted graph in
+ * exaspim_region_graph's output format -- edges_out_dev / count_out_dev / sum_out_dev hold edge_capacity
+ * entries, the first E' in an UNSPECIFIED order are written --, sizes_out_dev (int64, n_labels + 1
+ * entries: the first K' + 1 are sizes', the rest 0), map_dev (int32, n_labels + 1) and state_dev, int32[3]
+ * = (K', E', the overflow flag). The contraction's accumulator is an open-addressing table of
+ * edge_capacity slots in the workspace; edge_capacity >= n_edges always suffices, below that the flag
+ * may come up and the edge list is then unusable (map and sizes' are not affected). Input and output
+ * buffers must not overlap.
+ *  - Passes, each a launch of its own on "stream": one thread per edge bids for its tiny ends' best edge
+ *    (32-bit compare-and-swap, a total order), one thread per fragment resolves mutual pairs, pointer
+ *    doubling between two buffers ceil(log2 K) + 1 times, the sets' smallest ids by atomic minimum, a
+ *    prefix sum for the numbering, sizes' by 64-bit atomic adds, the edges through map into the table,
+ *    a prefix sum for the edge list. The number of launches depends on n_labels only. No lock, no
+ *    inter-workgroup waiting, nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer (the three edge inputs may be NULL when n_edges is 0), a negative
+ * n_labels, n_edges outside 0 .. 2^31 - 1, a NaN threshold, an edge_capacity that is not a power of two
+ * in 1 .. 2^30 or a misaligned buffer (workspace_dev 16 bytes, the 64-bit arrays 8, the int32 arrays 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_region_graph_premerge_workspace_bytes(n_labels, edge_capacity): all before anything is
+ * launched. */
+int exaspim_region_graph_premerge(const int32_t* edges_dev, const int64_t* count_dev, const uint64_t* sum_dev,
+                                  const int64_t* sizes_dev, int64_t n_edges, int32_t n_labels,
+                                  float threshold, int64_t size_floor, int64_t edge_capacity,
+                                  int32_t* edges_out_dev, int64_t* count_out_dev, uint64_t* sum_out_dev,
+                                  int64_t* sizes_out_dev, int32_t* map_dev, int32_t* state_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
