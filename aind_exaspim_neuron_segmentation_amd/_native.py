@@ -21,6 +21,7 @@ OPT_UPSAMPLE_PER_THREAD = 16
 OPT_PER_PATCH_ENCODER = 32
 OPT_SEPARATE_HEAD = 64   # the head as its own launch, nothing trimmed (bf16x3: same bits)
 OPT_ROW_SEPARATE_BORDERS = 256   # row mode: border faces as two thin launches + a column max-pool (same bits)
+OPT_CARRY_MAIN_ONLY = 512   # carried planes: the border launch and inc.0 write every plane (same bits)
 AFF_F32, AFF_F16 = 0, 1   # EXASPIM_AFF_*: element type of exaspim_components' input
 
 DTYPE_CODES = {

@@ -272,7 +272,8 @@ struct ConvArgs {
     int row_stride = 0;
     // Carry in (row mode, or conv3x3x3_t14_carry): planes [in_z0, in_z1) of dst and their pooled planes of pool_dst are already
     // there (an earlier launch's carry out). Whole z tiles of the depth the launcher picks, even bounds;
-    // the tile walk leaves them out and nothing is written for them. Empty: off.
+    // the tile walk leaves them out and nothing is written for them. Empty: off. (The row-mode border launch,
+    // kRowStageBordersCarry, masks its own 8-plane tiles at in_z0: the range need not be whole tiles of its.)
     unsigned short in_z0 = 0, in_z1 = 0;
     // Optional scratch for split-K (t14 kernel): launches with too few workgroups to fill
     // the device cut the input-channel chunks into up to 4 ranges, every range writes its
@@ -297,7 +298,7 @@ struct ConvLaunchRecord {
     const char* config = "";
     int ksplit = 0;
     bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride) ...
-    bool carry = false;  // ... or conv3x3x3_zpipe_rowz / conv3x3x3_t14_carry (a carry field of ConvArgs set)
+    bool carry = false;  // ... or conv3x3x3_zpipe_rowz / conv3x3x3_t14_carry / conv3x3x3_t14_borders_carry (a carry field of ConvArgs set)
 };
 ConvLaunchRecord& last_conv_launch();
 // The same for the inc.0 and upsampling launchers (layers.hip): the name of the kernel variant
@@ -341,9 +342,19 @@ constexpr int kRowStagesAll = kRowStageMain | kRowStageThin | kRowStagePool;
 // runs Main | Borders (EXASPIM_OPT_ROW_SEPARATE_BORDERS: Main | Thin | Pool).
 constexpr int kRowStageBorders = 8;
 constexpr int kRowStagesFused = kRowStageMain | kRowStageBorders;
+// kRowStageBordersCarry: the border launch honouring the carry fields of ConvArgs (conv3x3x3_t14_borders_carry):
+// it computes and stores no plane of [in_z0, in_z1) -- any even range, no whole border tiles needed -- and stores
+// planes [out_z0, out_z1) of its columns and pooled columns a second time, like the main launch. After Main |
+// BordersCarry of a predecessor the successor's buffers hold every x of the carried planes, and nothing reads
+// planes [in_z0 + 1, in_z1 - 1) of the source. With no carry field set it is kRowStageBorders; kRowStageBorders
+// itself clears the fields and writes every plane.
+constexpr int kRowStageBordersCarry = 16;
+constexpr int kRowStagesCarry = kRowStageMain | kRowStageBordersCarry;
 int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
 // Tile depth of the z-column kernel on a 32-cout slice of depth d without a fused head (launch_typed)
 int conv_zcol_tile_depth(int d);
+// Tile depth of the row-mode border launch at depth d (launch_row_borders)
+int conv_row_borders_tile_depth(int d);
 // Carried planes outside row mode (conv3x3x3_t14_carry): the tile depth if launch_conv3x3x3 runs this launch
 // (dtype, shape, channels, split-K scratch of a) on the configuration that has a carry symbol, else 0
 constexpr int kCarryT14TZ = 4;
@@ -357,9 +368,16 @@ static_assert(sizeof(ConvArgs) == 184, "ConvArgs: the carry fields fill padding,
 
 // xpad: scratch for the zero-bordered copy of x, n * (d+2)(h+2)(wd+2) floats
 // first_no_strips: keep the per-group kernel (the tests hold it to the row-strip kernel bit for bit)
+// [skip_z0, skip_z1): output planes no later launch reads (conv_first_skip_planes). The row-strip kernel stores
+// nothing to them; every other variant ignores the range and writes all planes, a legal superset. The planes
+// that are written have the same bits either way.
 int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                       void* dst, int n, int d, int h, int wd, int c0p, float slope,
-                      hipStream_t stream, bool first_no_strips = false);
+                      hipStream_t stream, bool first_no_strips = false, int skip_z0 = 0, int skip_z1 = 0);
+// Planes of inc.3's source that no computed tile of a row sequence Main | BordersCarry reads when planes
+// [in_z0, in_z1) are carried in: both launches compute [0, in_z0) and [in_z1, d) only, and a computed plane reads
+// its two neighbours, so [in_z0 + 1, in_z1 - 1). Empty ({0, 0}) without a carry in or for a range of 2 planes.
+void conv_first_skip_planes(int d, int in_z0, int in_z1, int32_t out[2]);
 // ConvTranspose3d(k=2, s=2): (n, d, h, w, cin) -> (n, 2d, 2h, 2w, cout), bias, no activation
 int launch_convt2(int dtype, const void* src, const void* weights, const float* bias, void* dst,
                   int n, int d, int h, int w, int cin, int cout, hipStream_t stream);

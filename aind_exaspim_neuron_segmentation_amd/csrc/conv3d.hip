@@ -595,16 +595,41 @@ static int launch_row_borders_cfg(const ConvArgs& a, hipStream_t stream) {
     return EXASPIM_OK;
 }
 
-// (a: whole patches, row arguments checked)
+// the tile depth launch_thin_typed picks for tiles thin along x
+int conv_row_borders_tile_depth(int d) {
+    auto planes = [&](int tz) { return (d + tz - 1) / tz * tz; };
+    return planes(8) * 0.78f <= planes(4) * 1.00f ? 8 : 4;
+}
+
+// ... with planes carried along z (kRowStageBordersCarry, conv3x3x3_t14_borders_carry): the z tiles cover
+// [0, in_z0) and [in_z1, d) only
+template <typename Tag, int TZ, int MT>
+static int launch_row_borders_carry_cfg(const ConvArgs& a, hipStream_t stream) {
+    const int tz = cdiv(a.in_z0, TZ) + cdiv(a.d - a.in_z1, TZ), ty = cdiv(a.h, 16);
+    const long long blocks = (long long)tz * ty * 2 * (a.n - 1);
+    if (blocks <= 0 || blocks > 0x7fffffffLL) {
+        set_error("conv: grid of %lld blocks out of range", blocks);
+        return EXASPIM_E_INVALID;
+    }
+    last_conv_launch() = {__PRETTY_FUNCTION__, 1};
+    last_conv_launch().carry = true;
+    conv3x3x3_t14_borders_carry<Tag, TZ, MT>
+        <<<dim3((unsigned)blocks, a.cout / 32, 1), 256, 0, stream>>>(a, tz, ty, 2);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+// (a: whole patches, row arguments checked; carry fields set: the launch honours them)
 template <typename Tag>
 static int launch_row_borders(const ConvArgs& a_in, hipStream_t stream) {
     ConvArgs a = a_in;
     a.partial = nullptr;   // no split-K
     a.ksplit = 1;
     a.row_stride = 0;
-    // the tile depth launch_thin_typed picks for tiles thin along x
-    auto planes = [&](int tz) { return (a.d + tz - 1) / tz * tz; };
-    if (planes(8) * 0.78f <= planes(4) * 1.00f) return launch_row_borders_cfg<Tag, 8, 2>(a, stream);
+    const bool deep = conv_row_borders_tile_depth(a.d) == 8;
+    if (conv_has_carry(a))
+        return deep ? launch_row_borders_carry_cfg<Tag, 8, 2>(a, stream) : launch_row_borders_carry_cfg<Tag, 4, 1>(a, stream);
+    if (deep) return launch_row_borders_cfg<Tag, 8, 2>(a, stream);
     return launch_row_borders_cfg<Tag, 4, 1>(a, stream);
 }
 
@@ -613,6 +638,11 @@ int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t s
     if (int rc = check_conv_args(dtype, a, kCheckEmpty)) return rc;   // (the main stage checks the rest)
     if (int rc = resolve_region(b)) return rc;
     if (int rc = check_row_args(dtype, b)) return rc;
+    // (the planes carried in are not computed by the border launch either: nothing could store them a second time)
+    EXA_CHECK_ARG(!(stages & kRowStageBordersCarry) || a.in_z0 == a.in_z1 || a.out_z0 == a.out_z1 ||
+                      a.out_z0 >= a.in_z1 || a.out_z1 <= a.in_z0,
+                  "conv: carry out [%d, %d) overlaps the planes carried in, [%d, %d)", (int)a.out_z0, (int)a.out_z1,
+                  (int)a.in_z0, (int)a.in_z1);
     int r = EXASPIM_OK;
     if (stages & kRowStageMain) r = launch_conv3x3x3(dtype, a, stream);
     // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
@@ -647,6 +677,15 @@ int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t s
         c.out_shift = 0;
         c.org[2] = 0;
         if (r == EXASPIM_OK)    // (check_row_args: a 16-bit type)
+            r = dtype == EXASPIM_DT_F16 ? launch_row_borders<F16Tag>(c, stream) : launch_row_borders<BF16Tag>(c, stream);
+    }
+    if (r == EXASPIM_OK && (stages & kRowStageBordersCarry)) {
+        // the same launch honouring the carry fields (check_row_args: even bounds inside [2, d - 2))
+        r = check_conv_args(dtype, a, kCheckPadded);
+        ConvArgs c = a;
+        for (int i = 0; i < 3; ++i) { c.org[i] = b.org[i]; c.ext[i] = b.ext[i]; }   // (resolved: whole patches)
+        c.org[2] = 0;
+        if (r == EXASPIM_OK)
             r = dtype == EXASPIM_DT_F16 ? launch_row_borders<F16Tag>(c, stream) : launch_row_borders<BF16Tag>(c, stream);
     }
     return r;

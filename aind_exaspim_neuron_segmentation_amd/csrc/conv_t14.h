@@ -53,6 +53,20 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, MINW) void conv3x3x3_t14_car
 #include "conv_t14_body.inc"
 }
 
+// The border launch of inc.3's row mode (ZORD and POOL, the TZ x 16 x 2 tile) with planes carried along z
+// (launch_conv3x3x3_row, kRowStageBordersCarry). Carry in [in_z0, in_z1), even bounds and any alignment to the
+// tiles: tiles_z counts the tiles over [0, in_z0) and [in_z1, d), the first segment's last tile is masked at
+// in_z0, and no plane or pooled plane of the range is computed or stored. Carry out as conv3x3x3_t14_carry's,
+// for both jobs in the patch's own frame: the successor's buffers then hold every x of the carried planes.
+// A symbol of its own for the reason above: conv3x3x3_t14's border instantiations keep their code.
+template <typename Tag, int TZ, int MT>
+__global__ __launch_bounds__(256, 4) void conv3x3x3_t14_borders_carry(
+    ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
+    constexpr int TY = 16, TX = 2, WAVES_M = 4, WAVES_N = 1, NT = 1, PD = 3;
+    constexpr bool ZORD = true, POOL = true, CARRY = true;
+#include "conv_t14_body.inc"
+}
+
 // Split-K reduction: adds the float32 partial sums of the chunk ranges in range order, then
 // bias, LeakyReLU and the conversion, and writes four channels of one voxel in the blocked
 // layout. One thread per (voxel, 4 channels).

@@ -1,4 +1,4 @@
-// Body of conv3x3x3_t14 and conv3x3x3_t14_carry (conv_t14.h), included inside the kernel: the template
+// Body of conv3x3x3_t14, conv3x3x3_t14_carry and conv3x3x3_t14_borders_carry (conv_t14.h), included inside the kernel: the template
 // parameters, a, tiles_z, tiles_y, tiles_x and the constant CARRY are the including kernel's.
     constexpr int G = Tag::kG;
     constexpr int KC = 2 * G;
@@ -54,13 +54,18 @@
     const int tx = bid % tiles_x; bid /= tiles_x;
     const int ty = bid % tiles_y; bid /= tiles_y;
     int tz = bid % tiles_z; bid /= tiles_z;
-    if (CARRY && tz >= a.in_z0 / TZ) tz += (a.in_z1 - a.in_z0) / TZ;   // (the z tiles already present)
     constexpr bool BORDERS = ZORD && POOL;
-    static_assert(!CARRY || (ES == 2 && !ZORD), "carry: 16-bit types, whole-patch tiles");
+    // CARRY with BORDERS (conv3x3x3_t14_borders_carry): the z tiles lie over the two segments [0, in_z0) and
+    // [in_z1, d), the first segment's last tile masked at in_z0 -- the carried range need not be whole tiles
+    constexpr bool BCARRY = CARRY && BORDERS;
+    if (CARRY && !BORDERS && tz >= a.in_z0 / TZ) tz += (a.in_z1 - a.in_z0) / TZ;   // (the z tiles already present)
+    static_assert(!CARRY || (ES == 2 && (!ZORD || BORDERS)), "carry: 16-bit types, whole-patch or border tiles");
     const int nb = BORDERS && tx == 0 ? bid + 1 : bid;
-    const int z0 = a.org[0] + tz * TZ, y0 = a.org[1] + ty * TY;
+    const int seg0 = BCARRY ? (a.in_z0 + TZ - 1) / TZ : 0;   // tiles of the first segment
+    const bool low = BCARRY && tz < seg0;
+    const int z0 = BCARRY && !low ? a.in_z1 + (tz - seg0) * TZ : a.org[0] + tz * TZ, y0 = a.org[1] + ty * TY;
     const int x0 = BORDERS ? (tx == 0 ? 0 : a.w - TX) : a.org[2] + tx * TX;
-    const int zend = a.org[0] + a.ext[0], yend = a.org[1] + a.ext[1];
+    const int zend = low ? (int)a.in_z0 : a.org[0] + a.ext[0], yend = a.org[1] + a.ext[1];
     const int xend = BORDERS ? x0 + TX : a.org[2] + a.ext[2];
 
     const int ntiles = a.cout >> 5;
@@ -300,7 +305,9 @@
             const int pz = rest % PZ; rest /= PZ;
             const int ck = rest % NPL, pwn = rest / NPL;
             const int qz = (z0 >> 1) + pz, qy = (y0 >> 1) + py, qx = (x0 >> 1) + px;
-            if (pp < NPIECE && qz < pd && qy < ph && qx < pw2) {
+            // (BCARRY: a pooled plane of the masked tile belongs to the carried range, whose planes this tile's
+            // LDS image does not hold; z0 and zend are even, so a pooled pair is never split)
+            if (pp < NPIECE && qz < pd && qy < ph && qx < pw2 && (!BCARRY || 2 * qz < zend)) {
                 uint4 mx;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {

@@ -70,6 +70,14 @@ static void carry_span(int d, int shift_z, int32_t out[2]) {
     if (lo < hi && hi + shift_z <= 254) { out[0] = lo; out[1] = hi; }
 }
 
+// What inc.0 need not write when inc.3 takes planes [in_z0, in_z1) over (common.h)
+void conv_first_skip_planes(int d, int in_z0, int in_z1, int32_t out[2]) {
+    out[0] = out[1] = 0;
+    if (in_z0 < 0 || in_z1 > d || in_z1 - in_z0 <= 2) return;
+    out[0] = in_z0 + 1;
+    out[1] = in_z1 - 1;
+}
+
 // Tile depth of down1.0 and down1.3 if the launcher runs both on the configuration that can carry planes and
 // down1.3 writes its own max-pool (the forward of a batch of n patches d x h x w), else 0
 static int carry1_tile_depth(const exaspim_unet* e, int n, int d, int h, int w) {
@@ -220,6 +228,14 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                           carry->out_z[1], carry->in_z[0], carry->in_z[1]);
         }
     }
+    // With a carry in the border launch leaves the carried planes out as well and carries out whenever the main
+    // launch does (kRowStageBordersCarry), and inc.0 skips the planes neither launch reads.
+    // EXASPIM_OPT_CARRY_MAIN_ONLY, or the three-launch borders: only the main launch carries, the border launch
+    // and inc.0 write every plane. An option of the handle: predecessor and successor agree on who writes the
+    // border columns of the carried planes.
+    const bool carry_borders = carry && !(e->options & (EXASPIM_OPT_CARRY_MAIN_ONLY | EXASPIM_OPT_ROW_SEPARATE_BORDERS));
+    int32_t first_skip[2] = {0, 0};
+    if (carry_borders) conv_first_skip_planes(d, carry->in_z[0], carry->in_z[1], first_skip);
     void* const x1 = carry ? carry->own_skip : skip(0);
     void* const x1_pool = carry ? carry->own_pool : A(1);
     // ... and (exaspim_unet_forward_prepared_carry1) down1.0's output, x2 and its max-pool
@@ -326,7 +342,8 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         }
         // (row mode: the row launch, then the border launch that finishes it)
         int r = x3 && has_head      ? launch_conv3x3x3_x3_head(a, stream)
-                : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, (e->options & EXASPIM_OPT_ROW_SEPARATE_BORDERS) ? kRowStagesAll : kRowStagesFused, stream)
+                : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, (e->options & EXASPIM_OPT_ROW_SEPARATE_BORDERS) ? kRowStagesAll
+                                                                 : carry_borders ? kRowStagesCarry : kRowStagesFused, stream)
                                    : launch_conv3x3x3(dt, a, stream);
         if (timed && r == EXASPIM_OK) {
             EXA_CHECK_HIP(hipEventRecord(t->stop[slot], stream));
@@ -357,7 +374,8 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                                    : const_cast<float*>(static_cast<const float*>(x_prepared)),
                           reinterpret_cast<const float*>(e->packed + p.first_w_off),
                           reinterpret_cast<const float*>(e->packed + p.first_b_off), A(0), n, d,
-                          h, w, p.c0p, kLeakySlope, stream, (e->options & EXASPIM_OPT_FIRST_PER_GROUP) != 0));
+                          h, w, p.c0p, kLeakySlope, stream, (e->options & EXASPIM_OPT_FIRST_PER_GROUP) != 0,
+                          first_skip[0], first_skip[1]));
     if (absmax) RUN(launch_absmax(dt, A(0), (size_t)n * d * h * w * p.c0p * dtype_size(dt), absmax, stream));
     RUN(conv(0, A(0), nullptr, x1, 0));                           // x1
     for (int l = 1; l <= 4; ++l) {
@@ -694,7 +712,8 @@ extern "C" int exaspim_unet_set_options(exaspim_unet* h, uint32_t options) {
     EXA_CHECK_ARG(h != nullptr, "set_options: NULL handle");
     EXA_CHECK_ARG((options & ~(uint32_t)(EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS | EXASPIM_OPT_PLAIN_UPSAMPLE | EXASPIM_OPT_FIRST_PER_GROUP |
                                           EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER |
-                                          EXASPIM_OPT_SEPARATE_HEAD | EXASPIM_OPT_ROW_SEPARATE_BORDERS)) == 0,
+                                          EXASPIM_OPT_SEPARATE_HEAD | EXASPIM_OPT_ROW_SEPARATE_BORDERS |
+                                          EXASPIM_OPT_CARRY_MAIN_ONLY)) == 0,
                   "set_options: unknown option bits 0x%x", options);
     h->options = options;
     return EXASPIM_OK;

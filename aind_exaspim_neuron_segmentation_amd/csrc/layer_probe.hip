@@ -121,7 +121,8 @@ int probe_conv3x3x3_row(int dtype, const void* src, int ca, const void* weights,
 }
 
 // probe_conv3x3x3_row with planes carried along z (ConvArgs::in_z0 .. out_shift); carry[0..4] = in_z0, in_z1,
-// out_z0, out_z1, out_shift. 1 from probe_last_carry if the main launch ran conv3x3x3_zpipe_rowz.
+// out_z0, out_z1, out_shift. 1 from probe_last_carry if the last launch ran conv3x3x3_zpipe_rowz or (stage 16)
+// conv3x3x3_t14_borders_carry.
 int probe_conv3x3x3_row_carry(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,
                               int cout, int n, int d, int h, int w, float slope, int row_stride, void* pool_dst,
                               const int32_t* carry, void* carry_dst, void* carry_pool_dst, int stages,
@@ -211,6 +212,21 @@ int probe_conv_first(int dtype, const float* x, float* xpad, const float* w, con
                      void* dst, int n, int d, int h, int wd, int c0p, float slope, int per_group,
                      hipStream_t stream) {
     return launch_conv_first(dtype, x, xpad, w, bias, dst, n, d, h, wd, c0p, slope, stream, per_group != 0);
+}
+
+// launch_conv_first with output planes [skip_z0, skip_z1) nobody reads
+int probe_conv_first_planes(int dtype, const float* x, float* xpad, const float* w, const float* bias,
+                            void* dst, int n, int d, int h, int wd, int c0p, float slope, int per_group,
+                            int skip_z0, int skip_z1, hipStream_t stream) {
+    return launch_conv_first(dtype, x, xpad, w, bias, dst, n, d, h, wd, c0p, slope, stream, per_group != 0, skip_z0,
+                             skip_z1);
+}
+// the planes inc.0 skips when inc.3 takes [in_z0, in_z1) over
+void probe_conv_first_skip_planes(int d, int in_z0, int in_z1, int32_t* out) { conv_first_skip_planes(d, in_z0, in_z1, out); }
+// the tile depths of inc.3's two launches at depth d: out[0] the main launch's, out[1] the border launch's
+void probe_row_tile_depths(int d, int32_t* out) {
+    out[0] = conv_zcol_tile_depth(d);
+    out[1] = conv_row_borders_tile_depth(d);
 }
 
 int probe_maxpool2(int dtype, const void* src, void* dst, int n, int d, int h, int w, int c,

@@ -615,7 +615,7 @@ constexpr int kStripRows = 4;
 template <typename T, int GPW>   // GPW: 32-voxel groups per wave and strip = width / 32
 __global__ __launch_bounds__(256) void conv_first16_strip_kernel(
     const unsigned* __restrict__ xp, const float* __restrict__ w, const float* __restrict__ bias,
-    void* __restrict__ dst, int n, int d, int h, int wd, int c0p, float slope) {
+    void* __restrict__ dst, int n, int d, int h, int wd, int c0p, float slope, int skip_z0, int skip_z1) {
     constexpr int G = T::kG;
     constexpr int ES = 16 / G;
     constexpr int RECB = 32 * ES;
@@ -669,17 +669,21 @@ __global__ __launch_bounds__(256) void conv_first16_strip_kernel(
     const size_t xpatch_bytes = (size_t)(d + 2) * phw * 4;
     const size_t opatch_bytes = (size_t)(c0p * ES / 32) * dhw * 32;
     const int strips_y = h / R;
-    const int nstrips = n * d * strips_y;
+    // planes [skip_z0, skip_z1) are nobody's to read (launch_conv_first): the walk covers the dz planes left and a
+    // strip's z steps over the gap -- every strip fetches its own three input planes, nothing else depends on z order
+    const int dz = d - (skip_z1 - skip_z0);
+    const int nstrips = n * dz * strips_y;
     const int gpr = wd / 32;                       // groups per row (= GPW: four rows, four waves)
 
     struct Strip { int nb, z, y0; };
     auto locate = [&](int sidx) {
         Strip t;
         const int si = __builtin_amdgcn_readfirstlane(sidx);
-        t.nb = si / (d * strips_y);
-        const int rem = si - t.nb * (d * strips_y);
-        t.z = rem / strips_y;
-        t.y0 = (rem - t.z * strips_y) * R;
+        t.nb = si / (dz * strips_y);
+        const int rem = si - t.nb * (dz * strips_y);
+        const int zi = rem / strips_y;
+        t.z = zi >= skip_z0 ? zi + (skip_z1 - skip_z0) : zi;
+        t.y0 = (rem - zi * strips_y) * R;
         return t;
     };
     unsigned stage[NLOAD];
@@ -1450,7 +1454,9 @@ const char*& last_layer_kernel() {
 
 int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, const float* bias,
                       void* dst, int n, int d, int h, int wd, int c0p, float slope,
-                      hipStream_t stream, bool first_no_strips) {
+                      hipStream_t stream, bool first_no_strips, int skip_z0, int skip_z1) {
+    EXA_CHECK_ARG(skip_z0 >= 0 && skip_z0 <= skip_z1 && skip_z1 <= d, "conv_first: skipped planes [%d, %d) outside [0, %d]",
+                  skip_z0, skip_z1, d);
     dtype = storage_dtype(dtype);   // (bf16x3: inc.0 is the float32 kernel)
     const size_t nvox = (size_t)n * d * h * wd;
     constexpr int MT = 4;
@@ -1477,11 +1483,14 @@ int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, co
     // row strips when the rows variant applies, a strip is whole rows and the tile fits the staging registers
     const bool strips = rows && !first_no_strips && h % kStripRows == 0 && wd <= 128;
     if (strips && dtype != EXASPIM_DT_F32) {
-        const int nstrips = n * d * (h / kStripRows);
+        // (only this kernel leaves [skip_z0, skip_z1) out; a launch of skipped planes only has nothing to do)
+        const int nstrips = n * (d - (skip_z1 - skip_z0)) * (h / kStripRows);
+        last_layer_kernel() = "conv_first16_strip";
+        if (nstrips == 0) return EXASPIM_OK;
         const size_t tile_bytes = ((size_t)3 * (kStripRows + 2) * (wd + 2) * 4 + 15) / 16 * 16;
         const size_t lds = 2 * tile_bytes + 4 * 32 * (32 * 2 + 16);
         dim3 sgrid((unsigned)(nstrips < 1024 ? nstrips : 1024), c0p / 32);
-#define STRIP(TT, GG) conv_first16_strip_kernel<TT, GG><<<sgrid, 256, lds, stream>>>(xsplit, w, bias, dst, n, d, h, wd, c0p, slope)
+#define STRIP(TT, GG) conv_first16_strip_kernel<TT, GG><<<sgrid, 256, lds, stream>>>(xsplit, w, bias, dst, n, d, h, wd, c0p, slope, skip_z0, skip_z1)
         const bool bf = dtype == EXASPIM_DT_BF16;
         switch (wd / 32) {
             case 1: if (bf) STRIP(BF16T, 1); else STRIP(F16T, 1); break;
@@ -1490,7 +1499,6 @@ int launch_conv_first(int dtype, const float* x, float* xpad, const float* w, co
             default: if (bf) STRIP(BF16T, 4); else STRIP(F16T, 4); break;
         }
 #undef STRIP
-        last_layer_kernel() = "conv_first16_strip";
         EXA_CHECK_HIP(hipGetLastError());
         return EXASPIM_OK;
     }

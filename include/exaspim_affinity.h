@@ -55,7 +55,8 @@ extern "C" {
  *    later within 5: exaspim_watershed_fragments, exaspim_watershed_workspace_bytes: steepest-ascent
  *    watershed fragments for the agglomeration;
  *    later within 5: exaspim_region_graph_premerge (and its workspace query): tiny fragments merged on
- *    the device before the host agglomeration */
+ *    the device before the host agglomeration;
+ *    later within 5: EXASPIM_OPT_CARRY_MAIN_ONLY (no new entry point) */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -329,6 +330,13 @@ int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, float* out_
 /* row mode of the first level: the patch faces that border a neighbour as two thin-tile launches and a
  * column max-pool instead of one launch that does both (same bits). (Bit 128 is not assigned.) */
 #define EXASPIM_OPT_ROW_SEPARATE_BORDERS 256u
+/* carried planes of the first level (exaspim_unet_forward_prepared_carry): only the row launch leaves the planes
+ * carried in out and carries out; the border launch recomputes its columns on every plane and the first
+ * convolution writes every plane (same bits). Without it the border launch carries as well, and the first
+ * convolution skips the planes no launch reads. Set it on every handle of a carry chain or on none: predecessor
+ * and successor must agree on who writes the border columns of the carried planes.
+ * (EXASPIM_OPT_ROW_SEPARATE_BORDERS implies it.) */
+#define EXASPIM_OPT_CARRY_MAIN_ONLY 512u
 int exaspim_unet_set_options(exaspim_unet* h, uint32_t options);
 
 /* Measurement hooks (bench.py's roofline leg). timing_begin arms HIP-event
