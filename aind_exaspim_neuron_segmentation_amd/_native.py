@@ -257,6 +257,11 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'`). "
                 "There is no CPU fallback."
             )
+        # torch first: its wheel ships a HIP runtime of its own, which this library then binds to by soname. Loaded
+        # the other way round the process holds two runtimes -- the system's for this library, torch's for the
+        # tensors -- and the kernels here fail with "no ROCm-capable device is detected"
+        import torch  # noqa: F401
+
         handle = ctypes.CDLL(path)
         for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(handle, name)

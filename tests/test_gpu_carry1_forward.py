@@ -48,35 +48,40 @@ def _model(state, dev, dtype):  # noqa: F811
     return state[("model", dtype)]
 
 
-def _setup(state, dev, dtype, name):  # noqa: F811
-    """Model, prepared batches of A and B, and B's reference output through the clipped entry."""
-    key = (dtype, name)
+def _setup(state, dev, dtype, name, model=None, tag=None, keep_hi=None, sigmoid=1):  # noqa: F811
+    """Model, prepared batches of A and B, and B's reference output through the clipped entry. model (with a tag
+    for the cache): another network than this file's; keep_hi: a clip (default: none); sigmoid: 0 for logits."""
+    key = (dtype, name) if model is None else (dtype, name, tag, keep_hi, sigmoid)
     if key in state:
         return state[key]
-    model = _model(state, dev, dtype)
+    model = _model(state, dev, dtype) if model is None else model
     patch, stride, shift, _ = GEOMETRIES[name]
     d, h, w = patch
     vol = synthetic.synth_volume((d + shift, h, w + stride), seed=79)
     mn, mx = np.percentile(np.minimum(vol, 1000), (1, 99.9))
     dvol = inference.DeviceVolume.from_array(vol, dev)
     layout = model.input_layout(dev)
-    prepared = []
+    prepared, gather = [], []
     for z in (0, shift):
         starts = torch.tensor([(z, 0, 0), (z, 0, stride)], dtype=torch.int32, device=dev)
         prepared.append(inference._get_batch_inputs(dvol, starts, patch, dev, clip=np.uint16(1000), mn=mn, mx=mx,
                                                     layout=layout))
+        gather.append((dvol, starts, patch, dev, dict(clip=np.uint16(1000), mn=mn, mx=mx)))
     lib = _native.lib()
     handle = model._ensure_engine(dev)
     need = lib.exaspim_unet_workspace_bytes(handle, 2, d, h, w)
     assert need, _native.last_error()
     ws = torch.zeros(need, dtype=torch.uint8, device=dev)
-    want = torch.empty((2, 3, d, h, w), dtype=torch.float32, device=dev)
-    keep_hi = _native.int3((d - TRIM, h - TRIM, w - TRIM))
+    want = torch.empty((2, model.output_channels, d, h, w), dtype=torch.float32, device=dev)
+    want.view(torch.uint8).fill_(SENTINEL)
+    keep_hi = _native.int3(keep_hi or (d - TRIM, h - TRIM, w - TRIM))
     _native.check(lib.exaspim_unet_forward_prepared_clipped(
-        handle, prepared[1].data_ptr(), want.data_ptr(), 2, d, h, w, 1, TRIM, stride, keep_hi, ws.data_ptr(), need,
-        torch.cuda.current_stream(dev).cuda_stream), "clipped")
+        handle, prepared[1].data_ptr(), want.data_ptr(), 2, d, h, w, sigmoid, TRIM, stride, keep_hi, ws.data_ptr(),
+        need, torch.cuda.current_stream(dev).cuda_stream), "clipped")
     torch.cuda.synchronize()
-    state[key] = dict(model=model, handle=handle, prepared=prepared, want=want.cpu(), need=need, keep_hi=keep_hi)
+    # (gather: the arguments of inference._get_batch_inputs for the float32 patches of A and B)
+    state[key] = dict(model=model, handle=handle, prepared=prepared, want=want.cpu(), need=need, keep_hi=keep_hi,
+                      gather=gather, sigmoid=sigmoid)
     return state[key]
 
 
@@ -119,7 +124,8 @@ def _carry1(own, in_z=(0, 0), out=None, out_z=(0, 0), out_shift=0, reserved=0):
 def _forward(S, dev, which, out, carry, carry1, ws, patch, stride):  # noqa: F811
     d, h, w = patch
     rc = _native.lib().exaspim_unet_forward_prepared_carry1(
-        S["handle"], S["prepared"][which].data_ptr(), out.data_ptr(), 2, d, h, w, 1, TRIM, stride, S["keep_hi"],
+        S["handle"], S["prepared"][which].data_ptr(), out.data_ptr(), 2, d, h, w, S.get("sigmoid", 1), TRIM, stride,
+        S["keep_hi"],
         ctypes.byref(carry) if carry is not None else None, ctypes.byref(carry1) if carry1 is not None else None,
         ws.data_ptr(), S["need"], torch.cuda.current_stream(dev).cuda_stream)
     torch.cuda.synchronize()

@@ -77,10 +77,10 @@ def _run_clipped(state, dev, model, case, trim, keep_hi, fill):  # noqa: F811
     return out[:numel].view(n, model.output_channels, d, h, w).cpu()
 
 
-def _check_clipped(state, dev, golden, dtype, case, trim, keep_hi):  # noqa: F811
-    model, _ = W._model(state, dev, dtype, "base")
+def _check_clipped(state, dev, golden, dtype, case, trim, keep_hi, variant="base"):  # noqa: F811
+    model, _ = W._model(state, dev, dtype, variant)
     patch, n, row_stride = W.CASES[case]
-    what = f"case {case} {dtype} trim {trim} keep_hi {keep_hi}"
+    what = f"case {case} {dtype} {variant} trim {trim} keep_hi {keep_hi}"
     want = W._run(state, dev, model, "row" if row_stride else "prepared", case, trim, "0x00")
     kept = torch.zeros((n, model.output_channels) + patch, dtype=torch.bool)
     kept[(Ellipsis,) + tuple(slice(trim, k) for k in keep_hi)] = True
@@ -107,6 +107,15 @@ def test_clipped_equals_trimmed_inside_the_box(state, dev, golden, case, trim, k
     if W.CASES[case][2]:
         W._assert_row_mode(case, dtype)
     _check_clipped(state, dev, golden, dtype, case, trim, keep_hi)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("variant", W.ROW_VARIANTS)
+def test_clipped_row_mode_on_model_variants(state, dev, golden, variant, dtype):  # noqa: F811
+    """Row mode with a clip on 1, 2 and 4 outputs, ConvTranspose3d up blocks and widths 0.75 and 0.5."""
+    model, _ = W._model(state, dev, dtype, variant)
+    W._assert_row_mode(7, dtype, model.channels)
+    _check_clipped(state, dev, golden, dtype, 7, 4, (9, 12, 92), variant)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16x3"])

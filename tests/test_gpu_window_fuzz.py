@@ -83,10 +83,10 @@ def _ledger(model, monkeypatch):
     return calls
 
 
-def _check_ledger(calls, case, model, dev, n_streams, rung, level1_expected):  # noqa: F811
+def _check_ledger(calls, case, model, dev, n_streams, rung, level1_expected, host=_RowModel):  # noqa: F811
     """The carry dicts run_sliding_window handed out against the schedule of the real model, and that against the
-    host model's."""
-    p = W.plan(case, _RowModel(level1=level1_expected), n_streams)
+    host model's (host(level1=...): carry_ref's stand-in for this network, by default the full-width one)."""
+    p = W.plan(case, host(level1=level1_expected), n_streams)
     starts, batch, patch, overlap = p["starts"], case["batch"], case["patch"], case["overlap"]
     links, peak, level1 = inference._carry_schedule(model, p["succ"], starts, batch, patch, overlap, n_streams, dev)
     links = links or [None] * len(p["batches"])
@@ -146,12 +146,18 @@ def _check_ledger(calls, case, model, dev, n_streams, rung, level1_expected):  #
 @pytest.mark.parametrize("case", CASES, ids=W.case_id)
 def test_every_plan_switch_keeps_the_bits_of_the_plain_plan(state, dev, dtype, case, monkeypatch):  # noqa: F811
     print(case)
-    model = _model(state, dev, dtype)
+    reference = _fp32_reference(state, dev, case)      # (before any switch is flipped)
+    _ladder(_model(state, dev, dtype), reference, case, dtype, dev, monkeypatch)
+
+
+def _ladder(model, reference, case, dtype, dev, monkeypatch, host_model=_RowModel, affinity_mode=True):  # noqa: F811
+    """Every plan switch turned on one after the other on `model`, each rung against the plain plan; rung 0 against
+    `reference`, the fp32 engine's predict(). host_model: _check_ledger's."""
     host = _volume(case)
     vol = inference.DeviceVolume.from_array(host, dev)     # one run_sliding_window call sees the whole window
-    kw = _kw(case)
+    kw = dict(_kw(case), affinity_mode=affinity_mode)
     streams = 2 + case["seed"] % 2
-    reference = _fp32_reference(state, dev, case)      # (before any switch is flipped)
+    out_shape = ((3,) if affinity_mode else ()) + tuple(case["shape"])
 
     def switches(**values):
         for name, value in values.items():
@@ -167,7 +173,7 @@ def test_every_plan_switch_keeps_the_bits_of_the_plain_plan(state, dev, dtype, c
     switches(PLAIN_GATHER=True, FULL_PATCHES=True, CLIP_TO_VOLUME=False, CARRY_Z=False)
     monkeypatch.setattr(model, "engine_options", _native.OPT_PER_PATCH_ENCODER)
     plain = inference.predict(vol, model, n_streams=1, **kw)
-    assert plain.shape == (3,) + tuple(case["shape"]) and plain.dtype == np.float32 and np.isfinite(plain).all()
+    assert plain.shape == out_shape == reference.shape and plain.dtype == np.float32 and np.isfinite(plain).all()
     err = float(np.abs(plain - reference).max())
     print(f"plain {dtype} plan vs the fp32 engine: max |diff| = {err:.3e} (bound {PROB_TOL[dtype]:.0e})")
     assert err < PROB_TOL[dtype], f"rung 0 (plain plan) vs the fp32 engine: {err:.3e}: {dtype} {case}"
@@ -184,22 +190,28 @@ def test_every_plan_switch_keeps_the_bits_of_the_plain_plan(state, dev, dtype, c
     calls = _ledger(model, monkeypatch)
     switches(CARRY_Z=True, CARRY_Z1=False)
     same(inference.predict(vol, model, n_streams=1, **kw), "5 (CARRY_Z)")
-    _check_ledger(calls, case, model, dev, 1, "rung 5 (CARRY_Z)", False)
+    _check_ledger(calls, case, model, dev, 1, "rung 5 (CARRY_Z)", False, host_model)
+    ledgers = {5: list(calls)}      # rung -> its run_prepared calls, for the caller
     switches(CARRY_Z1=True)
     del calls[:]
     same(inference.predict(vol, model, n_streams=1, **kw), "6 (CARRY_Z1)")
-    _check_ledger(calls, case, model, dev, 1, "rung 6 (CARRY_Z1)", True)
+    _check_ledger(calls, case, model, dev, 1, "rung 6 (CARRY_Z1)", True, host_model)
+    ledgers[6] = list(calls)
     del calls[:]
     same(inference.predict(vol, model, n_streams=streams, **kw), f"7 ({streams} streams)")
     n_batches = -(-len(W.plan(case)["starts"]) // case["batch"])
     links, peak, level1 = _check_ledger(calls, case, model, dev, min(streams, n_batches), f"rung 7 ({streams} streams)",
-                                        True)
+                                        True, host_model)
+    ledgers[7] = list(calls)
     if level1:      # a pool that admits the first level's buffers and not the second's
         pair_bytes = 2 * sum(model.carry_pair_elems((case["batch"],) + tuple(case["patch"])))
         switches(CARRY_POOL_BYTES=peak * pair_bytes + 1)
         del calls[:]
         same(inference.predict(vol, model, n_streams=streams, **kw), "8 (first level only under the cap)")
-        _check_ledger(calls, case, model, dev, min(streams, n_batches), "rung 8 (first level only under the cap)", False)
+        _check_ledger(calls, case, model, dev, min(streams, n_batches), "rung 8 (first level only under the cap)", False,
+                      host_model)
+        ledgers[8] = list(calls)
     monkeypatch.undo()      # every switch on, run_prepared and the engine options as they were
     assert model.engine_options == 0 and inference.CARRY_Z and inference.CARRY_Z1 and not inference.PLAIN_GATHER
     same(inference.predict(host, model, **kw), "9 (host array, slab pipeline)")
+    return plain, ledgers

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import layer_ref as R
+import variant_models as V
 from aind_exaspim_neuron_segmentation_amd import _native, inference
 from aind_exaspim_neuron_segmentation_amd.utils import synthetic
 from test_gpu_bf16x3 import PROB_TOL as PROB_TOL_BF16X3
@@ -37,8 +38,13 @@ GUARD = 256              # bytes behind the workspace and behind the output
 SENTINEL = 0x5A          # byte the output and its guard are filled with (0x5A5A5A5A: a finite float32)
 SENTINEL_WORD = 0x5A5A5A5A
 
-# model variants: (synth_state_dict seed, trilinear, width multiplier); "base" is the model of golden g4
-VARIANTS = {"base": (1, True, 1), "convt": (8, False, 1), "half": (3, True, 0.5), "double": (3, True, 2)}
+# model variants: (synth_state_dict seed, trilinear, width multiplier, output channels); "base" is the model of
+# golden g4; "foreground", "three_quarter" and "half2" (width 0.5 with 2 outputs) are variant_models.py's
+VARIANTS = {"base": (1, True, 1, 3), "convt": (8, False, 1, 3), "half": (3, True, 0.5, 3), "double": (3, True, 2, 3)}
+VARIANTS.update({{"half": "half2"}.get(k, k): (v["seed"], v["trilinear"], v["wm"], v["out"]) for k, v in V.VARIANTS.items()
+                 if k not in ("convt", "double")})
+assert all(VARIANTS[k] == tuple(V.VARIANTS[k][f] for f in ("seed", "trilinear", "wm", "out")) for k in ("convt", "double"))
+ROW_VARIANTS = ["foreground", "convt", "three_quarter", "half2"]     # variant_models.ROW_NAMES under this file's names
 
 # case -> (patch, n, row_stride): the smallest shapes at which each mechanism is live
 CASES = {
@@ -69,8 +75,9 @@ def state(dev):  # noqa: F811
 def _model(state, dev, dtype, variant):  # noqa: F811
     key = (dtype, variant)
     if key not in state["models"]:
-        seed, trilinear, wm = VARIANTS[variant]
-        state["models"][key] = make_model(dev, seed=seed, trilinear=trilinear, wm=wm, compute_dtype=dtype)
+        seed, trilinear, wm, out = VARIANTS[variant]
+        state["models"][key] = make_model(dev, out_channels=out, seed=seed, trilinear=trilinear, wm=wm,
+                                          compute_dtype=dtype)
     return state["models"][key]
 
 
@@ -239,12 +246,12 @@ def test_small_trims(state, dev, oracle, golden, trim, dtype):  # noqa: F811
     _check(state, dev, oracle, golden, dtype, "base", "trimmed", 5, trim)
 
 
-def _assert_row_mode(case, dtype):
+def _assert_row_mode(case, dtype, channels=(32, 64, 128, 256, 512)):
     """conv_row_mode_ok, the engine's own predicate, says yes to inc.3 of this case."""
     probe = R.load_probe()
     (_, _, w), n, stride = CASES[case]
     dt = {"fp16": "f16", "bf16": "bf16"}[dtype]
-    cout = R.plan_conv(probe, [32, 64, 128, 256, 512], 3, dt, 0)[5]
+    cout = R.plan_conv(probe, list(channels), 3, dt, 0)[5]
     assert probe.probe_conv_row_mode_ok(R.DTYPES[dt], cout, n, w, stride, 1) == 1
 
 
@@ -253,6 +260,17 @@ def _assert_row_mode(case, dtype):
 def test_row_mode(state, dev, oracle, golden, case, trim, dtype):  # noqa: F811
     _assert_row_mode(case, dtype)
     _check(state, dev, oracle, golden, dtype, "base", "row", case, trim)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("variant", ROW_VARIANTS)
+def test_row_mode_on_model_variants(state, dev, oracle, golden, variant, dtype):  # noqa: F811
+    """The row entry at the default x geometry on 1, 2 and 4 outputs, ConvTranspose3d up blocks and widths 0.75 and
+    0.5: inc.3's row and border launches write the padded channels of x1 and its max-pool themselves (the `stale`
+    fill leaves another forward's activations there)."""
+    model, _ = _model(state, dev, dtype, variant)
+    _assert_row_mode(7, dtype, model.channels)
+    _check(state, dev, oracle, golden, dtype, variant, "row", 7, 4)
 
 
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])

@@ -94,7 +94,8 @@ def traits(case, model=None):
     p = plan(case, model)
     patch, overlap, trim, shape = case["patch"], case["overlap"], case["trim"], case["shape"]
     links, batches = p["links"], p["batches"]
-    rows = [row_mode(len(b), patch[2], inference.batch_row_stride(b, patch, overlap)) for b in batches]
+    rows = [getattr(model, "row_mode", row_mode)(len(b), patch[2], inference.batch_row_stride(b, patch, overlap))
+            for b in batches]
     clipped = [inference.batch_keep_hi(b, patch, trim, shape) is not None for b in batches]
 
     def could_carry(bi, bj):
