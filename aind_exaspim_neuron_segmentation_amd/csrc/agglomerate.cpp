@@ -64,6 +64,11 @@ extern "C" int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, 
     EXA_CHECK_ARG(n_edges == 0 || (edges && counts && sums), "agglomerate: NULL edge list");
     EXA_CHECK_ARG(threshold == threshold, "agglomerate: the threshold is NaN");
     const int32_t K = n_labels;
+    // Pooled counts and sums are sums of the input's: with all counts together within 2^39 every pooled
+    // count stays within 2^39 and every pooled sum within 2^63, so neither wraps its uint64_t and each
+    // product below stays within 2^102.
+    const uint64_t kMaxTotal = 1ull << 39;
+    u128 total_count = 0;   // up to 2^31 edges of up to 2^34 each: 2^65
     for (int64_t e = 0; e < n_edges; ++e) {
         const int32_t lo = edges[2 * e], hi = edges[2 * e + 1];
         EXA_CHECK_ARG(lo >= 1 && lo < hi && hi <= K, "agglomerate: edge %lld is (%d, %d), needs 1 <= lo < hi <= %d",
@@ -73,6 +78,19 @@ extern "C" int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, 
         EXA_CHECK_ARG(counts[e] >= 1 && counts[e] <= (1ll << 34) && sums[e] <= ((uint64_t)counts[e] << 24),
                       "agglomerate: edge %lld has count %lld and sum %llu, needs 1 <= count <= 2^34 and sum <= count * 2^24",
                       (long long)e, (long long)counts[e], (unsigned long long)sums[e]);
+        total_count += (uint64_t)counts[e];
+    }
+    if (total_count > kMaxTotal) {
+        char digits[24];   // below 2^65: at most 20 digits, in two halves
+        const u128 half = 10000000000ull;
+        if (total_count >= half)
+            snprintf(digits, sizeof digits, "%llu%010llu", (unsigned long long)(total_count / half),
+                     (unsigned long long)(total_count % half));
+        else
+            snprintf(digits, sizeof digits, "%llu", (unsigned long long)total_count);
+        set_error("agglomerate: the counts add up to %s, needs a total of at most 2^39 = %llu (parallel edges are "
+                  "pooled in 64 bits)", digits, (unsigned long long)kMaxTotal);
+        return EXASPIM_E_INVALID;
     }
     for (int32_t l = 0; l <= K; ++l)
         EXA_CHECK_ARG(sizes[l] >= 0, "agglomerate: sizes[%d] is negative", l);

@@ -667,7 +667,11 @@ def agglomerate(edges, counts, sums, sizes, agglomeration_thresholds=(0.6, 0.8, 
     Parameters
     ----------
     edges, counts, sums, sizes : numpy.ndarray
-        What region_graph returns: K = len(sizes) - 1 fragments.
+        What region_graph returns: K = len(sizes) - 1 fragments. Every count
+        is in 1 .. 2^34, every sum at most count * 2^24, and all counts
+        together add up to at most 2^39 (sixteen times the voxel edges of a
+        4096 x 2048 x 2048 volume): pooled counts and sums then never wrap
+        their 64 bits. A larger total raises ValueError.
     agglomeration_thresholds : sequence of float, optional
         Non-decreasing; only the last one decides. Default is (0.6, 0.8, 0.9).
     min_segment_size : int, optional
@@ -710,13 +714,35 @@ def _checked_premerge(size_floor, rounds):
     return int(size_floor), int(rounds)
 
 
+# All counts of a region graph together: exaspim_agglomerate refuses more, and the device tables of the
+# pre-merge pool parallel edges in 64 bits, which is exact up to here (include/exaspim_affinity.h).
+MAX_TOTAL_COUNT = 1 << 39
+
+
+def _check_total_count(counts, what):
+    """
+    ValueError unless the int64 counts (a numpy array or a tensor, reduced
+    where they live) add up to at most 2^39. The high and the low 32 bits are
+    summed apart, so the total is exact for any values of up to 2^31 rows.
+    """
+    total = (int((counts >> 32).sum()) << 32) + int((counts & 0xFFFFFFFF).sum())
+    if not 0 <= total <= MAX_TOTAL_COUNT:
+        raise ValueError(f"{what}: the counts add up to {total}, needs a total of at most 2^39 = {MAX_TOTAL_COUNT} "
+                         "(parallel edges are pooled in 64 bits)")
+
+
 def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity,
-                        timings=None):
+                        timings=None, total_checked=False):
     """
     Rounds of exaspim_region_graph_premerge on a graph that is on the device,
     each on the previous one's output, until one merges nothing or "rounds"
     have run. One 12-byte read of the state per round; the maps are composed
     on the device (exaspim_apply_label_table on the composed map).
+
+    The counts must add up to at most 2^39 (the precondition of
+    exaspim_region_graph_premerge): unless total_checked says the caller has
+    seen to it, one reduction of the counts on the device checks it, and a
+    larger total raises ValueError before the first round.
 
     Parameters
     ----------
@@ -743,6 +769,8 @@ def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_flo
     stream = _stream(device)
     history, events = [], []
     with torch.cuda.device(device):
+        if not total_checked and n_edges:
+            _check_total_count(counts[:n_edges], "premerge_region_graph")
         composed = None
         need = lib.exaspim_region_graph_premerge_workspace_bytes(n_labels, capacity)
         if need == 0:
@@ -825,7 +853,11 @@ def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, 
     ----------
     edges, counts, sums, sizes : numpy.ndarray or torch.Tensor
         What region_graph returns, or the same on a HIP device (sums may be
-        int64 holding uint64 bits); numpy arrays are uploaded to cuda:0.
+        int64 holding uint64 bits); numpy arrays are uploaded to cuda:0. The
+        counts must add up to at most 2^39, agglomerate's bound (the device
+        pools parallel edges in 64 bits): one reduction of the counts, on the
+        side they live on, checks it, and a larger total raises ValueError
+        before the first round.
     threshold : float
         T of the mergeable test: the last agglomeration threshold.
     size_floor : int
@@ -850,14 +882,17 @@ def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, 
     if threshold != threshold:
         raise ValueError("the threshold is NaN")
     given = (edges, counts, sums, sizes)
+    on_host = not any(isinstance(a, torch.Tensor) for a in given)
     if all(isinstance(a, torch.Tensor) for a in given):
         device = sizes.device
         if device.type != "cuda" or any(a.device != device for a in given):
             raise RuntimeError("premerge_region_graph (MI355X) has no CPU path: the graph must be on one HIP device")
         edges, counts, sums, sizes = (a.contiguous() for a in given)
-    elif any(isinstance(a, torch.Tensor) for a in given):
+    elif not on_host:
         raise TypeError("premerge_region_graph needs the four arrays all on the host or all on the device")
     else:
+        # the counts are on the host: their total is checked here, before any device is asked for
+        _check_total_count(np.asarray(counts, dtype=np.int64), "premerge_region_graph")
         if not torch.cuda.is_available():
             raise RuntimeError("premerge_region_graph (MI355X) has no CPU path and no HIP device is present")
         device = torch.device("cuda:0")
@@ -873,7 +908,7 @@ def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, 
         raise ValueError("premerge_region_graph needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
     capacity = 1 << max(2 * n_edges - 1, 0).bit_length() if edge_capacity is None else int(edge_capacity)
     edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
-        edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity)
+        edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity, total_checked=on_host)
     with torch.cuda.device(device):
         graph = _download_graph(edges, counts, sums, sizes, n_edges)
         mapping = composed.cpu().numpy()

@@ -665,6 +665,9 @@ size_t exaspim_region_graph_stream_finish_workspace_bytes(int64_t edge_capacity)
  * format: edges_dev / count_dev / sum_dev hold st->edge_capacity entries, the first E in an unspecified
  * order are written, sizes_dev has n_labels + 1 entries, n_edges_dev[0] = E, n_edges_dev[1] = 1 if the
  * accumulator or the second table overflowed (the output is then unusable). Launches on "stream" only.
+ * PRECONDITION, not checked (the data is on the device): equal final keys are pooled in 64 bits, so the
+ * accumulated counts must add up to at most 2^39, exaspim_agglomerate's bound; beyond 2^40 a pooled sum
+ * can wrap. Counts of one volume's voxel edges (below 2^35.6 at 4096 x 2048 x 2048) are far inside it.
  * workspace_dev: 16-byte aligned, exaspim_region_graph_stream_finish_workspace_bytes(st->edge_capacity)
  * bytes, EXASPIM_E_WORKSPACE below that; EXASPIM_E_INVALID for a NULL or misaligned pointer, a bad
  * descriptor, table_len < 1 or a negative n_labels: all before anything is launched. */
@@ -677,7 +680,10 @@ int exaspim_region_graph_stream_finish(const exaspim_region_graph_stream* st, co
 /* Host only (no device is touched). Merges the fragments 1 .. n_labels of a region graph and numbers
  * what is left: table[0 .. n_labels] (int32), table[0] = 0, *n_segments = S.
  *  - Input: n_edges rows (lo, hi) of "edges" sorted by (lo, hi) without repeats, 1 <= lo < hi <= n_labels,
- *    with counts[i] >= 1 and sums[i] <= counts[i] * 2^24; sizes[0 .. n_labels] voxels per fragment.
+ *    with 1 <= counts[i] <= 2^34 and sums[i] <= counts[i] * 2^24; sizes[0 .. n_labels] voxels per fragment.
+ *    All counts together add up to at most 2^39 (a 4096 x 2048 x 2048 volume has 2^35.6 voxel edges):
+ *    pooled counts then stay within 2^39 and pooled sums within 2^63, so the 64-bit pools never wrap and
+ *    every 128-bit product is in range. A larger total is refused, with the total in the message.
  *  - Rule, exact in integers: m = rint((1 - (double)threshold) * 2^24). Among the CURRENT edges take the
  *    one with the largest mean sum / count (means compared by cross-multiplication in 128 bits; ties by
  *    the smaller lo, then the smaller hi, of the current root ids); merge it iff sum > m * count, else
@@ -688,7 +694,8 @@ int exaspim_region_graph_stream_finish(const exaspim_region_graph_stream* st, co
  *    (smallest) id; with fragments numbered in raster order of their first voxel that is the raster order
  *    of the segments' first voxels. A dropped segment's fragments map to 0.
  * EXASPIM_E_INVALID for a NULL pointer, a negative n_labels or n_edges, a NaN threshold, or an edge list
- * that breaks the input rules above. */
+ * that breaks the input rules above (the total of the counts included); table and *n_segments are then
+ * not written. */
 int exaspim_agglomerate(const int32_t* edges, const int64_t* counts, const uint64_t* sums, int64_t n_edges,
                         const int64_t* sizes, int32_t n_labels, float threshold, int64_t min_size,
                         int32_t* table, int32_t* n_segments);
@@ -794,6 +801,11 @@ size_t exaspim_region_graph_premerge_workspace_bytes(int32_t n_labels, int64_t e
  * edge_capacity slots in the workspace; edge_capacity >= n_edges always suffices, below that the flag
  * may come up and the edge list is then unusable (map and sizes' are not affected). Input and output
  * buffers must not overlap.
+ *  - PRECONDITION, not checked here (the data is on the device and nothing is read back before the
+ *    launches): 1 <= count <= 2^34 and sum <= count * 2^24 per row, and all counts together at most 2^39,
+ *    exaspim_agglomerate's bounds. The table pools parallel edges in 64 bits: within the bound a pooled sum
+ *    stays within 2^63 and every 128-bit comparison is exact, beyond it a pooled sum can wrap. A caller
+ *    that cannot vouch for its counts reduces them first.
  *  - Passes, each a launch of its own on "stream": one thread per edge bids for its tiny ends' best edge
  *    (32-bit compare-and-swap, a total order), one thread per fragment resolves mutual pairs, pointer
  *    doubling between two buffers ceil(log2 K) + 1 times, the sets' smallest ids by atomic minimum, a

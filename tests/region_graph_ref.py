@@ -11,7 +11,14 @@ plain way:
                                        each step, Python integers for every comparison
     agglomerate_affinities(aff, thresholds, min_size, fragment_threshold)
                                     -> labels int32, composed from these and components_ref.components
+    agglomerate_fast(edges, counts, sums, sizes, threshold, min_size)
+                                    -> agglomerate's (table, S) with a heap, for graphs of 10^4 fragments;
+                                       agglomerate stays the definition
+    mean_graph(seed, k, n_edges), wide_graph(seed, k, n_edges, levels, count_max, total_max, hubs)
+                                    -> random graphs (edges, counts, sums, sizes) for the tests
 """
+
+import heapq
 
 import numpy as np
 
@@ -96,6 +103,144 @@ def agglomerate(edges, counts, sums, sizes, threshold, min_size):
         else:
             table[label] = table[root[label]]
     return table, count
+
+
+class _Best:
+    """Heap entry of agglomerate_fast: the larger exact mean sorts first, then the smaller (lo, hi)."""
+
+    __slots__ = ("count", "sum", "lo", "hi")
+
+    def __init__(self, count, total, lo, hi):
+        self.count, self.sum, self.lo, self.hi = count, total, lo, hi
+
+    def __lt__(self, other):
+        left, right = self.sum * other.count, other.sum * self.count      # Python ints: exact at any width
+        if left != right:
+            return left > right
+        return (self.lo, self.hi) < (other.lo, other.hi)
+
+
+def agglomerate_fast(edges, counts, sums, sizes, threshold, min_size, merges=None):
+    """
+    agglomerate's contract in O(E log E) for the graphs the naive scan cannot reach; trusted only because
+    tests/test_agglomerate_scale_cpu.py holds it to agglomerate on small graphs. near[r] maps each current
+    neighbour root of root r to the contact's (count, sum); a heap entry is valid iff near[lo] still holds
+    its (count, sum) under hi. A merge moves the larger id's neighbours under the smaller id, pooling the
+    ones both have. "merges", a list, receives (lo, hi) of every merge in order.
+    """
+    k = len(sizes) - 1
+    m = int(np.rint((1.0 - float(np.float32(threshold))) * ONE))
+    near = {r: {} for r in range(k + 1)}        # one dict per current root id
+    heap = []
+    for (lo, hi), c, s in zip(np.asarray(edges).tolist(), np.asarray(counts).tolist(), np.asarray(sums).tolist()):
+        near[lo][hi] = near[hi][lo] = (c, s)
+        heap.append(_Best(c, s, lo, hi))
+    heapq.heapify(heap)
+    root = list(range(k + 1))
+    while heap:
+        top = heapq.heappop(heap)
+        u, v = top.lo, top.hi
+        if u not in near or near[u].get(v) != (top.count, top.sum):
+            continue
+        if not top.sum > m * top.count:
+            break
+        if merges is not None:
+            merges.append((u, v))
+        del near[u][v], near[v][u]
+        root[v] = u
+        for w, (c, s) in near[v].items():
+            del near[w][v]
+            if w in near[u]:
+                c, s = c + near[u][w][0], s + near[u][w][1]
+            near[u][w] = near[w][u] = (c, s)
+            heapq.heappush(heap, _Best(c, s, min(u, w), max(u, w)))
+        del near[v]
+    total = [0] * (k + 1)
+    for label in range(1, k + 1):      # root[v] < v, so root[root[label]] is final when label comes
+        root[label] = root[root[label]]
+        total[root[label]] += int(sizes[label])
+    table = np.zeros(k + 1, np.int32)
+    count = 0
+    for label in range(1, k + 1):
+        if root[label] == label:
+            if total[label] > min_size:
+                count += 1
+                table[label] = count
+        else:
+            table[label] = table[root[label]]
+    return table, count
+
+
+def _distinct_pairs(rng, k, n_edges, hubs=None):
+    """About n_edges distinct pairs lo < hi in 1 .. k, sorted; hubs=(n, degree) adds n stars of that degree."""
+    a = rng.integers(1, k + 1, n_edges)
+    b = rng.integers(1, k + 1, n_edges)
+    if hubs is not None:
+        n, degree = hubs
+        for hub in rng.choice(np.arange(1, k + 1), n, replace=False):
+            a = np.concatenate([a, np.full(degree, hub)])
+            b = np.concatenate([b, rng.choice(np.arange(1, k + 1), degree, replace=False)])
+    keep = a != b
+    keys = np.unique((np.minimum(a, b)[keep].astype(np.int64) << 32) | np.maximum(a, b)[keep])
+    return np.stack([keys >> 32, keys & 0xFFFFFFFF], axis=1).astype(np.int32).reshape(-1, 2)
+
+
+def mean_graph(seed, k, n_edges, count_max=49, max_size=40):
+    """A random graph with arbitrary means: counts 1 .. count_max, sums uniform in 0 .. count * 2^24."""
+    rng = np.random.default_rng(seed)
+    edges = _distinct_pairs(rng, k, n_edges)
+    counts = rng.integers(1, count_max + 1, len(edges)).astype(np.int64)
+    sums = rng.integers(0, counts * ONE + 1).astype(np.uint64)
+    return edges, counts, sums, rng.integers(1, max_size + 1, k + 1).astype(np.int64)
+
+
+def wide_graph(seed, k, n_edges, levels, count_max, total_max=1 << 39, hubs=None, max_size=40):
+    """
+    A random graph of near-ties between wide operands: about n_edges distinct pairs (plus the stars of
+    hubs=(n, degree)), counts uniform in 1 .. count_max but 1 once the running total would pass total_max,
+    sum = count * level + delta clamped to 0 .. count * 2^24, with level one of "levels" equally spaced
+    values of 0 .. 2^24 and delta in {-1, 0, 1}. With count_max near 2^34 the cross products of two
+    edges need more than 64 bits, and two means differ by far less than a double resolves.
+    """
+    rng = np.random.default_rng(seed)
+    edges = _distinct_pairs(rng, k, n_edges, hubs)
+    drawn = rng.integers(1, count_max + 1, len(edges)).tolist()
+    step = ONE // (levels - 1)
+    level = (rng.integers(0, levels, len(edges)) * step).tolist()
+    delta = rng.integers(-1, 2, len(edges)).tolist()
+    counts, sums, total = [], [], 0
+    for i, (c, q, d) in enumerate(zip(drawn, level, delta)):
+        if total + c + (len(drawn) - 1 - i) > total_max:     # the edges still to come count at least 1 each
+            c = 1
+        total += c
+        counts.append(c)
+        sums.append(min(max(c * q + d, 0), c * ONE))
+    return (edges, np.array(counts, np.int64).reshape(-1), np.array(sums, np.uint64).reshape(-1),
+            rng.integers(1, max_size + 1, k + 1).astype(np.int64))
+
+
+_VOLUMES = {}
+
+
+def fragment_volume(kind, dtype=np.float32, shape=(33, 65, 129)):
+    """
+    (aff, fragments, K, graph) of uniform random affinities with some 10^4 fragments, computed once per
+    session and read-only: kind "watershed" (basins between 0.3 and 0.7) or "components" (cut at 0.75).
+    """
+    import watershed_ref
+
+    key = (kind, np.dtype(dtype).name, tuple(shape))
+    if key not in _VOLUMES:
+        aff = np.array(watershed_ref.random_affinities("uniform", shape)).astype(dtype)
+        if kind == "watershed":
+            fragments, k = watershed_ref.fragments(aff, 0.3, 0.7)
+        else:
+            fragments, k = components_ref.components(aff, 0.75, 0)
+        graph = region_graph(fragments, aff, k)
+        for a in (aff, fragments) + graph:
+            a.setflags(write=False)
+        _VOLUMES[key] = (aff, fragments, k, graph)
+    return _VOLUMES[key]
 
 
 def agglomerate_affinities(aff, agglomeration_thresholds=(0.6, 0.8, 0.9), min_segment_size=100,

@@ -5,9 +5,13 @@ list after sorting by (lo, hi), map, sizes', K' and E' exact.
 
 The graphs sit where the kernels can go wrong: fragment counts around the scan's block of 2048, chains as
 long as the graph (pointer doubling), thousands of adds on one sizes' word and on one table slot, ties
-everywhere, the merge bound hit exactly. Every direct call runs with guard words behind every buffer and a
-workspace pre-filled with 0xFF.
+everywhere, the merge bound hit exactly, counts up to 2^27 whose cross products need the high words of the
+128-bit comparison and whose pooled sums pass 2^61. Every direct call runs with guard words behind every
+buffer and a workspace pre-filled with 0xFF. End to end the chain is also held to the oracles at 16 115
+watershed fragments (region_graph_ref.agglomerate_fast after premerge_ref.rounds).
 """
+
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -321,6 +325,104 @@ def test_premerge_region_graph_runs_rounds_on_host_and_device_arrays(dev):
     assert one[5] == want_history[:1]
 
 
+# ---- 7. wide operands: the high words of the 128-bit comparisons decide ----------------------------
+@pytest.mark.parametrize("k", [1, 2, 2047, 2048, 2049, 4097, 3000])
+def test_wide_near_ties_around_the_scan_block(dev, k):
+    """Counts up to 2^27, sum = count * level + {-1, 0, 1}: the cross products need up to 2^78, the
+    contracted counts and sums up to 2^39 and 2^63."""
+    graph = region_graph_ref.wide_graph(500 + k, k, 3 * k if k == 3000 else 2 * k, 5, 1 << 27)
+    edges, counts, sums, _ = graph
+    assert sum(counts.tolist()) <= 1 << 39
+    if k >= 2047:
+        products = [s * c for s, c in zip(sums[:-1].tolist(), counts[1:].tolist())]
+        assert 2 * sum(p >= 1 << 64 for p in products) >= len(products)
+    merged = False
+    for threshold, floor in ((0.3, 20), (0.55, 10), (0.8, 1000)):
+        want = check(dev, graph, threshold, floor)
+        merged |= len(want[3]) - 1 < k
+        assert k < 2047 or int(want[2].max()) > 1 << 50      # sums' far beyond 32 bits
+        want_graph, want_map, want_history = premerge_ref.rounds(*graph, threshold, floor, limit=4)
+        got = inference.premerge_region_graph(*graph, threshold, floor)
+        assert_same(got[:5], want_graph + (want_map,))
+        assert got[5] == want_history
+    assert k <= 2 or merged
+
+
+def wide_hub(tiny):
+    """
+    Fragment 2 is a hub of 3000 leaves (3 .. 3002), which all touch fragment 1 as well. The hub's contacts
+    have counts up to 2^27 and means a hair around 15/16 or 31/32, all above the bound of T = 0.1; the
+    contacts with fragment 1 have means around 7/8, below it. tiny="hub": the 3000 edges bid for the hub's
+    one word. tiny="leaves": every leaf joins the hub, and their contacts with 1 pool into one.
+    """
+    n = 3000
+    rng = np.random.default_rng(12)
+    leaves = np.arange(3, n + 3)
+    edges = np.array([(end, f) for end in (1, 2) for f in leaves], np.int32)
+    counts = rng.integers(1, (1 << 27) + 1, 2 * n).astype(np.int64)
+    level = np.concatenate([np.full(n, 7 * ONE // 8), rng.choice([15 * ONE // 16, 31 * ONE // 32], n)])
+    sums = (counts * level + rng.integers(-1, 2, 2 * n)).astype(np.uint64)
+    if tiny == "hub":
+        sizes = np.concatenate([[0, 10 ** 6, 1], np.full(n, 1000)]).astype(np.int64)
+    else:
+        sizes = np.concatenate([[0, 10 ** 6, 10 ** 5], rng.integers(1, 9, n)]).astype(np.int64)
+    assert sum(counts.tolist()) <= 1 << 39
+    return edges, counts, sums, sizes
+
+
+@pytest.mark.parametrize("tiny", ["hub", "leaves"])
+def test_a_hub_of_3000_wide_near_tied_contacts(dev, tiny):
+    graph = wide_hub(tiny)
+    edges, counts, sums, sizes = graph
+    m, _ = premerge_ref.merge_bound(0.1)
+    hub_edges = edges[:, 0] == 2
+    assert all(s > m * c for c, s in zip(counts[hub_edges].tolist(), sums[hub_edges].tolist()))
+    assert not any(s > m * c for c, s in zip(counts[~hub_edges].tolist(), sums[~hub_edges].tolist()))
+    e2, c2, s2, sizes2, mapping, _ = check(dev, graph, 0.1, 10)
+    if tiny == "hub":
+        # the hub joins one leaf: the exact maximum of 3000 means that agree to some 2^-27
+        best = max(np.flatnonzero(hub_edges).tolist(),
+                   key=lambda e: (Fraction(int(sums[e]), int(counts[e])), -int(edges[e, 1])))
+        assert len(sizes2) - 1 == 3001 and mapping[2] == mapping[edges[best, 1]] == 2
+        products = [s * c for s, c in zip(sums[hub_edges][:-1].tolist(), counts[hub_edges][1:].tolist())]
+        assert 2 * sum(p >= 1 << 64 for p in products) >= len(products)      # the high words decide
+    else:
+        assert len(sizes2) - 1 == 2 and e2.tolist() == [[1, 2]]
+        assert int(c2[0]) == sum(counts[~hub_edges].tolist()) > 1 << 37
+        assert int(s2[0]) == sum(sums[~hub_edges].tolist()) > 1 << 61
+    # two runs, the second on the first one's leftovers, and a fresh call
+    first, second = Call(dev, graph, 0.1, 10), Call(dev, graph, 0.1, 10)
+    assert first.run() == 0 and first.run() == 0 and second.run() == 0
+    assert first.guards_intact() and second.guards_intact() and first.inputs_untouched()
+    a, b = first.result(), second.result()
+    assert a[1] == b[1] == 0
+    assert_same(a[0], b[0])
+    assert_same(a[0], (e2, c2, s2, sizes2, mapping))
+    assert torch.equal(first.state[:3], second.state[:3]) and torch.equal(first.map, second.map)
+
+
+def test_a_total_count_above_2_39_is_refused_before_the_first_round(dev):
+    edges = np.array([(1, f) for f in range(2, 35)], np.int32)
+    counts = np.full(33, 1 << 34, np.int64)
+    sums = (counts * (ONE - 3)).astype(np.uint64)
+    sizes = np.full(35, 5, np.int64)
+    total = 33 << 34
+    with pytest.raises(ValueError, match=str(total)):
+        inference.premerge_region_graph(edges, counts, sums, sizes, 0.9, 10)
+    on_device = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+                 for a in (edges, counts, sums, sizes)]
+    with pytest.raises(ValueError, match=str(total)):
+        inference.premerge_region_graph(*on_device, 0.9, 10)
+    # two of the contacts halved: 2^39 exactly, which runs
+    counts[-1], counts[-2] = 1 << 33, 1 << 33
+    sums = (counts * (ONE - 3)).astype(np.uint64)
+    assert sum(counts.tolist()) == 1 << 39
+    on_device = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
+                 for a in (edges, counts, sums, sizes)]
+    got = inference.premerge_region_graph(*on_device, 0.9, 10, rounds=1)
+    assert_same(got[:5], premerge_ref.one_round(edges, counts, sums, sizes, 0.9, 10)[:5])
+
+
 THRESHOLDS = [0.6, 0.8, 0.9]
 _CHAIN = {}
 
@@ -385,4 +487,18 @@ def test_components_as_fragments_with_a_floor(dev):
     assert history[0] < k
     table, _ = region_graph_ref.agglomerate(*reduced, 0.5, 10)
     got = inference.agglomerate_affinities(aff, [0.5], 10, fragment_threshold=0.75, premerge_size=6)
+    np.testing.assert_array_equal(got, table[composed][fragments])
+
+
+@pytest.mark.parametrize("threshold", [0.6, 0.7])
+def test_end_to_end_at_sixteen_thousand_fragments(dev, threshold):
+    """(33, 65, 129) watershed fragments, floor 25: premerge_ref.rounds, then the heap oracle (the naive one
+    would take hours here)."""
+    aff, fragments, k, graph = region_graph_ref.fragment_volume("watershed")
+    aff = np.array(aff)                         # the shared one is read-only
+    reduced, composed, history = premerge_ref.rounds(*graph, threshold, 25, limit=4)
+    table, s = region_graph_ref.agglomerate_fast(*reduced, threshold, 0)
+    assert k >= 10000 and history[0] < k and 1 < s < history[-1]
+    got = inference.agglomerate_affinities(aff, [threshold], 0, fragments="watershed", aff_threshold_low=0.3,
+                                           aff_threshold_high=0.7, premerge_size=25)
     np.testing.assert_array_equal(got, table[composed][fragments])

@@ -7,7 +7,9 @@ The kernel reduces 8 x 8 x 32 tiles (with a +1 halo) in an LDS table of 2048 slo
 update per distinct key and tile into the global table; what finds no LDS slot goes to the global
 table directly. The shapes sit around the tile; "every voxel its own label" has about three distinct
 pairs per voxel, 6000 per tile, so the LDS table overflows; two slabs put all contention on one slot.
-Every direct call runs with guard words behind every buffer.
+Every direct call runs with guard words behind every buffer. The last section runs agglomerate_affinities
+and its streamed form at 16 115 watershed and 27 082 component fragments against the heap oracle
+(region_graph_ref.agglomerate_fast, itself held to the naive one in tests/test_agglomerate_scale_cpu.py).
 """
 
 import numpy as np
@@ -436,3 +438,37 @@ def test_predict_device_tensor_feeds_agglomeration(dev):
                                                return_device_tensor=True)
         np.testing.assert_array_equal(got.cpu().numpy(), table[fragments])
         assert int(got.max()) == s
+
+
+# ---- 13. end to end at 10^4 fragments, against the heap oracle ------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float16])
+def test_watershed_fragments_at_sixteen_thousand(dev, dtype):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    aff, fragments, k, graph = region_graph_ref.fragment_volume("watershed", dtype)
+    assert aff.dtype == dtype and k >= 10000
+    aff = np.array(aff)                         # the shared one is read-only
+    for threshold in (0.6, 0.7):
+        table, s = region_graph_ref.agglomerate_fast(*graph, threshold, 0)
+        assert 1 < s < k
+        got = inference.agglomerate_affinities(aff, [threshold], 0, fragments="watershed", aff_threshold_low=0.3,
+                                               aff_threshold_high=0.7)
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, table[fragments])
+
+
+def test_component_fragments_at_twenty_seven_thousand_whole_and_in_slabs(dev):
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    aff, fragments, k, graph = region_graph_ref.fragment_volume("components")
+    table, s = region_graph_ref.agglomerate_fast(*graph, 0.6, 10)
+    assert k >= 10000 and len(graph[0]) >= 3 * k and 1 < s < k
+    want = table[fragments]
+    aff = np.array(aff)                         # the shared one is read-only
+    whole = inference.agglomerate_affinities(aff, [0.6], 10, fragment_threshold=0.75)
+    np.testing.assert_array_equal(whole, want)
+    for slab_depth in (1, 8, 13):               # 33 planes: one-plane slabs, 4 x 8 + 1, 13 + 13 + 7
+        got = inference.agglomerate_affinities_streaming(aff, [0.6], 10, fragment_threshold=0.75,
+                                                         slab_depth=slab_depth)
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, whole, err_msg=f"slab_depth {slab_depth}")
