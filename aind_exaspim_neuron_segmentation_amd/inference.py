@@ -21,11 +21,20 @@ options are trailing keyword arguments. What differs is where the work runs:
   threads while the next layer computes (predict_streaming; predict() of a host
   array is that pipeline over the array).
 
+What lives here: predict, the sliding-window plan and its carry schedule, the
+percentiles, the slab pipeline, predict_streaming, and the two drivers that
+label slabs as the pipeline finishes them (predict_components_streaming,
+predict_agglomerate_streaming). Everything that starts from finished
+affinities -- components, watershed fragments, the region graph, pre-merge,
+agglomeration, ComponentsStream, RegionGraphStream and the drivers for
+affinities on the host -- lives in segmentation.py; those names are imported
+below, so each is reachable as inference.NAME as before and is the same
+object. The plan switches below are read by this module only.
+
 There is no CPU fallback: a model on a CPU device raises.
 """
 
 import collections
-import ctypes
 import itertools
 import threading
 import time
@@ -35,7 +44,15 @@ import numpy as np
 import torch
 
 from aind_exaspim_neuron_segmentation_amd import _native
+from aind_exaspim_neuron_segmentation_amd._device import _carrier, _stream
 from aind_exaspim_neuron_segmentation_amd.machine_learning.unet3d import UNet3D
+from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (importable from here as before)
+    DEFAULT_EDGE_CAPACITY, DEFAULT_ID_CAPACITY, MAX_TOTAL_COUNT, ComponentsStream, RegionGraphStream,
+    _AgglomerationLabeller, _ComponentsLabeller, _components_on_device, _default_edge_capacity, _LabelSink,
+    _last_threshold, _premerge_on_device, _premerged_table, _region_graph_device, _watershed_on_device,
+    affinities_to_components, affinities_to_components_streaming, agglomerate, agglomerate_affinities,
+    agglomerate_affinities_streaming, premerge_region_graph, region_graph, watershed_fragments,
+)
 from aind_exaspim_neuron_segmentation_amd.utils import img_util
 
 try:  # progress bar is cosmetic; the reference imports tqdm unconditionally
@@ -206,1501 +223,6 @@ def export_half(tensor, out=None):
         "exaspim_export_f16",
     )
     return out.view(tensor.shape)
-
-
-_AFF_CODES = {torch.float32: _native.AFF_F32, torch.float16: _native.AFF_F16}
-
-
-def _components_on_device(affinities, threshold=0.5, min_segment_size=100):
-    """
-    exaspim_components on a device tensor: the labels and the number of kept
-    segments, both left on the device (nothing is synchronised).
-
-    Parameters
-    ----------
-    affinities : torch.Tensor
-        float32 or float16 tensor on a HIP device, (3, D, H, W) affinities or
-        (D, H, W) foreground probabilities.
-    threshold : float, optional
-        Rounded to float32; an edge (a voxel, in foreground mode) is on iff
-        its value is >= it. Default is 0.5.
-    min_segment_size : int, optional
-        Components are kept iff they have more voxels than this. Default is 100.
-
-    Returns
-    -------
-    labels : torch.Tensor
-        int32 (D, H, W): 0 for background, 1 ... K in raster order of each
-        component's first voxel.
-    count : torch.Tensor
-        int32 (1,): K.
-    """
-    if not isinstance(affinities, torch.Tensor):
-        raise TypeError(f"_components_on_device needs a torch tensor, got {type(affinities).__name__}")
-    if affinities.dtype not in _AFF_CODES:
-        raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-    if affinities.dim() == 4:
-        if affinities.shape[0] != 3:
-            raise ValueError(f"4-D affinities must be (3, D, H, W), got {tuple(affinities.shape)}")
-        channels = 3
-    elif affinities.dim() == 3:
-        channels = 1
-    else:
-        raise ValueError("affinities must be (3, D, H, W) or a (D, H, W) foreground map, "
-                         f"got {affinities.dim()} dimensions")
-    if affinities.device.type != "cuda":
-        raise RuntimeError(
-            "affinities_to_components (MI355X) has no CPU path: the tensor must be on a HIP device, "
-            f"got {affinities.device}"
-        )
-    dims = tuple(int(v) for v in affinities.shape[-3:])
-    if min(dims) < 1:
-        raise ValueError(f"empty volume {dims}")
-    affinities = affinities.contiguous()
-    device = affinities.device
-    lib = _native.lib()
-    need = lib.exaspim_components_workspace_bytes(_native.int3(dims))
-    if need == 0:
-        raise ValueError(_native.last_error())
-    with torch.cuda.device(device):
-        labels = torch.empty(dims, dtype=torch.int32, device=device)
-        count = torch.empty(1, dtype=torch.int32, device=device)
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        _native.check(
-            lib.exaspim_components(affinities.data_ptr(), _AFF_CODES[affinities.dtype], channels,
-                                   _native.int3(dims), float(np.float32(threshold)), int(min_segment_size),
-                                   labels.data_ptr(), count.data_ptr(), workspace.data_ptr(), need,
-                                   _stream(device)),
-            "exaspim_components",
-        )
-    return labels, count
-
-
-def affinities_to_components(affinities, threshold=0.5, min_segment_size=100, *,
-                             return_device_tensor=False):
-    """
-    Labels the connected components of thresholded affinities on the device
-    and removes small ones.
-
-    What this is: the affinity graph in the reference's own convention
-    (img_util.get_affinity_channels, img_util.py:159-216: channel c at voxel v
-    is the edge between v and v + e_c, e = z, y, x; the entries at the last
-    index along axis c are ignored) cut at "threshold", its connected
-    components, then the reference's size filter (img_util.py:555-558: kept
-    iff size > min_segment_size) and a contiguous renumbering in raster order
-    of each component's first voxel. A voxel without an on edge is background.
-    A 3-D input is a foreground map: voxels >= threshold are on and
-    6-connected, and an on voxel alone is a component of size 1.
-
-    What this is not: waterz's watershed / agglomeration, which the
-    reference's affinities_to_segmentation runs (inference.py:196-237). That
-    stays a CPU library; nothing here merges or splits by affinity scores.
-
-    Parameters
-    ----------
-    affinities : torch.Tensor or numpy.ndarray
-        float32 or float16, (3, D, H, W) or (D, H, W): a tensor on a HIP
-        device (e.g. from predict(..., return_device_tensor=True)), or a numpy
-        array, which is uploaded to cuda:0. D * H * W must not exceed 2^31 - 1.
-    threshold : float, optional
-        Rounded to float32; on iff float32(value) >= it, NaN is off. Default
-        is 0.5.
-    min_segment_size : int, optional
-        Default is 100.
-    return_device_tensor : bool, optional
-        Return the labels as a device tensor instead of a numpy array.
-        Default is False.
-
-    Returns
-    -------
-    numpy.ndarray or torch.Tensor
-        int32 (D, H, W) labels: 4 bytes per voxel leave the device instead of
-        the 12 of the affinities.
-    """
-    if isinstance(affinities, np.ndarray):
-        if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
-            raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-        if affinities.ndim not in (3, 4):
-            raise ValueError("affinities must be (3, D, H, W) or a (D, H, W) foreground map, "
-                             f"got {affinities.ndim} dimensions")
-        if not torch.cuda.is_available():
-            raise RuntimeError("affinities_to_components (MI355X) has no CPU path and no HIP device is present")
-        affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
-    labels, _ = _components_on_device(affinities, threshold, min_segment_size)
-    if return_device_tensor:
-        return labels
-    return labels.cpu().numpy()
-
-
-# --- Watershed fragments (DESIGN 6g) ---
-def _watershed_on_device(affinities, low=0.1, high=0.9999, min_segment_size=0):
-    """
-    exaspim_watershed_fragments on a device tensor: the labels and the number
-    of kept fragments, both left on the device (nothing is synchronised).
-
-    Parameters
-    ----------
-    affinities : torch.Tensor
-        float32 or float16 (3, D, H, W) tensor on a HIP device.
-    low, high : float, optional
-        Rounded to float32; see watershed_fragments. Defaults are 0.1 and
-        0.9999.
-    min_segment_size : int, optional
-        Fragments are kept iff they have more voxels than this. Default is 0.
-
-    Returns
-    -------
-    labels : torch.Tensor
-        int32 (D, H, W): 0 for background, 1 ... K in raster order of each
-        fragment's first voxel.
-    count : torch.Tensor
-        int32 (1,): K.
-    """
-    if not isinstance(affinities, torch.Tensor):
-        raise TypeError(f"_watershed_on_device needs a torch tensor, got {type(affinities).__name__}")
-    if affinities.dtype not in _AFF_CODES:
-        raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-    if affinities.dim() != 4 or affinities.shape[0] != 3:
-        raise ValueError(f"watershed_fragments needs (3, D, H, W) affinities, got {tuple(affinities.shape)}; "
-                         "a foreground map has no affinities")
-    low, high = float(np.float32(low)), float(np.float32(high))
-    if low != low or high != high:
-        raise ValueError(f"aff_threshold_low and aff_threshold_high must not be NaN, got {low} and {high}")
-    if affinities.device.type != "cuda":
-        raise RuntimeError(
-            "watershed_fragments (MI355X) has no CPU path: the tensor must be on a HIP device, "
-            f"got {affinities.device}"
-        )
-    dims = tuple(int(v) for v in affinities.shape[-3:])
-    if min(dims) < 1:
-        raise ValueError(f"empty volume {dims}")
-    affinities = affinities.contiguous()
-    device = affinities.device
-    lib = _native.lib()
-    need = lib.exaspim_watershed_workspace_bytes(_native.int3(dims))
-    if need == 0:
-        raise ValueError(_native.last_error())
-    with torch.cuda.device(device):
-        labels = torch.empty(dims, dtype=torch.int32, device=device)
-        count = torch.empty(1, dtype=torch.int32, device=device)
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        _native.check(
-            lib.exaspim_watershed_fragments(affinities.data_ptr(), _AFF_CODES[affinities.dtype],
-                                            _native.int3(dims), low, high, int(min_segment_size),
-                                            labels.data_ptr(), count.data_ptr(), workspace.data_ptr(), need,
-                                            _stream(device)),
-            "exaspim_watershed_fragments",
-        )
-    return labels, count
-
-
-def watershed_fragments(affinities, aff_threshold_low=0.1, aff_threshold_high=0.9999, min_segment_size=0, *,
-                        return_device_tensor=False):
-    """
-    Labels the basins of a steepest-ascent watershed on the affinity graph on
-    the device: the fragments the reference's affinities_to_segmentation
-    starts from (inference.py:224-229, waterz.agglomerate(...,
-    aff_threshold_low=0.1, aff_threshold_high=0.9999)).
-
-    What this is, exactly: in the project's edge convention (channel c at
-    voxel v is the edge between v and v + e_c, e = z, y, x; the entries at the
-    last index along axis c are ignored), (1) an edge is eligible iff
-    float32(a) > aff_threshold_low, strictly (NaN never, +inf always); (2) a
-    voxel's steepest edge is its eligible incident edge of largest value,
-    among equal values the one whose other end has the smallest C-order
-    linear index (the order -z, -y, -x, +x, +y, +z); (3) an eligible edge is
-    on iff a >= aff_threshold_high or it is the steepest edge of one of its
-    two ends; (4) fragments are the connected components of the on edges, a
-    voxel without an on edge is background, a fragment is kept iff it has
-    more than max(min_segment_size, 1) voxels, and kept fragments are
-    numbered 1 ... K in raster order of each fragment's first voxel. No
-    relation between the two thresholds is required: with high <= low every
-    eligible edge is on.
-
-    What equals what: this equals the serial steepest-ascent watershed
-    (direction bits, plateau corners, breadth-first plateau division, pointer
-    chasing with ids in raster order) label for label on tie-free input, i.e.
-    where no voxel has two equal maximal eligible edges below
-    aff_threshold_high, by the oracle in tests/ (watershed_ref.py). Where
-    such ties exist the serial algorithm depends on its visiting order and
-    the two differ; this definition depends on no order. It has not been
-    compared with waterz itself, which also reads the same array as the
-    edges v -- v - e_c; the project keeps the convention the network was
-    trained in.
-
-    Parameters
-    ----------
-    affinities : torch.Tensor or numpy.ndarray
-        float32 or float16 (3, D, H, W): a tensor on a HIP device (e.g. from
-        predict(..., return_device_tensor=True)), or a numpy array, which is
-        uploaded to cuda:0. D * H * W must not exceed 2^31 - 1. A 3-D
-        foreground map has no affinities and raises ValueError.
-    aff_threshold_low, aff_threshold_high : float, optional
-        Rounded to float32, not NaN. Defaults are 0.1 and 0.9999, the
-        reference's.
-    min_segment_size : int, optional
-        Default is 0: every fragment is kept (the reference filters after
-        the agglomeration).
-    return_device_tensor : bool, optional
-        Return the labels as a device tensor instead of a numpy array.
-        Default is False.
-
-    Returns
-    -------
-    numpy.ndarray or torch.Tensor
-        int32 (D, H, W) labels.
-    """
-    if isinstance(affinities, np.ndarray):
-        if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
-            raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-        if affinities.ndim != 4 or affinities.shape[0] != 3:
-            raise ValueError(f"watershed_fragments needs (3, D, H, W) affinities, got {tuple(affinities.shape)}; "
-                             "a foreground map has no affinities")
-        if not torch.cuda.is_available():
-            raise RuntimeError("watershed_fragments (MI355X) has no CPU path and no HIP device is present")
-        affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
-    labels, _ = _watershed_on_device(affinities, aff_threshold_low, aff_threshold_high, min_segment_size)
-    if return_device_tensor:
-        return labels
-    return labels.cpu().numpy()
-
-
-# --- Mean-affinity agglomeration of components (DESIGN 6e) ---
-# Slots of the region graph's accumulator unless the caller says otherwise (edge_capacity): 48 bytes of
-# device memory each (24 in the table, 24 in the compacted list), so 192 MiB at most; a small volume
-# gets the next power of two above twice the 3 edges per voxel it can have at all.
-DEFAULT_EDGE_CAPACITY = 1 << 22
-
-
-def _default_edge_capacity(voxels):
-    want = 6 * int(voxels)
-    return min(DEFAULT_EDGE_CAPACITY, 1 << max(want - 1, 0).bit_length())
-
-
-def _region_graph_device(labels, affinities, n_labels, edge_capacity=None):
-    """
-    exaspim_region_graph on device tensors and the one read of its state: the
-    graph stays on the device.
-
-    Returns
-    -------
-    edges, counts, sums : torch.Tensor
-        int32 (capacity, 2), int64 (capacity,), int64 (capacity,) holding
-        uint64 bits: the first n_edges rows in an unspecified order.
-    sizes : torch.Tensor
-        int64 (n_labels + 1,).
-    n_edges : int
-    capacity : int
-
-    Raises
-    ------
-    RuntimeError
-        If the volume has more distinct pairs of adjacent labels than
-        edge_capacity.
-    """
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError(f"labels must be a 3-D int32 tensor, got {labels.dtype} with {labels.dim()} dimensions")
-    if affinities.dtype not in _AFF_CODES:
-        raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-    dims = tuple(int(v) for v in labels.shape)
-    if affinities.dim() != 4 or tuple(affinities.shape) != (3,) + dims:
-        raise ValueError(f"affinities must be (3, D, H, W) = {(3,) + dims}, got {tuple(affinities.shape)}; "
-                         "a foreground map has no affinities to score")
-    if min(dims) < 1:
-        raise ValueError(f"empty volume {dims}")
-    if labels.device.type != "cuda" or affinities.device != labels.device:
-        raise RuntimeError("region_graph (MI355X) has no CPU path: labels and affinities must be on one HIP "
-                           f"device, got {labels.device} and {affinities.device}")
-    n_labels = int(n_labels)
-    if n_labels < 0:
-        raise ValueError(f"n_labels must not be negative, got {n_labels}")
-    capacity = _default_edge_capacity(np.prod(dims, dtype=np.int64)) if edge_capacity is None else int(edge_capacity)
-    labels, affinities = labels.contiguous(), affinities.contiguous()
-    device = labels.device
-    lib = _native.lib()
-    need = lib.exaspim_region_graph_workspace_bytes(_native.int3(dims), n_labels, capacity)
-    if need == 0:
-        raise ValueError(_native.last_error())
-    with torch.cuda.device(device):
-        edges = torch.empty((capacity, 2), dtype=torch.int32, device=device)
-        counts = torch.empty(capacity, dtype=torch.int64, device=device)
-        sums = torch.empty(capacity, dtype=torch.int64, device=device)   # uint64 bits
-        sizes = torch.empty(n_labels + 1, dtype=torch.int64, device=device)
-        state = torch.empty(2, dtype=torch.int32, device=device)
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        _native.check(
-            lib.exaspim_region_graph(labels.data_ptr(), affinities.data_ptr(), _AFF_CODES[affinities.dtype],
-                                     _native.int3(dims), n_labels, capacity, edges.data_ptr(), counts.data_ptr(),
-                                     sums.data_ptr(), sizes.data_ptr(), state.data_ptr(), workspace.data_ptr(),
-                                     need, _stream(device)),
-            "exaspim_region_graph",
-        )
-        n_edges, overflow = (int(v) for v in state.cpu())   # the one read of the device state
-        if overflow:
-            raise RuntimeError(
-                f"region_graph: the volume has more pairs of adjacent labels than edge_capacity={capacity}; "
-                "run it again with a larger edge_capacity (a power of two)")
-    return edges, counts, sums, sizes, n_edges, capacity
-
-
-def _region_graph_on_device(labels, affinities, n_labels, edge_capacity=None):
-    """
-    exaspim_region_graph on device tensors, then the one small download.
-
-    Returns
-    -------
-    edges : numpy.ndarray
-        int32 (E, 2), rows (lo, hi) sorted by (lo, hi).
-    counts : numpy.ndarray
-        int64 (E,): voxel edges between the two labels.
-    sums : numpy.ndarray
-        uint64 (E,): the sum of q(affinity) over them, q in units of 2^-24.
-    sizes : numpy.ndarray
-        int64 (n_labels + 1,): voxels per label, index 0 the background.
-
-    Raises
-    ------
-    RuntimeError
-        If the volume has more distinct pairs of adjacent labels than
-        edge_capacity.
-    """
-    edges, counts, sums, sizes, n_edges, _ = _region_graph_device(labels, affinities, n_labels, edge_capacity)
-    with torch.cuda.device(labels.device):
-        return _download_graph(edges, counts, sums, sizes, n_edges)
-
-
-def _download_graph(edges, counts, sums, sizes, n_edges):
-    """The first n_edges rows of a device graph, and its sizes, as numpy arrays sorted by (lo, hi)."""
-    edges_h = edges[:n_edges].cpu().numpy().reshape(-1, 2)
-    counts_h = counts[:n_edges].cpu().numpy()
-    sums_h = sums[:n_edges].cpu().numpy().view(np.uint64)
-    sizes_h = sizes.cpu().numpy()
-    order = np.lexsort((edges_h[:, 1], edges_h[:, 0]))   # slot order depends on arrival: sort by (lo, hi)
-    return (np.ascontiguousarray(edges_h[order]), np.ascontiguousarray(counts_h[order]),
-            np.ascontiguousarray(sums_h[order]), sizes_h)
-
-
-def region_graph(labels, affinities, *, edge_capacity=None):
-    """
-    The region graph of a labelled volume on the device: for every pair of
-    adjacent labels the number of voxel edges between them and the sum of
-    their affinities, and the number of voxels per label.
-
-    For every in-volume voxel edge (img_util.get_affinity_channels'
-    convention: channel c at voxel v is the edge between v and v + e_c,
-    e = z, y, x; the entries at the last index along axis c are ignored)
-    whose two labels are positive and differ: key = (smaller, larger label),
-    count[key] += 1, sum[key] += q(a) with q(a) = rint(clamp(float32(a), 0,
-    1) * 2^24), NaN as 0. Counts and sums are 64-bit integers, so the result
-    does not depend on the order in which the device adds them.
-
-    Parameters
-    ----------
-    labels : torch.Tensor or numpy.ndarray
-        int32 (D, H, W); labels <= 0 are background.
-    affinities : torch.Tensor or numpy.ndarray
-        float32 or float16 (3, D, H, W). Device tensors are used where they
-        are; numpy arrays are uploaded to cuda:0.
-    edge_capacity : int, optional
-        Slots of the device hash table, a power of two. Default is the
-        smaller of 2^22 and the next power of two >= 6 * D * H * W.
-
-    Returns
-    -------
-    edges : numpy.ndarray
-        int32 (E, 2), rows (lo, hi) sorted by (lo, hi).
-    counts : numpy.ndarray
-        int64 (E,).
-    sums : numpy.ndarray
-        uint64 (E,), in units of 2^-24: sums / counts / 2^24 is the mean
-        affinity of the contact.
-    sizes : numpy.ndarray
-        int64 (labels.max() + 1,): voxels per label, index 0 the voxels
-        labelled 0 (negative labels are counted nowhere).
-    """
-    def on_device(a, what, dtypes):
-        if isinstance(a, np.ndarray):
-            if a.dtype not in dtypes:
-                raise TypeError(f"{what} must be {' or '.join(str(np.dtype(d)) for d in dtypes)}, got {a.dtype}")
-            if not torch.cuda.is_available():
-                raise RuntimeError("region_graph (MI355X) has no CPU path and no HIP device is present")
-            return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-        if not isinstance(a, torch.Tensor):
-            raise TypeError(f"{what} must be a torch tensor or a numpy array, got {type(a).__name__}")
-        return a
-
-    labels = on_device(labels, "labels", (np.int32,))
-    affinities = on_device(affinities, "affinities", (np.float32, np.float16))
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError(f"labels must be a 3-D int32 tensor, got {labels.dtype} with {labels.dim()} dimensions")
-    n_labels = max(int(labels.max()), 0) if labels.numel() else 0
-    return _region_graph_on_device(labels, affinities, n_labels, edge_capacity)
-
-
-def _last_threshold(agglomeration_thresholds):
-    """The threshold that decides (the reference keeps only the last segmentation, deque(maxlen=1))."""
-    thresholds = [float(t) for t in agglomeration_thresholds]
-    if not thresholds:
-        raise ValueError("agglomeration_thresholds is empty")
-    if any(t != t for t in thresholds):
-        raise ValueError(f"agglomeration_thresholds holds a NaN: {thresholds}")
-    if any(b < a for a, b in zip(thresholds, thresholds[1:])):
-        raise ValueError(f"agglomeration_thresholds must be non-decreasing, got {thresholds}")
-    return thresholds[-1]
-
-
-def agglomerate(edges, counts, sums, sizes, agglomeration_thresholds=(0.6, 0.8, 0.9), min_segment_size=100):
-    """
-    Merges the fragments of a region graph by the mean affinity of their
-    contacts (exaspim_agglomerate: host code, no device is touched).
-
-    Among the current edges the one with the largest mean sum / count goes
-    first (ties: the smaller lo, then the smaller hi, of the current root
-    ids); it is merged iff sum > rint((1 - T) * 2^24) * count, T the last
-    threshold rounded to float32, i.e. iff 1 - mean affinity < T; the larger
-    root goes under the smaller and parallel edges to a common neighbour add
-    their counts and sums. All comparisons are exact integer ones. Then a
-    segment is kept iff the sizes of its fragments sum to more than
-    min_segment_size, and kept segments are numbered 1 ... S by their
-    smallest fragment id.
-
-    Parameters
-    ----------
-    edges, counts, sums, sizes : numpy.ndarray
-        What region_graph returns: K = len(sizes) - 1 fragments. Every count
-        is in 1 .. 2^34, every sum at most count * 2^24, and all counts
-        together add up to at most 2^39 (sixteen times the voxel edges of a
-        4096 x 2048 x 2048 volume): pooled counts and sums then never wrap
-        their 64 bits. A larger total raises ValueError.
-    agglomeration_thresholds : sequence of float, optional
-        Non-decreasing; only the last one decides. Default is (0.6, 0.8, 0.9).
-    min_segment_size : int, optional
-        Default is 100.
-
-    Returns
-    -------
-    table : numpy.ndarray
-        int32 (K + 1,): fragment id -> segment label, table[0] = 0.
-    count : int
-        S, the number of kept segments.
-    """
-    threshold = _last_threshold(agglomeration_thresholds)
-    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
-    counts = np.ascontiguousarray(counts, dtype=np.int64)
-    sums = np.ascontiguousarray(sums, dtype=np.uint64)
-    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
-    if sizes.ndim != 1 or sizes.size < 1 or counts.shape != (edges.shape[0],) or sums.shape != counts.shape:
-        raise ValueError("agglomerate needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
-    table = np.zeros(sizes.size, np.int32)
-    n_segments = ctypes.c_int32(0)
-    _native.check(
-        _native.lib().exaspim_agglomerate(edges.ctypes.data, counts.ctypes.data, sums.ctypes.data, edges.shape[0],
-                                          sizes.ctypes.data, sizes.size - 1, float(np.float32(threshold)),
-                                          int(min_segment_size), table.ctypes.data, ctypes.addressof(n_segments)),
-        "exaspim_agglomerate",
-    )
-    return table, int(n_segments.value)
-
-
-def _checked_premerge(size_floor, rounds):
-    """(size_floor, rounds) as ints; ValueError for negatives and non-integers, before any device call."""
-    for what, v, least in (("the size floor", size_floor, 0), ("the number of rounds", rounds, 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{what} must be an integer, got {v!r}")
-        if v < least:
-            raise ValueError(f"{what} must be at least {least}, got {v}")
-    if size_floor >= 1 << 63:
-        raise ValueError(f"the size floor must fit in 63 bits, got {size_floor}")
-    return int(size_floor), int(rounds)
-
-
-# All counts of a region graph together: exaspim_agglomerate refuses more, and the device tables of the
-# pre-merge pool parallel edges in 64 bits, which is exact up to here (include/exaspim_affinity.h).
-MAX_TOTAL_COUNT = 1 << 39
-
-
-def _check_total_count(counts, what):
-    """
-    ValueError unless the int64 counts (a numpy array or a tensor, reduced
-    where they live) add up to at most 2^39. The high and the low 32 bits are
-    summed apart, so the total is exact for any values of up to 2^31 rows.
-    """
-    total = (int((counts >> 32).sum()) << 32) + int((counts & 0xFFFFFFFF).sum())
-    if not 0 <= total <= MAX_TOTAL_COUNT:
-        raise ValueError(f"{what}: the counts add up to {total}, needs a total of at most 2^39 = {MAX_TOTAL_COUNT} "
-                         "(parallel edges are pooled in 64 bits)")
-
-
-def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity,
-                        timings=None, total_checked=False):
-    """
-    Rounds of exaspim_region_graph_premerge on a graph that is on the device,
-    each on the previous one's output, until one merges nothing or "rounds"
-    have run. One 12-byte read of the state per round; the maps are composed
-    on the device (exaspim_apply_label_table on the composed map).
-
-    The counts must add up to at most 2^39 (the precondition of
-    exaspim_region_graph_premerge): unless total_checked says the caller has
-    seen to it, one reduction of the counts on the device checks it, and a
-    larger total raises ValueError before the first round.
-
-    Parameters
-    ----------
-    edges, counts, sums, sizes : torch.Tensor
-        The graph in exaspim_region_graph's output format (sums holds uint64
-        bits); edges, counts and sums hold at least n_edges rows. Only read.
-    timings : list, optional
-        If given, HIP events time every round and the milliseconds are
-        appended (a measurement aid: it synchronises once at the end).
-
-    Returns
-    -------
-    edges, counts, sums, sizes : torch.Tensor
-        The reduced graph: n_edges rows in an unspecified order, K' + 1 sizes.
-    n_edges : int
-    composed : torch.Tensor
-        int32 (K + 1,): fragment id -> id in the reduced graph.
-    history : list of (int, int)
-        (K', E') after every round that ran.
-    """
-    device = sizes.device
-    n_labels = int(sizes.numel()) - 1
-    lib = _native.lib()
-    stream = _stream(device)
-    history, events = [], []
-    with torch.cuda.device(device):
-        if not total_checked and n_edges:
-            _check_total_count(counts[:n_edges], "premerge_region_graph")
-        composed = None
-        need = lib.exaspim_region_graph_premerge_workspace_bytes(n_labels, capacity)
-        if need == 0:
-            raise ValueError(_native.last_error())
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        state = torch.empty(3, dtype=torch.int32, device=device)
-        spare = None   # the buffers the round after next may write: never the caller's
-        for _ in range(rounds):
-            k = int(sizes.numel()) - 1
-            if spare is None:
-                out = (torch.empty((capacity, 2), dtype=torch.int32, device=device),
-                       torch.empty(capacity, dtype=torch.int64, device=device),
-                       torch.empty(capacity, dtype=torch.int64, device=device))
-            else:
-                out, spare = spare, None
-            sizes_out = torch.empty(k + 1, dtype=torch.int64, device=device)
-            mapping = torch.empty(k + 1, dtype=torch.int32, device=device)
-            if timings is not None:
-                events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                events[-1][0].record()
-            _native.check(
-                lib.exaspim_region_graph_premerge(edges.data_ptr(), counts.data_ptr(), sums.data_ptr(),
-                                                  sizes.data_ptr(), n_edges, k, float(np.float32(threshold)),
-                                                  size_floor, capacity, out[0].data_ptr(), out[1].data_ptr(),
-                                                  out[2].data_ptr(), sizes_out.data_ptr(), mapping.data_ptr(),
-                                                  state.data_ptr(), workspace.data_ptr(), need, stream),
-                "exaspim_region_graph_premerge",
-            )
-            if composed is None:
-                composed = mapping
-            else:
-                _native.check(
-                    lib.exaspim_apply_label_table(composed.data_ptr(), composed.numel(), mapping.data_ptr(),
-                                                  mapping.numel(), stream),
-                    "exaspim_apply_label_table",
-                )
-            if timings is not None:
-                events[-1][1].record()
-            k_new, e_new, overflow = (int(v) for v in state.cpu())   # the round's one read of the device
-            if overflow:
-                raise RuntimeError(
-                    f"premerge_region_graph: the contracted graph found no room in edge_capacity={capacity} "
-                    "slots; run it again with a larger edge_capacity (a power of two)")
-            if history:   # this round's input was an earlier round's output: free for the next one
-                spare = (edges, counts, sums)
-            edges, counts, sums = out
-            sizes, n_edges = sizes_out[:k_new + 1], e_new
-            history.append((k_new, e_new))
-            if k_new == k:
-                break
-        if timings is not None:
-            torch.cuda.synchronize(device)
-            timings.extend(a.elapsed_time(b) for a, b in events)
-    return edges, counts, sums, sizes, n_edges, composed, history
-
-
-def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, rounds=4, edge_capacity=None):
-    """
-    Merges the tiny fragments of a region graph into their best neighbours
-    on the device (exaspim_region_graph_premerge), so that
-    agglomerate starts from far fewer fragments.
-
-    One round: an edge is mergeable iff sum > rint((1 - T) * 2^24) * count
-    (agglomerate's test at threshold T); every fragment with fewer than
-    size_floor voxels that has a mergeable edge joins the neighbour across
-    its mergeable edge of largest mean (equal means: the smaller neighbour
-    id; of two fragments that choose each other the smaller id stays), whole
-    chains at once; the sets are numbered by their smallest member id, sizes
-    add up, edges inside a set vanish and parallel edges add their counts and
-    sums. Rounds run on their own output until one merges nothing or
-    "rounds" of them have run. All comparisons are exact integer ones.
-
-    This is not agglomerate's rule: a tiny fragment joins its best neighbour
-    at once, whatever that neighbour would have merged with first, so
-    agglomerating the reduced graph can give another segmentation than
-    agglomerating the input. size_floor 0 (and 1, when no fragment is empty)
-    returns the input.
-
-    Parameters
-    ----------
-    edges, counts, sums, sizes : numpy.ndarray or torch.Tensor
-        What region_graph returns, or the same on a HIP device (sums may be
-        int64 holding uint64 bits); numpy arrays are uploaded to cuda:0. The
-        counts must add up to at most 2^39, agglomerate's bound (the device
-        pools parallel edges in 64 bits): one reduction of the counts, on the
-        side they live on, checks it, and a larger total raises ValueError
-        before the first round.
-    threshold : float
-        T of the mergeable test: the last agglomeration threshold.
-    size_floor : int
-        Fragments below this many voxels are merged. Not negative.
-    rounds : int, optional
-        The most rounds to run. Default is 4.
-    edge_capacity : int, optional
-        Slots of the device hash table, a power of two. Default is the next
-        power of two >= 2 * E.
-
-    Returns
-    -------
-    edges, counts, sums, sizes : numpy.ndarray
-        The reduced graph in region_graph's format, sorted by (lo, hi).
-    mapping : numpy.ndarray
-        int32 (K + 1,): fragment id -> id in the reduced graph, map[0] = 0.
-    history : list of int
-        The number of fragments after every round that ran.
-    """
-    size_floor, rounds = _checked_premerge(size_floor, rounds)
-    threshold = float(threshold)
-    if threshold != threshold:
-        raise ValueError("the threshold is NaN")
-    given = (edges, counts, sums, sizes)
-    on_host = not any(isinstance(a, torch.Tensor) for a in given)
-    if all(isinstance(a, torch.Tensor) for a in given):
-        device = sizes.device
-        if device.type != "cuda" or any(a.device != device for a in given):
-            raise RuntimeError("premerge_region_graph (MI355X) has no CPU path: the graph must be on one HIP device")
-        edges, counts, sums, sizes = (a.contiguous() for a in given)
-    elif not on_host:
-        raise TypeError("premerge_region_graph needs the four arrays all on the host or all on the device")
-    else:
-        # the counts are on the host: their total is checked here, before any device is asked for
-        _check_total_count(np.asarray(counts, dtype=np.int64), "premerge_region_graph")
-        if not torch.cuda.is_available():
-            raise RuntimeError("premerge_region_graph (MI355X) has no CPU path and no HIP device is present")
-        device = torch.device("cuda:0")
-        edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).to(device)
-        counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(device)
-        sums = torch.from_numpy(np.ascontiguousarray(sums, dtype=np.uint64).view(np.int64)).to(device)
-        sizes = torch.from_numpy(np.ascontiguousarray(sizes, dtype=np.int64)).to(device)
-    if (edges.dtype != torch.int32 or counts.dtype != torch.int64 or sums.dtype != torch.int64
-            or sizes.dtype != torch.int64):
-        raise TypeError("premerge_region_graph needs int32 edges and 64-bit counts, sums and sizes")
-    n_edges = int(counts.numel())
-    if (sizes.dim() != 1 or sizes.numel() < 1 or edges.numel() != 2 * n_edges or sums.numel() != n_edges):
-        raise ValueError("premerge_region_graph needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
-    capacity = 1 << max(2 * n_edges - 1, 0).bit_length() if edge_capacity is None else int(edge_capacity)
-    edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
-        edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity, total_checked=on_host)
-    with torch.cuda.device(device):
-        graph = _download_graph(edges, counts, sums, sizes, n_edges)
-        mapping = composed.cpu().numpy()
-    return graph + (mapping, [k for k, _ in history])
-
-
-def _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity, premerge_size,
-                     premerge_rounds, stats=None):
-    """
-    The fragment -> segment table of agglomerate_affinities with a size
-    floor, as a device tensor: the region graph stays on the device, the
-    pre-merge rounds run there, only the reduced graph is downloaded and
-    agglomerated, and the final table is composed with the rounds' map on the
-    device. "stats", a dict, receives the rounds' history, their device
-    milliseconds, the host merging time and the number of segments.
-    """
-    device = labels.device
-    edges, counts, sums, sizes, n_edges, capacity = _region_graph_device(labels, affinities, n_fragments,
-                                                                         edge_capacity)
-    timings = None if stats is None else []
-    edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
-        edges, counts, sums, sizes, n_edges, thresholds[-1], premerge_size, premerge_rounds, capacity, timings)
-    with torch.cuda.device(device):
-        graph = _download_graph(edges, counts, sums, sizes, n_edges)
-        t0 = time.perf_counter()
-        table, n_segments = agglomerate(*graph, thresholds, min_segment_size)
-        host_ms = (time.perf_counter() - t0) * 1e3
-        table_dev = torch.from_numpy(table).to(device)
-        _native.check(
-            _native.lib().exaspim_apply_label_table(composed.data_ptr(), composed.numel(), table_dev.data_ptr(),
-                                                    table.size, _stream(device)),
-            "exaspim_apply_label_table",
-        )
-    if stats is not None:
-        stats.update(fragments=n_fragments, history=history, round_ms=timings, host_ms=host_ms,
-                     segments=n_segments)
-    return composed
-
-
-def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
-                           fragment_threshold=0.5, edge_capacity=None, return_device_tensor=False,
-                           fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999,
-                           premerge_size=0, premerge_rounds=4):
-    """
-    Segments affinities by mean-affinity agglomeration of fragments, in the
-    reference's order of operations.
-
-    What this is: the three steps of the reference's
-    affinities_to_segmentation (inference.py:196-237) with exactly defined
-    parts. (1) Fragments: with fragments="components", the default, the
-    connected components of the affinity graph cut at fragment_threshold
-    (affinities_to_components with no size filter); with
-    fragments="watershed" the basins of a steepest-ascent watershed between
-    aff_threshold_low and aff_threshold_high (watershed_fragments with no
-    size filter), which is the kind of fragment the reference starts from.
-    (2) Fragments whose contact surface has a high mean affinity are merged,
-    greedily in order of the score waterz uses by default, 1 - mean affinity
-    of the contact, while that score is below the last agglomeration
-    threshold (see agglomerate for the exact integer rule). The contact
-    counts and affinity sums come from one pass on the device
-    (exaspim_region_graph), the merging runs on the host on the graph of
-    fragments. (3) Only then segments of at most min_segment_size voxels are
-    removed (img_util.py:555-558) and the rest is numbered 1 ... S in raster
-    order of each segment's first voxel. The positional arguments and their
-    defaults are those of affinities_to_segmentation.
-
-    What this is not: waterz. Connected components at a threshold are not
-    watershed basins: one voxel edge above fragment_threshold fuses two
-    neurites for good, and agglomeration only merges. The watershed
-    fragments equal the serial steepest-ascent watershed on tie-free input
-    (no voxel with two equal maximal eligible edges below
-    aff_threshold_high), label for label, by the oracle in tests/
-    (watershed_ref.py); where affinities tie, the serial algorithm depends
-    on its visiting order and the two differ. Neither kind has been compared
-    with waterz itself, which reads the same array as the edges v -- v - e_c
-    while the project keeps the convention the network was trained in, so
-    the name differs on purpose. Only the segmentation of the last threshold
-    is returned, as in the reference (deque(maxlen=1)); greedy merging in
-    score order makes it independent of the intermediate stops.
-
-    Parameters
-    ----------
-    affinities : torch.Tensor or numpy.ndarray
-        float32 or float16 (3, D, H, W): a tensor on a HIP device (e.g. from
-        predict(..., return_device_tensor=True)), or a numpy array, which is
-        uploaded to cuda:0. A 3-D foreground map has no affinities to score.
-    agglomeration_thresholds : sequence of float, optional
-        Non-decreasing. Default is [0.6, 0.8, 0.9].
-    min_segment_size : int, optional
-        Default is 100.
-    fragment_threshold : float, optional
-        Used with fragments="components". Default is 0.5.
-    edge_capacity : int, optional
-        See region_graph.
-    return_device_tensor : bool, optional
-        Return the labels as a device tensor instead of a numpy array.
-        Default is False.
-    fragments : {"components", "watershed"}, optional
-        The kind of fragments. Default is "components".
-    aff_threshold_low, aff_threshold_high : float, optional
-        Used with fragments="watershed". Defaults are 0.1 and 0.9999, the
-        reference's.
-    premerge_size : int, optional
-        0, the default, is the path described above. A positive value
-        CHANGES THE SEGMENTATION: before the host merging, every fragment
-        with fewer than premerge_size voxels joins, on the device, the
-        neighbour across its contact of largest mean affinity among those
-        the last threshold would merge (premerge_region_graph), whole chains
-        at once and whatever that neighbour would itself have merged with
-        first; the greedy merging then starts from the reduced graph, which
-        is the only one downloaded. Watershed fragments of a large volume are
-        millions of tiny basins, and this is what makes the host step
-        affordable there. 1 gives the labels of 0 (no fragment is empty).
-        Negative values and non-integers raise ValueError.
-    premerge_rounds : int, optional
-        The most pre-merge rounds; they stop when one merges nothing.
-        Default is 4.
-
-    Returns
-    -------
-    numpy.ndarray or torch.Tensor
-        int32 (D, H, W) labels: 4 bytes per voxel leave the device.
-    """
-    thresholds = list(agglomeration_thresholds)
-    _last_threshold(thresholds)
-    premerge_size, premerge_rounds = _checked_premerge(premerge_size, premerge_rounds)
-    if fragments not in ("components", "watershed"):
-        raise ValueError(f'fragments must be "components" or "watershed", got {fragments!r}')
-    if isinstance(affinities, np.ndarray):
-        if affinities.dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
-            raise TypeError(f"affinities must be float32 or float16, got {affinities.dtype}")
-        ndim = affinities.ndim
-    elif isinstance(affinities, torch.Tensor):
-        ndim = affinities.dim()
-    else:
-        raise TypeError(f"affinities must be a torch tensor or a numpy array, got {type(affinities).__name__}")
-    if ndim != 4 or affinities.shape[0] != 3:
-        raise ValueError(f"agglomerate_affinities needs (3, D, H, W) affinities, got {tuple(affinities.shape)}; "
-                         "a foreground map has no affinities to score")
-    if isinstance(affinities, np.ndarray):
-        if not torch.cuda.is_available():
-            raise RuntimeError("agglomerate_affinities (MI355X) has no CPU path and no HIP device is present")
-        affinities = torch.from_numpy(np.ascontiguousarray(affinities)).to("cuda:0")
-    affinities = affinities.contiguous()
-    if fragments == "watershed":
-        labels, count = _watershed_on_device(affinities, aff_threshold_low, aff_threshold_high, 0)
-    else:
-        labels, count = _components_on_device(affinities, fragment_threshold, 0)
-    n_fragments = int(count.cpu()[0])
-    device = labels.device
-    if premerge_size:
-        table_dev = _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity,
-                                     premerge_size, premerge_rounds)
-    else:
-        edges, counts, sums, sizes = _region_graph_on_device(labels, affinities, n_fragments, edge_capacity)
-        table, _ = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
-        with torch.cuda.device(device):
-            table_dev = torch.from_numpy(table).to(device)
-    with torch.cuda.device(device):
-        _native.check(
-            _native.lib().exaspim_apply_label_table(labels.data_ptr(), labels.numel(), table_dev.data_ptr(),
-                                                    table_dev.numel(), _stream(device)),
-            "exaspim_apply_label_table",
-        )
-    if return_device_tensor:
-        return labels
-    return labels.cpu().numpy()
-
-
-# Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes
-# of device memory each, so 256 MiB at most; a volume with fewer voxels gets as many ids as voxels.
-DEFAULT_ID_CAPACITY = 1 << 24
-
-
-class ComponentsStream:
-    """
-    affinities_to_components for a volume that arrives in z slabs:
-    every slab is labelled while it sits on the device, components are joined
-    across the seams between slabs, and the final labels equal, bit for bit,
-    those of the whole volume -- which may have more than 2^31 - 1 voxels and
-    never has to be anywhere in one piece.
-
-        cs = ComponentsStream((D, H, W), threshold, min_segment_size)
-        for slab in slabs_in_z_order:          # (3, d, H, W) device tensors
-            provisional = cs.push(slab)        # int32 (d, H, W), provisional ids
-            ...keep or download provisional...
-        table, k = cs.finish()                 # provisional id -> final label
-        cs.apply(provisional)                  # in place, any run of voxels
-
-    Parameters
-    ----------
-    shape : Tuple[int]
-        (D, H, W) of the whole volume; H * W and every slab must stay within
-        2^31 - 1 voxels, D * H * W need not.
-    threshold, min_segment_size
-        As in affinities_to_components.
-    foreground : bool, optional
-        Slabs are (d, H, W) foreground probabilities instead of (3, d, H, W)
-        affinities. Default is False.
-    device : torch.device, optional
-        Default is cuda:0.
-    id_capacity : int, optional
-        Most provisional ids the volume may use (1 .. 2^31 - 2). An id goes
-        to every slab-local component with more than min_segment_size voxels
-        and to every one with an edge across a seam, so shallow slabs of noisy
-        affinities need more. The id count stays on the device while slabs are
-        pushed; finish() raises if it went past the capacity. 16 bytes of
-        device memory per id. Default: DEFAULT_ID_CAPACITY (2^24), or the
-        number of voxels if that is less.
-    """
-
-    def __init__(self, shape, threshold=0.5, min_segment_size=100, *, foreground=False, device=None,
-                 id_capacity=None):
-        shape = tuple(int(v) for v in shape)
-        if len(shape) != 3 or min(shape) < 1:
-            raise ValueError(f"shape must be a non-empty (D, H, W), got {shape}")
-        if shape[1] * shape[2] > 2**31 - 1:
-            raise ValueError(f"a plane of {shape[1]} x {shape[2]} voxels exceeds 2^31 - 1")
-        device = torch.device("cuda:0" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError(f"ComponentsStream (MI355X) has no CPU path: it needs a HIP device, got {device}")
-        if id_capacity is None:
-            id_capacity = min(DEFAULT_ID_CAPACITY, shape[0] * shape[1] * shape[2])
-        id_capacity = int(id_capacity)
-        if not 1 <= id_capacity <= 2**31 - 2:
-            raise ValueError(f"id_capacity must be 1 .. 2^31 - 2, got {id_capacity}")
-        self.shape, self.device, self.foreground, self.id_capacity = shape, device, bool(foreground), id_capacity
-        self.finished = False
-        plane = shape[1] * shape[2]
-        with torch.cuda.device(device):
-            self.id_parent = torch.empty(id_capacity + 1, dtype=torch.int32, device=device)
-            self.id_count = torch.empty(id_capacity + 1, dtype=torch.int64, device=device)
-            self.table = torch.empty(id_capacity + 1, dtype=torch.int32, device=device)
-            self.state = torch.zeros(4, dtype=torch.int32, device=device)
-            self.seam_ids = torch.empty(plane, dtype=torch.int32, device=device)
-            self.seam_bits = torch.empty(plane, dtype=torch.uint8, device=device)
-        self.workspace = None
-        d = self.desc = _native.ComponentsStreamDesc()
-        d.dims[:] = shape
-        d.channels = 1 if foreground else 3
-        d.threshold = float(np.float32(threshold))
-        d.capacity = id_capacity
-        d.min_size = int(min_segment_size)
-        d.next_z = 0
-        d.id_parent_dev, d.id_count_dev = self.id_parent.data_ptr(), self.id_count.data_ptr()
-        d.table_dev, d.state_dev = self.table.data_ptr(), self.state.data_ptr()
-        d.seam_ids_dev, d.seam_bits_dev = self.seam_ids.data_ptr(), self.seam_bits.data_ptr()
-
-    @property
-    def next_z(self):
-        """Planes pushed so far."""
-        return int(self.desc.next_z)
-
-    def _scratch(self, need):
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self.workspace
-
-    def push(self, slab, z0=None, out=None):
-        """
-        Labels the next slab. Nothing is synchronised.
-
-        Parameters
-        ----------
-        slab : torch.Tensor
-            float32 or float16 on the stream's device: (3, d, H, W), or
-            (d, H, W) in foreground mode, planes [next_z, next_z + d).
-        z0 : int, optional
-            The slab's first plane, checked against next_z. Default: next_z.
-        out : torch.Tensor, optional
-            Contiguous int32 (d, H, W) device tensor to write into.
-
-        Returns
-        -------
-        torch.Tensor
-            int32 (d, H, W) provisional ids (0: certainly background).
-        """
-        if self.finished:
-            raise RuntimeError("ComponentsStream: push() after finish()")
-        if not isinstance(slab, torch.Tensor):
-            raise TypeError(f"push needs a torch tensor, got {type(slab).__name__}")
-        if slab.dtype not in _AFF_CODES:
-            raise TypeError(f"slab must be float32 or float16, got {slab.dtype}")
-        if slab.device != self.device:
-            raise RuntimeError(f"slab is on {slab.device}, the stream on {self.device}")
-        want_dims = 3 if self.foreground else 4
-        if slab.dim() != want_dims or (not self.foreground and slab.shape[0] != 3):
-            raise ValueError("slab must be " + ("(d, H, W)" if self.foreground else "(3, d, H, W)") +
-                             f", got {tuple(slab.shape)}")
-        dims = tuple(int(v) for v in slab.shape[-3:])
-        if min(dims) < 1:
-            raise ValueError(f"empty slab {dims}")
-        slab = slab.contiguous()
-        lib = _native.lib()
-        need = lib.exaspim_components_stream_slab_workspace_bytes(_native.int3(dims))
-        if need == 0:
-            raise ValueError(_native.last_error())
-        with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty(dims, dtype=torch.int32, device=self.device)
-            elif (out.dtype != torch.int32 or tuple(out.shape) != dims or not out.is_contiguous()
-                  or out.device != self.device):
-                raise ValueError(f"out must be a contiguous int32 {dims} tensor on {self.device}")
-            ws = self._scratch(need)
-            _native.check(
-                lib.exaspim_components_stream_slab(
-                    ctypes.byref(self.desc), slab.data_ptr(), _AFF_CODES[slab.dtype], _native.int3(dims),
-                    self.next_z if z0 is None else int(z0), out.data_ptr(), ws.data_ptr(), need,
-                    _stream(self.device)),
-                "exaspim_components_stream_slab",
-            )
-        return out
-
-    def finish(self):
-        """
-        After the last slab: the table from provisional ids to final labels.
-        Reads the device's id count and overflow flag, once (this synchronises).
-
-        Returns
-        -------
-        table : torch.Tensor
-            int32 (id_capacity + 1,) on the device, table[0] = 0.
-        count : int
-            K, the number of kept components.
-
-        Raises
-        ------
-        RuntimeError
-            If the volume needed more provisional ids than id_capacity.
-        """
-        if self.finished:
-            raise RuntimeError("ComponentsStream: finish() called twice")
-        lib = _native.lib()
-        need = lib.exaspim_components_stream_finish_workspace_bytes(self.id_capacity)
-        with torch.cuda.device(self.device):
-            ws = self._scratch(need)
-            _native.check(
-                lib.exaspim_components_stream_finish(ctypes.byref(self.desc), ws.data_ptr(), need,
-                                                     _stream(self.device)),
-                "exaspim_components_stream_finish",
-            )
-            self.finished = True
-            used, overflow, count, _ = (int(v) for v in self.state.cpu())
-        if overflow:
-            raise RuntimeError(
-                f"ComponentsStream: the volume needs more than id_capacity={self.id_capacity} provisional ids; "
-                "the labels handed out are unusable. Label it again with a larger id_capacity (or deeper slabs)")
-        self.ids_used = used
-        return self.table, count
-
-    def apply(self, labels):
-        """Provisional ids -> final labels, in place, on a contiguous int32 device tensor of any shape."""
-        if not self.finished:
-            raise RuntimeError("ComponentsStream: apply() before finish()")
-        if (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.device != self.device
-                or not labels.is_contiguous()):
-            raise ValueError(f"apply needs a contiguous int32 tensor on {self.device}")
-        with torch.cuda.device(self.device):
-            _native.check(
-                _native.lib().exaspim_components_stream_apply(ctypes.byref(self.desc), labels.data_ptr(),
-                                                              labels.numel(), _stream(self.device)),
-                "exaspim_components_stream_apply",
-            )
-        return labels
-
-
-def _labels_fit_on_device(device, shape):
-    """The provisional labels of the whole volume stay in HBM if they take under a quarter of what is free."""
-    free, _ = torch.cuda.mem_get_info(device)
-    return int(np.prod(shape, dtype=np.int64)) * 4 <= free // 4
-
-
-def _relabel_host_array(cs, result, planes):
-    """The second pass when the provisional labels did not stay on the device: "planes" at a time they
-    go up, through the table and back into the same host array."""
-    for z0 in range(0, result.shape[0], planes):
-        part = torch.from_numpy(result[z0:z0 + planes]).to(cs.device)
-        result[z0:z0 + planes] = cs.apply(part).cpu().numpy()
-
-
-def affinities_to_components_streaming(source, threshold=0.5, min_segment_size=100, *, slab_depth,
-                                       write_block=None, id_capacity=None, device=None,
-                                       keep_labels_resident=None):
-    """
-    affinities_to_components for affinities that sit in a host array, a
-    memmap or a zarr-like array too large for the device (or for 2^31 - 1
-    voxels): z slabs of "slab_depth" planes are uploaded and labelled one
-    after the other (ComponentsStream), and the result is the whole volume's.
-
-    Parameters
-    ----------
-    source : array-like
-        float32 or float16, (3, D, H, W) affinities or a (D, H, W) foreground
-        map; only source[..., z0:z1, :, :] is ever read.
-    threshold, min_segment_size
-        As in affinities_to_components.
-    slab_depth : int
-        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
-    write_block : Callable[[int, int, numpy.ndarray], None], optional
-        The two-pass contract of chunked segmentation: receives every slab
-        once, in z order, as write_block(z0, z1, block) with block int32
-        (z1 - z0, H, W) of PROVISIONAL ids; the function then returns the
-        table that maps them to final labels instead of the labels.
-    id_capacity : int, optional
-        See ComponentsStream.
-    device : torch.device, optional
-        Default is cuda:0.
-    keep_labels_resident : bool, optional
-        Keep the provisional labels in HBM and relabel them there. Default:
-        True if they take less than a quarter of the free device memory;
-        otherwise they are relabelled slab by slab in a second device pass
-        over the downloaded array.
-
-    Returns
-    -------
-    numpy.ndarray
-        int32 (D, H, W) final labels; or, with "write_block", the tuple
-        (table, K): table int32 with final = table[provisional], K kept
-        components.
-    """
-    if not hasattr(source, "shape") or not hasattr(source, "dtype"):
-        source = np.asarray(source)
-    if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
-        raise TypeError(f"affinities must be float32 or float16, got {source.dtype}")
-    shape = tuple(int(v) for v in source.shape)
-    if len(shape) == 4 and shape[0] == 3:
-        foreground = False
-    elif len(shape) == 3:
-        foreground = True
-    else:
-        raise ValueError(f"affinities must be (3, D, H, W) or a (D, H, W) foreground map, got shape {shape}")
-    vshape = shape[-3:]
-    slab_depth = int(slab_depth)
-    if slab_depth < 1:
-        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("affinities_to_components_streaming (MI355X) has no CPU path and no HIP device is present")
-    cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=foreground, device=device,
-                          id_capacity=id_capacity)
-    device = cs.device
-    with torch.cuda.device(device):
-        if keep_labels_resident is None:
-            keep_labels_resident = _labels_fit_on_device(device, vshape)
-        resident = result = None
-        if write_block is None:
-            if keep_labels_resident:
-                resident = torch.empty(vshape, dtype=torch.int32, device=device)
-            else:
-                result = np.empty(vshape, dtype=np.int32)
-        for z0 in range(0, vshape[0], slab_depth):
-            z1 = min(z0 + slab_depth, vshape[0])
-            block = np.asarray(source[..., z0:z1, :, :])
-            labels = cs.push(_carrier(block).to(device), z0, None if resident is None else resident[z0:z1])
-            if write_block is not None:
-                write_block(z0, z1, labels.cpu().numpy())
-            elif result is not None:
-                result[z0:z1] = labels.cpu().numpy()
-        table, count = cs.finish()
-        if write_block is not None:
-            return table[: cs.ids_used + 1].cpu().numpy(), count
-        if resident is not None:
-            return cs.apply(resident).cpu().numpy()
-        _relabel_host_array(cs, result, slab_depth)
-    return result
-
-
-class RegionGraphStream:
-    """
-    region_graph for a volume that arrives in z slabs: every slab
-    is pushed with its labels -- provisional ids, e.g. ComponentsStream's --
-    and its affinities while both sit on the device; finish() maps the ids
-    through a table and returns the region graph of the final labels, bit for
-    bit what region_graph gives on table[labels] of the whole volume, which
-    may have more than 2^31 - 1 voxels and never has to be anywhere in one
-    piece.
-
-        cs = ComponentsStream((D, H, W), fragment_threshold, 0)
-        rgs = RegionGraphStream((D, H, W))
-        for slab in slabs_in_z_order:              # (3, d, H, W) device tensors
-            rgs.push(cs.push(slab), slab)
-        table, k = cs.finish()
-        edges, counts, sums, sizes = rgs.finish(table, k)
-
-    Two planes are carried from slab to slab, the last plane's ids and its
-    quantised z affinities: ComponentsStream's own seam plane has already
-    moved on to the current slab when the graph sees it.
-
-    Parameters
-    ----------
-    shape : Tuple[int]
-        (D, H, W) of the whole volume; H * W and every slab must stay within
-        2^31 - 1 voxels, D * H * W need not.
-    device : torch.device, optional
-        Default is cuda:0.
-    id_capacity : int, optional
-        The largest id that counts (1 .. 2^31 - 2): labels beyond it are
-        counted nowhere. 8 bytes of device memory per id. Default:
-        DEFAULT_ID_CAPACITY (2^24), or the number of voxels if that is less,
-        as in ComponentsStream.
-    edge_capacity : int, optional
-        Slots of the accumulator, a power of two; 24 bytes each, and as many
-        again while finish() runs. It holds pairs of PROVISIONAL ids: a slab
-        cannot know that two of its ids belong to one fragment, so shallow
-        slabs need more slots than the final graph has edges. Default is the
-        smaller of 2^22 and the next power of two >= 6 * D * H * W.
-    """
-
-    def __init__(self, shape, *, device=None, id_capacity=None, edge_capacity=None):
-        shape = tuple(int(v) for v in shape)
-        if len(shape) != 3 or min(shape) < 1:
-            raise ValueError(f"shape must be a non-empty (D, H, W), got {shape}")
-        if shape[1] * shape[2] > 2**31 - 1:
-            raise ValueError(f"a plane of {shape[1]} x {shape[2]} voxels exceeds 2^31 - 1")
-        device = torch.device("cuda:0" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError(f"RegionGraphStream (MI355X) has no CPU path: it needs a HIP device, got {device}")
-        voxels = shape[0] * shape[1] * shape[2]
-        if id_capacity is None:
-            id_capacity = min(DEFAULT_ID_CAPACITY, voxels)
-        id_capacity = int(id_capacity)
-        if not 1 <= id_capacity <= 2**31 - 2:
-            raise ValueError(f"id_capacity must be 1 .. 2^31 - 2, got {id_capacity}")
-        edge_capacity = _default_edge_capacity(voxels) if edge_capacity is None else int(edge_capacity)
-        if not 1 <= edge_capacity <= 1 << 30 or edge_capacity & (edge_capacity - 1):
-            raise ValueError(f"edge_capacity must be a power of two in 1 .. 2^30, got {edge_capacity}")
-        self.shape, self.device = shape, device
-        self.id_capacity, self.edge_capacity = id_capacity, edge_capacity
-        plane = shape[1] * shape[2]
-        with torch.cuda.device(device):
-            self.keys = torch.empty(edge_capacity, dtype=torch.int64, device=device)     # uint64 bits
-            self.counts = torch.empty(edge_capacity, dtype=torch.int64, device=device)
-            self.sums = torch.empty(edge_capacity, dtype=torch.int64, device=device)
-            self.sizes_by_id = torch.empty(id_capacity + 1, dtype=torch.int64, device=device)
-            self.seam_ids = torch.empty(plane, dtype=torch.int32, device=device)
-            self.seam_q = torch.empty(plane, dtype=torch.int32, device=device)            # uint32 bits
-            self.state = torch.zeros(2, dtype=torch.int32, device=device)
-        d = self.desc = _native.RegionGraphStreamDesc()
-        d.dims[:] = shape
-        d.id_capacity, d.edge_capacity, d.next_z = id_capacity, edge_capacity, 0
-        d.keys_dev, d.counts_dev, d.sums_dev = self.keys.data_ptr(), self.counts.data_ptr(), self.sums.data_ptr()
-        d.sizes_by_id_dev = self.sizes_by_id.data_ptr()
-        d.seam_ids_dev, d.seam_q_dev = self.seam_ids.data_ptr(), self.seam_q.data_ptr()
-        d.state_dev = self.state.data_ptr()
-
-    @property
-    def next_z(self):
-        """Planes pushed so far."""
-        return int(self.desc.next_z)
-
-    def push(self, labels, slab, z0=None):
-        """
-        Adds the next slab to the graph. Nothing is synchronised.
-
-        Parameters
-        ----------
-        labels : torch.Tensor
-            int32 (d, H, W) on the stream's device: the slab's ids.
-        slab : torch.Tensor
-            float32 or float16 (3, d, H, W) on the same device, planes
-            [next_z, next_z + d).
-        z0 : int, optional
-            The slab's first plane, checked against next_z. Default: next_z.
-        """
-        if not isinstance(labels, torch.Tensor) or not isinstance(slab, torch.Tensor):
-            raise TypeError(f"push needs torch tensors, got {type(labels).__name__} and {type(slab).__name__}")
-        if labels.dtype != torch.int32:
-            raise TypeError(f"labels must be int32, got {labels.dtype}")
-        if slab.dtype not in _AFF_CODES:
-            raise TypeError(f"slab must be float32 or float16, got {slab.dtype}")
-        if labels.device != self.device or slab.device != self.device:
-            raise RuntimeError(f"labels are on {labels.device} and the slab on {slab.device}, the stream on "
-                               f"{self.device}")
-        if slab.dim() != 4 or slab.shape[0] != 3:
-            raise ValueError(f"slab must be (3, d, H, W), got {tuple(slab.shape)}; "
-                             "a foreground map has no affinities to score")
-        dims = tuple(int(v) for v in slab.shape[-3:])
-        if tuple(labels.shape) != dims:
-            raise ValueError(f"labels must be (d, H, W) = {dims}, got {tuple(labels.shape)}")
-        if min(dims) < 1:
-            raise ValueError(f"empty slab {dims}")
-        labels, slab = labels.contiguous(), slab.contiguous()
-        with torch.cuda.device(self.device):
-            _native.check(
-                _native.lib().exaspim_region_graph_stream_slab(
-                    ctypes.byref(self.desc), labels.data_ptr(), slab.data_ptr(), _AFF_CODES[slab.dtype],
-                    _native.int3(dims), self.next_z if z0 is None else int(z0), _stream(self.device)),
-                "exaspim_region_graph_stream_slab",
-            )
-
-    def finish(self, table, n_labels):
-        """
-        After the last slab: the region graph of table[ids]. Reads the edge
-        count and the overflow flag, once (this synchronises). The accumulated
-        graph of ids is left as it is, so finish may be called again with
-        another table.
-
-        Parameters
-        ----------
-        table : torch.Tensor or numpy.ndarray
-            int32 (n,): id -> final label; ids at or beyond n are background.
-        n_labels : int
-            Final labels are 1 .. n_labels; what the table maps elsewhere
-            forms no edge and counts as background.
-
-        Returns
-        -------
-        edges, counts, sums, sizes
-            As region_graph returns them, sorted by (lo, hi).
-
-        Raises
-        ------
-        RuntimeError
-            If the slabs had more distinct pairs of adjacent ids than
-            edge_capacity.
-        """
-        if isinstance(table, np.ndarray):
-            if table.dtype != np.dtype(np.int32):
-                raise TypeError(f"table must be int32, got {table.dtype}")
-            table = torch.from_numpy(np.ascontiguousarray(table)).to(self.device)
-        if not isinstance(table, torch.Tensor):
-            raise TypeError(f"table must be a torch tensor or a numpy array, got {type(table).__name__}")
-        if table.dtype != torch.int32 or table.dim() != 1 or table.numel() < 1:
-            raise TypeError(f"table must be a non-empty 1-D int32 tensor, got {table.dtype} {tuple(table.shape)}")
-        if table.device != self.device:
-            raise RuntimeError(f"table is on {table.device}, the stream on {self.device}")
-        n_labels = int(n_labels)
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
-        if self.next_z != self.shape[0]:
-            raise RuntimeError(f"RegionGraphStream: finish() after {self.next_z} of {self.shape[0]} planes")
-        table = table.contiguous()
-        capacity = self.edge_capacity
-        lib = _native.lib()
-        need = lib.exaspim_region_graph_stream_finish_workspace_bytes(capacity)
-        if need == 0:
-            raise ValueError(_native.last_error())
-        with torch.cuda.device(self.device):
-            edges = torch.empty((capacity, 2), dtype=torch.int32, device=self.device)
-            counts = torch.empty(capacity, dtype=torch.int64, device=self.device)
-            sums = torch.empty(capacity, dtype=torch.int64, device=self.device)   # uint64 bits
-            sizes = torch.empty(n_labels + 1, dtype=torch.int64, device=self.device)
-            state = torch.empty(2, dtype=torch.int32, device=self.device)
-            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            _native.check(
-                lib.exaspim_region_graph_stream_finish(
-                    ctypes.byref(self.desc), table.data_ptr(), min(table.numel(), 2**31 - 1), n_labels,
-                    edges.data_ptr(), counts.data_ptr(), sums.data_ptr(), sizes.data_ptr(), state.data_ptr(),
-                    workspace.data_ptr(), need, _stream(self.device)),
-                "exaspim_region_graph_stream_finish",
-            )
-            n_edges, overflow = (int(v) for v in state.cpu())   # the one read of the device state
-            if overflow:
-                raise RuntimeError(
-                    f"RegionGraphStream: the slabs have more pairs of adjacent provisional ids than "
-                    f"edge_capacity={capacity}. Shallow slabs need more slots than the final graph has edges: "
-                    "two ids of one fragment look like two fragments until finish. Run it again with a larger "
-                    "edge_capacity (a power of two) or deeper slabs")
-            edges_h = edges[:n_edges].cpu().numpy()
-            counts_h = counts[:n_edges].cpu().numpy()
-            sums_h = sums[:n_edges].cpu().numpy().view(np.uint64)
-            sizes_h = sizes.cpu().numpy()
-        order = np.lexsort((edges_h[:, 1], edges_h[:, 0]))   # slot order depends on arrival: sort by (lo, hi)
-        return (np.ascontiguousarray(edges_h[order]), np.ascontiguousarray(counts_h[order]),
-                np.ascontiguousarray(sums_h[order]), sizes_h)
-
-
-class _ComposedTable:
-    """What _relabel_host_array needs of a ComponentsStream, for the table segment[fragment[id]]."""
-
-    def __init__(self, device, table):
-        self.device, self.table = device, table
-
-    def apply(self, labels):
-        with torch.cuda.device(self.device):
-            _native.check(
-                _native.lib().exaspim_apply_label_table(labels.data_ptr(), labels.numel(), self.table.data_ptr(),
-                                                        self.table.numel(), _stream(self.device)),
-                "exaspim_apply_label_table",
-            )
-        return labels
-
-
-def _agglomerate_streams(cs, rgs, thresholds, min_segment_size):
-    """
-    After the last slab of both streams: the fragments' graph, its merging on
-    the host, and the table provisional id -> segment, composed on the device
-    by sending the fragment table itself through the segment table.
-
-    Returns
-    -------
-    composed : _ComposedTable
-        composed.table is int32 (ids_used + 1,) on the device.
-    count : int
-        S, the number of kept segments.
-    """
-    fragment_table, n_fragments = cs.finish()
-    edges, counts, sums, sizes = rgs.finish(fragment_table[: cs.ids_used + 1], n_fragments)
-    segment_table, n_segments = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
-    device = cs.device
-    with torch.cuda.device(device):
-        composed = _ComposedTable(device, torch.from_numpy(segment_table).to(device))
-        table = composed.apply(fragment_table[: cs.ids_used + 1].clone())
-    return _ComposedTable(device, table), n_segments
-
-
-def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
-                                     fragment_threshold=0.5, slab_depth, write_block=None, id_capacity=None,
-                                     edge_capacity=None, device=None, keep_labels_resident=None):
-    """
-    agglomerate_affinities for affinities that sit in a host array, a memmap
-    or a zarr-like array too large for the device (or for 2^31 - 1 voxels):
-    z slabs of "slab_depth" planes are uploaded one after the other, each is
-    labelled (ComponentsStream with no size filter) and added to the region
-    graph of provisional ids (RegionGraphStream) while it sits on the device;
-    at the end the graph of fragments is merged on the host and the
-    provisional labels go through the composed table segment[fragment[id]]
-    once. The result equals agglomerate_affinities on the whole volume, bit
-    for bit.
-
-    Parameters
-    ----------
-    source : array-like
-        float32 or float16 (3, D, H, W); only source[..., z0:z1, :, :] is ever
-        read. A foreground map has no affinities to score.
-    agglomeration_thresholds, min_segment_size, fragment_threshold
-        As in agglomerate_affinities.
-    slab_depth : int
-        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
-    write_block : Callable[[int, int, numpy.ndarray], None], optional
-        Receives every slab once, in z order, as write_block(z0, z1, block)
-        with block int32 (z1 - z0, H, W) of PROVISIONAL ids; the function then
-        returns the table that maps them to segment labels.
-    id_capacity : int, optional
-        See ComponentsStream.
-    edge_capacity : int, optional
-        See RegionGraphStream.
-    device : torch.device, optional
-        Default is cuda:0.
-    keep_labels_resident : bool, optional
-        As in affinities_to_components_streaming.
-
-    Returns
-    -------
-    numpy.ndarray
-        int32 (D, H, W) segment labels; or, with "write_block", the tuple
-        (table, S): table int32 with segment = table[provisional], S kept
-        segments.
-    """
-    thresholds = list(agglomeration_thresholds)
-    _last_threshold(thresholds)
-    if not hasattr(source, "shape") or not hasattr(source, "dtype"):
-        source = np.asarray(source)
-    if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
-        raise TypeError(f"affinities must be float32 or float16, got {source.dtype}")
-    shape = tuple(int(v) for v in source.shape)
-    if len(shape) != 4 or shape[0] != 3:
-        raise ValueError(f"agglomerate_affinities_streaming needs (3, D, H, W) affinities, got {shape}; "
-                         "a foreground map has no affinities to score")
-    vshape = shape[-3:]
-    slab_depth = int(slab_depth)
-    if slab_depth < 1:
-        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("agglomerate_affinities_streaming (MI355X) has no CPU path and no HIP device is present")
-    cs = ComponentsStream(vshape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
-    device = cs.device
-    rgs = RegionGraphStream(vshape, device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
-    with torch.cuda.device(device):
-        if keep_labels_resident is None:
-            keep_labels_resident = _labels_fit_on_device(device, vshape)
-        resident = result = None
-        if write_block is None:
-            if keep_labels_resident:
-                resident = torch.empty(vshape, dtype=torch.int32, device=device)
-            else:
-                result = np.empty(vshape, dtype=np.int32)
-        for z0 in range(0, vshape[0], slab_depth):
-            z1 = min(z0 + slab_depth, vshape[0])
-            slab = _carrier(np.asarray(source[..., z0:z1, :, :])).to(device)
-            labels = cs.push(slab, z0, None if resident is None else resident[z0:z1])
-            rgs.push(labels, slab, z0)
-            if write_block is not None:
-                write_block(z0, z1, labels.cpu().numpy())
-            elif result is not None:
-                result[z0:z1] = labels.cpu().numpy()
-        composed, count = _agglomerate_streams(cs, rgs, thresholds, min_segment_size)
-        if write_block is not None:
-            return composed.table.cpu().numpy(), count
-        if resident is not None:
-            return composed.apply(resident).cpu().numpy()
-        _relabel_host_array(composed, result, slab_depth)
-    return result
 
 
 def _predict_batch(img, model, starts, patch_shape, trim=8, *, clip=None, mn=0.0, mx=1.0):
@@ -2174,10 +696,6 @@ def _start_ranges(dims, patch_shape, overlap):
         range(0, d - ps + (ps - ov), ps - ov)
         for d, ps, ov in zip(dims, patch_shape, overlap)
     ]
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 _WORKER_STREAMS = {}
@@ -2790,16 +1308,6 @@ def _device_voxel_dtype(np_dtype, whole=None, clip=None):
     return np_dtype, lambda block: block
 
 
-def _carrier(block):
-    """numpy block -> torch CPU tensor (uint16 rides as int16 bits)."""
-    block = np.ascontiguousarray(block)
-    if not block.flags.writeable:      # read-only memmap / zarr chunk: torch wants a writable buffer
-        block = block.copy()
-    if block.dtype == np.uint16:
-        block = block.view(np.int16)
-    return torch.from_numpy(block)
-
-
 class DeviceShardOps:
     """
     What run_slab_pipeline does on the device, as overridable steps (the CPU tests replace the
@@ -3181,6 +1689,38 @@ def _stream_whole_volume(volume, model, affinity_mode, batch_size, brightness_cl
                           progress="Predict" if verbose else None, **sink)
 
 
+def _label_predicted_slabs(labeller, finish_key, write_block, keep_labels_resident, timings, volume, model,
+                           affinity_mode, *window, **pipeline):
+    """
+    The streaming driver's feeder for affinities that are predicted here:
+    _stream_whole_volume with a "label" callback that pushes every finished,
+    divided slab into "labeller" (segmentation.py) where predict_streaming
+    would have started its download. "window": _stream_whole_volume's
+    arguments from batch_size to n_streams; "pipeline": its keyword arguments.
+    timings[finish_key] gets the wall seconds from the last slab to the final
+    labels.
+    """
+    sink = _LabelSink(labeller, write_block, keep_labels_resident)
+    _, height, width = labeller.shape
+
+    def label(z0, z1, out, slot):
+        aff = out if affinity_mode else out[0]
+        if sink.resident is not None:
+            labeller.push(aff, z0, sink.resident[z0:z1])
+            return None
+        labels = slot[: (z1 - z0) * height * width].view(z1 - z0, height, width)
+        return labeller.push(aff, z0, labels).view((1,) + tuple(labels.shape))
+
+    _stream_whole_volume(volume, model, affinity_mode, *window, np.float32, write_block, result=sink.result,
+                         label=label, timings=timings, **pipeline)
+    t0 = time.perf_counter()
+    # the second pass, where there is one, goes through the device in pieces of one pinned staging slot
+    out = sink.finish(max(1, PINNED_SLOT_BYTES // (4 * height * width)))
+    if timings is not None:
+        timings[finish_key] = time.perf_counter() - t0
+    return out
+
+
 def predict_streaming(
     source,
     model,
@@ -3339,44 +1879,12 @@ def predict_components_streaming(
     """
     device = _hip_device(model)
     volume = _open_volume(source, shape, dtype)
-    vshape = volume[1]
-    cs = ComponentsStream(vshape, threshold, min_segment_size, foreground=not affinity_mode, device=device,
+    cs = ComponentsStream(volume[1], threshold, min_segment_size, foreground=not affinity_mode, device=device,
                           id_capacity=id_capacity)
-    keep = keep_labels_resident
-    if write_block is not None:
-        keep = False
-    elif keep is None:
-        keep = _labels_fit_on_device(device, vshape)
-    resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
-    result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
-    plane = vshape[1] * vshape[2]
-
-    def label(z0, z1, out, slot):
-        aff = out if affinity_mode else out[0]
-        if resident is not None:
-            cs.push(aff, z0, resident[z0:z1])
-            return None
-        labels = slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2])
-        return cs.push(aff, z0, labels).view((1,) + tuple(labels.shape))
-
-    _stream_whole_volume(volume, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles,
-                         patch_shape, overlap, trim, verbose, n_streams, np.float32, write_block, result=result,
-                         label=label, copy_threads=copy_threads, keep_input_resident=keep_input_resident,
-                         timings=timings)
-    t0 = time.perf_counter()
-    with torch.cuda.device(device):
-        table, count = cs.finish()
-        if write_block is not None:
-            out = table[: cs.ids_used + 1].cpu().numpy(), count
-        elif resident is not None:
-            out = cs.apply(resident).cpu().numpy()
-        else:
-            planes = max(1, PINNED_SLOT_BYTES // (4 * cs.shape[1] * cs.shape[2]))
-            _relabel_host_array(cs, result, planes)
-            out = result
-    if timings is not None:
-        timings["components_finish"] = time.perf_counter() - t0
-    return out
+    return _label_predicted_slabs(
+        _ComponentsLabeller(cs), "components_finish", write_block, keep_labels_resident, timings,
+        volume, model, affinity_mode, batch_size, brightness_clip, normalization_percentiles, patch_shape, overlap,
+        trim, verbose, n_streams, copy_threads=copy_threads, keep_input_resident=keep_input_resident)
 
 
 def predict_agglomerate_streaming(
@@ -3456,41 +1964,10 @@ def predict_agglomerate_streaming(
                          "a foreground map has no affinities to score")
     device = _hip_device(model)
     volume = _open_volume(source, shape, dtype)
-    vshape = volume[1]
-    cs = ComponentsStream(vshape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
-    rgs = RegionGraphStream(vshape, device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
-    keep = keep_labels_resident
-    if write_block is not None:
-        keep = False
-    elif keep is None:
-        keep = _labels_fit_on_device(device, vshape)
-    resident = torch.empty(vshape, dtype=torch.int32, device=device) if keep else None
-    result = None if keep or write_block is not None else np.empty(vshape, dtype=np.int32)
-    plane = vshape[1] * vshape[2]
-
-    def label(z0, z1, out, slot):
-        if resident is not None:
-            rgs.push(cs.push(out, z0, resident[z0:z1]), out, z0)
-            return None
-        labels = cs.push(out, z0, slot[: (z1 - z0) * plane].view(z1 - z0, vshape[1], vshape[2]))
-        rgs.push(labels, out, z0)
-        return labels.view((1,) + tuple(labels.shape))
-
-    _stream_whole_volume(volume, model, True, batch_size, brightness_clip, normalization_percentiles,
-                         patch_shape, overlap, trim, verbose, n_streams, np.float32, write_block, result=result,
-                         label=label, copy_threads=copy_threads, keep_input_resident=keep_input_resident,
-                         timings=timings)
-    t0 = time.perf_counter()
-    with torch.cuda.device(device):
-        composed, count = _agglomerate_streams(cs, rgs, thresholds, min_segment_size)
-        if write_block is not None:
-            out = composed.table.cpu().numpy(), count
-        elif resident is not None:
-            out = composed.apply(resident).cpu().numpy()
-        else:
-            planes = max(1, PINNED_SLOT_BYTES // (4 * vshape[1] * vshape[2]))
-            _relabel_host_array(composed, result, planes)
-            out = result
-    if timings is not None:
-        timings["agglomerate_finish"] = time.perf_counter() - t0
-    return out
+    cs = ComponentsStream(volume[1], fragment_threshold, 0, device=device, id_capacity=id_capacity)
+    rgs = RegionGraphStream(volume[1], device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
+    return _label_predicted_slabs(
+        _AgglomerationLabeller(cs, rgs, thresholds, min_segment_size), "agglomerate_finish", write_block,
+        keep_labels_resident, timings,
+        volume, model, True, batch_size, brightness_clip, normalization_percentiles, patch_shape, overlap,
+        trim, verbose, n_streams, copy_threads=copy_threads, keep_input_resident=keep_input_resident)

@@ -48,6 +48,8 @@ def main():
     import torch
 
     from aind_exaspim_neuron_segmentation_amd import _native, inference
+    # agglomerate_affinities resolves agglomerate in segmentation's globals: that is the name to rebind
+    from aind_exaspim_neuron_segmentation_amd import segmentation as seg_module
     from aind_exaspim_neuron_segmentation_amd.utils import synthetic
 
     dev = torch.device("cuda:0")
@@ -135,7 +137,7 @@ def main():
         host = []
 
         def whole():
-            real = inference.agglomerate
+            real = seg_module.agglomerate
 
             def clocked(*a, **kw):
                 t0 = time.perf_counter()
@@ -143,13 +145,13 @@ def main():
                 host.append((time.perf_counter() - t0) * 1e3)
                 return out
 
-            inference.agglomerate = clocked
+            seg_module.agglomerate = clocked
             try:
                 return inference.agglomerate_affinities(aff, thresholds, min_size,
                                                         fragment_threshold=fragment_threshold,
                                                         edge_capacity=capacity, return_device_tensor=True)
             finally:
-                inference.agglomerate = real
+                seg_module.agglomerate = real
 
         legs = {
             "components": lambda: inference._components_on_device(aff, fragment_threshold, 0),

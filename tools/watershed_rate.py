@@ -63,6 +63,8 @@ def main():
     import torch
 
     from aind_exaspim_neuron_segmentation_amd import _native, inference
+    # agglomerate_affinities resolves agglomerate in segmentation's globals: that is the name to rebind
+    from aind_exaspim_neuron_segmentation_amd import segmentation as seg_module
     from aind_exaspim_neuron_segmentation_amd.utils import synthetic
 
     dev = torch.device("cuda:0")
@@ -183,7 +185,7 @@ def main():
 
         def whole(name, capacity, floor=0):
             def call():
-                real = inference.agglomerate
+                real = seg_module.agglomerate
 
                 def clocked(*a, **kw):
                     t0 = time.perf_counter()
@@ -191,14 +193,14 @@ def main():
                     host.append((time.perf_counter() - t0) * 1e3)
                     return out
 
-                inference.agglomerate = clocked
+                seg_module.agglomerate = clocked
                 try:
                     return inference.agglomerate_affinities(
                         aff, thresholds, min_size, fragment_threshold=COMPONENTS_THRESHOLD, edge_capacity=capacity,
                         return_device_tensor=True, fragments=name, aff_threshold_low=LOW, aff_threshold_high=HIGH,
                         premerge_size=floor)
                 finally:
-                    inference.agglomerate = real
+                    seg_module.agglomerate = real
             return call
 
         if args.premerge_only:
