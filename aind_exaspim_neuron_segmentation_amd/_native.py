@@ -224,6 +224,10 @@ SIGNATURES = {
     "exaspim_watershed_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_watershed_fragments": (_i32, [_vp, _i32, _I32x3, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp,
                                            _vp, _vp, _sz, _vp]),
+    "exaspim_dbf_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_dbf": (_i32, [_vp, _I32x3, _i32, _vp, _vp, _sz, _vp]),
+    "exaspim_segment_table_workspace_bytes": (_sz, [_i32]),
+    "exaspim_segment_table": (_i32, [_vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

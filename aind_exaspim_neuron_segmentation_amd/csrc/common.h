@@ -399,5 +399,10 @@ int launch_absmax(int dtype, const void* src, size_t bytes, float* out, hipStrea
 int launch_head(int dtype, const void* src, const float* w, const float* bias,
                 float* out, int n, int d, int h, int wd, int c0p, int out_channels,
                 int apply_sigmoid, hipStream_t stream);
+// (dbf.hip) one pass of exaspim_dbf: axis 2 (x) writes f to out from the labels alone ("in" is not read),
+// axis 1 (y) and axis 0 (z) read the previous pass's field from "in", which must not be "out".
+// EXASPIM_E_INVALID for dims exaspim_dbf refuses; the pointers are the caller's to check.
+int launch_dbf_pass(int axis, const int32_t* labels, const int32_t* in, int32_t* out, const int32_t dims[3],
+                    int black_border, hipStream_t stream);
 
 }  // namespace exaspim

@@ -278,4 +278,11 @@ int probe_plan_conv(const int32_t channels[5], int32_t out_channels, int32_t dty
     return EXASPIM_OK;
 }
 
+// One pass of exaspim_dbf on its own (launch_dbf_pass), for tools/dbf_rate.py to time the passes apart.
+int probe_dbf_pass(int axis, const int32_t* labels, const int32_t* in, int32_t* out, const int32_t dims[3],
+                   int black_border, hipStream_t stream) {
+    EXA_CHECK_ARG(labels && out && dims && (axis == 2 || (in && in != out)), "probe_dbf_pass: NULL or aliased buffer");
+    return launch_dbf_pass(axis, labels, in, out, dims, black_border, stream);
+}
+
 }  // extern "C"

@@ -26,8 +26,9 @@ percentiles, the slab pipeline, predict_streaming, and the two drivers that
 label slabs as the pipeline finishes them (predict_components_streaming,
 predict_agglomerate_streaming). Everything that starts from finished
 affinities -- components, watershed fragments, the region graph, pre-merge,
-agglomeration, ComponentsStream, RegionGraphStream and the drivers for
-affinities on the host -- lives in segmentation.py; those names are imported
+agglomeration, ComponentsStream, RegionGraphStream, the drivers for
+affinities on the host, and the distance-to-boundary field and segment
+table of finished labels -- lives in segmentation.py; those names are imported
 below, so each is reachable as inference.NAME as before and is the same
 object. The plan switches below are read by this module only.
 
@@ -47,11 +48,12 @@ from aind_exaspim_neuron_segmentation_amd import _native
 from aind_exaspim_neuron_segmentation_amd._device import _carrier, _stream
 from aind_exaspim_neuron_segmentation_amd.machine_learning.unet3d import UNet3D
 from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (importable from here as before)
-    DEFAULT_EDGE_CAPACITY, DEFAULT_ID_CAPACITY, MAX_TOTAL_COUNT, ComponentsStream, RegionGraphStream,
+    DBF_INF, DEFAULT_EDGE_CAPACITY, DEFAULT_ID_CAPACITY, MAX_TOTAL_COUNT, ComponentsStream, RegionGraphStream,
     _AgglomerationLabeller, _ComponentsLabeller, _components_on_device, _default_edge_capacity, _LabelSink,
     _last_threshold, _premerge_on_device, _premerged_table, _region_graph_device, _watershed_on_device,
     affinities_to_components, affinities_to_components_streaming, agglomerate, agglomerate_affinities,
-    agglomerate_affinities_streaming, premerge_region_graph, region_graph, watershed_fragments,
+    agglomerate_affinities_streaming, distance_to_boundary, premerge_region_graph, region_graph, segment_table,
+    watershed_fragments,
 )
 from aind_exaspim_neuron_segmentation_amd.utils import img_util
 

@@ -8,6 +8,9 @@ with exactly defined parts.
 * the region graph of a labelled volume, the pre-merge of tiny fragments on
   the device and the mean-affinity agglomeration on the host (region_graph,
   premerge_region_graph, agglomerate, agglomerate_affinities; DESIGN 6e, 6h);
+* what the reference's skeletonize (257-291) starts from: the
+  distance-to-boundary field of all labels and the per-label table of sizes,
+  boxes and field maxima (distance_to_boundary, segment_table; DESIGN 6i);
 * the same for volumes that arrive in z slabs (ComponentsStream,
   RegionGraphStream) and the one streaming driver behind
   affinities_to_components_streaming and agglomerate_affinities_streaming
@@ -888,6 +891,204 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     if return_device_tensor:
         return labels
     return labels.cpu().numpy()
+
+
+# What distance_to_boundary gives a voxel that has no boundary at all (EXASPIM_DBF_INF)
+DBF_INF = 2**31 - 1
+
+
+def _checked_labels(labels, fn):
+    """
+    The front matter of distance_to_boundary and segment_table: labels as a
+    contiguous int32 (D, H, W) tensor on a HIP device and its dims. A numpy
+    array is checked before any device is asked for.
+    """
+
+    def check(a):
+        if a.ndim != 3:
+            raise ValueError(f"{fn}: labels must be (D, H, W), got {tuple(a.shape)}")
+        if min(a.shape) < 1:
+            raise ValueError(f"{fn}: empty volume {tuple(a.shape)}")
+
+    labels = _on_device(labels, fn, "labels", (np.int32,), check=check)
+    if labels.dtype != torch.int32:
+        raise TypeError(f"labels must be int32, got {labels.dtype}")
+    check(labels)
+    if labels.device.type != "cuda":
+        raise RuntimeError(f"{fn} (MI355X) has no CPU path: labels must be on a HIP device, got {labels.device}")
+    return labels.contiguous(), tuple(int(v) for v in labels.shape)
+
+
+def distance_to_boundary(labels, *, black_border=False, return_device_tensor=False):
+    """
+    The distance-to-boundary field of every label at once, on the device:
+    for each foreground voxel the squared distance to the nearest voxel of
+    another label.
+
+    What this is: the field TEASAR starts from -- the reference's
+    skeletonize (inference.py:257-291) runs kimimaro.skeletonize, which asks
+    the edt package for it -- with an exact definition in integers. A voxel
+    with labels <= 0 is background and gets 0. A voxel v with label L > 0
+    gets the minimum of |v - u|^2 over all in-volume voxels u with
+    labels[u] != L, background and every other label alike (two touching
+    segments bound each other), voxel centre to voxel centre at unit
+    spacing. With black_border the volume counts as surrounded by one layer
+    of background: index i of an axis of length n also has the candidates
+    (i + 1)^2 and (n - i)^2. A voxel with no candidate at all (one label
+    filling the volume, no black_border) gets DBF_INF. The values are
+    squared and nothing is rounded; the caller takes the root.
+
+    What this is not: compared with edt, which the tests do not depend on
+    (the oracle in tests/dbf_ref.py is brute force and a per-label scipy
+    EDT); anisotropic (the reference passes (1, 1, 1));
+    TEASAR's paths, its fill_holes or its fix_borders, which stay with the
+    host skeletoniser.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device (e.g. from
+        agglomerate_affinities(..., return_device_tensor=True)), or a numpy
+        array, which is uploaded to cuda:0. It is only read.
+    black_border : bool, optional
+        Treat the volume's faces as boundaries. Default is False.
+    return_device_tensor : bool, optional
+        Return the field as a device tensor instead of a numpy array.
+        Default is False.
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W), squared distances.
+
+    Raises
+    ------
+    TypeError
+        If labels is not int32.
+    ValueError
+        If labels is not 3-D, is empty, or (D+1)^2 + (H+1)^2 + (W+1)^2
+        reaches 2^31 - 1.
+    RuntimeError
+        If labels is a tensor on a CPU device, or there is no HIP device to
+        upload an array to.
+    """
+    labels, dims = _checked_labels(labels, "distance_to_boundary")
+    device = labels.device
+    lib = _native.lib()
+    need = lib.exaspim_dbf_workspace_bytes(_native.int3(dims))
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        dbf = torch.empty(dims, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_dbf(labels.data_ptr(), _native.int3(dims), int(bool(black_border)), dbf.data_ptr(),
+                            workspace.data_ptr(), need, _stream(device)),
+            "exaspim_dbf",
+        )
+        if return_device_tensor:
+            return dbf
+        return dbf.cpu().numpy()
+
+
+def segment_table(labels, dbf=None, *, n_labels=None, return_device_tensors=False):
+    """
+    Per-label facts of a labelled volume, on the device: voxel count,
+    bounding box, the largest value of a distance-to-boundary field and
+    where it lies.
+
+    What this is: what a skeletoniser crops and roots each segment with
+    (inference.py:257-291: kimimaro.skeletonize crops every label to its
+    bounding box, starts TEASAR at the field's maximum and compares that
+    maximum with soma_detection_threshold), as one pass over labels and
+    dbf. Every output has K + 1 rows, K = n_labels, and is a pure function
+    of the input.
+
+    What this is not: TEASAR. The paths, fill_holes, fix_borders and the
+    SWC export stay with the host skeletoniser, which downloads the field
+    and this table instead of recomputing an EDT of the whole volume.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W), as for distance_to_boundary.
+    dbf : torch.Tensor or numpy.ndarray, optional
+        int32, of the labels' shape, on the labels' device (an array is
+        uploaded to cuda:0): distance_to_boundary's result, or any other
+        field. Default is None: peak is 0 and peak_index the first voxel.
+    n_labels : int, optional
+        K. Default is max(labels.max(), 0), one read of the device. Labels
+        above K and negative labels are counted nowhere.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+
+    Returns
+    -------
+    sizes : numpy.ndarray or torch.Tensor
+        int64 (K + 1,): voxels per label; row 0 counts the voxels labelled
+        exactly 0, as region_graph does.
+    boxes : numpy.ndarray or torch.Tensor
+        int32 (K + 1, 6): (z0, y0, x0, z1, y1, x1), half-open; zeros for an
+        absent label and for row 0.
+    peak : numpy.ndarray or torch.Tensor
+        int32 (K + 1,): the largest dbf value of the label; 0 for an absent
+        label, for row 0 and without dbf.
+    peak_index : numpy.ndarray or torch.Tensor
+        int32 (K + 1,): the smallest C-order linear index at which the
+        label attains its peak (numpy.unravel_index gives z, y, x); -1 for
+        an absent label and for row 0.
+
+    Raises
+    ------
+    TypeError
+        If labels or dbf is not int32.
+    ValueError
+        If labels is not 3-D or is empty, dbf has another shape, n_labels
+        is negative, or the dims are ones distance_to_boundary refuses.
+    RuntimeError
+        If labels is a tensor on a CPU device, dbf is on another device, or
+        there is no HIP device to upload an array to.
+    """
+    if isinstance(dbf, np.ndarray):   # both arrays are checked before either is uploaded
+        if dbf.dtype != np.int32:
+            raise TypeError(f"dbf must be int32, got {dbf.dtype}")
+        if isinstance(labels, np.ndarray) and dbf.shape != labels.shape:
+            raise ValueError(f"segment_table: dbf must have the labels' shape {labels.shape}, got {dbf.shape}")
+    labels, dims = _checked_labels(labels, "segment_table")
+    device = labels.device
+    if dbf is not None:
+        dbf = _on_device(dbf, "segment_table", "dbf", (np.int32,))
+        if dbf.dtype != torch.int32:
+            raise TypeError(f"dbf must be int32, got {dbf.dtype}")
+        if tuple(dbf.shape) != dims:
+            raise ValueError(f"segment_table: dbf must have the labels' shape {dims}, got {tuple(dbf.shape)}")
+        if dbf.device != device:
+            raise RuntimeError(f"segment_table: dbf must be on the labels' device {device}, got {dbf.device}")
+        dbf = dbf.contiguous()
+    if n_labels is None:
+        n_labels = max(int(labels.max()), 0)   # the one read of the device
+    n_labels = int(n_labels)
+    if n_labels < 0:
+        raise ValueError(f"n_labels must not be negative, got {n_labels}")
+    lib = _native.lib()
+    need = lib.exaspim_segment_table_workspace_bytes(n_labels)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        sizes = torch.empty(n_labels + 1, dtype=torch.int64, device=device)
+        boxes = torch.empty((n_labels + 1, 6), dtype=torch.int32, device=device)
+        peak = torch.empty(n_labels + 1, dtype=torch.int32, device=device)
+        peak_index = torch.empty(n_labels + 1, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_segment_table(labels.data_ptr(), None if dbf is None else dbf.data_ptr(), _native.int3(dims),
+                                      n_labels, sizes.data_ptr(), boxes.data_ptr(), peak.data_ptr(),
+                                      peak_index.data_ptr(), workspace.data_ptr(), need, _stream(device)),
+            "exaspim_segment_table",
+        )
+        if return_device_tensors:
+            return sizes, boxes, peak, peak_index
+        return tuple(t.cpu().numpy() for t in (sizes, boxes, peak, peak_index))
 
 
 # Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes

@@ -56,7 +56,9 @@ extern "C" {
  *    watershed fragments for the agglomeration;
  *    later within 5: exaspim_region_graph_premerge (and its workspace query): tiny fragments merged on
  *    the device before the host agglomeration;
- *    later within 5: EXASPIM_OPT_CARRY_MAIN_ONLY (no new entry point) */
+ *    later within 5: EXASPIM_OPT_CARRY_MAIN_ONLY (no new entry point);
+ *    later within 5: exaspim_dbf, exaspim_segment_table (and their workspace queries, EXASPIM_DBF_INF):
+ *    the distance-to-boundary field and the per-label table a skeletoniser starts from */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -824,6 +826,74 @@ int exaspim_region_graph_premerge(const int32_t* edges_dev, const int64_t* count
                                   int32_t* edges_out_dev, int64_t* count_out_dev, uint64_t* sum_out_dev,
                                   int64_t* sizes_out_dev, int32_t* map_dev, int32_t* state_dev,
                                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- distance-to-boundary field and per-label table for the skeletoniser ------
+ *      (later within ABI 5). The reference's skeletonize (inference.py:257-291) hands the labels
+ *      to kimimaro's TEASAR, which begins with two data-parallel stages: the distance-to-boundary field
+ *      of every label at once, and per-label facts (bounding box, voxel count, the field's maximum, which
+ *      is also its soma test, and where it lies) with which each segment is cropped and rooted. These are
+ *      those two stages with an exact definition in integers; the serial remainder (Dijkstra on a
+ *      per-label crop, the paths, SWC export) stays on the host. Checked against the oracle in tests/, not
+ *      against a run of edt or kimimaro.
+ *
+ *      labels are int32 (dims), C order; a voxel with label <= 0 is background. EXASPIM_DBF_INF = 2^31 - 1.
+ *       1. dbf[v] = 0 for a background voxel.
+ *       2. For a voxel v with label L > 0, dbf[v] = the minimum of |v - u|^2 over all in-volume voxels u
+ *          with labels[u] != L (background and every other label alike: touching segments bound each
+ *          other), voxel centre to voxel centre, unit spacing. Squared, in integers, nothing rounded.
+ *       3. With black_border != 0 the volume is surrounded by one layer of background: a voxel at index i
+ *          of an axis of length n also has the candidates (i + 1)^2 and (n - i)^2 on every axis. With
+ *          black_border == 0 the faces are no boundary.
+ *       4. A voxel without any candidate (black_border == 0 and one label filling the volume) gets
+ *          EXASPIM_DBF_INF.
+ *      Volumes with (D+1)^2 + (H+1)^2 + (W+1)^2 >= 2^31 - 1 are refused, so every finite value is below
+ *      EXASPIM_DBF_INF and int32 never wraps. */
+#define EXASPIM_DBF_INF 2147483647
+
+/* Scratch bytes of exaspim_dbf: one int32 field, 4 bytes per voxel rounded up to 16. 0 (and a message) if
+ * a dim is not positive, the volume has more than 2^31 - 1 voxels or the diagonal bound above fails. */
+size_t exaspim_dbf_workspace_bytes(const int32_t dims[3]);
+
+/* dbf_dev (int32, dims) = the field defined above (inference.py:257-291: the first stage of
+ * kimimaro.skeletonize). A pure function of the input; labels_dev is only read. Three launches on "stream"
+ * (along x by run ends from two scans, then along y and along z by a window that grows while k^2 is below
+ * the best value so far; the middle field lives in the workspace), no atomics, no inter-workgroup waiting,
+ * nothing allocated, nothing synchronised. The cost of the y and z passes is the window depth per voxel,
+ * about the square root of the result; a run whose field is still EXASPIM_DBF_INF is walked to its end.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1
+ * voxels, the diagonal bound, or a misaligned buffer (workspace_dev 16 bytes, labels_dev and dbf_dev 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than exaspim_dbf_workspace_bytes(dims): all before
+ * anything is launched. */
+int exaspim_dbf(const int32_t* labels_dev, const int32_t dims[3], int32_t black_border,
+                int32_t* dbf_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Scratch bytes of exaspim_segment_table: 8 bytes per row of the table, n_labels + 1 rows, rounded up to
+ * 16. 0 (and a message) if n_labels is negative. */
+size_t exaspim_segment_table_workspace_bytes(int32_t n_labels);
+
+/* Per-label facts of a labelled volume (inference.py:257-291: what kimimaro.skeletonize crops and roots
+ * each segment with), K = n_labels, every output with K + 1 rows:
+ *   sizes_dev (int64)       voxels per label; row 0 counts the voxels labelled exactly 0, as
+ *                           exaspim_region_graph does. Negative labels and labels above K are counted
+ *                           nowhere and never become an address.
+ *   boxes_dev (int32, x 6)  (z0, y0, x0, z1, y1, x1), half-open; all 0 for an absent label and for row 0.
+ *   peak_dev (int32)        the largest dbf value of the label; 0 for an absent label and row 0, and
+ *                           everywhere when dbf_dev is NULL.
+ *   peak_index_dev (int32)  the smallest C-order linear index at which the label attains its peak; -1
+ *                           for an absent label and row 0. With dbf_dev NULL: the label's first voxel in
+ *                           raster order.
+ * dbf_dev (int32, dims) may be NULL; it is only read, and so is labels_dev. A pure function of the input:
+ * sizes by 64-bit atomic adds, boxes by int32 atomic minima and maxima, the peak by a 64-bit atomic
+ * maximum of (dbf, 2^32 - 1 - index), runs of equal labels reduced inside a wave first. Three launches on
+ * "stream", no inter-workgroup waiting, nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer other than dbf_dev, dims that exaspim_dbf refuses, a negative
+ * n_labels or a misaligned buffer (workspace_dev 16 bytes, sizes_dev 8, the int32 arrays 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than exaspim_segment_table_workspace_bytes(n_labels):
+ * all before anything is launched. */
+int exaspim_segment_table(const int32_t* labels_dev, const int32_t* dbf_dev /* may be NULL */,
+                          const int32_t dims[3], int32_t n_labels,
+                          int64_t* sizes_dev, int32_t* boxes_dev, int32_t* peak_dev, int32_t* peak_index_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
