@@ -221,6 +221,9 @@ SIGNATURES = {
     "exaspim_region_graph_premerge": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, ctypes.c_float,
                                              ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _sz, _vp]),
+    "exaspim_region_graph_contract_dominant_workspace_bytes": (_sz, [_i32, ctypes.c_int64]),
+    "exaspim_region_graph_contract_dominant": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, ctypes.c_float,
+                                                      ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_watershed_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_watershed_fragments": (_i32, [_vp, _i32, _I32x3, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp,
                                            _vp, _vp, _sz, _vp]),

@@ -1,4 +1,4 @@
-// What region_graph.hip and premerge.hip share: the global open-addressing table of edges (a 64-bit
+// What region_graph.hip, premerge.hip and dominant.hip share: the global open-addressing table of edges (a 64-bit
 // key, count and sum per slot), its claim-and-add, the scan's predicate and sink that turn the occupied
 // slots into the edge list, and the workspace layout of one such table. Device code in a header: every
 // file that includes it gets its own copies (anonymous namespace), as with label_scan.h.

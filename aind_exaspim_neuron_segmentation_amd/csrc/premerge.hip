@@ -7,8 +7,9 @@
 // that waits for another one; the number of launches depends on n_labels alone, never on device data):
 //   memsets      best := none, the table's keys := empty, its counts and sums := 0, sizes' := 0, state := 0;
 //   choose       one thread per edge: a mergeable edge bids for the best[] word of each tiny end in a
-//                32-bit atomicCAS loop. The order of bids is total, so the winner is the maximum whatever
-//                order they arrive in;
+//                32-bit atomicCAS loop (graph_contract.h, shared with dominant.hip like the round's tail
+//                from the numbering on). The order of bids is total, so the winner is the maximum
+//                whatever order they arrive in;
 //   resolve      one thread per fragment: the other end of best[f], or f itself; of a mutual pair the
 //                smaller id keeps itself. Written to a second array, best[] is only read;
 //   double       parent'[f] = parent[parent[f]] between two buffers, ceil(log2 K) + 1 times: a chain of
@@ -22,64 +23,10 @@
 // An edge with an end outside 1 .. K or with equal ends is skipped by choose and by contract, so nothing
 // read from device memory becomes an address unchecked: best[] holds only edges that passed the check,
 // parent[] only their ends.
-#include "edge_table.h"
+#include "graph_contract.h"
 
 namespace exaspim {
 namespace {
-
-constexpr unsigned kNone = 0xFFFFFFFFu;   // best[f]: no bid yet (an edge index is at most 2^31 - 2)
-
-struct Graph {
-    const int* edges;                  // (E, 2)
-    const unsigned long long* count;   // int64 in the ABI, >= 1
-    const unsigned long long* sum;
-    const long long* sizes;            // K + 1
-    long long n_edges;
-    int n_labels;
-};
-
-// a * b in 128 bits
-struct Wide {
-    unsigned long long hi, lo;
-};
-__device__ __forceinline__ Wide wide_mul(unsigned long long a, unsigned long long b) {
-    return Wide{__umul64hi(a, b), a * b};
-}
-__device__ __forceinline__ int wide_cmp(const Wide& x, const Wide& y) {
-    if (x.hi != y.hi) return x.hi < y.hi ? -1 : 1;
-    return x.lo == y.lo ? 0 : x.lo < y.lo ? -1 : 1;
-}
-
-// the two ends of edge e, or false if they are no fragments of the graph
-__device__ __forceinline__ bool ends_of(const Graph& g, long long e, int* a, int* b) {
-    const int lo = g.edges[2 * e], hi = g.edges[2 * e + 1];
-    *a = lo;
-    *b = hi;
-    return lo >= 1 && hi >= 1 && lo <= g.n_labels && hi <= g.n_labels && lo != hi;
-}
-
-__device__ __forceinline__ int other_end(const Graph& g, unsigned e, int f) {
-    const int lo = g.edges[2 * (size_t)e], hi = g.edges[2 * (size_t)e + 1];
-    return lo == f ? hi : lo;
-}
-
-// Edge e (count c, sum s, other end w) bids for best[f]: larger mean first, then the smaller neighbour
-// id, then (only a list with repeated pairs gets here) the smaller edge index.
-__device__ void bid(const Graph& g, unsigned* best, int f, unsigned e, unsigned long long c,
-                    unsigned long long s, int w) {
-    unsigned cur = __hip_atomic_load(best + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (;;) {
-        if (cur != kNone) {
-            const int order = wide_cmp(wide_mul(s, g.count[cur]), wide_mul(g.sum[cur], c));
-            const int w2 = other_end(g, cur, f);
-            const bool better = order > 0 || (order == 0 && (w < w2 || (w == w2 && e < cur)));
-            if (!better) return;
-        }
-        const unsigned seen = atomicCAS(best + f, cur, e);
-        if (seen == cur) return;
-        cur = seen;   // somebody else got in: compare with that one
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void choose(Graph g, unsigned long long m, bool merge_all, long long floor,
                                                   unsigned* best) {
@@ -89,10 +36,7 @@ __global__ __launch_bounds__(kThreads) void choose(Graph g, unsigned long long m
         if (!ends_of(g, e, &a, &b)) continue;
         const unsigned long long c = g.count[e], s = g.sum[e];
         if (c == 0) continue;   // no contact at all: it has no mean
-        if (!merge_all) {
-            const Wide bound = wide_mul(m, c);
-            if (bound.hi != 0 || !(s > bound.lo)) continue;
-        }
+        if (!mergeable(c, s, m, merge_all)) continue;
         if (g.sizes[a] < floor) bid(g, best, a, (unsigned)e, c, s, b);
         if (g.sizes[b] < floor) bid(g, best, b, (unsigned)e, c, s, a);
     }
@@ -127,47 +71,6 @@ __global__ __launch_bounds__(kThreads) void set_min(const int* __restrict__ root
     for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < n; f += stride) {
         const int r = root[f];
         if (r != (int)f) atomicMin(min_id + r, (int)f);
-    }
-}
-
-// the scan's predicate and sink: the smallest member of every set, in id order, is numbered 1 .. K'
-struct SetHead {
-    const int* root;
-    const int* min_id;
-    int* map;
-    __device__ __forceinline__ bool operator()(size_t v) const { return v >= 1 && min_id[root[v]] == (int)v; }
-    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const {
-        if (flag) map[v] = rank + 1;
-    }
-};
-
-// map[] of the members that are not their set's smallest (those entries are only written here, the
-// smallest members' only read), and the sizes of the sets
-__global__ __launch_bounds__(kThreads) void finish_map(const int* __restrict__ root, const int* __restrict__ min_id,
-                                                      const long long* __restrict__ sizes, int* map,
-                                                      unsigned long long* sizes_out, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < n; f += stride) {
-        if (f == 0) {
-            map[0] = 0;
-            sizes_out[0] = (unsigned long long)sizes[0];
-            continue;
-        }
-        const int head = min_id[root[f]];
-        const int j = map[head];
-        if (head != (int)f) map[f] = j;
-        atomicAdd(sizes_out + j, (unsigned long long)sizes[f]);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void contract(Graph g, const int* __restrict__ map, Table to) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < g.n_edges; e += stride) {
-        int a, b;
-        if (!ends_of(g, e, &a, &b)) continue;
-        const int la = map[a], lb = map[b];
-        if (la == lb) continue;
-        global_add(to, edge_key(la, lb), g.count[e], g.sum[e]);
     }
 }
 
@@ -282,7 +185,7 @@ extern "C" int exaspim_region_graph_premerge(const int32_t* edges_dev, const int
     scan_block_sums<<<1, kSumThreads, 0, s>>>(label_blocks, l.n_scan_blocks, state_dev);
     scan_assign<<<label_scan_grid, kThreads, 0, s>>>(head, label_blocks, n);
     finish_map<<<label_grid, kThreads, 0, s>>>(parent, min_id, g.sizes, map_dev, sizes_out, n);
-    contract<<<edge_grid, kThreads, 0, s>>>(g, map_dev, to);
+    contract<<<edge_grid, kThreads, 0, s>>>(g, map_dev, to, false);
     const UsedSlot used{to.keys, to.counts, to.sums, edges_out_dev, reinterpret_cast<long long*>(count_out_dev),
                         reinterpret_cast<unsigned long long*>(sum_out_dev)};
     const unsigned table_scan_grid = (unsigned)l.table.n_scan_blocks;

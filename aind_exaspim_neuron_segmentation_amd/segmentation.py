@@ -5,9 +5,11 @@ with exactly defined parts.
 
 * connected components of thresholded affinities (affinities_to_components,
   DESIGN 6c) and watershed fragments (watershed_fragments, DESIGN 6g);
-* the region graph of a labelled volume, the pre-merge of tiny fragments on
-  the device and the mean-affinity agglomeration on the host (region_graph,
-  premerge_region_graph, agglomerate, agglomerate_affinities; DESIGN 6e, 6h);
+* the region graph of a labelled volume, the pre-merge of tiny fragments and
+  the exact contraction of dominant edges on the device, and the
+  mean-affinity agglomeration on the host (region_graph,
+  premerge_region_graph, contract_dominant_edges, agglomerate,
+  agglomerate_affinities; DESIGN 6e, 6h, 6j);
 * what the reference's skeletonize (257-291) starts from: the
   distance-to-boundary field of all labels and the per-label table of sizes,
   boxes and field maxima (distance_to_boundary, segment_table; DESIGN 6i);
@@ -569,6 +571,76 @@ def _check_total_count(counts, what):
                          "(parallel edges are pooled in 64 bits)")
 
 
+def _rounds_on_device(kernel, extra, fn, is_last, edges, counts, sums, sizes, n_edges, threshold, rounds, capacity,
+                      timings=None, total_checked=False):
+    """
+    The round loop behind _premerge_on_device and _contract_dominant_on_device:
+    the library function "kernel" (whose arguments between the threshold and
+    the capacity are "extra") on a graph that is on the device, each round on
+    the previous one's output, until is_last(K, K') says so or "rounds" have
+    run. One 12-byte read of the state per round; the maps are composed on
+    the device (exaspim_apply_label_table on the composed map). "fn" is the
+    public function in whose name errors are raised.
+    """
+    device = sizes.device
+    n_labels = int(sizes.numel()) - 1
+    lib = _native.lib()
+    stream = _stream(device)
+    history, events = [], []
+    with torch.cuda.device(device):
+        if not total_checked and n_edges:
+            _check_total_count(counts[:n_edges], fn)
+        composed = None
+        need = getattr(lib, kernel + "_workspace_bytes")(n_labels, capacity)
+        if need == 0:
+            raise ValueError(_native.last_error())
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        state = torch.empty(3, dtype=torch.int32, device=device)
+        spare = None   # the buffers the round after next may write: never the caller's
+        for _ in range(rounds):
+            k = int(sizes.numel()) - 1
+            if spare is None:
+                out = (torch.empty((capacity, 2), dtype=torch.int32, device=device),
+                       torch.empty(capacity, dtype=torch.int64, device=device),
+                       torch.empty(capacity, dtype=torch.int64, device=device))
+            else:
+                out, spare = spare, None
+            sizes_out = torch.empty(k + 1, dtype=torch.int64, device=device)
+            mapping = torch.empty(k + 1, dtype=torch.int32, device=device)
+            if timings is not None:
+                events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                events[-1][0].record()
+            _native.check(
+                getattr(lib, kernel)(edges.data_ptr(), counts.data_ptr(), sums.data_ptr(), sizes.data_ptr(), n_edges,
+                                     k, float(np.float32(threshold)), *extra, capacity, out[0].data_ptr(),
+                                     out[1].data_ptr(), out[2].data_ptr(), sizes_out.data_ptr(), mapping.data_ptr(),
+                                     state.data_ptr(), workspace.data_ptr(), need, stream),
+                kernel,
+            )
+            if composed is None:
+                composed = mapping
+            else:
+                _apply_table(composed, mapping)
+            if timings is not None:
+                events[-1][1].record()
+            k_new, e_new, overflow = (int(v) for v in state.cpu())   # the round's one read of the device
+            if overflow:
+                raise RuntimeError(
+                    f"{fn}: the contracted graph found no room in edge_capacity={capacity} "
+                    "slots; run it again with a larger edge_capacity (a power of two)")
+            if history:   # this round's input was an earlier round's output: free for the next one
+                spare = (edges, counts, sums)
+            edges, counts, sums = out
+            sizes, n_edges = sizes_out[:k_new + 1], e_new
+            history.append((k_new, e_new))
+            if is_last(k, k_new):
+                break
+        if timings is not None:
+            torch.cuda.synchronize(device)
+            timings.extend(a.elapsed_time(b) for a, b in events)
+    return edges, counts, sums, sizes, n_edges, composed, history
+
+
 def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity,
                         timings=None, total_checked=False):
     """
@@ -601,64 +673,73 @@ def _premerge_on_device(edges, counts, sums, sizes, n_edges, threshold, size_flo
     history : list of (int, int)
         (K', E') after every round that ran.
     """
-    device = sizes.device
-    n_labels = int(sizes.numel()) - 1
-    lib = _native.lib()
-    stream = _stream(device)
-    history, events = [], []
-    with torch.cuda.device(device):
-        if not total_checked and n_edges:
-            _check_total_count(counts[:n_edges], "premerge_region_graph")
-        composed = None
-        need = lib.exaspim_region_graph_premerge_workspace_bytes(n_labels, capacity)
-        if need == 0:
-            raise ValueError(_native.last_error())
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        state = torch.empty(3, dtype=torch.int32, device=device)
-        spare = None   # the buffers the round after next may write: never the caller's
-        for _ in range(rounds):
-            k = int(sizes.numel()) - 1
-            if spare is None:
-                out = (torch.empty((capacity, 2), dtype=torch.int32, device=device),
-                       torch.empty(capacity, dtype=torch.int64, device=device),
-                       torch.empty(capacity, dtype=torch.int64, device=device))
-            else:
-                out, spare = spare, None
-            sizes_out = torch.empty(k + 1, dtype=torch.int64, device=device)
-            mapping = torch.empty(k + 1, dtype=torch.int32, device=device)
-            if timings is not None:
-                events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                events[-1][0].record()
-            _native.check(
-                lib.exaspim_region_graph_premerge(edges.data_ptr(), counts.data_ptr(), sums.data_ptr(),
-                                                  sizes.data_ptr(), n_edges, k, float(np.float32(threshold)),
-                                                  size_floor, capacity, out[0].data_ptr(), out[1].data_ptr(),
-                                                  out[2].data_ptr(), sizes_out.data_ptr(), mapping.data_ptr(),
-                                                  state.data_ptr(), workspace.data_ptr(), need, stream),
-                "exaspim_region_graph_premerge",
-            )
-            if composed is None:
-                composed = mapping
-            else:
-                _apply_table(composed, mapping)
-            if timings is not None:
-                events[-1][1].record()
-            k_new, e_new, overflow = (int(v) for v in state.cpu())   # the round's one read of the device
-            if overflow:
-                raise RuntimeError(
-                    f"premerge_region_graph: the contracted graph found no room in edge_capacity={capacity} "
-                    "slots; run it again with a larger edge_capacity (a power of two)")
-            if history:   # this round's input was an earlier round's output: free for the next one
-                spare = (edges, counts, sums)
-            edges, counts, sums = out
-            sizes, n_edges = sizes_out[:k_new + 1], e_new
-            history.append((k_new, e_new))
-            if k_new == k:
-                break
-        if timings is not None:
-            torch.cuda.synchronize(device)
-            timings.extend(a.elapsed_time(b) for a, b in events)
-    return edges, counts, sums, sizes, n_edges, composed, history
+    return _rounds_on_device("exaspim_region_graph_premerge", (size_floor,), "premerge_region_graph",
+                             lambda k, k_new: k_new == k, edges, counts, sums, sizes, n_edges, threshold, rounds,
+                             capacity, timings, total_checked)
+
+
+def _dominant_round_is_last(k, k_new):
+    """The cost rule of the dominant rounds: one that removes fewer than max(1, K // 64) fragments is the last."""
+    return k - k_new < max(1, k // 64)
+
+
+def _contract_dominant_on_device(edges, counts, sums, sizes, n_edges, threshold, rounds, capacity,
+                                 timings=None, total_checked=False):
+    """
+    Rounds of exaspim_region_graph_contract_dominant on a graph that is on
+    the device, each on the previous one's output; arguments, the check of
+    the total count and the returned tuple are those of _premerge_on_device.
+
+    Stopping rule: at most "rounds" rounds, and a round that removes fewer
+    than max(1, K // 64) of its K fragments is the last. A chain of rising
+    means contracts one pair per round, and the host does such a tail faster
+    than launches do. The result of agglomerating the reduced graph does not
+    depend on where the rounds stop, so this is purely a cost rule.
+    """
+    return _rounds_on_device("exaspim_region_graph_contract_dominant", (), "contract_dominant_edges",
+                             _dominant_round_is_last, edges, counts, sums, sizes, n_edges, threshold, rounds,
+                             capacity, timings, total_checked)
+
+
+def _graph_arguments(fn, edges, counts, sums, sizes):
+    """
+    The front matter of premerge_region_graph and contract_dominant_edges:
+    the four arrays of a region graph, all numpy (their total count is
+    checked on the host, before any device is asked for, and they are
+    uploaded to cuda:0) or all tensors on one HIP device.
+
+    Returns
+    -------
+    edges, counts, sums, sizes : torch.Tensor
+    n_edges : int
+    device : torch.device
+    on_host : bool
+        The arrays came from the host, so their total count is checked.
+    """
+    given = (edges, counts, sums, sizes)
+    on_host = not any(isinstance(a, torch.Tensor) for a in given)
+    if all(isinstance(a, torch.Tensor) for a in given):
+        device = sizes.device
+        if device.type != "cuda" or any(a.device != device for a in given):
+            raise RuntimeError(f"{fn} (MI355X) has no CPU path: the graph must be on one HIP device")
+        edges, counts, sums, sizes = (a.contiguous() for a in given)
+    elif not on_host:
+        raise TypeError(f"{fn} needs the four arrays all on the host or all on the device")
+    else:
+        # the counts are on the host: their total is checked here, before any device is asked for
+        _check_total_count(np.asarray(counts, dtype=np.int64), fn)
+        device = _upload_device(fn)
+        edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).to(device)
+        counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(device)
+        sums = torch.from_numpy(np.ascontiguousarray(sums, dtype=np.uint64).view(np.int64)).to(device)
+        sizes = torch.from_numpy(np.ascontiguousarray(sizes, dtype=np.int64)).to(device)
+    if (edges.dtype != torch.int32 or counts.dtype != torch.int64 or sums.dtype != torch.int64
+            or sizes.dtype != torch.int64):
+        raise TypeError(f"{fn} needs int32 edges and 64-bit counts, sums and sizes")
+    n_edges = int(counts.numel())
+    if (sizes.dim() != 1 or sizes.numel() < 1 or edges.numel() != 2 * n_edges or sums.numel() != n_edges):
+        raise ValueError(f"{fn} needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
+    return edges, counts, sums, sizes, n_edges, device, on_host
 
 
 def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, rounds=4, edge_capacity=None):
@@ -715,32 +796,80 @@ def premerge_region_graph(edges, counts, sums, sizes, threshold, size_floor, *, 
     threshold = float(threshold)
     if threshold != threshold:
         raise ValueError("the threshold is NaN")
-    given = (edges, counts, sums, sizes)
-    on_host = not any(isinstance(a, torch.Tensor) for a in given)
-    if all(isinstance(a, torch.Tensor) for a in given):
-        device = sizes.device
-        if device.type != "cuda" or any(a.device != device for a in given):
-            raise RuntimeError("premerge_region_graph (MI355X) has no CPU path: the graph must be on one HIP device")
-        edges, counts, sums, sizes = (a.contiguous() for a in given)
-    elif not on_host:
-        raise TypeError("premerge_region_graph needs the four arrays all on the host or all on the device")
-    else:
-        # the counts are on the host: their total is checked here, before any device is asked for
-        _check_total_count(np.asarray(counts, dtype=np.int64), "premerge_region_graph")
-        device = _upload_device("premerge_region_graph")
-        edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)).to(device)
-        counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(device)
-        sums = torch.from_numpy(np.ascontiguousarray(sums, dtype=np.uint64).view(np.int64)).to(device)
-        sizes = torch.from_numpy(np.ascontiguousarray(sizes, dtype=np.int64)).to(device)
-    if (edges.dtype != torch.int32 or counts.dtype != torch.int64 or sums.dtype != torch.int64
-            or sizes.dtype != torch.int64):
-        raise TypeError("premerge_region_graph needs int32 edges and 64-bit counts, sums and sizes")
-    n_edges = int(counts.numel())
-    if (sizes.dim() != 1 or sizes.numel() < 1 or edges.numel() != 2 * n_edges or sums.numel() != n_edges):
-        raise ValueError("premerge_region_graph needs edges (E, 2), counts (E,), sums (E,) and sizes (K + 1,)")
+    edges, counts, sums, sizes, n_edges, device, on_host = _graph_arguments("premerge_region_graph", edges, counts,
+                                                                          sums, sizes)
     capacity = 1 << max(2 * n_edges - 1, 0).bit_length() if edge_capacity is None else int(edge_capacity)
     edges, counts, sums, sizes, n_edges, composed, history = _premerge_on_device(
         edges, counts, sums, sizes, n_edges, threshold, size_floor, rounds, capacity, total_checked=on_host)
+    with torch.cuda.device(device):
+        graph = _download_graph(edges, counts, sums, sizes, n_edges)
+        mapping = composed.cpu().numpy()
+    return graph + (mapping, [k for k, _ in history])
+
+
+def _checked_rounds(what, rounds, least):
+    """rounds as an int; ValueError for non-integers and values below "least", before any device call."""
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)):
+        raise ValueError(f"{what} must be an integer, got {rounds!r}")
+    if rounds < least:
+        raise ValueError(f"{what} must be at least {least}, got {rounds}")
+    return int(rounds)
+
+
+def contract_dominant_edges(edges, counts, sums, sizes, threshold, *, rounds=64, edge_capacity=None):
+    """
+    Contracts the dominant edges of a region graph on the device
+    (exaspim_region_graph_contract_dominant): agglomerate on the
+    reduced graph, composed through the mapping, gives exactly the table and
+    the segment count it gives on the input.
+
+    One round: an edge is mergeable iff sum > rint((1 - T) * 2^24) * count
+    (agglomerate's test at threshold T); it is dominant iff it is mergeable
+    and its mean is strictly larger than that of every other mergeable edge
+    at either of its ends (128-bit cross products); every dominant edge is
+    contracted: its two fragments become one set, numbered with the
+    singletons by smallest member id, sizes add up, and parallel edges add
+    their counts and sums. The greedy merging takes a dominant edge before
+    any other edge at its two ends, which is why nothing changes. Equal means
+    are not resolved here: such edges wait for agglomerate, whose tie-break
+    then applies unchanged. A round that removes fewer than max(1, K // 64)
+    of its K fragments is the last (the host does a thin tail faster than
+    launches do).
+
+    Parameters
+    ----------
+    edges, counts, sums, sizes : numpy.ndarray or torch.Tensor
+        What region_graph returns (no pair twice), or the same on a HIP
+        device (sums may be int64 holding uint64 bits); numpy arrays are
+        uploaded to cuda:0. The counts must add up to at most 2^39, as for
+        premerge_region_graph, and a larger total raises ValueError before
+        the first round.
+    threshold : float
+        T of the mergeable test: the last agglomeration threshold.
+    rounds : int, optional
+        The most rounds to run, at least 1. Default is 64.
+    edge_capacity : int, optional
+        Slots of the device hash table, a power of two. Default is the next
+        power of two >= 2 * E.
+
+    Returns
+    -------
+    edges, counts, sums, sizes : numpy.ndarray
+        The reduced graph in region_graph's format, sorted by (lo, hi).
+    mapping : numpy.ndarray
+        int32 (K + 1,): fragment id -> id in the reduced graph, map[0] = 0.
+    history : list of int
+        The number of fragments after every round that ran.
+    """
+    rounds = _checked_rounds("the number of rounds", rounds, 1)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("the threshold is NaN")
+    edges, counts, sums, sizes, n_edges, device, on_host = _graph_arguments("contract_dominant_edges", edges, counts,
+                                                                          sums, sizes)
+    capacity = 1 << max(2 * n_edges - 1, 0).bit_length() if edge_capacity is None else int(edge_capacity)
+    edges, counts, sums, sizes, n_edges, composed, history = _contract_dominant_on_device(
+        edges, counts, sums, sizes, n_edges, threshold, rounds, capacity, total_checked=on_host)
     with torch.cuda.device(device):
         graph = _download_graph(edges, counts, sums, sizes, n_edges)
         mapping = composed.cpu().numpy()
@@ -775,10 +904,48 @@ def _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_si
     return composed
 
 
+def _device_merged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity, premerge_size,
+                         premerge_rounds, device_merge_rounds, stats=None):
+    """
+    The fragment -> segment table of agglomerate_affinities with
+    device_merge_rounds > 0, as a device tensor: the region graph stays on
+    the device, the pre-merge rounds run there if premerge_size > 0, then up
+    to device_merge_rounds dominant rounds, only the reduced graph is
+    downloaded and agglomerated, and the final table is composed with the
+    rounds' maps on the device. "stats", a dict, receives the history and the
+    device milliseconds of both kinds of round, the host merging time and the
+    number of segments.
+    """
+    device = labels.device
+    edges, counts, sums, sizes, n_edges, capacity = _region_graph_device(labels, affinities, n_fragments,
+                                                                         edge_capacity)
+    timings = None if stats is None else ([], [])
+    composed, premerge_history = None, []
+    if premerge_size:
+        edges, counts, sums, sizes, n_edges, composed, premerge_history = _premerge_on_device(
+            edges, counts, sums, sizes, n_edges, thresholds[-1], premerge_size, premerge_rounds, capacity,
+            timings and timings[0])
+    # a contraction keeps the total count or lowers it: what the pre-merge has checked stays checked
+    edges, counts, sums, sizes, n_edges, dominant, history = _contract_dominant_on_device(
+        edges, counts, sums, sizes, n_edges, thresholds[-1], device_merge_rounds, capacity, timings and timings[1],
+        total_checked=composed is not None)
+    with torch.cuda.device(device):
+        composed = dominant if composed is None else _apply_table(composed, dominant)
+        graph = _download_graph(edges, counts, sums, sizes, n_edges)
+        t0 = time.perf_counter()
+        table, n_segments = agglomerate(*graph, thresholds, min_segment_size)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        _apply_table(composed, torch.from_numpy(table).to(device))
+    if stats is not None:
+        stats.update(fragments=n_fragments, premerge_history=premerge_history, premerge_round_ms=timings[0],
+                     history=history, round_ms=timings[1], host_ms=host_ms, segments=n_segments)
+    return composed
+
+
 def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
                            fragment_threshold=0.5, edge_capacity=None, return_device_tensor=False,
                            fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999,
-                           premerge_size=0, premerge_rounds=4):
+                           premerge_size=0, premerge_rounds=4, device_merge_rounds=0):
     """
     Segments affinities by mean-affinity agglomeration of fragments, in the
     reference's order of operations.
@@ -853,6 +1020,19 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     premerge_rounds : int, optional
         The most pre-merge rounds; they stop when one merges nothing.
         Default is 4.
+    device_merge_rounds : int, optional
+        0, the default, is the path described above. R > 0 changes where
+        the work is done and nothing else: the labels are those of
+        device_merge_rounds=0, bit for bit. Without premerge_size those are
+        the labels agglomerate_affinities has always defined; with it, they
+        are the labels of the same call without dominant rounds. The region
+        graph stays on the device, the pre-merge rounds run first if
+        premerge_size > 0, then up to R rounds contract every dominant edge
+        (contract_dominant_edges: a mergeable contact whose mean affinity is
+        strictly the largest at both its fragments, which the greedy merging
+        takes before any other contact of the two), and only the reduced
+        graph is downloaded and merged on the host. Negative values and
+        non-integers raise ValueError.
 
     Returns
     -------
@@ -862,6 +1042,7 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
     thresholds = list(agglomeration_thresholds)
     _last_threshold(thresholds)
     premerge_size, premerge_rounds = _checked_premerge(premerge_size, premerge_rounds)
+    device_merge_rounds = _checked_rounds("device_merge_rounds", device_merge_rounds, 0)
     if fragments not in ("components", "watershed"):
         raise ValueError(f'fragments must be "components" or "watershed", got {fragments!r}')
 
@@ -879,7 +1060,10 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
         labels, count = _components_on_device(affinities, fragment_threshold, 0)
     n_fragments = int(count.cpu()[0])
     device = labels.device
-    if premerge_size:
+    if device_merge_rounds:
+        table_dev = _device_merged_table(labels, affinities, n_fragments, thresholds, min_segment_size,
+                                         edge_capacity, premerge_size, premerge_rounds, device_merge_rounds)
+    elif premerge_size:
         table_dev = _premerged_table(labels, affinities, n_fragments, thresholds, min_segment_size, edge_capacity,
                                      premerge_size, premerge_rounds)
     else:

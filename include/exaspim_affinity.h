@@ -58,7 +58,9 @@ extern "C" {
  *    the device before the host agglomeration;
  *    later within 5: EXASPIM_OPT_CARRY_MAIN_ONLY (no new entry point);
  *    later within 5: exaspim_dbf, exaspim_segment_table (and their workspace queries, EXASPIM_DBF_INF):
- *    the distance-to-boundary field and the per-label table a skeletoniser starts from */
+ *    the distance-to-boundary field and the per-label table a skeletoniser starts from;
+ *    later within 5: exaspim_region_graph_contract_dominant (and its workspace query): the exact
+ *    contraction of dominant edges on the device before the host agglomeration */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -826,6 +828,72 @@ int exaspim_region_graph_premerge(const int32_t* edges_dev, const int64_t* count
                                   int32_t* edges_out_dev, int64_t* count_out_dev, uint64_t* sum_out_dev,
                                   int64_t* sizes_out_dev, int32_t* map_dev, int32_t* state_dev,
                                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- dominant-edge contraction of a region graph -------------------------------
+ *      (later within ABI 5). The reduction of the graph that changes NOTHING: one ROUND
+ *      contracts every edge that exaspim_agglomerate is bound to merge before any other edge at its two
+ *      ends, so the host merging starts from fewer fragments and ends with the same partition.
+ *
+ *      Input as for exaspim_region_graph_premerge: K = n_labels fragments, E = n_edges rows (lo, hi) with
+ *      1 <= lo < hi <= K without repeats in any order, count >= 1 and sum per row, sizes[0 .. K]; m and
+ *      merge_all from the threshold T exactly as in exaspim_agglomerate. Everything in integers, a pure
+ *      function of the input:
+ *       1. An edge is mergeable iff merge_all or sum > m * count.
+ *       2. Edge e DOMINATES AT fragment f iff e is mergeable, f is an end of e, and every other mergeable
+ *          row e' at f has sum_e * count_e' > sum_e' * count_e (128-bit products, strict): e's mean is
+ *          strictly the largest among the mergeable edges at f.
+ *       3. e is contracted iff it dominates at both its ends. The contracted edges form a matching (a
+ *          strict maximum at a shared end is unique): a set is a pair or a single fragment.
+ *       4. Sets are numbered 1 .. K' in order of their smallest member id; map, sizes' and the pooled
+ *          edges follow rules 6 - 9 of the pre-merge round above.
+ *       5. A row with an end outside 1 .. K, with equal ends or with count == 0 is ignored by every rule
+ *          and never becomes an address; in particular it neither dominates nor ties anything, and it
+ *          does not reach the output.
+ *      So: the total size is kept, E' <= E, and a round in which no edge dominates is the identity. Equal
+ *      means are never resolved here: they make an edge non-dominant, and it waits for the host, whose
+ *      tie-break then applies unchanged.
+ *
+ *      THEOREM. For a row list without repeated pairs, exaspim_agglomerate(T, min_size) on the input
+ *      graph and on the round's output, composed through map, give the same table and the same number
+ *      of segments. (Until the greedy merges a dominant edge e = (i, j), every other edge at i or j has
+ *      a mean strictly below e's -- pooling two edges gives a mean that is at most the larger of the
+ *      two --, so no edge at i or j goes before e; e is mergeable, so the greedy reaches it; up to then
+ *      the top edge of the graph is also the top edge of the graph with e contracted, no pooled edge at
+ *      the merged fragment ties it, and contractions commute because pooling is additive. Numbering sets by their
+ *      smallest member is monotone, so ties by current root id and the final numbering mean what they
+ *      meant. DESIGN 6j has the proof.) Rounds may be repeated on their own output and stopped anywhere.
+ *      NOT covered: a row list with repeated pairs. Two rows of the same pair are compared as two edges
+ *      here, while exaspim_agglomerate pools them first; pool such a list before the first round (the
+ *      round's own output never repeats a pair). */
+
+/* Scratch bytes of exaspim_region_graph_contract_dominant: a table of edge_capacity slots, 24 bytes each,
+ * plus 4 bytes per 2048 slots, plus 12 bytes per fragment and 4 bytes per 2048 fragments. 0 (and a
+ * message) if n_labels is negative or edge_capacity is not a power of two in 1 .. 2^30. */
+size_t exaspim_region_graph_contract_dominant_workspace_bytes(int32_t n_labels, int64_t edge_capacity);
+
+/* One round, on the device. Inputs, outputs, state_dev = (K', E', the overflow flag), the table, the
+ * PRECONDITION on counts and sums (1 <= count <= 2^34, sum <= count * 2^24, all counts together at most
+ * 2^39; not checked here) and the refusals are those of exaspim_region_graph_premerge; there is no size
+ * floor. Input and output buffers must not overlap.
+ *  - Passes, each a launch of its own on "stream": one thread per edge bids for the best edge of both its
+ *    ends (32-bit compare-and-swap, a total order), one thread per edge marks the ends whose best mean it
+ *    equals without being the best (plain stores of one value), one thread per fragment pairs the two
+ *    ends of an edge that is the best of both with neither marked, a prefix sum for the numbering, sizes'
+ *    by 64-bit atomic adds, the edges through map into the table, a prefix sum for the edge list. The
+ *    number of launches is a constant. No lock, no inter-workgroup waiting, nothing allocated, nothing
+ *    synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer (the three edge inputs may be NULL when n_edges is 0), a negative
+ * n_labels, n_edges outside 0 .. 2^31 - 1, a NaN threshold, an edge_capacity that is not a power of two
+ * in 1 .. 2^30 or a misaligned buffer (workspace_dev 16 bytes, the 64-bit arrays 8, the int32 arrays 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_region_graph_contract_dominant_workspace_bytes(n_labels, edge_capacity): all before anything is
+ * launched, and every output buffer is left alone. */
+int exaspim_region_graph_contract_dominant(const int32_t* edges_dev, const int64_t* count_dev,
+                                           const uint64_t* sum_dev, const int64_t* sizes_dev, int64_t n_edges,
+                                           int32_t n_labels, float threshold, int64_t edge_capacity,
+                                           int32_t* edges_out_dev, int64_t* count_out_dev, uint64_t* sum_out_dev,
+                                           int64_t* sizes_out_dev, int32_t* map_dev, int32_t* state_dev,
+                                           void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- distance-to-boundary field and per-label table for the skeletoniser ------
  *      (later within ABI 5). The reference's skeletonize (inference.py:257-291) hands the labels
