@@ -10,6 +10,10 @@ aff is (3, D, H, W) affinities (channel c at voxel v = edge v -- v + e_c, e = z,
 index along axis c is ignored; a voxel without an on edge is background) or a (D, H, W)
 foreground map (voxels >= threshold are on and 6-connected; a lone on voxel is a component of
 size 1). float16 input is widened exactly; the threshold is rounded to float32; NaN is off.
+
+affinities_of_foreground and drop_singletons derive an affinity-mode case and its labels from a foreground
+and scipy.ndimage.label, for volumes where components() itself is too slow; tests/test_components_cpu.py
+holds the two to components().
 """
 
 import numpy as np
@@ -74,6 +78,29 @@ def components(aff, threshold=0.5, min_size=100):
     new_id = np.zeros(size.size, np.int32)
     new_id[kept] = np.arange(1, kept.size + 1, dtype=np.int32)
     return new_id[comp].reshape(shape), int(kept.size)
+
+
+def affinities_of_foreground(on):
+    """(3, D, H, W) float32 affinities of a boolean foreground: aff[c][v] = on[v] & on[v + e_c], 0 on the
+    high faces. At any threshold in (0, 1] their components are the foreground's without its lone voxels."""
+    on = np.asarray(on, dtype=bool)
+    aff = np.zeros((3,) + on.shape, np.float32)
+    for axis in range(3):
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        aff[axis][tuple(lo)] = on[tuple(lo)] & on[tuple(hi)]
+    return aff
+
+
+def drop_singletons(labels, k):
+    """(labels, K) without the components of one voxel, the rest renumbered in the order they had: what
+    affinity mode makes of a foreground labelling in raster order (scipy.ndimage.label's)."""
+    sizes = np.bincount(labels.ravel(), minlength=k + 1)
+    keep = sizes > 1
+    keep[0] = False
+    new_id = np.where(keep, np.cumsum(keep), 0).astype(np.int32)
+    return new_id[labels], int(keep.sum())
 
 
 def same_partition(a, b):

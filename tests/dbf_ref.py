@@ -7,9 +7,11 @@ written from the definition in include/exaspim_affinity.h and not from the kerne
                 plus a margin; the squared distance comes from the integer index differences it returns,
                 never from its float distances;
   segment_table numpy: bincount, ndimage.find_objects and a stable argmax (and segment_table_sorted, the
-                same from one stable sort, for volumes with many thousands of labels).
+                same from one stable sort, for volumes with many thousands of labels);
+  tiled_rows    a tall volume of small blocks between zero rows and its dbf, composed from per_label of the
+                blocks: for volumes of 10^7 voxels, where a whole-volume EDT is too slow.
 
-tests/test_dbf_ref_cpu.py holds the first two to each other exactly.
+tests/test_dbf_ref_cpu.py holds the first two to each other exactly, and tiled_rows to per_label.
 """
 
 import numpy as np
@@ -125,6 +127,30 @@ def segment_table_sorted(labels, dbf=None, n_labels=None):
     at_peak = field == np.repeat(best, np.diff(np.r_[starts, order.size]))
     peak_index[present] = np.minimum.reduceat(np.where(at_peak, order, flat.size), starts)
     return sizes, boxes, peak, peak_index
+
+
+def tiled_rows(blocks, choice, black_border=False):
+    """
+    (labels, expected): a tall volume composed of small blocks, and its dbf composed of theirs; for volumes
+    too large for per_label. blocks are (D, bh, W) label arrays of one shape. The volume is one zero row
+    (a y index, over all z and x), then for every c in choice blocks[c] followed by one zero row:
+    H = 1 + (bh + 1) * len(choice). A block's field is per_label of the block between two zero rows.
+    Exact in both border modes: whatever lies beyond a zero row is farther away than that row's voxel at the
+    same (z, x), which is of another label, and a block's z and x faces are the volume's own.
+    tests/test_dbf_ref_cpu.py holds it to per_label of the whole volume.
+    """
+    blocks = np.stack([np.asarray(b, dtype=np.int32) for b in blocks])
+    between = ((0, 0), (1, 1), (0, 0))
+    fields = np.stack([per_label(np.pad(b, between), black_border)[:, 1:-1, :] for b in blocks])
+    choice = np.asarray(choice, dtype=np.int64)
+    _, d, bh, w = blocks.shape
+
+    def compose(parts):
+        rows = np.pad(parts, ((0, 0), (0, 0), (0, 1), (0, 0)))[choice]          # every block with its zero row
+        tall = np.moveaxis(rows, 0, 1).reshape(d, choice.size * (bh + 1), w)
+        return np.ascontiguousarray(np.pad(tall, ((0, 0), (1, 0), (0, 0))))
+
+    return compose(blocks), compose(fields)
 
 
 def stretched_labels(rng, shape, top=3, longest=40):

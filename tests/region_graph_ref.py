@@ -16,6 +16,9 @@ plain way:
                                        agglomerate stays the definition
     mean_graph(seed, k, n_edges), wide_graph(seed, k, n_edges, levels, count_max, total_max, hubs)
                                     -> random graphs (edges, counts, sums, sizes) for the tests
+    fragment_volume(kind, dtype), stride_volume(dtype)
+                                    -> volumes with their oracles, shared by the GPU tests: 10^4 fragments;
+                                       more than twice the tiles of one capped launch
 """
 
 import heapq
@@ -240,6 +243,40 @@ def fragment_volume(kind, dtype=np.float32, shape=(33, 65, 129)):
         for a in (aff, fragments) + graph:
             a.setflags(write=False)
         _VOLUMES[key] = (aff, fragments, k, graph)
+    return _VOLUMES[key]
+
+
+STRIDE_SHAPE = (8 * 73728, 9, 2)      # 73728 * 2 * 1 = 147 456 tiles of 8 x 8 x 32, 10.6M voxels
+STRIDE_FIRST_TRIP = 65536             # workgroups of one capped launch: the tiles of every workgroup's first trip
+
+
+def stride_volume(dtype=np.float32):
+    """
+    (labels, aff, K, graph, behind) of a long thin volume with more than twice the tiles one capped launch
+    of tile_graph covers, so every workgroup makes two or three trips; computed once per session and
+    read-only. The labels are slabs of random thickness 1 .. 23 along z, each with an id of its own and
+    split in y at row 5 (the second tile row in y holds one voxel row), with 2 % of the voxels set to 0:
+    some three edges per slab, the contact inside a slab with up to 46 voxel edges. behind is the oracle's
+    graph of the planes behind the first STRIDE_FIRST_TRIP tiles alone (the tiles run along z here, two to
+    a step of 8 planes).
+    """
+    key = ("stride", np.dtype(dtype).name)
+    if key not in _VOLUMES:
+        d, h, w = STRIDE_SHAPE
+        rng = np.random.default_rng(47)
+        thickness = rng.integers(1, 24, size=d)                  # more slabs than the volume can hold
+        slab = np.repeat(np.arange(1, d + 1, dtype=np.int32), thickness)[:d]
+        labels = np.repeat(slab * 2, h * w).reshape(STRIDE_SHAPE)
+        labels[:, :5] -= 1
+        labels[rng.random(STRIDE_SHAPE) < 0.02] = 0
+        k = int(labels.max())
+        aff = rng.random((3,) + STRIDE_SHAPE, dtype=np.float32).astype(dtype)
+        graph = region_graph(labels, aff, k)
+        z = STRIDE_FIRST_TRIP // (-(-h // 8) * -(-w // 32)) * 8
+        behind = region_graph(labels[z:], aff[:, z:], k)
+        for a in (labels, aff) + graph + behind:
+            a.setflags(write=False)
+        _VOLUMES[key] = (labels, aff, k, graph, behind)
     return _VOLUMES[key]
 
 

@@ -1,7 +1,8 @@
 """
 CPU-only checks around exaspim_components: the oracle the GPU tests hold the kernels to
 (tests/components_ref.py) against the reference's own label mask and affinities (golden g10,
-img_util.get_affinity_channels) and against scipy.ndimage.label, and the host side of
+img_util.get_affinity_channels) and against scipy.ndimage.label, the affinity-mode case derived from a
+foreground (affinities_of_foreground, drop_singletons), and the host side of
 inference.affinities_to_components.
 """
 
@@ -41,6 +42,24 @@ def test_oracle_recovers_the_reference_partition(g10):
     assert components_ref.components(aff, 0.5, 25)[1] == 6
     assert components_ref.components(aff, 0.5, 2803)[1] == 1
     assert components_ref.components(aff, 0.5, 2804)[1] == 0
+
+
+def test_affinities_of_a_foreground_give_its_components_without_lone_voxels():
+    """The identity behind tests/test_gpu_components.py's stride test of affinity mode, on a thin column."""
+    on = np.random.default_rng(23).random((20, 9, 9), dtype=np.float32) >= np.float32(0.5)
+    aff = components_ref.affinities_of_foreground(on)
+    assert aff.dtype == np.float32 and aff.shape == (3, 20, 9, 9)
+    assert not aff[0, -1].any() and not aff[1, :, -1].any() and not aff[2, :, :, -1].any()
+    assert aff[0, :-1].any() and aff[1, :, :-1].any() and aff[2, :, :, :-1].any()
+    labelled, n = ndimage.label(on)
+    want, k = components_ref.drop_singletons(labelled, n)
+    lone = int((np.bincount(labelled.ravel())[1:] == 1).sum())
+    assert lone >= 5 and k == n - lone and want.dtype == np.int32
+    for threshold in (0.5, 1.0):
+        got, got_k = components_ref.components(aff, threshold, 0)
+        assert got_k == k
+        np.testing.assert_array_equal(got, want)
+    assert not np.array_equal(want, labelled)      # ids move down, they do not just vanish
 
 
 def test_oracle_foreground_mode_is_ndimage_label():

@@ -2,7 +2,9 @@
 The two oracles of the distance-to-boundary field (tests/dbf_ref.py) agree exactly -- brute force over
 all voxel pairs and the per-label scipy EDT read through its integer indices -- on seeded volumes of
 side 1 .. 14 in both border modes, on the degenerate volumes by name, and on hand-built rows along each
-axis whose values are written out. The numpy segment table is held to a loop over the voxels.
+axis whose values are written out. The oracle composed of small blocks between zero rows (tiled_rows, for
+the volumes of 10^7 voxels of tests/test_gpu_dbf.py) is held to per_label of the whole composed volume.
+The numpy segment table is held to a loop over the voxels.
 """
 
 import numpy as np
@@ -118,6 +120,24 @@ def test_a_diagonal_neighbour_is_found():
     want = (np.indices(labels.shape) ** 2).sum(axis=0)
     for fn in (dbf_ref.brute_force, dbf_ref.per_label):
         np.testing.assert_array_equal(fn(labels, False), want)
+
+
+@pytest.mark.parametrize("border", MODES)
+def test_tiled_rows_equal_per_label_of_the_whole_volume(border):
+    rng = np.random.default_rng(53)
+    shape = (3, 11, 70)
+    blocks = [dbf_ref.stretched_labels(rng, shape, top=3, longest=90) for _ in range(4)]
+    blocks.append(np.full(shape, 2, dtype=np.int32))                 # one label throughout: bounded by the zero rows
+    choice = [4, 0, 1, 4, 4, 2, 3, 0, 2]                             # the solid block first, and twice in a row
+    labels, expected = dbf_ref.tiled_rows(blocks, choice, border)
+    assert labels.shape == expected.shape == (3, 1 + 12 * len(choice), 70)
+    assert labels.dtype == expected.dtype == np.int32 and labels.flags.c_contiguous
+    assert not labels[:, ::12].any() and not expected[:, ::12].any()
+    for i, c in enumerate(choice):
+        np.testing.assert_array_equal(labels[:, 1 + 12 * i:12 + 12 * i], blocks[c])
+    np.testing.assert_array_equal(expected, dbf_ref.per_label(labels, border))
+    solid = expected[:, 1:12]                                         # the first block is the solid one
+    assert solid.max() == (36 if not border else 4)                   # 6 rows to a zero row; 2 planes to a z face
 
 
 def test_segment_table_against_a_loop():

@@ -4,7 +4,8 @@ the CPU oracle (tests/components_ref.py): the reference's own affinities (golden
 affinities around bond percolation, a serpentine (the longest parent chain a volume admits),
 degenerate shapes, the edge convention, the threshold rule, float16 input, foreground mode,
 determinism and memory discipline, a long thin volume with more voxels and more tiles than one
-launch covers, and predict() feeding it on the device.
+launch covers (in foreground mode and, with affinities derived from the same foreground, in affinity
+mode), and predict() feeding it on the device.
 
 The kernels merge 8 x 8 x 32 tiles in LDS and then across tile faces; the random cases assert from
 the oracle that components cross tile faces. "One larger than a tile" is held as a voxel count
@@ -257,6 +258,21 @@ def test_determinism_guards_and_workspace_check(dev):
 
 
 # ---- 9b. more voxels and more tiles than one launch covers ----------------------------------------
+_STRIDE = []
+
+
+def stride_case():
+    """(on, labels, K): the foreground of the two stride tests and scipy.ndimage.label of it, computed once."""
+    from scipy import ndimage
+
+    if not _STRIDE:
+        on = np.random.default_rng(23).random((262152, 9, 9), dtype=np.float32) >= np.float32(0.5)
+        want, k = ndimage.label(on)
+        want.setflags(write=False)      # on goes to the device through torch.from_numpy, which wants it writable
+        _STRIDE.append((on, want, k))
+    return _STRIDE[0]
+
+
 def test_grid_stride_tails_against_ndimage_label(dev):
     """
     The per-voxel kernels launch at most 65536 workgroups of 256 threads and tile_pass at most 65536
@@ -267,17 +283,34 @@ def test_grid_stride_tails_against_ndimage_label(dev):
     gives components that run through many tiles along z. scipy.ndimage.label numbers in raster
     order as well, so the arrays are compared as they are.
     """
-    from scipy import ndimage
-
     from aind_exaspim_neuron_segmentation_amd import inference
 
-    shape = (262152, 9, 9)
+    on, want, k = stride_case()
+    shape = on.shape
     assert np.prod(shape) > 65536 * 256
     assert -(-shape[0] // TILE[0]) * -(-shape[1] // TILE[1]) * -(-shape[2] // TILE[2]) > 65536
-    on = np.random.default_rng(23).random(shape, dtype=np.float32) >= np.float32(0.5)
-    want, k = ndimage.label(on)
     assert k >= 2 and np.ptp(np.nonzero(want == np.bincount(want.ravel())[1:].argmax() + 1)[0]) >= 2 * TILE[0]
     got, count = inference._components_on_device(torch.from_numpy(on).to(dev).to(torch.float32), 0.5, 0)
+    assert int(count.cpu()[0]) == k
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+
+
+def test_grid_stride_tails_in_affinity_mode(dev):
+    """
+    The same volume through edge_mask_affinity (a width of 9 is its scalar form, one voxel per thread: more
+    voxels than one capped launch covers): affinities that are on exactly between two on voxels of the
+    foreground above. Their components are the foreground's without the lone voxels, which affinity mode
+    never keeps, numbered in the same raster order (tests/test_components_cpu.py holds that identity to the
+    oracle).
+    """
+    from aind_exaspim_neuron_segmentation_amd import inference
+
+    on, labelled, n = stride_case()
+    assert np.prod(on.shape) > 65536 * 256 and on.shape[2] % 4 != 0
+    want, k = components_ref.drop_singletons(labelled, n)
+    assert 2 <= k < n
+    aff = torch.from_numpy(components_ref.affinities_of_foreground(on)).to(dev)
+    got, count = inference._components_on_device(aff, 0.5, 0)
     assert int(count.cpu()[0]) == k
     np.testing.assert_array_equal(got.cpu().numpy(), want)
 

@@ -3,7 +3,7 @@ The slab-by-slab components on the GPU (-m gpu): inference.ComponentsStream (exa
 DESIGN 6d) against the whole-volume CPU oracle (tests/components_ref.py), labels and K bit for bit --
 random affinities near percolation under tile-aligned, ragged and one-plane slabs, a serpentine that
 crosses every seam, the singleton rule, numbering, float16, foreground mode, degenerate shapes, purity,
-the capacity guard, refused arguments, 64-bit sizes -- and predict_components_streaming /
+a slab with more tiles and voxels than one capped launch covers (against scipy.ndimage.label), the capacity guard, refused arguments, 64-bit sizes -- and predict_components_streaming /
 affinities_to_components_streaming end to end against predict_streaming's own affinities.
 """
 
@@ -19,6 +19,7 @@ from aind_exaspim_neuron_segmentation_amd.utils import synthetic
 
 pytestmark = pytest.mark.gpu
 
+TILE = (8, 8, 32)
 
 @pytest.fixture(scope="module")
 def dev():
@@ -255,6 +256,32 @@ def test_purity(dev):
     c = stream(dev, aff, 0.75, 100, [8, 16])
     assert a[0].tobytes() == b[0].tobytes() == c[0].tobytes() and a[1] == b[1] == c[1]
     assert a[2].tobytes() == c[2].tobytes() and a[3].tobytes() == c[3].tobytes()
+
+
+# ---- 5b. a slab of more tiles and voxels than one capped launch covers -----------------------------------------
+def test_grid_stride_over_a_slab_against_ndimage_label(dev):
+    """
+    Every kernel of a slab launches at most 65536 workgroups, of one tile or of 256 voxels, and strides
+    beyond that. (1000003, 9, 2) cut at 950001: the first slab has 237 502 tiles and 17.1M voxels, so
+    tile_pass, the foreground mask, face_merge, flatten, sizes and relabel all stride. Foreground mode at
+    p = 0.7 in a 9 x 2 column gives components that run through many tiles along z. Numbering follows the
+    first voxel of the whole component, as scipy.ndimage.label's does, so the arrays are compared as they are.
+    """
+    from scipy import ndimage
+
+    shape, cut = (1000003, 9, 2), 950001
+    per_step = -(-shape[1] // TILE[1]) * -(-shape[2] // TILE[2])      # tiles to a step of 8 planes
+    assert -(-cut // TILE[0]) * per_step > 65536 and cut * shape[1] * shape[2] > 65536 * 256
+    p = np.random.default_rng(29).random(shape, dtype=np.float32)
+    want, k = ndimage.label(p >= np.float32(0.3))
+    assert want.dtype == np.int32
+    assert ((want[cut - 1] == want[cut]) & (want[cut] > 0)).any()      # a component crosses the seam
+    behind = 65536 // per_step * TILE[0]      # tiles run along z here: tile 65536 starts at plane 262144
+    spans = [s[0] for s in ndimage.find_objects(want)]
+    assert any(s.start >= behind and s.stop <= cut and s.stop - s.start >= 2 * TILE[0] for s in spans)
+    got, got_k, _, _ = stream(dev, p, 0.3, 0, [cut])
+    assert got_k == k
+    np.testing.assert_array_equal(got, want)
 
 
 # ---- 6. capacity ---------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@ exaspim_dbf / exaspim_segment_table and inference.distance_to_boundary / segment
 (-m gpu), array_equal against the CPU oracle written from the definition (tests/dbf_ref.py;
 tests/test_dbf_ref_cpu.py holds its brute force and its scipy form to each other): rows around the
 chunk of the x scan with runs that cross every chunk boundary, thin volumes and deep windows for the
-y and z passes, the degenerate volumes, brute-force parity on seeded volumes, the pipeline from
+y and z passes, a tall volume with more rows and voxels than one capped launch covers, the degenerate volumes, brute-force parity on seeded volumes, the pipeline from
 agglomerate_affinities' device tensor, the table with absent and out-of-range ids and tied peaks,
 determinism, and every refusal. Every run through the C ABI writes into buffers pre-filled with 0xFF
 bytes whose guard bytes must not change. Nothing here provokes a fault: every refused call is rejected
@@ -136,6 +136,32 @@ def test_two_halves_without_background(dev):
         want = np.where(c < cut, cut - c, c - cut + 1) ** 2      # the distance to the interface only
         np.testing.assert_array_equal(run_dbf(dev, labels, False), want)
         np.testing.assert_array_equal(run_dbf(dev, labels, True), dbf_ref.per_label(labels, True))
+
+
+# ---- 2b. more rows and more voxels than one capped launch covers ----------------------------------------
+def test_grid_stride_over_rows_and_voxels(dev):
+    """
+    dbf_x launches at most 65536 workgroups of one row each and dbf_axis at most 65536 of 256 voxels; beyond
+    that they stride, dbf_x with its LDS table of chunk carries and its register carry rebuilt per row.
+    (4, 21961, 260) has 87 844 rows and 22.8M voxels: 1830 blocks of (4, 11, 260) between zero rows, drawn
+    from 64 with runs of up to 300 voxels (a row is two chunks) and one that is a single label, so the oracle
+    is composed of 65 small ones (dbf_ref.tiled_rows; no EDT of the whole volume, and no axis beyond 46 339).
+    """
+    rng = np.random.default_rng(59)
+    blocks = [dbf_ref.stretched_labels(rng, (4, 11, 260), top=3, longest=300) for _ in range(64)]
+    blocks.append(np.full((4, 11, 260), 3, dtype=np.int32))
+    assert all(((b[:, :, CHUNK - 1] == b[:, :, CHUNK]) & (b[:, :, CHUNK] > 0)).any() for b in blocks)   # across the chunk
+    choice = rng.integers(0, len(blocks), size=1830)
+    # plane z = 3 (rows 65883 on, voxels 17.1M on) lies wholly in the second trip of all three passes
+    assert len(set(choice.tolist())) == len(blocks) and 3 * 21961 > 65536 and 3 * 21961 * 260 > 65536 * 256
+    for border in MODES:
+        labels, want = dbf_ref.tiled_rows(blocks, choice, border)
+        d, h, w = labels.shape
+        assert (d, h, w) == (4, 21961, 260)
+        assert d * h > 65536 and d * h * w > 65536 * 256
+        got = run_dbf(dev, labels, border)
+        assert got.dtype == np.int32
+        np.testing.assert_array_equal(got, want, err_msg=f"black_border={border}")
 
 
 # ---- 3. degenerate volumes ----------------------------------------------------------------------------

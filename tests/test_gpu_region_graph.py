@@ -9,7 +9,9 @@ table directly. The shapes sit around the tile; "every voxel its own label" has 
 pairs per voxel, 6000 per tile, so the LDS table overflows; two slabs put all contention on one slot.
 Every direct call runs with guard words behind every buffer. The last section runs agglomerate_affinities
 and its streamed form at 16 115 watershed and 27 082 component fragments against the heap oracle
-(region_graph_ref.agglomerate_fast, itself held to the naive one in tests/test_agglomerate_scale_cpu.py).
+(region_graph_ref.agglomerate_fast, itself held to the naive one in tests/test_agglomerate_scale_cpu.py);
+section 14 a long thin volume of 147 456 tiles, more than twice what one capped launch covers, in both
+affinity types.
 """
 
 import numpy as np
@@ -25,6 +27,7 @@ pytestmark = pytest.mark.gpu
 
 ONE = 1 << 24
 GUARD = 64
+TILE = (8, 8, 32)
 
 
 @pytest.fixture(scope="module")
@@ -472,3 +475,22 @@ def test_component_fragments_at_twenty_seven_thousand_whole_and_in_slabs(dev):
                                                          slab_depth=slab_depth)
         assert got.dtype == np.int32
         np.testing.assert_array_equal(got, whole, err_msg=f"slab_depth {slab_depth}")
+
+
+# ---- 14. more tiles than one capped launch covers ---------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float16])
+def test_grid_stride_over_tiles(dev, dtype):
+    """
+    tile_graph launches at most 65536 workgroups of one tile each and strides beyond that; its LDS table is
+    cleared once and left empty by every flush. (589824, 9, 2) has 147 456 tiles: every workgroup makes two
+    or three trips, and what the planes behind the first 65536 tiles add has edges of its own with more than
+    one voxel edge each. The table has four slots per edge of the oracle: six per voxel, as capacity_for
+    sizes it, would be 2^26 slots.
+    """
+    labels, aff, k, want, behind = region_graph_ref.stride_volume(dtype)
+    shape = labels.shape
+    assert aff.dtype == dtype
+    assert -(-shape[0] // TILE[0]) * -(-shape[1] // TILE[1]) * -(-shape[2] // TILE[2]) >= 2 * 65536
+    assert len(behind[0]) >= 1000 and int(behind[1].max()) >= 2
+    capacity = 1 << (4 * len(want[0]) - 1).bit_length()
+    assert_same(device_graph(dev, labels, aff, k, capacity), want)      # asserts the guards and the overflow flag

@@ -7,7 +7,8 @@ tests/components_ref.py) after sorting the edge list by (lo, hi).
 The cases are those of tests/test_region_graph_stream_cpu.py, whose numpy model
 (tests/region_graph_stream_ref.py) follows the device step for step: seam edges, keys that vanish
 because both ids belong to one fragment, keys that pool. Every direct call runs with guard words behind
-every buffer, the two carried planes and the counts per id included.
+every buffer, the two carried planes and the counts per id included. Section 8b pushes a slab of more than
+twice the tiles one capped launch covers, as the first slab and as the second.
 """
 
 import ctypes
@@ -28,6 +29,7 @@ ONE = 1 << 24
 GUARD = 64
 P64, P32 = -7654321, -1234567      # what every buffer holds before a call
 RAGGED = [1, 2, 3, 9, 20, 22]
+TILE = (8, 8, 32)
 CODES = {torch.float32: _native.AFF_F32, torch.float16: _native.AFF_F16}
 
 
@@ -387,6 +389,27 @@ def test_sizes_are_summed_in_64_bits(dev):
     (edges, _, _, sizes), overflow = st.finish(np.array([0, 3, 3, 1, 1, 1], np.int32), 3)
     assert overflow == 0 and len(edges) == 0
     assert sizes.tolist() == [12, 0, 0, 3_000_000_000]
+
+
+# ---- 8b. a slab of more tiles than one capped launch covers -------------------------------------------
+@pytest.mark.parametrize("cuts", [[560003], [3]], ids=["first", "second"])
+def test_grid_stride_over_the_tiles_of_a_slab(dev, cuts):
+    """
+    The volume of test_gpu_region_graph.test_grid_stride_over_tiles (147 456 tiles) in two slabs, against the
+    whole volume's oracle. Cut at 560003 the slab that resets the table has 140 002 tiles and the seam lies
+    at a plane that is no multiple of 8; cut at 3 the striding slab is the second one, which adds to a table
+    it did not reset and to the voxel counts of the first.
+    """
+    labels, aff, k, want, _ = region_graph_ref.stride_volume()
+    shape = labels.shape
+    z0, z1 = max(bounds_of(cuts, shape[0]), key=lambda b: b[1] - b[0])
+    assert -(-(z1 - z0) // TILE[0]) * -(-shape[1] // TILE[1]) * -(-shape[2] // TILE[2]) >= 2 * 65536
+    assert (z0 == 0) == (cuts == [560003]) and cuts[0] % TILE[0] != 0
+    capacity = 1 << (4 * len(want[0]) - 1).bit_length()
+    st = Stream(dev, shape, k, capacity).push_all(labels, aff, cuts)
+    got, overflow = st.finish(np.arange(k + 1, dtype=np.int32), k)      # asserts the guards
+    assert overflow == 0
+    assert_same(got, want)
 
 
 # ---- 9. refusals, before anything is launched ----------------------------------------------------------

@@ -4,7 +4,8 @@ fragments="watershed") on the GPU (-m gpu), label for label against the CPU orac
 definition (tests/watershed_ref.py fragments(); tests/test_watershed_cpu.py holds that oracle to the
 serial watershed): shapes around the 8 x 8 x 32 tile of the mask kernel, the scalar path (a width that
 is no multiple of the vector, a base pointer off by one element), float16 input with tied values, the
-hand-built lines along all three axes, more tiles than one capped launch covers, memory discipline,
+hand-built lines along all three axes, more tiles than one capped launch covers (on the scalar and on the
+vector path), memory discipline,
 every refusal, the agglomeration end to end and predict() feeding it on the device.
 
 The mask kernel decides an edge from the steepest edges of both of its ends and computes those of the
@@ -189,15 +190,17 @@ def test_no_relation_between_low_and_high_is_required(dev):
 
 
 # ---- 5. more tiles than one capped launch covers ---------------------------------------------------------
-def test_grid_stride_over_tiles(dev):
+@pytest.mark.parametrize("shape", [(262152, 9, 9), (262160, 9, 4)], ids=["scalar", "vector"])
+def test_grid_stride_over_tiles(dev, shape):
     """
     The mask kernel launches at most 65536 workgroups of one tile each and strides beyond that;
     (262152, 9, 9), the shape tests/test_gpu_components.py uses for the same purpose, has 65538 tiles
     (and more voxels and scan blocks than one launch of the later passes covers). A width of 9 is the
-    scalar path; every tile has voxels beyond the volume in y and x.
+    scalar path; every tile has voxels beyond the volume in y and x. (262160, 9, 4) has 65540 tiles and a
+    width of one vector: the four-voxel path, whose second trip starts from the remapped tile of the first.
     """
-    shape = (262152, 9, 9)
     assert -(-shape[0] // TILE[0]) * -(-shape[1] // TILE[1]) * -(-shape[2] // TILE[2]) > 65536
+    assert (shape[2] % 4 == 0) == (shape == (262160, 9, 4))
     aff = np.random.default_rng(23).random((3,) + shape, dtype=np.float32)
     want, k = watershed_ref.fragments(aff, 0.3, 0.7, 0)
     assert k >= 2 and tiles_per_fragment(want[-64:]).max() >= 2
