@@ -22,6 +22,7 @@ OPT_PER_PATCH_ENCODER = 32
 OPT_SEPARATE_HEAD = 64   # the head as its own launch, nothing trimmed (bf16x3: same bits)
 OPT_ROW_SEPARATE_BORDERS = 256   # row mode: border faces as two thin launches + a column max-pool (same bits)
 OPT_CARRY_MAIN_ONLY = 512   # carried planes: the border launch and inc.0 write every plane (same bits)
+OPT_CARRY_NO_ROWS = 2048    # carried rows: the y fields are ignored, every row is computed (same bits)
 AFF_F32, AFF_F16 = 0, 1   # EXASPIM_AFF_*: element type of exaspim_components' input
 
 DTYPE_CODES = {
@@ -143,6 +144,23 @@ class UNetCarry1(ctypes.Structure):
     ]
 
 
+class UNetCarryY(ctypes.Structure):
+    """exaspim_unet_carry_y: the row range already present in the forward's own buffers, the (skip, pool) of the
+    y successor and of the diagonal successor with the rows to store there, and an event to record after inc.3."""
+
+    _fields_ = [
+        ("in_y", ctypes.c_int32 * 2),
+        ("out_skip_y", ctypes.c_void_p),
+        ("out_pool_y", ctypes.c_void_p),
+        ("out_skip_d", ctypes.c_void_p),
+        ("out_pool_d", ctypes.c_void_p),
+        ("out_y", ctypes.c_int32 * 2),
+        ("out_shift_y", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("encoder_event", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 _I32x5 = ctypes.c_int32 * 5
@@ -180,6 +198,10 @@ SIGNATURES = {
     "exaspim_unet_forward_prepared_carry1": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, ctypes.POINTER(UNetCarry),
                ctypes.POINTER(UNetCarry1), _vp, _sz, _vp]),
+    "exaspim_unet_carry_rows": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_int32 * 2]),
+    "exaspim_unet_forward_prepared_carry_y": (
+        _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32x3, ctypes.POINTER(UNetCarry),
+               ctypes.POINTER(UNetCarry1), ctypes.POINTER(UNetCarryY), _vp, _sz, _vp]),
     "exaspim_unet_forward_absmax": (
         _i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_unet_set_options": (_i32, [_vp, ctypes.c_uint32]),

@@ -291,6 +291,29 @@ struct ConvArgs {
 #endif
 };
 
+// Rows carried along y (row mode, conv3x3x3_zpipe_rowzy only: a second kernel argument of that symbol, so
+// ConvArgs and the argument block of every other kernel stay as they are). The launch computes
+// {planes outside [in_z0, in_z1)} x {rows outside [in_y0, in_y1)} and stores again only what it computes:
+//  * carry in: rows [in_y0, in_y1) of dst and their pooled rows of pool_dst are already there. Whole 8-row
+//    tiles, inside [2, h - 2); the tile walk leaves them out. Empty: off.
+//  * y carry out: rows [out_y0, out_y1) of every plane the launch stores go to y_dst / y_pool_dst as well, at
+//    row - out_shift_y (pooled: half of it), own frame and x neighbour like the z carry. Even bounds. Null: off.
+//  * diagonal carry out: planes [out_z0, out_z1) x rows [out_y0, out_y1) go to d_dst / d_pool_dst at
+//    plane - out_shift and row - out_shift_y: the block that neither the z nor the y successor computes,
+//    because each takes it over from this launch. Needs both the z and the y carry out. Null: off.
+struct ConvCarryY {
+    void* y_dst = nullptr;
+    void* y_pool_dst = nullptr;
+    void* d_dst = nullptr;
+    void* d_pool_dst = nullptr;
+    unsigned short in_y0 = 0, in_y1 = 0;
+    unsigned short out_y0 = 0, out_y1 = 0;
+    unsigned short out_shift_y = 0;
+};
+inline bool conv_has_carry_y(const ConvCarryY& y) {
+    return y.y_dst || y.y_pool_dst || y.d_dst || y.d_pool_dst || y.in_y0 || y.in_y1 || y.out_y0 || y.out_y1 || y.out_shift_y;
+}
+
 // Host-side record of the last convolution configuration this thread launched (the launcher's
 // __PRETTY_FUNCTION__, template arguments included) and its split-K factor: read by the tests'
 // layer probe (layer_probe.hip) to assert which dispatch path a case took.
@@ -298,6 +321,7 @@ struct ConvLaunchRecord {
     const char* config = "";
     int ksplit = 0;
     bool row = false;    // the launch ran conv3x3x3_zpipe_row (ConvArgs::row_stride) ...
+    bool carry_y = false;  // the launch ran conv3x3x3_zpipe_rowzy (a field of ConvCarryY set)
     bool carry = false;  // ... or conv3x3x3_zpipe_rowz / conv3x3x3_t14_carry / conv3x3x3_t14_borders_carry (a carry field of ConvArgs set)
 };
 ConvLaunchRecord& last_conv_launch();
@@ -350,7 +374,9 @@ constexpr int kRowStagesFused = kRowStageMain | kRowStageBorders;
 // itself clears the fields and writes every plane.
 constexpr int kRowStageBordersCarry = 16;
 constexpr int kRowStagesCarry = kRowStageMain | kRowStageBordersCarry;
-int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream);
+// y (optional): rows carried along y by the main launch (ConvCarryY, conv3x3x3_zpipe_rowzy). The border launches
+// are as without it: they compute every row of their columns, in the batch's own buffers and the z target.
+int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream, const ConvCarryY* y = nullptr);
 // Tile depth of the z-column kernel on a 32-cout slice of depth d without a fused head (launch_typed)
 int conv_zcol_tile_depth(int d);
 // Tile depth of the row-mode border launch at depth d (launch_row_borders)

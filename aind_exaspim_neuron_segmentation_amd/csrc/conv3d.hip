@@ -165,6 +165,30 @@ static int launch_zpipe(const ConvArgs& a, hipStream_t stream) {
     return EXASPIM_OK;
 }
 
+// The row launch with rows carried along y (ConvCarryY) on top of the z carry: launch_zpipe's grid for the
+// row-mode fused-pool instantiation, less the y tiles already present. (a: row arguments checked, so this is
+// the configuration launch_typed picks for the layer; y: checked by check_row_y_args.)
+template <typename Tag, int TZ>
+static int launch_zpipe_rowzy(const ConvArgs& a, const ConvCarryY& y, hipStream_t stream) {
+    constexpr int TY = 8, TX = 16, MINW = 2, D = 4;
+    TileGrid g;
+    if (int rc = tile_grid(a, TZ, TY, TX, a.n * a.row_stride + a.w - a.row_stride, 1, g)) return rc;
+    g.tz -= (a.in_z1 - a.in_z0) / TZ;
+    g.ty -= (y.in_y1 - y.in_y0) / TY;
+    g.blocks = (long long)g.tz * g.ty * g.tx;
+    const int slices = a.cout / 32;
+    long long wgs = resident_workgroups(MINW) / slices / 8 * 8;
+    if (wgs < 8) wgs = 8;
+    if (wgs > g.blocks) wgs = g.blocks;
+    dim3 grid((unsigned)wgs, slices);
+    last_conv_launch() = {__PRETTY_FUNCTION__, 1};
+    last_conv_launch().carry = true;
+    last_conv_launch().carry_y = true;
+    conv3x3x3_zpipe_rowzy<Tag, TZ, TY, TX, MINW, D><<<grid, TY * TX * 2, 0, stream>>>(a, y, g.tz, g.ty, g.tx);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
 // ---- host side: pick a tile configuration per layer -----------------------
 
 template <typename Tag, int TZ, int TY, int TX, int WAVES_M, int WAVES_N, int MT, int NT, int MINW, int PD = 3,
@@ -459,6 +483,33 @@ static int check_row_args(int dtype, const ConvArgs& a) {
     return EXASPIM_OK;
 }
 
+// Rows carried along y (ConvCarryY; a: row arguments checked). Carry in: whole 8-row tiles of the z-column
+// kernel inside [2, h - 2). Carry out: even bounds, source and target rows inside [2, h - 2); it stores again
+// only rows this launch computes, so a range that meets the rows carried in is refused. The diagonal target
+// needs both carries out.
+static int check_row_y_args(const ConvArgs& a, const ConvCarryY& y) {
+    constexpr int TY = 8;
+    EXA_CHECK_ARG(y.in_y0 <= y.in_y1 && y.in_y0 % TY == 0 && y.in_y1 % TY == 0 &&
+                      (y.in_y0 == y.in_y1 || (y.in_y0 >= 2 && y.in_y1 <= a.h - 2)),
+                  "conv: y carry in [%d, %d) must be whole %d-row tiles inside [2, %d)", (int)y.in_y0, (int)y.in_y1, TY,
+                  a.h - 2);
+    const bool out = y.y_dst || y.y_pool_dst || y.d_dst || y.d_pool_dst || y.out_y0 || y.out_y1 || y.out_shift_y;
+    EXA_CHECK_ARG(!out || (y.y_dst && y.y_pool_dst && y.out_y0 < y.out_y1 && y.out_y0 % 2 == 0 && y.out_y1 % 2 == 0 &&
+                           y.out_y0 >= 2 && y.out_y1 <= a.h - 2 && y.out_shift_y > 0 && y.out_shift_y % 2 == 0 &&
+                           (int)y.out_y0 - y.out_shift_y >= 2),
+                  "conv: y carry out [%d, %d) shifted by %d needs both targets, even bounds and source and target rows "
+                  "inside [2, %d)", (int)y.out_y0, (int)y.out_y1, (int)y.out_shift_y, a.h - 2);
+    EXA_CHECK_ARG(!out || y.in_y0 == y.in_y1 || y.out_y0 >= y.in_y1 || y.out_y1 <= y.in_y0,
+                  "conv: y carry out [%d, %d) overlaps the rows carried in, [%d, %d)", (int)y.out_y0, (int)y.out_y1,
+                  (int)y.in_y0, (int)y.in_y1);
+    EXA_CHECK_ARG(!y.d_dst == !y.d_pool_dst && (!y.d_dst || (out && a.carry_dst)),
+                  "conv: the diagonal carry out needs both targets and both the z and the y carry out");
+    EXA_CHECK_ARG(!y.d_dst || a.in_z0 == a.in_z1 || a.out_z0 >= a.in_z1 || a.out_z1 <= a.in_z0,
+                  "conv: carry out [%d, %d) overlaps the planes carried in, [%d, %d)", (int)a.out_z0, (int)a.out_z1,
+                  (int)a.in_z0, (int)a.in_z1);
+    return EXASPIM_OK;
+}
+
 // Carried planes without row mode (conv3x3x3_t14_carry; a: region resolved): planes whose inputs stay clear of
 // the zero padding along z, [2, d - 2), in whole tiles and whole plane pairs
 static int check_carry_args(int dtype, const ConvArgs& a, bool whole) {
@@ -633,18 +684,31 @@ static int launch_row_borders(const ConvArgs& a_in, hipStream_t stream) {
     return launch_row_borders_cfg<Tag, 4, 1>(a, stream);
 }
 
-int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream) {
+int launch_conv3x3x3_row(int dtype, const ConvArgs& a, int stages, hipStream_t stream, const ConvCarryY* y) {
     ConvArgs b = a;
     if (int rc = check_conv_args(dtype, a, kCheckEmpty)) return rc;   // (the main stage checks the rest)
     if (int rc = resolve_region(b)) return rc;
     if (int rc = check_row_args(dtype, b)) return rc;
+    const bool carry_y = y && conv_has_carry_y(*y);
+    if (carry_y) {
+        if (int rc = check_row_y_args(b, *y)) return rc;
+    }
     // (the planes carried in are not computed by the border launch either: nothing could store them a second time)
     EXA_CHECK_ARG(!(stages & kRowStageBordersCarry) || a.in_z0 == a.in_z1 || a.out_z0 == a.out_z1 ||
                       a.out_z0 >= a.in_z1 || a.out_z1 <= a.in_z0,
                   "conv: carry out [%d, %d) overlaps the planes carried in, [%d, %d)", (int)a.out_z0, (int)a.out_z1,
                   (int)a.in_z0, (int)a.in_z1);
     int r = EXASPIM_OK;
-    if (stages & kRowStageMain) r = launch_conv3x3x3(dtype, a, stream);
+    if ((stages & kRowStageMain) && carry_y) {
+        // (the main launch alone takes rows over: the border launches compute every row of their columns)
+        r = check_conv_args(dtype, a, kCheckAll);
+        const bool six = conv_zcol_tile_depth(a.d) == 6;
+        if (r == EXASPIM_OK)    // (check_row_args: a 16-bit type, whole patches, the fused pool, no head)
+            r = dtype == EXASPIM_DT_F16 ? (six ? launch_zpipe_rowzy<F16Tag, 6>(b, *y, stream) : launch_zpipe_rowzy<F16Tag, 4>(b, *y, stream))
+                                        : (six ? launch_zpipe_rowzy<BF16Tag, 6>(b, *y, stream) : launch_zpipe_rowzy<BF16Tag, 4>(b, *y, stream));
+    } else if (stages & kRowStageMain) {
+        r = launch_conv3x3x3(dtype, a, stream);
+    }
     // x in [0, 2) of patches 1 .. n-1 and [w - 2, w) of patches 0 .. n-2, then pooled x 0 and
     // w/2 - 1 of every patch
     b.pool_dst = nullptr;

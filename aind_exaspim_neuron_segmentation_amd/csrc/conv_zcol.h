@@ -27,8 +27,10 @@ namespace exaspim {
 //    layout a load instruction covers whole halo rows of contiguous bytes (the
 //    texture addresser works per 64-byte segment: 16 cycles per instruction
 //    instead of 64 with one voxel record per lane).
-template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD, bool POOL, bool ROW, bool CARRY = false>
-__device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int tiles_y, int tiles_x) {
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D, int HEAD, bool POOL, bool ROW, bool CARRY = false,
+          bool CARRYY = false>
+__device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int tiles_y, int tiles_x,
+                                           const ConvCarryY& cy = ConvCarryY{}) {
     constexpr int G = Tag::kG;
     constexpr int KC = 2 * G;
     constexpr int ES = 16 / G;
@@ -84,6 +86,8 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
     static_assert(!ROW || (POOL && ES == 2 && HEAD == 0), "row mode: 16-bit fused-pool epilogue");
     // carry (ConvArgs::in_z0 .. out_shift): tiles_z counts the z tiles that are left
     static_assert(!CARRY || ROW, "carry: row mode only");
+    // carry along y (ConvCarryY): tiles_y counts the y tiles that are left
+    static_assert(!CARRYY || (CARRY && TY % 2 == 0 && TX == 16), "y carry: on top of the z carry, a wave owns a row pair");
     const int total = tiles_z * tiles_y * tiles_x * (row ? 1 : a.n);
     int t_first, t_count, t_step;
     {
@@ -107,7 +111,13 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
         const int rx = (id % tiles_x) * TX; id /= tiles_x;
         const int nb = min(max(rx - ho, 0) / s, a.n - 1);
         t.x0 = __builtin_amdgcn_readfirstlane(rx - nb * s);
-        t.y0 = __builtin_amdgcn_readfirstlane((id % tiles_y) * TY); id /= tiles_y;
+        if constexpr (CARRYY) {
+            int ty = id % tiles_y; id /= tiles_y;
+            if (ty >= cy.in_y0 / TY) ty += (cy.in_y1 - cy.in_y0) / TY;   // (the y tiles already present)
+            t.y0 = __builtin_amdgcn_readfirstlane(ty * TY);
+        } else {
+            t.y0 = __builtin_amdgcn_readfirstlane((id % tiles_y) * TY); id /= tiles_y;
+        }
         int tz = id % tiles_z;
         if (CARRY && tz >= a.in_z0 / TZ) tz += (a.in_z1 - a.in_z0) / TZ;   // (the z tiles already present)
         t.z0 = __builtin_amdgcn_readfirstlane(tz * TZ);
@@ -495,6 +505,17 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                                  ((size_t)cur.nb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
             char* const cnplane = static_cast<char*>(a.carry_dst) - cshift + nbase +
                                   ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+            // y and diagonal carry out (ConvCarryY): a wave's row pair starts at an even row and the bounds are
+            // even, so "row in [out_y0, out_y1)" is wave-uniform and rides in the descriptors like the plane
+            bool y_on = false, d_on = false;
+            long long yshift = 0;
+            if constexpr (CARRYY) {
+                const int wy = cur.y0 + 2 * wave;
+                const bool yrow = wy >= cy.out_y0 && wy < cy.out_y1;
+                y_on = cy.y_dst != nullptr && yrow;
+                d_on = cy.d_dst != nullptr && yrow;
+                yshift = (long long)cy.out_shift_y * a.w * 32;
+            }
 #pragma unroll
             for (int zp = 0; zp < TZ / 2; ++zp) {
                 uint2 grp[2][4];
@@ -531,6 +552,30 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                             if (shared)
                                 buf_store16(rec, make_rsrc(cnplane, cz ? nbytes : (size_t)0), nlane ? ovoff : kOutOfRange,
                                             ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                        }
+                        if constexpr (CARRYY) if (y_on) {    // (every plane of the patch this tile stores)
+                            const bool yz = gz < a.org[0] + a.ext[0];
+                            const size_t poff = ((size_t)cur.nb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+                            buf_store16(rec, make_rsrc(static_cast<char*>(cy.y_dst) - yshift + poff, yz ? (size_t)2 * patch_vox * 32 : (size_t)0),
+                                        ovoff, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                            if (shared) {
+                                const size_t npoff = ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+                                buf_store16(rec, make_rsrc(static_cast<char*>(cy.y_dst) - yshift + nbase + npoff, yz ? nbytes : (size_t)0),
+                                            nlane ? ovoff : kOutOfRange,
+                                            ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                            }
+                        }
+                        if constexpr (CARRYY) if (d_on) {
+                            const bool dz = gz >= a.out_z0 && gz < a.out_z1;
+                            const size_t poff = ((size_t)cur.nb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+                            buf_store16(rec, make_rsrc(static_cast<char*>(cy.d_dst) - cshift - yshift + poff, dz ? (size_t)2 * patch_vox * 32 : (size_t)0),
+                                        ovoff, ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                            if (shared) {
+                                const size_t npoff = ((size_t)nnb * (a.cout / KC) + ntile0 * 2) * patch_vox * 32;
+                                buf_store16(rec, make_rsrc(static_cast<char*>(cy.d_dst) - cshift - yshift + nbase + npoff, dz ? nbytes : (size_t)0),
+                                            nlane ? ovoff : kOutOfRange,
+                                            ((unsigned)ck * (unsigned)patch_vox + (unsigned)gz * (unsigned)plane_vox) * 32u);
+                            }
                         }
                     }
                 }
@@ -584,6 +629,28 @@ __device__ __forceinline__ void zpipe_body(const ConvArgs& a, int tiles_z, int t
                             const int nqx = qx + nshift / 2;
                             buf_store16(m, make_rsrc(cnpplane, (size_t)((long long)CPT * pvox * 32 - nbase / 2)),
                                         nqx >= 1 && nqx < pw2 - 1 ? cpvoff : kOutOfRange, 0u);
+                        }
+                    }
+                    if constexpr (CARRYY) if (y_on || d_on) {   // (pooled row qy = wy / 2: the wave's own, in the range with wy)
+                        const long long ypshift = (long long)(cy.out_shift_y >> 1) * pw2 * 32;
+                        const size_t ppoff = ((size_t)cur.nb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
+                        const size_t nppoff = ((size_t)nnb * (a.cout / KC) + ntile0 * CPT) * pvox * 32;
+                        const int nqx = qx + nshift / 2;
+                        const bool nq = nqx >= 1 && nqx < pw2 - 1;
+                        if (y_on) {
+                            buf_store16(m, make_rsrc(static_cast<char*>(cy.y_pool_dst) - ypshift + ppoff, (size_t)CPT * pvox * 32), pvoff, 0u);
+                            if (shared)
+                                buf_store16(m, make_rsrc(static_cast<char*>(cy.y_pool_dst) - ypshift + nbase / 2 + nppoff,
+                                                         (size_t)((long long)CPT * pvox * 32 - nbase / 2)),
+                                            nq ? pvoff : kOutOfRange, 0u);
+                        }
+                        if (d_on) {
+                            const unsigned dpvoff = 2 * qz >= a.out_z0 && 2 * qz < a.out_z1 ? pvoff : kOutOfRange;
+                            buf_store16(m, make_rsrc(static_cast<char*>(cy.d_pool_dst) - cpshift - ypshift + ppoff, (size_t)CPT * pvox * 32), dpvoff, 0u);
+                            if (shared)
+                                buf_store16(m, make_rsrc(static_cast<char*>(cy.d_pool_dst) - cpshift - ypshift + nbase / 2 + nppoff,
+                                                         (size_t)((long long)CPT * pvox * 32 - nbase / 2)),
+                                            nq ? dpvoff : kOutOfRange, 0u);
                         }
                     }
                 }
@@ -717,6 +784,15 @@ template <typename Tag, int TZ, int TY, int TX, int MINW, int D>
 __global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe_rowz(
     ConvArgs a, int tiles_z, int tiles_y, int tiles_x) {
     zpipe_body<Tag, TZ, TY, TX, MINW, D, 0, true, true, true>(a, tiles_z, tiles_y, tiles_x);
+}
+
+// ... and rows carried along y on top (ConvCarryY, a second argument of this symbol only): y tiles an earlier
+// launch left in dst are not computed either, and the rows that feed the y and the diagonal successor are stored
+// to their tensors as well. conv3x3x3_zpipe_rowz keeps its code.
+template <typename Tag, int TZ, int TY, int TX, int MINW, int D>
+__global__ __launch_bounds__(TY* TX * 2, MINW) void conv3x3x3_zpipe_rowzy(
+    ConvArgs a, ConvCarryY cy, int tiles_z, int tiles_y, int tiles_x) {
+    zpipe_body<Tag, TZ, TY, TX, MINW, D, 0, true, true, true, true>(a, tiles_z, tiles_y, tiles_x, cy);
 }
 
 }  // namespace exaspim

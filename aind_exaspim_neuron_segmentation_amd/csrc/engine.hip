@@ -70,6 +70,16 @@ static void carry_span(int d, int shift_z, int32_t out[2]) {
     if (lo < hi && hi + shift_z <= 254) { out[0] = lo; out[1] = hi; }
 }
 
+// The same along y: rows of a forward's own frame that hold what a forward shift_y rows earlier computed at its
+// rows + shift_y: the whole 8-row tiles of the z-column kernel inside [2, h - shift_y - 2). Empty: {0, 0}.
+static void carry_row_span(int h, int shift_y, int32_t out[2]) {
+    out[0] = out[1] = 0;
+    if (shift_y <= 0 || shift_y % 2 != 0 || shift_y >= h) return;
+    constexpr int ty = 8;
+    const int lo = ty, hi = (h - shift_y - 2) / ty * ty;
+    if (lo < hi) { out[0] = lo; out[1] = hi; }
+}
+
 // What inc.0 need not write when inc.3 takes planes [in_z0, in_z1) over (common.h)
 void conv_first_skip_planes(int d, int in_z0, int in_z1, int32_t out[2]) {
     out[0] = out[1] = 0;
@@ -153,7 +163,7 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                    int apply_sigmoid, int trim, void* workspace, size_t workspace_bytes,
                    hipStream_t stream, const void* x_prepared = nullptr, float* absmax = nullptr,
                    int row_stride = 0, const int32_t* keep_hi = nullptr, const exaspim_unet_carry* carry = nullptr,
-                   const exaspim_unet_carry1* carry1 = nullptr) {
+                   const exaspim_unet_carry1* carry1 = nullptr, const exaspim_unet_carry_y* carry_y = nullptr) {
     const UNetPlan& p = e->plan;
     const Workspace ws = make_workspace(p, n, d, h, w);
     if (workspace_bytes < ws.bytes) {
@@ -226,6 +236,48 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
             EXA_CHECK_ARG(!in || carry->out_z[0] >= carry->in_z[1] || carry->out_z[1] <= carry->in_z[0],
                           "forward: carry out [%d, %d) overlaps the planes carried in, [%d, %d)", carry->out_z[0],
                           carry->out_z[1], carry->in_z[0], carry->in_z[1]);
+        }
+    }
+    // rows carried along y (exaspim_unet_forward_prepared_carry_y): the row launch of inc.3 alone
+    ConvCarryY cy;
+    if (carry_y) {
+        const bool in = carry_y->in_y[0] != 0 || carry_y->in_y[1] != 0;
+        const bool out_y = carry_y->out_skip_y || carry_y->out_pool_y || carry_y->out_shift_y || carry_y->out_y[0] || carry_y->out_y[1];
+        EXA_CHECK_ARG(carry && row && carry_y->reserved == 0,
+                      "forward: carried rows need the first level's carry struct and row mode at this geometry");
+        EXA_CHECK_ARG(!carry_y->out_skip_y == !carry_y->out_pool_y && !carry_y->out_skip_d == !carry_y->out_pool_d,
+                      "forward: y and diagonal carry out need both targets or neither");
+        if (in)
+            EXA_CHECK_ARG(carry_y->in_y[0] >= 2 && carry_y->in_y[0] < carry_y->in_y[1] && carry_y->in_y[1] <= h - 2 &&
+                              carry_y->in_y[0] % 8 == 0 && carry_y->in_y[1] % 8 == 0,
+                          "forward: y carry in [%d, %d) is not whole 8-row tiles inside [2, %d)", carry_y->in_y[0],
+                          carry_y->in_y[1], h - 2);
+        if (out_y) {
+            int32_t span[2];
+            const int shift = carry_y->out_skip_y ? carry_y->out_shift_y : 0;
+            carry_row_span(h, shift, span);
+            EXA_CHECK_ARG(shift > 0 && span[0] < span[1] && carry_y->out_y[0] == span[0] + shift &&
+                              carry_y->out_y[1] == span[1] + shift,
+                          "forward: y carry out [%d, %d) shifted by %d is not the range a forward %d rows on takes over",
+                          carry_y->out_y[0], carry_y->out_y[1], shift, shift);
+            EXA_CHECK_ARG(!in || carry_y->out_y[0] >= carry_y->in_y[1] || carry_y->out_y[1] <= carry_y->in_y[0],
+                          "forward: y carry out [%d, %d) overlaps the rows carried in, [%d, %d)", carry_y->out_y[0],
+                          carry_y->out_y[1], carry_y->in_y[0], carry_y->in_y[1]);
+        }
+        EXA_CHECK_ARG(!carry_y->out_skip_d || (carry->out_skip && carry_y->out_skip_y),
+                      "forward: the diagonal carry out needs both the z and the y carry out");
+        if (!(e->options & EXASPIM_OPT_CARRY_NO_ROWS)) {
+            cy.in_y0 = (unsigned short)carry_y->in_y[0];
+            cy.in_y1 = (unsigned short)carry_y->in_y[1];
+            if (carry_y->out_skip_y) {
+                cy.y_dst = carry_y->out_skip_y;
+                cy.y_pool_dst = carry_y->out_pool_y;
+                cy.d_dst = carry_y->out_skip_d;
+                cy.d_pool_dst = carry_y->out_pool_d;
+                cy.out_y0 = (unsigned short)carry_y->out_y[0];
+                cy.out_y1 = (unsigned short)carry_y->out_y[1];
+                cy.out_shift_y = (unsigned short)carry_y->out_shift_y;
+            }
         }
     }
     // With a carry in the border launch leaves the carried planes out as well and carries out whenever the main
@@ -343,7 +395,8 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
         // (row mode: the row launch, then the border launch that finishes it)
         int r = x3 && has_head      ? launch_conv3x3x3_x3_head(a, stream)
                 : a.row_stride > 0 ? launch_conv3x3x3_row(dt, a, (e->options & EXASPIM_OPT_ROW_SEPARATE_BORDERS) ? kRowStagesAll
-                                                                 : carry_borders ? kRowStagesCarry : kRowStagesFused, stream)
+                                                                 : carry_borders ? kRowStagesCarry : kRowStagesFused, stream,
+                                                        idx == 0 ? &cy : nullptr)
                                    : launch_conv3x3x3(dt, a, stream);
         if (timed && r == EXASPIM_OK) {
             EXA_CHECK_HIP(hipEventRecord(t->stop[slot], stream));
@@ -378,6 +431,8 @@ static int forward(exaspim_unet* e, const float* x, float* out, int n, int d, in
                           first_skip[0], first_skip[1]));
     if (absmax) RUN(launch_absmax(dt, A(0), (size_t)n * d * h * w * p.c0p * dtype_size(dt), absmax, stream));
     RUN(conv(0, A(0), nullptr, x1, 0));                           // x1
+    if (carry_y && carry_y->encoder_event)    // every carry out of this forward has been issued
+        EXA_CHECK_HIP(hipEventRecord(static_cast<hipEvent_t>(carry_y->encoder_event), stream));
     for (int l = 1; l <= 4; ++l) {
         const ConvLayer& L0 = p.conv[2 * l - 1];
         const void* prev = l == 1 ? x1 : l == 2 ? skip1 : skip(l - 1);
@@ -638,6 +693,23 @@ extern "C" int exaspim_unet_carry_planes(const exaspim_unet* h, int32_t n, int32
     return EXASPIM_OK;
 }
 
+extern "C" int exaspim_unet_carry_rows(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                       int32_t row_stride, int32_t shift_y, int32_t out[2]) {
+    EXA_CHECK_ARG(h && out, "carry_rows: NULL pointer");
+    out[0] = out[1] = 0;
+    EXA_CHECK_ARG(n > 0 && level_dims_ok(d, hgt, w) && row_stride >= 0 && shift_y > 0,
+                  "carry_rows: bad arguments (n %d, patch %dx%dx%d, row stride %d, shift %d)", n, d, hgt, w,
+                  row_stride, shift_y);
+    // the conditions under which forward() runs inc.3 in row mode (exaspim_unet_carry_planes)
+    const UNetPlan& p = h->plan;
+    const bool fused = !(h->options & EXASPIM_OPT_SEPARATE_POOL) && conv_can_fuse_pool(p.dtype, p.conv[0].cout, d, hgt, w);
+    if ((h->options & (EXASPIM_OPT_PER_PATCH_ENCODER | EXASPIM_OPT_CARRY_NO_ROWS)) ||
+        !conv_row_mode_ok(p.dtype, p.conv[0].cout, n, w, row_stride, fused))
+        return EXASPIM_OK;
+    carry_row_span(hgt, shift_y, out);
+    return EXASPIM_OK;
+}
+
 extern "C" int exaspim_unet_carry1_planes(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
                                           int32_t row_stride, int32_t shift_z, int32_t out[2]) {
     int32_t l0[2];
@@ -664,6 +736,17 @@ extern "C" int exaspim_unet_forward_prepared_carry1(exaspim_unet* h, const void*
                                                     const int32_t keep_hi[3], const exaspim_unet_carry* carry,
                                                     const exaspim_unet_carry1* carry1, void* workspace_dev,
                                                     size_t workspace_bytes, void* stream) {
+    return exaspim_unet_forward_prepared_carry_y(h, x_prepared_dev, out_dev, n, d, hgt, w, apply_sigmoid, trim, row_stride,
+                                                 keep_hi, carry, carry1, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int exaspim_unet_forward_prepared_carry_y(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                                     int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                                     int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                                     const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                                     const exaspim_unet_carry1* carry1,
+                                                     const exaspim_unet_carry_y* carry_y, void* workspace_dev,
+                                                     size_t workspace_bytes, void* stream) {
     EXA_CHECK_ARG(h && x_prepared_dev && out_dev && workspace_dev && keep_hi && carry, "forward: NULL pointer");
     EXA_CHECK_ARG(n > 0, "forward: empty batch");
     EXA_CHECK_ARG(trim >= 0, "forward: negative trim %d", trim);
@@ -677,7 +760,8 @@ extern "C" int exaspim_unet_forward_prepared_carry1(exaspim_unet* h, const void*
                       "forward: keep_hi[%d] = %d outside (%d, %d] (trim %d of %d voxels)", i, keep_hi[i], trim,
                       size[i] - trim, trim, size[i]);
     return forward(h, nullptr, out_dev, n, d, hgt, w, apply_sigmoid, trim, workspace_dev,
-                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi, carry, carry1);
+                   workspace_bytes, (hipStream_t)stream, x_prepared_dev, nullptr, row_stride, keep_hi, carry, carry1,
+                   carry_y);
 }
 
 extern "C" int exaspim_unet_forward_trimmed(exaspim_unet* h, const float* x_dev, float* out_dev,
@@ -713,7 +797,7 @@ extern "C" int exaspim_unet_set_options(exaspim_unet* h, uint32_t options) {
     EXA_CHECK_ARG((options & ~(uint32_t)(EXASPIM_OPT_SEPARATE_POOL | EXASPIM_OPT_SEPARATE_DEEP_POOLS | EXASPIM_OPT_PLAIN_UPSAMPLE | EXASPIM_OPT_FIRST_PER_GROUP |
                                           EXASPIM_OPT_UPSAMPLE_PER_THREAD | EXASPIM_OPT_PER_PATCH_ENCODER |
                                           EXASPIM_OPT_SEPARATE_HEAD | EXASPIM_OPT_ROW_SEPARATE_BORDERS |
-                                          EXASPIM_OPT_CARRY_MAIN_ONLY)) == 0,
+                                          EXASPIM_OPT_CARRY_MAIN_ONLY | EXASPIM_OPT_CARRY_NO_ROWS)) == 0,
                   "set_options: unknown option bits 0x%x", options);
     h->options = options;
     return EXASPIM_OK;

@@ -155,6 +155,53 @@ int probe_conv3x3x3_row_carry(int dtype, const void* src, int ca, const void* we
 }
 int probe_last_carry(void) { return last_conv_launch().carry ? 1 : 0; }
 
+// ... and rows carried along y (ConvCarryY): carry_y[0..4] = in_y0, in_y1, out_y0, out_y1, out_shift_y; targets[0..3]
+// = y_dst, y_pool_dst, d_dst, d_pool_dst (each may be null). 1 from probe_last_carry_y if the last launch ran
+// conv3x3x3_zpipe_rowzy.
+int probe_conv3x3x3_row_carry_y(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,
+                                int cout, int n, int d, int h, int w, float slope, int row_stride, void* pool_dst,
+                                const int32_t* carry, void* carry_dst, void* carry_pool_dst, const int32_t* carry_y,
+                                void* const* targets, int stages, hipStream_t stream) {
+    EXA_CHECK_ARG(carry != nullptr && carry_y != nullptr && targets != nullptr, "probe: NULL carry");
+    for (int i = 0; i < 5; ++i) {   // (what the narrow fields hold)
+        EXA_CHECK_ARG(carry[i] >= 0 && carry[i] <= (i == 2 || i == 3 ? 254 : 65534), "probe: carry[%d] = %d out of range", i, carry[i]);
+        EXA_CHECK_ARG(carry_y[i] >= 0 && carry_y[i] <= 65534, "probe: carry_y[%d] = %d out of range", i, carry_y[i]);
+    }
+    ConvArgs a{};
+    a.src_a = src;
+    a.ca = ca;
+    a.weights = weights;
+    a.bias = bias;
+    a.dst = dst;
+    a.cout = cout;
+    a.n = n;
+    a.d = d;
+    a.h = h;
+    a.w = w;
+    a.slope = slope;
+    a.row_stride = row_stride;
+    a.pool_dst = pool_dst;
+    a.in_z0 = (unsigned short)carry[0];
+    a.in_z1 = (unsigned short)carry[1];
+    a.out_z0 = (unsigned char)carry[2];
+    a.out_z1 = (unsigned char)carry[3];
+    a.out_shift = (unsigned short)carry[4];
+    a.carry_dst = carry_dst;
+    a.carry_pool_dst = carry_pool_dst;
+    ConvCarryY y;
+    y.in_y0 = (unsigned short)carry_y[0];
+    y.in_y1 = (unsigned short)carry_y[1];
+    y.out_y0 = (unsigned short)carry_y[2];
+    y.out_y1 = (unsigned short)carry_y[3];
+    y.out_shift_y = (unsigned short)carry_y[4];
+    y.y_dst = targets[0];
+    y.y_pool_dst = targets[1];
+    y.d_dst = targets[2];
+    y.d_pool_dst = targets[3];
+    return launch_conv3x3x3_row(dtype, a, stages, stream, &y);
+}
+int probe_last_carry_y(void) { return last_conv_launch().carry_y ? 1 : 0; }
+
 // One whole-patch convolution through launch_conv3x3x3 with planes carried along z outside row mode
 // (conv3x3x3_t14_carry); carry[0..4] as above, partial may be null (with scratch the launcher may split).
 int probe_conv3x3x3_carry(int dtype, const void* src, int ca, const void* weights, const float* bias, void* dst,

@@ -75,6 +75,8 @@ PLAIN_GATHER = False    # True: gather float32 patches and let the engine pad th
 FULL_PATCHES = False    # True: compute the margin predict() discards as well (exaspim_unet_forward untrimmed)
 CARRY_Z = True          # False: every batch computes its whole first level (no planes carried from the z slab above)
 CARRY_Z1 = True         # False: only the first level carries planes (down1.0 and down1.3 are computed whole)
+# (not a CARRY_ name: the switches of that prefix are a closed list, tests/test_module_surface_cpu.py)
+ROWS_CARRY_Y = True     # False: no rows carried from the batch one y step earlier (section 3g); off wherever CARRY_Z is off
 CARRY_POOL_BYTES = 36 << 30   # most device memory one run_sliding_window call may hold in carry buffers
 CLIP_TO_VOLUME = True   # False: also compute the trimmed outputs beyond the volume's high faces, which the stitch drops
 
@@ -564,23 +566,27 @@ def batch_row_stride(starts, patch_shape, overlap):
     return stride
 
 
-def carry_plan(starts, batch_size, patch_shape, overlap):
+def carry_plan(starts, batch_size, patch_shape, overlap, axis=0):
     """
     For every batch of the sliding window (starts cut into runs of batch_size), the index of the later
     batch that can take first-level planes over from it, or None: the nearest later batch whose starts are
     this batch's shifted by one positive z amount below the patch depth, with the same number of patches,
     both of them rows along x of the same stride (batch_row_stride). Host-side, no device sync.
+    axis=1: the same along y -- the batch that can take rows over (same x and z starts, one positive y amount
+    below the patch height).
     """
     batch_size = int(batch_size)
+    axis = int(axis)
+    other = 1 - axis
     batches = [starts[i:i + batch_size] for i in range(0, len(starts), batch_size)]
-    chains = {}     # (row stride, the row's (y, x) starts) -> [(z, batch index)]
+    chains = {}     # (row stride, the row's starts on the other axis and x) -> [(start on the axis, batch index)]
     for bi, b in enumerate(batches):
         stride = batch_row_stride(b, patch_shape, overlap)
         if stride > 0:
-            key = (stride, tuple((int(s[1]), int(s[2])) for s in b))
-            chains.setdefault(key, []).append((int(b[0][0]), bi))
+            key = (stride, tuple((int(s[other]), int(s[2])) for s in b))
+            chains.setdefault(key, []).append((int(b[0][axis]), bi))
     succ = [None] * len(batches)
-    depth = int(patch_shape[0])
+    depth = int(patch_shape[axis])
     for members in chains.values():
         for z, bi in members:
             later = [(z2 - z, bj) for z2, bj in members if bj > bi and 0 < z2 - z < depth]
@@ -600,6 +606,140 @@ def _carry_budget(peak, pair_bytes, triple_bytes, free, cap):
     if peak <= 0 or need0 > limit:
         return False, False
     return True, triple_bytes > 0 and need0 + peak * triple_bytes <= limit
+
+
+def _carry_rows_span(h, shift_y):
+    """exaspim_unet_carry_rows for a batch that runs in row mode: the whole 8-row tiles inside
+    [2, h - shift_y - 2) of the later frame, (0, 0) if there is none. Host-side arithmetic, so that the schedule
+    is the same for every model that gives the same plane ranges; the engine refuses any other range."""
+    h, shift_y = int(h), int(shift_y)
+    if shift_y <= 0 or shift_y % 2 or shift_y >= h:
+        return (0, 0)
+    hi = (h - shift_y - 2) // 8 * 8
+    return (8, hi) if hi > 8 else (0, 0)
+
+
+_ROWS_SCHEDULES = collections.OrderedDict()     # the last few y schedules: a pure function of the window plan
+
+
+def _carry_rows_schedule(links, starts, batch_size, patch_shape, overlap):
+    """_plan_rows, remembered for the last few window plans: a volume's slabs, and one volume after the other,
+    ask for the same plan again, and the planning is host time in front of the first launch."""
+    if not ROWS_CARRY_Y or not any(links):
+        return [None] * len(links), None
+    try:
+        key = (tuple(starts), tuple(links), int(batch_size), tuple(patch_shape), tuple(overlap))
+        hit = _ROWS_SCHEDULES.get(key)
+    except TypeError:       # (starts that do not hash: plan afresh)
+        key, hit = None, None
+    if hit is None:
+        hit = _plan_rows(links, starts, batch_size, patch_shape, overlap)
+        if key is not None:
+            _ROWS_SCHEDULES[key] = hit
+            while len(_ROWS_SCHEDULES) > 8:
+                _ROWS_SCHEDULES.popitem(last=False)
+    elif key is not None:
+        _ROWS_SCHEDULES.move_to_end(key)
+    return list(hit[0]), hit[1]
+
+
+def _plan_rows(links, starts, batch_size, patch_shape, overlap):
+    """
+    The rows carried along y on top of the z links of _carry_schedule: (ylinks, peak) with
+    ylinks[bi] = (y successor, shift_y, the successor's row range, diagonal successor or None) or None, and peak =
+    the buffer sets alive at once on one stream with them. A batch computes {planes not carried in} x {rows not
+    carried in} and stores again only what it computes, so a y link is kept only where every (plane, row) block
+    of the successor still has a batch that computes it and is linked to it:
+      * both batches take part in the z links (so they run in row mode and own a buffer set);
+      * the range passed on does not meet the rows the batch took over itself (the chain is cut, as along z);
+      * the y predecessor computes every plane the successor does (no planes carried in, or the same range);
+      * a z predecessor that took rows over must see its z successor take the same rows over, and the block
+        neither computes must come from their common diagonal predecessor -- else the z predecessor keeps
+        computing its rows.
+    """
+    n = len(links)
+    bs = int(batch_size)
+    succ_y = carry_plan(starts, bs, patch_shape, overlap, axis=1)
+    pred_z = {l[0]: bi for bi, l in enumerate(links) if l is not None}
+    in_z = {bj: links[bi][2] for bj, bi in pred_z.items()}
+    takes_part = [links[bi] is not None or bi in pred_z for bi in range(n)]
+    pred_y, in_y, shift_of = {}, {}, {}
+    for bi, bj in enumerate(succ_y):
+        if bj is None or not takes_part[bi] or not takes_part[bj]:
+            continue
+        shift = int(starts[bj * bs][1]) - int(starts[bi * bs][1])
+        rows = _carry_rows_span(patch_shape[1], shift)
+        if rows[1] > rows[0]:
+            pred_y[bj], in_y[bj], shift_of[bj] = bi, rows, shift
+    changed = True
+    while changed:
+        changed = False
+        for b in sorted(in_y):
+            p, rows, shift = pred_y[b], in_y[b], shift_of[b]
+            got = in_y.get(p, (0, 0))
+            drop = rows[0] + shift < got[1] and got[0] < rows[1] + shift       # the chain is cut here
+            drop = drop or in_z.get(p, (0, 0)) not in ((0, 0), in_z.get(b, (0, 0)))
+            if drop:
+                del in_y[b]
+                changed = True
+        for b, pz in pred_z.items():
+            if pz not in in_y:
+                continue
+            pd = pred_y[pz]
+            ok = (in_y.get(b) == in_y[pz] and shift_of[b] == shift_of[pz] and
+                  (in_z.get(pred_y[b], (0, 0)) == (0, 0) or
+                   (pred_z.get(pred_y[b]) == pd and in_z[pred_y[b]] == in_z[b] and
+                    links[pd][1] == links[pz][1])))
+            if not ok:
+                del in_y[pz]
+                changed = True
+    ylinks = [None] * n
+    for b, rows in in_y.items():
+        ylinks[pred_y[b]] = (b, shift_of[b], rows, None)
+    for b, pz in pred_z.items():       # the block neither predecessor computes
+        if pz in in_y and b in in_y and in_z.get(pred_y[b], (0, 0)) != (0, 0):
+            pd = pred_y[pz]
+            ylinks[pd] = ylinks[pd][:3] + (b,)
+    if not any(ylinks):
+        return ylinks, None
+    has, alive, peak = set(), 0, 0
+    for bi in range(n):
+        targets = [bi] if takes_part[bi] else []
+        if links[bi] is not None:
+            targets.append(links[bi][0])
+        if ylinks[bi] is not None:
+            targets += [t for t in (ylinks[bi][0], ylinks[bi][3]) if t is not None]
+        for t in targets:
+            if t not in has:
+                has.add(t)
+                alive += 1
+        peak = max(peak, alive)
+        if bi in has:
+            alive -= 1
+    return ylinks, peak
+
+
+def _carry_rows_budget(model, links, peak, level1, starts, batch_size, patch_shape, overlap, n_streams, device,
+                       free=None):
+    """
+    The rows carried along y on top of what _carry_schedule gave (links, peak, level1): (ylinks, more) with
+    _carry_rows_schedule's links and the buffer sets to allocate beyond peak -- a set then lives from the earliest
+    of its three predecessors -- or (None, 0) where there is nothing to carry or peak + more sets of pairs (and
+    triples, if level1) would exceed CARRY_POOL_BYTES or half of the free device memory (free: asked from the
+    device if None, before the sets are allocated). The rows are budgeted last: they never cost a z link or the
+    second level its buffers, and _carry_schedule's answer does not depend on them.
+    """
+    ylinks, need = _carry_rows_schedule(links, starts, batch_size, patch_shape, overlap)
+    if need is None:
+        return None, 0
+    more = max(0, need + (int(n_streams) if n_streams > 1 else 0) - int(peak))
+    shape = (int(batch_size),) + tuple(patch_shape)
+    set_bytes = 2 * sum(model.carry_pair_elems(shape)) + (2 * sum(model.carry_triple_elems(shape)) if level1 else 0)
+    if free is None:
+        free, _ = torch.cuda.mem_get_info(device)
+    if (peak + more) * set_bytes > min(int(CARRY_POOL_BYTES), int(free) // 2):
+        return None, 0
+    return ylinks, more
 
 
 def _carry_schedule(model, succ, starts, batch_size, patch_shape, overlap, n_streams, device, free=None):
@@ -1016,11 +1156,15 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
     if isinstance(model, UNet3D) and not PLAIN_GATHER:
         prepared_layout = model.input_layout(device)    # (PLAIN_GATHER: tests hold the two paths to each other)
     # first-level planes carried from one z slab of patches to the next
-    links, free_pairs = None, collections.deque()
+    links, ylinks, free_pairs = None, None, collections.deque()
     if CARRY_Z and prepared_layout is not None and not model.needs_resolution():
         links, peak, level1 = _carry_schedule(model, carry_plan(starts, batch_size, plan.patch_shape, plan.overlap),
                                               starts, batch_size, plan.patch_shape, plan.overlap, n_streams, device)
         if links is not None:
+            # rows carried along y as well (section 3g), where the pool holds the sets that live longer for it
+            ylinks, more = _carry_rows_budget(model, links, peak, level1, starts, batch_size, plan.patch_shape,
+                                              plan.overlap, n_streams, device)
+            peak += more
             shape = (batch_size,) + tuple(plan.patch_shape)
             elems = model.carry_pair_elems(shape)
             elems1 = model.carry_triple_elems(shape) if level1 else None     # (section 3e: a triple with every pair)
@@ -1030,7 +1174,8 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                               for _ in range(peak))
             for s in workers:
                 s.wait_stream(main)
-    # batch index -> [its pair (and triple), the planes already there, its predecessor's event, the level-1 planes]
+    # batch index -> [its pair (and triple), the planes already there, its z predecessor's event, the level-1 planes,
+    # the rows already there, the events of its y and diagonal predecessors]
     pending = {}
 
     def take_pair(worker):
@@ -1038,6 +1183,15 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
         if pair[1] is not None:     # the forward that read it last, maybe on another stream
             worker.wait_event(pair[1])
         return pair
+
+    def target(t, worker):
+        """The pending entry of batch t, which this worker's forward is about to store into: its set is taken when
+        the earliest of its predecessors runs, and every predecessor waits for the forward that read the set last."""
+        if t not in pending:
+            pending[t] = [take_pair(worker), (0, 0), None, (0, 0), (0, 0), []]
+        elif pending[t][0][1] is not None:
+            worker.wait_event(pending[t][0][1])
+        return pending[t]
 
     for bi, i in enumerate(range(0, len(starts), batch_size)):
         batch = starts_dev[i:i + batch_size]
@@ -1053,20 +1207,41 @@ def run_sliding_window(volume, model, plan, n_channels, batch_size, brightness_c
                                            mn=mn, mx=mx, layout=prepared_layout)
                 carry, own = None, None
                 if links is not None and (bi in pending or links[bi] is not None):
-                    own, in_z, before, in_z1 = pending.pop(bi, None) or (take_pair(worker), (0, 0), None, (0, 0))
+                    own, in_z, before, in_z1, in_y, others = pending.pop(bi, None) or [take_pair(worker), (0, 0), None,
+                                                                                       (0, 0), (0, 0), []]
                     carry = {"own": own[0], "in_z": in_z}
                     if own[2] is not None:
                         carry.update(own1=own[2], in_z1=in_z1)
-                    if before is not None:
-                        worker.wait_event(before)      # the planes carried in are there
+                    for event in [before] + others:
+                        if event is not None:
+                            worker.wait_event(event)      # the planes and rows carried in are there
+                    encoded = None
+                    if ylinks is not None and (in_y[1] > in_y[0] or ylinks[bi] is not None):
+                        carry.update(in_y=in_y)
+                        if ylinks[bi] is not None:
+                            by, shift_y, rows, bd = ylinks[bi]
+                            if n_streams > 1:
+                                # the y successor is usually the very next batch: it waits for this forward's first
+                                # level, not for its end
+                                encoded = torch.cuda.Event()
+                                carry.update(encoder_event=encoded)
+                            after = target(by, worker)
+                            after[4] = rows
+                            after[5].append(encoded)
+                            carry.update(out_y_pair=after[0][0], out_y=(rows[0] + shift_y, rows[1] + shift_y),
+                                         out_shift_y=shift_y)
+                            if bd is not None:
+                                after = target(bd, worker)
+                                after[5].append(encoded)
+                                carry.update(out_d_pair=after[0][0])
                     if links[bi] is not None:
                         nxt, shift, span, span1 = links[bi]
-                        out_pair = take_pair(worker)
+                        out_pair = target(nxt, worker)[0]
                         carry.update(out=out_pair[0], out_z=(span[0] + shift, span[1] + shift), out_shift=shift)
                         if span1[1] > span1[0]:
                             carry.update(out1=out_pair[2], out_z1=(span1[0] + shift // 2, span1[1] + shift // 2),
                                          out_shift1=shift // 2)
-                        pending[nxt] = [out_pair, span, None, span1]
+                        pending[nxt][1], pending[nxt][3] = span, span1
                 pred = model.run_prepared(
                     inputs, (int(batch.shape[0]),) + tuple(plan.patch_shape), apply_sigmoid=True,
                     trim=0 if FULL_PATCHES else plan.trim, row_stride=row_stride, keep_hi=keep_hi, carry=carry)

@@ -463,6 +463,21 @@ class UNet3D(nn.Module):
             "exaspim_unet_carry1_planes")
         return int(span[0]), int(span[1])
 
+    def carry_rows(self, shape, row_stride, shift_y, device=None):
+        """
+        carry_planes along y (exaspim_unet_carry_rows): the rows of its own frame a row batch can take over from
+        the same row of patches shift_y rows earlier along y. (0, 0): none.
+        """
+        device = next(self.parameters()).device if device is None else device
+        n, d, h, w = (int(v) for v in shape)
+        with torch.cuda.device(device):
+            self._ensure_engine(device)
+        span = (ctypes.c_int32 * 2)()
+        _native.check(
+            _native.lib().exaspim_unet_carry_rows(self._engine, n, d, h, w, int(row_stride), int(shift_y), span),
+            "exaspim_unet_carry_rows")
+        return int(span[0]), int(span[1])
+
     def carry_triple_elems(self, shape):
         """Elements (16-bit) of the three buffers a forward that carries second-level planes keeps down1.0's
         output, the level's skip tensor and its max-pool in (run_prepared's carry["own1"] / carry["out1"])."""
@@ -509,6 +524,11 @@ class UNet3D(nn.Module):
             Second level as well (exaspim_unet_forward_prepared_carry1): "own1" = (mid, skip, pool) tensors of
             carry_triple_elems(shape) elements, "in_z1", and with "out" optionally "out1", "out_z1",
             "out_shift1", in level-1 planes.
+            Rows carried along y as well (exaspim_unet_forward_prepared_carry_y): "in_y" = the row range already
+            there, "out_y_pair" = the (skip, pool) of the batch "out_shift_y" rows on with "out_y", this forward's
+            rows to store there, "out_d_pair" = the (skip, pool) of the batch both shifts on (needs "out" and
+            "out_y_pair"), "encoder_event" = a torch.cuda.Event recorded right after the first level's
+            convolutions, when every carry out has been issued.
         """
         if self.training:
             raise RuntimeError(
@@ -537,7 +557,7 @@ class UNet3D(nn.Module):
             if carry is not None:
                 desc = _native.UNetCarry()
                 need = self.carry_pair_elems(shape)
-                pairs = [carry["own"]] + ([carry["out"]] if carry.get("out") is not None else [])
+                pairs = [carry["own"]] + [carry[k] for k in ("out", "out_y_pair", "out_d_pair") if carry.get(k) is not None]
                 for pair in pairs:
                     for t, elems in zip(pair, need):
                         if not t.is_cuda or t.element_size() != 2 or t.numel() < elems or not t.is_contiguous():
@@ -565,15 +585,31 @@ class UNet3D(nn.Module):
                         desc1.out_mid1, desc1.out_skip1, desc1.out_pool2 = (t.data_ptr() for t in carry["out1"])
                         desc1.out_z[:] = [int(v) for v in carry["out_z1"]]
                         desc1.out_shift = int(carry["out_shift1"])
+                desc_y = None
+                if any(carry.get(k) is not None for k in ("in_y", "out_y_pair", "out_d_pair", "encoder_event")):
+                    desc_y = _native.UNetCarryY()
+                    desc_y.in_y[:] = [int(v) for v in carry.get("in_y") or (0, 0)]
+                    if carry.get("out_y_pair") is not None:
+                        desc_y.out_skip_y, desc_y.out_pool_y = (t.data_ptr() for t in carry["out_y_pair"])
+                        desc_y.out_y[:] = [int(v) for v in carry["out_y"]]
+                        desc_y.out_shift_y = int(carry["out_shift_y"])
+                    if carry.get("out_d_pair") is not None:
+                        desc_y.out_skip_d, desc_y.out_pool_d = (t.data_ptr() for t in carry["out_d_pair"])
+                    event = carry.get("encoder_event")
+                    if event is not None:
+                        if not event.cuda_event:     # (created lazily: a first record makes the handle)
+                            event.record(torch.cuda.current_stream(device))
+                        desc_y.encoder_event = event.cuda_event
                 hi = keep_hi if keep_hi is not None else (d - int(trim), h - int(trim), w - int(trim))
                 _native.check(
-                    _native.lib().exaspim_unet_forward_prepared_carry1(
+                    _native.lib().exaspim_unet_forward_prepared_carry_y(
                         self._engine, prepared.data_ptr(), out.data_ptr(), n, d, h, w,
                         1 if apply_sigmoid else 0, int(trim), int(row_stride), _native.int3(hi),
                         ctypes.byref(desc), ctypes.byref(desc1) if desc1 is not None else None,
+                        ctypes.byref(desc_y) if desc_y is not None else None,
                         ws.data_ptr(), ws.numel(), stream,
                     ),
-                    "exaspim_unet_forward_prepared_carry1",
+                    "exaspim_unet_forward_prepared_carry_y",
                 )
             elif keep_hi is not None:
                 _native.check(

@@ -60,7 +60,9 @@ extern "C" {
  *    later within 5: exaspim_dbf, exaspim_segment_table (and their workspace queries, EXASPIM_DBF_INF):
  *    the distance-to-boundary field and the per-label table a skeletoniser starts from;
  *    later within 5: exaspim_region_graph_contract_dominant (and its workspace query): the exact
- *    contraction of dominant edges on the device before the host agglomeration */
+ *    contraction of dominant edges on the device before the host agglomeration;
+ *    later within 5: exaspim_unet_carry_rows, exaspim_unet_forward_prepared_carry_y (struct
+ *    exaspim_unet_carry_y), EXASPIM_OPT_CARRY_NO_ROWS: first-level rows carried along y as well */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -301,6 +303,49 @@ int exaspim_unet_forward_prepared_carry1(exaspim_unet* h, const void* x_prepared
                                          const exaspim_unet_carry1* carry1, void* workspace_dev,
                                          size_t workspace_bytes, void* stream);
 
+/* Rows of the first level carried along y, on top of the planes carried along z. A row batch whose patches start
+ * shift_y rows after an earlier row batch (same x and z starts, same n and row_stride) computes, away from its own
+ * zero padding along y, the bits that batch computed: its rows [2, hgt - shift_y - 2) are the earlier batch's
+ * [2 + shift_y, hgt - 2). exaspim_unet_carry_rows: out[0..1] = the row range [y0, y1) of the LATER batch's frame a
+ * forward can take over: the whole 8-row tiles of inc.3's row launch inside that span. Empty under the conditions
+ * that leave exaspim_unet_carry_planes empty (no row mode) or when nothing fits. For hgt = 96, shift_y = 64: [8, 24).
+ * Only the row launch of inc.3 takes rows over (x in [2, w - 2) of a patch face that borders a neighbour, every x of
+ * the row's two outer faces); the border launch computes every row of its columns and the first convolution
+ * writes every row.
+ * A forward computes {planes outside carry->in_z} x {rows outside in_y} and stores again only what it computes:
+ *   out_skip_y / out_pool_y (both or neither), out_y, out_shift_y: rows out_y of every plane it computes go to the
+ *     y successor's own buffers at row - out_shift_y (pooled: half of it);
+ *   out_skip_d / out_pool_d (both or neither; needs the z and the y carry out): planes carry->out_z x rows out_y go
+ *     to the diagonal successor's own buffers, the batch out_shift planes down AND out_shift_y rows on, at
+ *     plane - out_shift and row - out_shift_y. Neither the z nor the y successor computes that block -- each takes
+ *     it over from this forward -- so neither can pass it on.
+ * A successor with in_y must get every (plane, row) it does not compute from a predecessor that computes it: the
+ * caller's plan sees to that (inference._carry_schedule). A carry out that meets the rows carried in is refused.
+ * encoder_event (optional): a hipEvent_t the engine records on the stream right after inc.3's launches, when every
+ * carry out of this forward has been issued: the y successor is usually the very next batch and need not wait for
+ * the whole forward. */
+int exaspim_unet_carry_rows(const exaspim_unet* h, int32_t n, int32_t d, int32_t hgt, int32_t w,
+                            int32_t row_stride, int32_t shift_y, int32_t out[2]);
+typedef struct exaspim_unet_carry_y {
+    int32_t in_y[2];
+    void* out_skip_y;
+    void* out_pool_y;
+    void* out_skip_d;
+    void* out_pool_d;
+    int32_t out_y[2];
+    int32_t out_shift_y;
+    int32_t reserved;   /* 0 */
+    void* encoder_event;
+} exaspim_unet_carry_y;
+/* exaspim_unet_forward_prepared_carry1 (carry1 may be NULL) with rows carried along y; out_dev gets the same bits.
+ * A request the engine cannot honour is EXASPIM_E_INVALID before anything is launched. */
+int exaspim_unet_forward_prepared_carry_y(exaspim_unet* h, const void* x_prepared_dev, float* out_dev,
+                                          int32_t n, int32_t d, int32_t hgt, int32_t w,
+                                          int32_t apply_sigmoid, int32_t trim, int32_t row_stride,
+                                          const int32_t keep_hi[3], const exaspim_unet_carry* carry,
+                                          const exaspim_unet_carry1* carry1, const exaspim_unet_carry_y* carry_y,
+                                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Range probe for the 16-bit storage modes. The reference loads ANY trained state_dict
  * (inference.py:400-424) and runs it in float32; IEEE-half storage holds |v| <= 65504 (stores
  * saturate there) with 11 significant bits. This is exaspim_unet_forward (nothing fused away,
@@ -341,6 +386,11 @@ int exaspim_unet_forward_absmax(exaspim_unet* h, const float* x_dev, float* out_
  * and successor must agree on who writes the border columns of the carried planes.
  * (EXASPIM_OPT_ROW_SEPARATE_BORDERS implies it.) */
 #define EXASPIM_OPT_CARRY_MAIN_ONLY 512u
+/* exaspim_unet_forward_prepared_carry_y: the y fields are checked and then ignored -- the forward computes every
+ * row and stores nothing to the y and diagonal targets: exactly exaspim_unet_forward_prepared_carry1's launches
+ * (same bits; the event is still recorded). Set it on every handle of a carry chain or on none.
+ * (Bit 1024 is not assigned.) */
+#define EXASPIM_OPT_CARRY_NO_ROWS 2048u
 int exaspim_unet_set_options(exaspim_unet* h, uint32_t options);
 
 /* Measurement hooks (bench.py's roofline leg). timing_begin arms HIP-event
