@@ -253,6 +253,8 @@ SIGNATURES = {
     "exaspim_dbf": (_i32, [_vp, _I32x3, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_segment_table_workspace_bytes": (_sz, [_i32]),
     "exaspim_segment_table": (_i32, [_vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_fill_holes_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_fill_holes": (_i32, [_vp, _I32x3, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

@@ -430,5 +430,12 @@ int launch_head(int dtype, const void* src, const float* w, const float* bias,
 // EXASPIM_E_INVALID for dims exaspim_dbf refuses; the pointers are the caller's to check.
 int launch_dbf_pass(int axis, const int32_t* labels, const int32_t* in, int32_t* out, const int32_t dims[3],
                     int black_border, hipStream_t stream);
+// (components.hip) the passes first .. last of exaspim_fill_holes, which runs all of them: 0 the background's
+// edge mask, 1 tile_pass, 2 face_merge, 3 flatten, 4 the survey (its two words reset, the faces, the
+// neighbours), 5 the fill (counts zeroed first). Each pass reads what the ones before it left in the
+// workspace. EXASPIM_E_INVALID for dims exaspim_fill_holes refuses; the pointers are the caller's to check.
+constexpr int kFillHolesPasses = 6;
+int launch_fill_holes_passes(const int32_t* labels, const int32_t dims[3], int32_t* out, int64_t* counts,
+                             void* workspace, int first, int last, hipStream_t stream);
 
 }  // namespace exaspim

@@ -28,6 +28,10 @@
 // Watershed fragments (exaspim_watershed_fragments) differ in pass (a) alone:
 // edge_mask_watershed writes the same mask byte from each voxel's steepest edge and its neighbours',
 // and passes (b) to (g) run on it as they are.
+//
+// Enclosed cavities (exaspim_fill_holes) are the components of a labelled volume's background:
+// edge_mask_background writes the mask byte from the labels, passes (b) to (d) run on it as they are into
+// a parent array in the workspace, and survey_faces, survey and fill decide per cavity and write the labels.
 #include "label_scan.h"
 
 namespace exaspim {
@@ -469,6 +473,185 @@ __global__ __launch_bounds__(kThreads) void relabel(int* labels, const int* __re
         labels[g] = aux[labels[g]];
 }
 
+// ---- enclosed cavities (exaspim_fill_holes) -------------------------------------------------
+// The cavities of a labelled volume are the components of its background: edge_mask_background writes the
+// mask byte of pass (a) from the labels, passes (b) to (d) run on it as they are into a parent array in
+// the workspace (a foreground voxel has no bit set and stays a root of its own), and three passes follow:
+//   survey_faces  every background voxel on a face of the volume marks its cavity open: lo[root] = 0;
+//   survey        lo[root] = the smallest, hi[root] = the largest positive label next to the cavity;
+//   fill          a background voxel whose root has lo == hi > 0 becomes that label.
+constexpr int kNoLabel = 2147483647;   // lo of a cavity nobody has reported a neighbour of (hi: 0)
+
+// VEC voxels along x per thread (16-byte loads, or VEC = 1); w % VEC == 0, so a group never straddles a
+// row. A bit is set iff this voxel and the next one along the axis are both background.
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void edge_mask_background(const int* __restrict__ labels,
+                                                                unsigned char* __restrict__ mask, Dims dm) {
+    struct alignas(4 * VEC) Pack { int v[VEC]; };
+    struct alignas(VEC) Bytes { unsigned char b[VEC]; };
+    const size_t groups = (size_t)dm.n / VEC;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const unsigned hw = (unsigned)dm.h * (unsigned)dm.w;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
+        const unsigned i = (unsigned)(g * VEC);
+        const unsigned row = i / (unsigned)dm.w, x0 = i - row * (unsigned)dm.w;
+        const unsigned z = row / (unsigned)dm.h, y = row - z * (unsigned)dm.h;
+        const bool zin = (int)z < dm.d - 1, yin = (int)y < dm.h - 1;
+        const Pack me = *reinterpret_cast<const Pack*>(labels + i);
+        Pack up_z = me, up_y = me;   // overwritten where the upper neighbour exists
+        if (zin) up_z = *reinterpret_cast<const Pack*>(labels + i + hw);
+        if (yin) up_y = *reinterpret_cast<const Pack*>(labels + i + (unsigned)dm.w);
+        // the voxel after the group; past the row's end a foreground value stands for "no edge"
+        const int after = (int)(x0 + VEC) < dm.w ? labels[i + VEC] : 1;
+        Bytes out;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            unsigned m = 0;
+            if (me.v[k] <= 0) {
+                m = kBitOn;
+                if (zin && up_z.v[k] <= 0) m |= kBitZ;
+                if (yin && up_y.v[k] <= 0) m |= kBitY;
+                if ((k + 1 < VEC ? me.v[(k + 1) % VEC] : after) <= 0) m |= kBitX;
+            }
+            out.b[k] = (unsigned char)m;
+        }
+        *reinterpret_cast<Bytes*>(mask + i) = out;
+    }
+}
+
+// The six faces as three pairs of planes, one thread per face voxel (edges and corners more than once,
+// and both planes of an axis of length 1 are the same one: every store is the same 0). parent is flattened.
+__global__ __launch_bounds__(kThreads) void survey_faces(const int* __restrict__ labels,
+                                                        const int* __restrict__ parent, int* lo, Dims dm) {
+    const size_t hw = (size_t)dm.h * dm.w, dw = (size_t)dm.d * dm.w, dh = (size_t)dm.d * dm.h;
+    const size_t total = 2 * (hw + dw + dh);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
+        size_t j = g, z, y, x;
+        if (j < 2 * hw) {
+            z = j < hw ? 0 : (size_t)dm.d - 1;
+            if (j >= hw) j -= hw;
+            y = j / (size_t)dm.w;
+            x = j - y * (size_t)dm.w;
+        } else if (j < 2 * (hw + dw)) {
+            j -= 2 * hw;
+            y = j < dw ? 0 : (size_t)dm.h - 1;
+            if (j >= dw) j -= dw;
+            z = j / (size_t)dm.w;
+            x = j - z * (size_t)dm.w;
+        } else {
+            j -= 2 * (hw + dw);
+            x = j < dh ? 0 : (size_t)dm.w - 1;
+            if (j >= dh) j -= dh;
+            z = j / (size_t)dm.h;
+            y = j - z * (size_t)dm.h;
+        }
+        const size_t v = (z * dm.h + y) * dm.w + x;
+        if (labels[v] > 0) continue;
+        const int r = parent[v];
+        if (lo[r] != 0) lo[r] = 0;   // a stale read only repeats the store
+    }
+}
+
+// One thread per voxel. A background voxel offers the positive labels among its six neighbours to its
+// cavity's root; a neighbour across an on edge of the mask is background and is not read. lo[root] == 0
+// was stored by survey_faces, a launch that has finished: such a cavity is open for good and its voxels
+// read nothing more, which is nearly every voxel of a neurite volume (its background is one cavity).
+// Lanes of a wave hold consecutive voxels: a run of lanes with the same root is reduced in the wave and
+// its first lane updates the two words, and only where a whole load does not already cover the run's
+// value. Minima and maxima: the result does not depend on the order in which they arrive.
+__global__ __launch_bounds__(kThreads) void survey(const int* __restrict__ labels,
+                                                  const unsigned char* __restrict__ mask,
+                                                  const int* __restrict__ parent, int* lo, int* hi, Dims dm) {
+    const size_t n = (size_t)dm.n, stride = (size_t)gridDim.x * blockDim.x;
+    const unsigned hw = (unsigned)dm.h * (unsigned)dm.w;
+    const int lane = threadIdx.x & 63;
+    const size_t rounds = (n + stride - 1) / stride;   // whole waves stay in the loop together
+    size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t it = 0; it < rounds; ++it, g += stride) {
+        int root = -1 - lane;   // foreground and out-of-range lanes: distinct, never an address
+        int mn = kNoLabel, mx = 0;
+        if (g < n) {
+            const unsigned m = mask[g];
+            if (m & kBitOn) {
+                root = parent[g];
+                // a plain load, through L1: only the launch before this one stores a 0, this one's minima are
+                // positive, and any other value read here, whatever its age, only means "not marked open"
+                if (lo[root] != 0) {
+                    const unsigned i = (unsigned)g;
+                    const unsigned row = i / (unsigned)dm.w, x = i - row * (unsigned)dm.w;
+                    const unsigned z = row / (unsigned)dm.h, y = row - z * (unsigned)dm.h;
+                    auto offer = [&](int l) {
+                        if (l > 0) {
+                            mn = min(mn, l);
+                            mx = max(mx, l);
+                        }
+                    };
+                    if (z > 0) offer(labels[i - hw]);
+                    if (y > 0) offer(labels[i - (unsigned)dm.w]);
+                    if (x > 0) offer(labels[i - 1]);
+                    // the mask holds no edge that leaves the volume: a cleared bit may be the face
+                    if (!(m & kBitX) && (int)x < dm.w - 1) offer(labels[i + 1]);
+                    if (!(m & kBitY) && (int)y < dm.h - 1) offer(labels[i + (unsigned)dm.w]);
+                    if (!(m & kBitZ) && (int)z < dm.d - 1) offer(labels[i + hw]);
+                }
+            }
+        }
+        if (!__ballot(mx > 0)) continue;   // the same in every lane of the wave
+        const int prev = __shfl_up(root, 1);
+        const bool head = lane == 0 || prev != root;
+        const unsigned long long heads = __ballot(head);
+        const int mine = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));   // my run's first lane
+        // the smallest and the largest offer of [lane, end of the run]
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int other_mn = __shfl_down(mn, d), other_mx = __shfl_down(mx, d);
+            const int theirs = __shfl_down(mine, d);
+            if (lane + d < 64 && theirs == mine) {
+                mn = min(mn, other_mn);
+                mx = max(mx, other_mx);
+            }
+        }
+        if (head && mx > 0) {
+            if (__hip_atomic_load(lo + root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > mn) atomicMin(lo + root, mn);
+            if (__hip_atomic_load(hi + root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mx) atomicMax(hi + root, mx);
+        }
+    }
+}
+
+// out[v] = labels[v], or the one label around the cavity of a background voxel whose cavity is a hole.
+// out may be labels: a thread reads only its own voxel of it before writing it. counts[0] += holes (counted
+// at the cavity's root voxel), counts[1] += filled voxels: summed per wave, one 64-bit add each.
+__global__ __launch_bounds__(kThreads) void fill(const int* labels, const int* __restrict__ parent,
+                                                const int* __restrict__ lo, const int* __restrict__ hi, int* out,
+                                                unsigned long long* counts, int n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const size_t rounds = ((size_t)n + stride - 1) / stride;   // whole waves stay in the loop together
+    size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long holes = 0, voxels = 0;
+    for (size_t it = 0; it < rounds; ++it, g += stride) {
+        bool filled = false, at_root = false;
+        if (g < (size_t)n) {
+            int l = labels[g];
+            if (l <= 0) {
+                const int r = parent[g];
+                const int a = lo[r];
+                if (a > 0 && a == hi[r]) {
+                    l = a;
+                    filled = true;
+                    at_root = r == (int)g;
+                }
+            }
+            out[g] = l;
+        }
+        voxels += (unsigned long long)__popcll(__ballot(filled));
+        holes += (unsigned long long)__popcll(__ballot(at_root));
+    }
+    if (lane == 0 && voxels) atomicAdd(counts + 1, voxels);
+    if (lane == 0 && holes) atomicAdd(counts, holes);
+}
+
 // ---- streamed slabs -----------------------------------------------------------------
 // state words on the device
 constexpr int kIdsUsed = 0, kOverflow = 1, kSegments = 2, kSlabIds = 3;
@@ -593,6 +776,22 @@ SlabLayout slab_layout_of(const Dims& dm) {
     return l;
 }
 
+// exaspim_fill_holes: the parent array, the two survey words and the mask, 13 bytes per voxel
+struct HolesLayout {
+    size_t parent_off, lo_off, hi_off, mask_off, bytes;
+};
+
+HolesLayout holes_layout_of(const Dims& dm) {
+    HolesLayout l;
+    const size_t words = align_up((size_t)dm.n * 4, 256);
+    l.parent_off = 0;
+    l.lo_off = words;
+    l.hi_off = 2 * words;
+    l.mask_off = 3 * words;
+    l.bytes = l.mask_off + align_up((size_t)dm.n, 256);
+    return l;
+}
+
 constexpr int kMaxCapacity = 2147483646;   // ids 1 .. capacity, capacity + 1 table entries
 
 long long table_scan_blocks(int capacity) { return ((long long)capacity + 1 + kScanBlock - 1) / kScanBlock; }
@@ -675,6 +874,56 @@ void label_from_mask(const Dims& dm, const Layout& l, char* ws, int min_eff, int
 }
 
 }  // namespace
+
+int launch_fill_holes_passes(const int32_t* labels, const int32_t dims[3], int32_t* out, int64_t* counts,
+                             void* workspace, int first, int last, hipStream_t s) {
+    Dims dm;
+    if (!valid_dims(dims, &dm) || first < 0 || last >= kFillHolesPasses) return EXASPIM_E_INVALID;
+    const HolesLayout l = holes_layout_of(dm);
+    char* ws = static_cast<char*>(workspace);
+    int* parent = reinterpret_cast<int*>(ws + l.parent_off);
+    int* lo = reinterpret_cast<int*>(ws + l.lo_off);
+    int* hi = reinterpret_cast<int*>(ws + l.hi_off);
+    unsigned char* mask = reinterpret_cast<unsigned char*>(ws + l.mask_off);
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads);
+    for (int pass = first; pass <= last; ++pass) {
+        switch (pass) {
+        case 0:
+            if (dm.w % 4 == 0 && ((uintptr_t)labels & 15) == 0)
+                edge_mask_background<4><<<capped_grid((size_t)dm.n / 4, kThreads), kThreads, 0, s>>>(labels, mask, dm);
+            else
+                edge_mask_background<1><<<grid, kThreads, 0, s>>>(labels, mask, dm);
+            break;
+        case 1:
+            tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(mask, parent, dm, tiles_x, tiles_y, n_tiles);
+            break;
+        case 2:
+            face_merge<<<grid, kThreads, 0, s>>>(mask, parent, dm);
+            break;
+        case 3:
+            flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+            break;
+        case 4: {
+            EXA_CHECK_HIP(hipMemsetD32Async(lo, kNoLabel, (size_t)dm.n, s));
+            EXA_CHECK_HIP(hipMemsetAsync(hi, 0, (size_t)dm.n * 4, s));
+            const size_t faces = 2 * ((size_t)dm.h * dm.w + (size_t)dm.d * dm.w + (size_t)dm.d * dm.h);
+            survey_faces<<<capped_grid(faces, kThreads), kThreads, 0, s>>>(labels, parent, lo, dm);
+            survey<<<grid, kThreads, 0, s>>>(labels, mask, parent, lo, hi, dm);
+            break;
+        }
+        default:
+            EXA_CHECK_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
+            fill<<<grid, kThreads, 0, s>>>(labels, parent, lo, hi, out, reinterpret_cast<unsigned long long*>(counts),
+                                           dm.n);
+            break;
+        }
+    }
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
 }  // namespace exaspim
 
 using namespace exaspim;
@@ -762,6 +1011,33 @@ extern "C" int exaspim_watershed_fragments(const void* aff_dev, int32_t aff_dtyp
     label_from_mask(dm, l, ws, min_eff, labels_dev, n_fragments_dev, s);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
+}
+
+extern "C" size_t exaspim_fill_holes_workspace_bytes(const int32_t dims[3]) {
+    Dims dm;
+    if (!valid_dims(dims, &dm)) {
+        set_error("fill_holes_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return holes_layout_of(dm).bytes;
+}
+
+extern "C" int exaspim_fill_holes(const int32_t* labels_dev, const int32_t dims[3], int32_t* out_dev,
+                                  int64_t* counts_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* stream) {
+    EXA_CHECK_ARG(labels_dev && dims && out_dev && counts_dev && workspace_dev, "fill_holes: NULL argument");
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(dims, &dm), "fill_holes: dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && ((uintptr_t)counts_dev & 7) == 0 &&
+                      (((uintptr_t)labels_dev | (uintptr_t)out_dev) & 3) == 0,
+                  "fill_holes: misaligned buffer");
+    const size_t need = holes_layout_of(dm).bytes;
+    if (workspace_bytes < need) {
+        set_error("fill_holes: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return EXASPIM_E_WORKSPACE;
+    }
+    return launch_fill_holes_passes(labels_dev, dims, out_dev, counts_dev, workspace_dev, 0, kFillHolesPasses - 1,
+                                    (hipStream_t)stream);
 }
 
 // ---- the streamed form ---------------------------------------------------------------------------

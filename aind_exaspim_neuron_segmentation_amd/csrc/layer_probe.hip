@@ -332,4 +332,14 @@ int probe_dbf_pass(int axis, const int32_t* labels, const int32_t* in, int32_t* 
     return launch_dbf_pass(axis, labels, in, out, dims, black_border, stream);
 }
 
+// The passes first .. last of exaspim_fill_holes on their own (launch_fill_holes_passes), for
+// tools/holes_rate.py to time them apart. The workspace is one of exaspim_fill_holes_workspace_bytes(dims).
+int probe_fill_holes_passes(const int32_t* labels, const int32_t dims[3], int32_t* out, int64_t* counts,
+                            void* workspace, int first, int last, hipStream_t stream) {
+    EXA_CHECK_ARG(labels && dims && out && counts && workspace, "probe_fill_holes_passes: NULL buffer");
+    EXA_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)counts & 7) == 0,
+                  "probe_fill_holes_passes: misaligned buffer");
+    return launch_fill_holes_passes(labels, dims, out, counts, workspace, first, last, stream);
+}
+
 }  // extern "C"

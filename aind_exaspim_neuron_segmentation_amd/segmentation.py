@@ -10,7 +10,8 @@ with exactly defined parts.
   mean-affinity agglomeration on the host (region_graph,
   premerge_region_graph, contract_dominant_edges, agglomerate,
   agglomerate_affinities; DESIGN 6e, 6h, 6j);
-* what the reference's skeletonize (257-291) starts from: the
+* what the reference's skeletonize (257-291) starts from: the enclosed
+  cavities of every label closed (fill_holes), then the
   distance-to-boundary field of all labels and the per-label table of sizes,
   boxes and field maxima (distance_to_boundary, segment_table; DESIGN 6i);
 * the same for volumes that arrive in z slabs (ComponentsStream,
@@ -1103,6 +1104,118 @@ def _checked_labels(labels, fn):
     return labels.contiguous(), tuple(int(v) for v in labels.shape)
 
 
+def _fill_holes_on_device(labels):
+    """
+    exaspim_fill_holes on a device tensor: the filled labels and the two
+    counts, both left on the device (nothing is synchronised).
+
+    Parameters
+    ----------
+    labels : torch.Tensor
+        int32 (D, H, W) tensor on a HIP device. It is only read.
+
+    Returns
+    -------
+    filled : torch.Tensor
+        int32 (D, H, W), a new tensor.
+    counts : torch.Tensor
+        int64 (2,): the number of holes filled and the number of voxels
+        filled.
+    """
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"_fill_holes_on_device needs a torch tensor, got {type(labels).__name__}")
+    labels, dims = _checked_labels(labels, "fill_holes")
+    device = labels.device
+    lib = _native.lib()
+    need = lib.exaspim_fill_holes_workspace_bytes(_native.int3(dims))
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        filled = torch.empty(dims, dtype=torch.int32, device=device)
+        counts = torch.empty(2, dtype=torch.int64, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_fill_holes(labels.data_ptr(), _native.int3(dims), filled.data_ptr(), counts.data_ptr(),
+                                   workspace.data_ptr(), need, _stream(device)),
+            "exaspim_fill_holes",
+        )
+    return filled, counts
+
+
+def fill_holes(labels, *, return_counts=False, return_device_tensor=False):
+    """
+    Closes the enclosed cavities of every label at once, on the device: what
+    the reference's skeletonize (inference.py:257-291) asks of
+    kimimaro.skeletonize with fill_holes=True before the distance-to-boundary
+    field is taken, so that a few dark voxels inside a soma or a thick neurite
+    do not bound the field from the inside.
+
+    What this is, exactly, in integers: a voxel is background iff labels <= 0
+    (distance_to_boundary's convention). A cavity is a 6-connected component
+    of background voxels. A cavity is a hole of label L iff (1) none of its
+    voxels lies on a face of the volume, i.e. at index 0 or n - 1 of any
+    axis, and (2) the positive labels among the six neighbours of its voxels
+    are exactly the one value L. Every voxel of a hole of L becomes L,
+    negative voxels inside the hole included; every other voxel keeps its
+    value bit for bit. So cavities that touch a face stay; cavities bounded
+    by two or more labels stay, and so does a cavity that also holds an
+    island of another label M (its neighbours are {L, M}); a cavity that holds
+    a floating piece of L itself is filled; positive voxels never change, so a
+    label enclosed by another label is not removed; with a single-voxel axis
+    every voxel lies on a face and nothing is filled, which is what
+    scipy.ndimage.binary_fill_holes gives on a 3-D array of depth 1.
+
+    What equals what: for every L take binary_fill_holes(labels == L) with
+    scipy's default 6-connected structure. On volumes where no positive voxel
+    lies inside the filled region of another label, the result equals the
+    union of that per-label fill over every L (tests/holes_ref.py holds the
+    two forms to each other).
+
+    What this is not: the name follows the reference's keyword; the result
+    is not claimed to equal the fill_voids package or kimimaro, neither of
+    which the project or its tests depend on. No slab-streamed form, no
+    removal of labels enclosed by other labels, no fix_borders.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device (e.g. from
+        agglomerate_affinities(..., return_device_tensor=True)), or a numpy
+        array, which is uploaded to cuda:0. It is only read, never changed.
+        D * H * W must not exceed 2^31 - 1.
+    return_counts : bool, optional
+        Also return the number of holes and of voxels filled (one read of
+        the device). Default is False.
+    return_device_tensor : bool, optional
+        Return the labels as a device tensor instead of a numpy array.
+        Default is False.
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W), a new array or tensor; with return_counts the tuple
+        (labels, n_holes, n_voxels), the two counts as ints.
+
+    Raises
+    ------
+    TypeError
+        If labels is not int32.
+    ValueError
+        If labels is not 3-D, is empty or has more than 2^31 - 1 voxels.
+    RuntimeError
+        If labels is a tensor on a CPU device, or there is no HIP device to
+        upload an array to.
+    """
+    labels, _ = _checked_labels(labels, "fill_holes")
+    filled, counts = _fill_holes_on_device(labels)
+    with torch.cuda.device(filled.device):
+        out = filled if return_device_tensor else filled.cpu().numpy()
+        if return_counts:
+            n_holes, n_voxels = (int(v) for v in counts.cpu())
+            return out, n_holes, n_voxels
+    return out
+
+
 def distance_to_boundary(labels, *, black_border=False, return_device_tensor=False):
     """
     The distance-to-boundary field of every label at once, on the device:
@@ -1125,8 +1238,9 @@ def distance_to_boundary(labels, *, black_border=False, return_device_tensor=Fal
     What this is not: compared with edt, which the tests do not depend on
     (the oracle in tests/dbf_ref.py is brute force and a per-label scipy
     EDT); anisotropic (the reference passes (1, 1, 1));
-    TEASAR's paths, its fill_holes or its fix_borders, which stay with the
-    host skeletoniser.
+    TEASAR's paths or its fix_borders, which stay with the host
+    skeletoniser. The reference fills holes first: fill_holes does that on
+    the device, and this function takes the labels as they are given.
 
     Parameters
     ----------
@@ -1188,9 +1302,10 @@ def segment_table(labels, dbf=None, *, n_labels=None, return_device_tensors=Fals
     dbf. Every output has K + 1 rows, K = n_labels, and is a pure function
     of the input.
 
-    What this is not: TEASAR. The paths, fill_holes, fix_borders and the
-    SWC export stay with the host skeletoniser, which downloads the field
-    and this table instead of recomputing an EDT of the whole volume.
+    What this is not: TEASAR. The paths, fix_borders and the SWC export
+    stay with the host skeletoniser, which downloads the field and this
+    table instead of recomputing an EDT of the whole volume (fill_holes is a
+    function of its own here, run on the labels before the field).
 
     Parameters
     ----------

@@ -62,7 +62,9 @@ extern "C" {
  *    later within 5: exaspim_region_graph_contract_dominant (and its workspace query): the exact
  *    contraction of dominant edges on the device before the host agglomeration;
  *    later within 5: exaspim_unet_carry_rows, exaspim_unet_forward_prepared_carry_y (struct
- *    exaspim_unet_carry_y), EXASPIM_OPT_CARRY_NO_ROWS: first-level rows carried along y as well */
+ *    exaspim_unet_carry_y), EXASPIM_OPT_CARRY_NO_ROWS: first-level rows carried along y as well;
+ *    later within 5: exaspim_fill_holes (and its workspace query): the enclosed cavities of every label
+ *    closed on the device before the distance-to-boundary field is taken */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -1012,6 +1014,51 @@ int exaspim_segment_table(const int32_t* labels_dev, const int32_t* dbf_dev /* m
                           const int32_t dims[3], int32_t n_labels,
                           int64_t* sizes_dev, int32_t* boxes_dev, int32_t* peak_dev, int32_t* peak_index_dev,
                           void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- enclosed cavities of every label, closed (later within ABI 5) ------
+ *      The reference's skeletonize (inference.py:257-291) calls kimimaro.skeletonize(..., fill_holes=True):
+ *      every segment has its enclosed cavities closed before the distance-to-boundary field is taken. This
+ *      is that step for all labels at once, with an exact definition in integers. It is named after the
+ *      reference's keyword and checked against the two oracles in tests/ (holes_ref.py); it is not claimed
+ *      to equal the fill_voids package or kimimaro.
+ *
+ *      labels are int32 (dims), C order.
+ *       1. A voxel is background iff its label is <= 0 (exaspim_dbf's convention).
+ *       2. A cavity is a 6-connected component of background voxels.
+ *       3. A cavity is a hole of label L iff (a) none of its voxels lies on a face of the volume (index 0
+ *          or n - 1 of any axis) and (b) the positive labels among the six neighbours of its voxels are
+ *          exactly the one value L.
+ *       4. Every voxel of a hole of L becomes L, negative voxels inside the hole included. Every other
+ *          voxel keeps its value bit for bit.
+ *      So: cavities that touch a face stay; cavities bounded by two or more labels stay (an island of
+ *      another label M inside a cavity of L makes its neighbours {L, M}); a floating piece of L itself
+ *      inside the cavity does not keep it open; positive voxels never change (a label enclosed by another
+ *      label is not removed); with a single-voxel axis every voxel lies on a face and nothing is filled,
+ *      which is what scipy.ndimage.binary_fill_holes gives on a 3-D array of depth 1.
+ *      Relation to the per-label oracle: on volumes where no positive voxel lies inside the filled region
+ *      of another label, the result equals the union over every L of binary_fill_holes(labels == L) with
+ *      scipy's default 6-connected structure, each written as L. */
+
+/* Scratch bytes of exaspim_fill_holes: a parent array, two survey words and a mask byte per voxel, about
+ * 13 bytes per voxel. 0 (and a message) if a dim is not positive or the volume has more than 2^31 - 1
+ * voxels. */
+size_t exaspim_fill_holes_workspace_bytes(const int32_t dims[3]);
+
+/* out_dev (int32, dims) = labels_dev with every hole filled, as defined above (inference.py:257-291: the
+ * fill_holes=True of kimimaro.skeletonize); counts_dev[0] = the number of holes filled, counts_dev[1] =
+ * the number of voxels filled. A pure function of the input. labels_dev is only read, and out_dev ==
+ * labels_dev is allowed: the last pass reads and writes the same voxel only. Launches on "stream" alone:
+ * the background's edge mask, the tile-local union-find of exaspim_components with its face merge and
+ * flatten, a survey of each cavity (its faces first, then atomic minima and maxima of the neighbouring
+ * labels per cavity root, reduced inside a wave first), and the fill; minima, maxima and integer adds, so
+ * nothing depends on arrival order. No inter-workgroup waiting, nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels
+ * or a misaligned buffer (workspace_dev 16 bytes, counts_dev 8, labels_dev and out_dev 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than exaspim_fill_holes_workspace_bytes(dims): all before
+ * anything is launched, and no output is touched. */
+int exaspim_fill_holes(const int32_t* labels_dev, const int32_t dims[3], int32_t* out_dev,
+                       int64_t* counts_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
+                       void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
