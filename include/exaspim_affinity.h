@@ -64,7 +64,9 @@ extern "C" {
  *    later within 5: exaspim_unet_carry_rows, exaspim_unet_forward_prepared_carry_y (struct
  *    exaspim_unet_carry_y), EXASPIM_OPT_CARRY_NO_ROWS: first-level rows carried along y as well;
  *    later within 5: exaspim_fill_holes (and its workspace query): the enclosed cavities of every label
- *    closed on the device before the distance-to-boundary field is taken */
+ *    closed on the device before the distance-to-boundary field is taken;
+ *    later within 5: exaspim_geodesic_begin, exaspim_geodesic_sweeps, exaspim_geodesic_farthest (and their
+ *    workspace queries): the geodesic distance-from-source field of every label and its farthest voxels */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -1059,6 +1061,92 @@ size_t exaspim_fill_holes_workspace_bytes(const int32_t dims[3]);
 int exaspim_fill_holes(const int32_t* labels_dev, const int32_t dims[3], int32_t* out_dev,
                        int64_t* counts_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
                        void* stream);
+
+/* ---- geodesic distance-from-source field of every label (later within ABI 5) ------
+ *      The reference's skeletonize (inference.py:257-291) hands the labels to kimimaro's TEASAR, which
+ *      needs a root for every segment and the distance-from-root field (DAF): the root is the maximum of
+ *      the distance-to-boundary field of a soma, otherwise the voxel farthest from an arbitrary voxel of
+ *      the segment; the DAF gives TEASAR its targets and the second term of its penalty field. kimimaro
+ *      takes both from one serial Dijkstra per label on the host. This is the single-source field of all
+ *      labels at once, with an exact definition in float32. Checked against the two oracles in tests/
+ *      (geodesic_ref.py); not claimed to equal dijkstra3d or kimimaro, whose background and unreachable
+ *      conventions were not compared.
+ *
+ *      labels are int32 (dims), C order; a voxel with label <= 0 is background. K = n_labels.
+ *      sources is int32 (K + 1): the C-order linear index of the source voxel of each label; row 0 is
+ *      ignored, -1 means the label has no source. Any other row L is valid iff 0 <= s < D*H*W and
+ *      labels[s] == L; an invalid row is counted and the label treated as having no source.
+ *       1. Voxels u, v are adjacent iff they differ by at most 1 in every coordinate, are not equal
+ *          (the 26-neighbourhood, in-volume only) and carry the same label L with 1 <= L <= K.
+ *       2. The step weight w(u -> v), float32. Euclidean mode (cost NULL): 1.0f, 0x3FB504F3 (fl32(sqrt 2))
+ *          or 0x3FDDB3D7 (fl32(sqrt 3)) by the number of coordinates that differ; constants, no root is
+ *          taken on the device. Cost mode (cost float32, dims): w = cost[v], the cost of the voxel
+ *          entered, if cost[v] >= 0 (-0.0 counts as 0); a voxel whose cost is negative, NaN or +inf
+ *          cannot be entered (w = +inf).
+ *       3. The field d (float32, dims) is the least solution of d[source] = 0 and
+ *          d[v] = min over adjacent u of fl32(d[u] + w(u -> v)), every sum one IEEE round-to-nearest
+ *          float32 addition. Adding a non-negative float32 is monotone and never decreases its argument,
+ *          so the least fixed point is unique, independent of the order of relaxation, and equal bit for
+ *          bit to what a heap Dijkstra computing in float32 returns.
+ *       4. A background voxel gets 0.0. A foreground voxel of a label without a valid source, of a label
+ *          above K, or not reachable from the source inside its label gets +inf.
+ *      The farthest table (K + 1 rows): far_value (float32) the largest finite value of the label,
+ *      far_index (int32) the smallest C-order index attaining it; +inf voxels are ignored; row 0, absent
+ *      labels and labels without a valid source get 0.0 and -1. */
+
+/* Scratch bytes of exaspim_geodesic_begin and _sweeps: a 16-byte header (which flag array is current, the
+ * tiles flagged in either, the invalid rows) and two int32 flags per 8 x 8 x 32 tile. 0 (and a message)
+ * if a dim is not positive or the volume has more than 2^31 - 1 voxels (exaspim_fill_holes' bound: the
+ * squared diagonal that exaspim_dbf also bounds has no part in a float32 field). */
+size_t exaspim_geodesic_workspace_bytes(const int32_t dims[3]);
+
+/* Starts the field defined above (inference.py:257-291: the root search and the distance-from-root field
+ * of kimimaro.skeletonize): field_dev = +inf on foreground and 0 on background, 0 at every valid source,
+ * the tiles that hold one or see it in their halo flagged for the first sweep. state_dev[0] = the number of tiles flagged,
+ * state_dev[1] = the number of invalid source rows. labels_dev and sources_dev are only read; the
+ * workspace carries the flags to exaspim_geodesic_sweeps and must not be touched in between. Three
+ * launches on "stream", nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels,
+ * a negative n_labels or a misaligned buffer (workspace_dev 16 bytes, the rest 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_geodesic_workspace_bytes(dims): all before anything is launched, and no output is touched. */
+int exaspim_geodesic_begin(const int32_t* labels_dev, const int32_t dims[3], const int32_t* sources_dev,
+                           int32_t n_labels, float* field_dev, int32_t* state_dev /* [2] */,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Runs "sweeps" >= 1 sweeps of the relaxation on a field exaspim_geodesic_begin started (the same labels,
+ * dims, n_labels and workspace; inference.py:257-291). A sweep is one workgroup per flagged tile: the tile
+ * and a one-voxel halo are relaxed in LDS until nothing in the tile changes (at most 2049 rounds, after
+ * which it has converged anyway), the voxels that fell are stored, and the tiles that see one of them in
+ * their halo -- faces, edges and corners -- are flagged for the next sweep. state_dev[0] = the number of
+ * tiles flagged for the sweep after the last one, 0 meaning that field_dev is the field defined above;
+ * state_dev[1] = the invalid source rows, as before. Once converged, further sweeps do nothing. Tiles of
+ * one sweep may read each other's voxels before or after they are stored: both values bound the answer
+ * from above and the writer flags the reader, so no workgroup waits for another and the result does not
+ * depend on the schedule. cost_dev (float32, dims) selects cost mode and is only read; pass the same
+ * value to every call of one field. Two launches per sweep on "stream", nothing allocated, nothing
+ * synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer other than cost_dev, dims as above, a negative n_labels,
+ * sweeps < 1 or a misaligned buffer; EXASPIM_E_WORKSPACE for a short workspace: all before
+ * anything is launched, and no output is touched. */
+int exaspim_geodesic_sweeps(const int32_t* labels_dev, const float* cost_dev /* may be NULL */,
+                            const int32_t dims[3], int32_t n_labels, float* field_dev, int32_t sweeps,
+                            int32_t* state_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+
+/* Scratch bytes of exaspim_geodesic_farthest: 8 bytes per row, n_labels + 1 rows, rounded up to 16. 0 (and
+ * a message) if n_labels is negative. */
+size_t exaspim_geodesic_farthest_workspace_bytes(int32_t n_labels);
+
+/* The farthest table of a converged field, as defined above (inference.py:257-291: kimimaro's find_root
+ * and TEASAR's first target): a 64-bit atomic maximum of (field bits, 2^32 - 1 - index) per label over the
+ * finite voxels, runs of equal labels reduced inside a wave first; a pure function of the input. Three
+ * launches on "stream", nothing allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL pointer,
+ * dims as above, a negative n_labels or a misaligned buffer (workspace_dev 16 bytes, the rest 4);
+ * EXASPIM_E_WORKSPACE for a short workspace: all before anything is launched. */
+int exaspim_geodesic_farthest(const int32_t* labels_dev, const float* field_dev, const int32_t dims[3],
+                              int32_t n_labels, float* far_value_dev, int32_t* far_index_dev,
+                              void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
