@@ -260,6 +260,10 @@ SIGNATURES = {
     "exaspim_geodesic_sweeps": (_i32, [_vp, _vp, _I32x3, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_geodesic_farthest_workspace_bytes": (_sz, [_i32]),
     "exaspim_geodesic_farthest": (_i32, [_vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_geodesic_parents_begin": (_i32, [_vp, _I32x3, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_geodesic_parents_sweeps": (_i32, [_vp, _vp, _vp, _I32x3, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "exaspim_geodesic_parents_finish": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp]),
+    "exaspim_trace_paths": (_i32, [_vp, _vp, _I32x3, _vp, _i32, _vp, _vp, ctypes.c_int64, _vp, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

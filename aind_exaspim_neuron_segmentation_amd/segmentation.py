@@ -16,7 +16,10 @@ with exactly defined parts.
   boxes and field maxima (distance_to_boundary, segment_table; DESIGN 6i);
 * TEASAR's next whole-volume stage: the 26-connected geodesic distance of
   every voxel from its label's source, bit for bit a float32 Dijkstra, and
-  each label's farthest voxel (geodesic_field, DESIGN 6l);
+  each label's farthest voxel (geodesic_field); then the parental
+  field of that field by an order-free definition of its own and the paths
+  from the sources to given targets (geodesic_parents, trace_paths, DESIGN
+  6m);
 * the same for volumes that arrive in z slabs (ComponentsStream,
   RegionGraphStream) and the one streaming driver behind
   affinities_to_components_streaming and agglomerate_affinities_streaming
@@ -1085,25 +1088,26 @@ def agglomerate_affinities(affinities, agglomeration_thresholds=[0.6, 0.8, 0.9],
 DBF_INF = 2**31 - 1
 
 
-def _checked_labels(labels, fn):
+def _checked_labels(labels, fn, what="labels"):
     """
     The front matter of distance_to_boundary and segment_table: labels as a
     contiguous int32 (D, H, W) tensor on a HIP device and its dims. A numpy
-    array is checked before any device is asked for.
+    array is checked before any device is asked for. "what" names the
+    argument in the messages.
     """
 
     def check(a):
         if a.ndim != 3:
-            raise ValueError(f"{fn}: labels must be (D, H, W), got {tuple(a.shape)}")
+            raise ValueError(f"{fn}: {what} must be (D, H, W), got {tuple(a.shape)}")
         if min(a.shape) < 1:
             raise ValueError(f"{fn}: empty volume {tuple(a.shape)}")
 
-    labels = _on_device(labels, fn, "labels", (np.int32,), check=check)
+    labels = _on_device(labels, fn, what, (np.int32,), check=check)
     if labels.dtype != torch.int32:
-        raise TypeError(f"labels must be int32, got {labels.dtype}")
+        raise TypeError(f"{what} must be int32, got {labels.dtype}")
     check(labels)
     if labels.device.type != "cuda":
-        raise RuntimeError(f"{fn} (MI355X) has no CPU path: labels must be on a HIP device, got {labels.device}")
+        raise RuntimeError(f"{fn} (MI355X) has no CPU path: {what} must be on a HIP device, got {labels.device}")
     return labels.contiguous(), tuple(int(v) for v in labels.shape)
 
 
@@ -1484,6 +1488,80 @@ def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_swee
     return field, far_value, far_index
 
 
+def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_read, max_sweeps, field=None):
+    """
+    The front matter geodesic_field and geodesic_parents share: every argument
+    checked in one order, arrays before any device is asked for, then labels,
+    sources and cost as contiguous tensors on one HIP device. "field", which
+    geodesic_parents alone has, is float32 of the labels' shape as cost is and
+    is checked after it. Returns (labels, dims, sources, cost, field).
+    """
+    for name, value in (("sweeps_per_read", sweeps_per_read), ("max_sweeps", max_sweeps)):
+        if value is None and name == "max_sweeps":
+            continue
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise TypeError(f"{fn}: {name} must be an integer, got {type(value).__name__}")
+    if sweeps_per_read < 1:
+        raise ValueError(f"{fn}: sweeps_per_read must be at least 1, got {sweeps_per_read}")
+    if max_sweeps is not None and max_sweeps < 0:
+        raise ValueError(f"{fn}: max_sweeps must not be negative, got {max_sweeps}")
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
+        if n_labels < 0:
+            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+
+    def check_sources(a):
+        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
+            rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
+            raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
+
+    def check_cost(a, shape, what="cost"):
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{fn}: {what} must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
+
+    # every array is checked before any of them is uploaded
+    for what, a, dtype in (("sources", sources, np.int32), ("cost", cost, np.float32),
+                           ("field", field, np.float32)):
+        if isinstance(a, np.ndarray) and a.dtype != dtype:
+            raise TypeError(f"{what} must be {np.dtype(dtype)}, got {a.dtype}")
+    if isinstance(sources, np.ndarray):
+        check_sources(sources)
+    for what, a in (("cost", cost), ("field", field)):
+        if isinstance(a, np.ndarray) and isinstance(labels, (np.ndarray, torch.Tensor)):
+            check_cost(a, labels.shape, what)
+    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
+        if isinstance(sources, torch.Tensor):
+            if sources.dtype != torch.int32:
+                raise TypeError(f"sources must be int32, got {sources.dtype}")
+            check_sources(sources)
+        for what, a in (("cost", cost), ("field", field)):
+            if isinstance(a, torch.Tensor):
+                if a.dtype != torch.float32:
+                    raise TypeError(f"{what} must be float32, got {a.dtype}")
+                check_cost(a, labels.shape, what)
+    labels, dims = _checked_labels(labels, fn)
+    device = labels.device
+    sources = _on_device(sources, fn, "sources", (np.int32,))
+    if sources.dtype != torch.int32:
+        raise TypeError(f"sources must be int32, got {sources.dtype}")
+    check_sources(sources)
+    if sources.device != device:
+        raise RuntimeError(f"{fn}: sources must be on the labels' device {device}, got {sources.device}")
+    both = []
+    for what, a in (("cost", cost), ("field", field)):
+        if a is not None:
+            a = _on_device(a, fn, what, (np.float32,))
+            if a.dtype != torch.float32:
+                raise TypeError(f"{what} must be float32, got {a.dtype}")
+            check_cost(a, dims, what)
+            if a.device != device:
+                raise RuntimeError(f"{fn}: {what} must be on the labels' device {device}, got {a.device}")
+            a = a.contiguous()
+        both.append(a)
+    return labels, dims, sources.contiguous(), both[0], both[1]
+
+
 def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read=32, max_sweeps=None,
                    return_farthest=False, return_device_tensors=False, stats=None):
     """
@@ -1529,9 +1607,10 @@ def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read
 
     What this is not: equal to dijkstra3d or kimimaro (their background and
     unreachable conventions were not compared; neither is a dependency of
-    the project or its tests); the parental field, path extraction, rolling
-    invalidation, fix_borders or the SWC export; anisotropic (the reference
-    passes (1, 1, 1)); multi-source; slab-streamed.
+    the project or its tests); the parental field or path extraction (those
+    are geodesic_parents and trace_paths); rolling invalidation, fix_borders
+    or the SWC export; anisotropic (the reference passes (1, 1, 1));
+    multi-source; slab-streamed.
 
     Parameters
     ----------
@@ -1579,72 +1658,302 @@ def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read
         another device, there is no HIP device to upload an array to, or
         max_sweeps is exceeded.
     """
-    fn = "geodesic_field"
-    for name, value in (("sweeps_per_read", sweeps_per_read), ("max_sweeps", max_sweeps)):
-        if value is None and name == "max_sweeps":
-            continue
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-            raise TypeError(f"{fn}: {name} must be an integer, got {type(value).__name__}")
-    if sweeps_per_read < 1:
-        raise ValueError(f"{fn}: sweeps_per_read must be at least 1, got {sweeps_per_read}")
-    if max_sweeps is not None and max_sweeps < 0:
-        raise ValueError(f"{fn}: max_sweeps must not be negative, got {max_sweeps}")
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
-
-    def check_sources(a):
-        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
-            rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
-            raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
-
-    def check_cost(a, shape):
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError(f"{fn}: cost must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
-
-    # every array is checked before any of them is uploaded
-    for what, a, dtype in (("sources", sources, np.int32), ("cost", cost, np.float32)):
-        if isinstance(a, np.ndarray) and a.dtype != dtype:
-            raise TypeError(f"{what} must be {np.dtype(dtype)}, got {a.dtype}")
-    if isinstance(sources, np.ndarray):
-        check_sources(sources)
-    if isinstance(cost, np.ndarray) and isinstance(labels, (np.ndarray, torch.Tensor)):
-        check_cost(cost, labels.shape)
-    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
-        if isinstance(sources, torch.Tensor):
-            if sources.dtype != torch.int32:
-                raise TypeError(f"sources must be int32, got {sources.dtype}")
-            check_sources(sources)
-        if isinstance(cost, torch.Tensor):
-            if cost.dtype != torch.float32:
-                raise TypeError(f"cost must be float32, got {cost.dtype}")
-            check_cost(cost, labels.shape)
-    labels, dims = _checked_labels(labels, fn)
+    labels, dims, sources, cost, _ = _checked_geodesic_arguments(
+        "geodesic_field", labels, sources, cost, n_labels, sweeps_per_read, max_sweeps)
     device = labels.device
-    sources = _on_device(sources, fn, "sources", (np.int32,))
-    if sources.dtype != torch.int32:
-        raise TypeError(f"sources must be int32, got {sources.dtype}")
-    check_sources(sources)
-    if sources.device != device:
-        raise RuntimeError(f"{fn}: sources must be on the labels' device {device}, got {sources.device}")
-    if cost is not None:
-        cost = _on_device(cost, fn, "cost", (np.float32,))
-        if cost.dtype != torch.float32:
-            raise TypeError(f"cost must be float32, got {cost.dtype}")
-        check_cost(cost, dims)
-        if cost.device != device:
-            raise RuntimeError(f"{fn}: cost must be on the labels' device {device}, got {cost.device}")
-        cost = cost.contiguous()
     field, far_value, far_index = _geodesic_on_device(
-        labels, sources.contiguous(), cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps),
+        labels, sources, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps),
         bool(return_farthest), stats)
     with torch.cuda.device(device):
         out = (field, far_value, far_index) if return_farthest else (field,)
         if not return_device_tensors:
             out = tuple(t.cpu().numpy() for t in out)
     return out if return_farthest else out[0]
+
+
+def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_per_read=32, max_sweeps=None,
+                                stats=None):
+    """
+    geodesic_parents on checked device tensors: the field from
+    _geodesic_on_device if none is given, exaspim_geodesic_parents_begin, then
+    exaspim_geodesic_parents_sweeps(sweeps_per_read) and one 12-byte read of
+    the state until no tile is flagged, exaspim_geodesic_parents_finish and
+    one more read. Everything stays on the device.
+
+    Parameters
+    ----------
+    labels, sources, cost, sweeps_per_read, max_sweeps
+        As in _geodesic_on_device.
+    field : torch.Tensor, optional
+        float32 (D, H, W) on the labels' device: the converged field of these
+        labels, sources and cost. Default is None: it is computed first.
+    stats : dict, optional
+        Receives "sweeps", "reads" and "tiles_flagged" of the hops pass, and
+        under "field" those of the field pass if it ran here.
+
+    Returns
+    -------
+    parents, hops : torch.Tensor
+        int32 (D, H, W).
+
+    Raises
+    ------
+    ValueError
+        For invalid rows of sources and for orphans.
+    RuntimeError
+        If max_sweeps is exceeded.
+    """
+    fn = "geodesic_parents"
+    dims = tuple(int(v) for v in labels.shape)
+    n_labels = int(sources.numel()) - 1
+    device = labels.device
+    if field is None:
+        field_stats = {}
+        field, _, _ = _geodesic_on_device(labels, sources, cost, sweeps_per_read, max_sweeps, False, field_stats)
+        if stats is not None:
+            stats["field"] = field_stats
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = lib.exaspim_geodesic_workspace_bytes(dims3)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    cost_ptr = None if cost is None else cost.data_ptr()
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        hops = torch.empty(dims, dtype=torch.int32, device=device)
+        parents = torch.empty(dims, dtype=torch.int32, device=device)
+        state = torch.zeros(3, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_geodesic_parents_begin(labels.data_ptr(), dims3, sources.data_ptr(), n_labels, field.data_ptr(),
+                                               hops.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
+            "exaspim_geodesic_parents_begin",
+        )
+        flagged, invalid, _ = (int(v) for v in state.cpu())
+        if invalid:
+            raise ValueError(f"{fn}: {invalid} row(s) of sources name no voxel of their label with a field of 0 "
+                             "(a row L must be -1 or the linear index of a voxel with labels == L and field == 0)")
+        sweeps, reads, history = 0, 1, [flagged]
+        while flagged:
+            if max_sweeps is not None and sweeps >= max_sweeps:
+                raise RuntimeError(f"{fn}: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
+                                   f"{flagged} tile(s) still flagged")
+            batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+            _native.check(
+                lib.exaspim_geodesic_parents_sweeps(labels.data_ptr(), cost_ptr, field.data_ptr(), dims3, n_labels,
+                                                    hops.data_ptr(), batch, state.data_ptr(), workspace.data_ptr(),
+                                                    need, stream),
+                "exaspim_geodesic_parents_sweeps",
+            )
+            sweeps += batch
+            flagged = int(state.cpu()[0])
+            reads += 1
+            history.append(flagged)
+        _native.check(
+            lib.exaspim_geodesic_parents_finish(labels.data_ptr(), cost_ptr, field.data_ptr(), hops.data_ptr(), dims3,
+                                                n_labels, parents.data_ptr(), state.data_ptr(), stream),
+            "exaspim_geodesic_parents_finish",
+        )
+        orphans = int(state.cpu()[2])
+        reads += 1
+        if stats is not None:
+            stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
+        if orphans:
+            raise ValueError(f"{fn}: {orphans} voxel(s) with a finite field have no tight predecessor: field is not "
+                             "the geodesic field of these labels, sources and cost")
+    return parents, hops
+
+
+def geodesic_parents(labels, sources, *, field=None, cost=None, n_labels=None, sweeps_per_read=32, max_sweeps=None,
+                     return_hops=False, return_device_tensors=False, stats=None):
+    """
+    The parental field of every label's geodesic field, on the device: for
+    every voxel the neighbour that leads back to the source of its label.
+
+    What this is: the step of TEASAR that follows the fields. The reference's
+    skeletonize (inference.py:257-291) runs kimimaro.skeletonize, which takes
+    one parental field per label over its penalty field
+    (dijkstra3d.parental_field) from a serial Dijkstra on the host and reads
+    every path off it. Here, exactly, in integers: labels, sources, cost,
+    adjacency, K and the weights w(u -> v) are geodesic_field's, and d is
+    "field", the converged result of geodesic_field on exactly these inputs.
+    An edge u -> v is tight iff u and v are adjacent, d[u] and d[v] are
+    finite, v is not its label's source, and fl32(d[u] + w(u -> v)) has the
+    bit pattern of d[v] (the one float32 addition the field was built with).
+    hops h (int32) is the least solution of h[source] = 0,
+    h[v] = 1 + min over tight u -> v of h[u]: the breadth-first distance from
+    the source over tight edges. Every voxel with finite d has one, and as an
+    integer least fixed point it is unique and independent of any order.
+    parents (int32, C-order linear index): a source gets its own index; any
+    other voxel the tight predecessor u with h[u] = h[v] - 1 that has the
+    smallest linear index. hops fall by exactly 1 along parents, so there is
+    no cycle even on a plateau where d[u] = d[v] because a cost was absorbed;
+    the chain from v reaches the source in h[v] steps, and re-adding the
+    weights along it reproduces d bit for bit. Everything else gets h = -1
+    and parent = -1: background, labels above K, labels without a source,
+    voxels with d = +inf. A voxel with finite d that is no source and has no
+    tight predecessor (an orphan) exists only if field is not the field of
+    these inputs; orphans are counted and raise, never guessed at.
+
+    The TEASAR chain, all on the device: the DAF from the root,
+    daf = geodesic_field(labels, roots); the penalty "cost" from the DBF and
+    the DAF with torch element-wise operations; pdrf =
+    geodesic_field(labels, roots, cost=cost, return_farthest=True); parents,
+    hops = geodesic_parents(labels, roots, field=pdrf, cost=cost,
+    return_hops=True); trace_paths(parents, hops, far_index) with the
+    far_index of the DAF. Only the path voxels leave the card.
+
+    What this is not: equal to dijkstra3d.parental_field or kimimaro (their
+    parents are one Dijkstra run's tie-breaks, 1-based with 0 for "none";
+    neither is a dependency of the project or its tests); rolling
+    invalidation or the choice of the next target, fix_borders, the SWC
+    export; anisotropic; multi-source; slab-streamed.
+
+    Parameters
+    ----------
+    labels, sources, cost, n_labels, sweeps_per_read, max_sweeps
+        As in geodesic_field.
+    field : torch.Tensor or numpy.ndarray, optional
+        float32 of the labels' shape, on the labels' device if a tensor: the
+        converged geodesic_field of these labels, sources and cost. Default
+        is None: it is computed first, on the device.
+    return_hops : bool, optional
+        Also return hops. Default is False.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+    stats : dict, optional
+        Receives "sweeps", "reads" and "tiles_flagged" of the hops pass (see
+        _geodesic_parents_on_device).
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W) parents; with return_hops the tuple (parents, hops).
+
+    Raises
+    ------
+    TypeError
+        As geodesic_field; also if field is not float32.
+    ValueError
+        As geodesic_field; also if field has another shape, a source's field
+        is not 0, or there are orphans: field is not the geodesic field of
+        these labels, sources and cost.
+    RuntimeError
+        As geodesic_field.
+    """
+    labels, dims, sources, cost, field = _checked_geodesic_arguments(
+        "geodesic_parents", labels, sources, cost, n_labels, sweeps_per_read, max_sweeps, field)
+    parents, hops = _geodesic_parents_on_device(
+        labels, sources, field, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps), stats)
+    with torch.cuda.device(labels.device):
+        out = (parents, hops) if return_hops else (parents,)
+        if not return_device_tensors:
+            out = tuple(t.cpu().numpy() for t in out)
+    return out if return_hops else out[0]
+
+
+def trace_paths(parents, hops, targets, *, return_device_tensors=False):
+    """
+    The paths from the sources to "targets" read off a parental field, on the
+    device (the reference's skeletonize, inference.py:257-291: kimimaro's
+    path_from_parents).
+
+    The path of a target t with hops[t] >= 0 is the hops[t] + 1 voxels
+    source = p_0, ..., p_h = t with parents[p_i] = p_(i-1): voxel v stands at
+    position hops[v] of its path. Path i is
+    voxels[offsets[i]:offsets[i + 1]], source first; offsets is the
+    exclusive cumulative sum of hops[targets] + 1, taken on the device. One
+    thread walks each target and takes at most hops[target] steps.
+
+    Parameters
+    ----------
+    parents, hops : torch.Tensor or numpy.ndarray
+        int32 (D, H, W), geodesic_parents' results: tensors on one HIP
+        device, or numpy arrays, which are uploaded to cuda:0.
+    targets : torch.Tensor or numpy.ndarray
+        int32 (T,), T >= 0: C-order linear indices; duplicates are allowed.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+
+    Returns
+    -------
+    voxels : numpy.ndarray or torch.Tensor
+        int32 (N,), N the sum of the path lengths.
+    offsets : numpy.ndarray or torch.Tensor
+        int64 (T + 1,).
+
+    Raises
+    ------
+    TypeError
+        If parents, hops or targets is not int32.
+    ValueError
+        If parents is not 3-D or is empty, hops has another shape, targets is
+        not 1-D, or a target is out of range or has hops < 0.
+    RuntimeError
+        If parents is a tensor on a CPU device, hops or targets is on another
+        device, there is no HIP device to upload an array to, or a walk is
+        broken: it leaves the volume, meets -1 or does not end on a source.
+    """
+    fn = "trace_paths"
+
+    def check_hops(a, shape):
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{fn}: hops must have the parents' shape {tuple(shape)}, got {tuple(a.shape)}")
+
+    def check_targets(a):
+        if a.ndim != 1:
+            raise ValueError(f"{fn}: targets must be (T,), got {tuple(a.shape)}")
+
+    for what, a in (("hops", hops), ("targets", targets)):
+        if isinstance(a, np.ndarray) and a.dtype != np.int32:
+            raise TypeError(f"{what} must be int32, got {a.dtype}")
+        if isinstance(a, torch.Tensor) and a.dtype != torch.int32:
+            raise TypeError(f"{what} must be int32, got {a.dtype}")
+    if isinstance(hops, (np.ndarray, torch.Tensor)) and isinstance(parents, (np.ndarray, torch.Tensor)):
+        check_hops(hops, parents.shape)
+    if isinstance(targets, (np.ndarray, torch.Tensor)):
+        check_targets(targets)
+    parents, dims = _checked_labels(parents, fn, "parents")
+    device = parents.device
+    hops = _on_device(hops, fn, "hops", (np.int32,))
+    targets = _on_device(targets, fn, "targets", (np.int32,))
+    for what, a in (("hops", hops), ("targets", targets)):
+        if a.dtype != torch.int32:
+            raise TypeError(f"{what} must be int32, got {a.dtype}")
+        if a.device != device:
+            raise RuntimeError(f"{fn}: {what} must be on the parents' device {device}, got {a.device}")
+    check_hops(hops, dims)
+    check_targets(targets)
+    hops, targets = hops.contiguous(), targets.contiguous()
+    n, n_targets = int(parents.numel()), int(targets.numel())
+    lib = _native.lib()
+    with torch.cuda.device(device):
+        offsets = torch.zeros(n_targets + 1, dtype=torch.int64, device=device)
+        total = 0
+        if n_targets:
+            wide = targets.to(torch.int64)
+            inside = (wide >= 0) & (wide < n)
+            lengths = torch.where(inside, hops.reshape(-1)[wide.clamp(0, n - 1)].to(torch.int64), -1) + 1
+            bad = int((lengths < 1).sum())      # the read that also orders the sizes below
+            if bad:
+                raise ValueError(f"{fn}: {bad} target(s) out of range or with hops < 0 (not reached from a source)")
+            torch.cumsum(lengths, 0, out=offsets[1:])
+            total = int(offsets[-1])
+        voxels = torch.empty(total, dtype=torch.int32, device=device)
+        state = torch.zeros(2, dtype=torch.int32, device=device)
+        _native.check(
+            lib.exaspim_trace_paths(parents.data_ptr(), hops.data_ptr(), _native.int3(dims),
+                                    targets.data_ptr() if n_targets else None, n_targets, offsets.data_ptr(),
+                                    voxels.data_ptr() if total else None, total, state.data_ptr(), _stream(device)),
+            "exaspim_trace_paths",
+        )
+        refused, broken = (int(v) for v in state.cpu())
+        if refused or broken:
+            raise RuntimeError(f"{fn}: {broken} broken walk(s) and {refused} refused row(s): parents and hops are not "
+                               "the results of one geodesic_parents call")
+        if not return_device_tensors:
+            return voxels.cpu().numpy(), offsets.cpu().numpy()
+    return voxels, offsets
 
 
 # Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes

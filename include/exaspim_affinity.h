@@ -66,7 +66,10 @@ extern "C" {
  *    later within 5: exaspim_fill_holes (and its workspace query): the enclosed cavities of every label
  *    closed on the device before the distance-to-boundary field is taken;
  *    later within 5: exaspim_geodesic_begin, exaspim_geodesic_sweeps, exaspim_geodesic_farthest (and their
- *    workspace queries): the geodesic distance-from-source field of every label and its farthest voxels */
+ *    workspace queries): the geodesic distance-from-source field of every label and its farthest voxels;
+ *    later within 5: exaspim_geodesic_parents_begin, exaspim_geodesic_parents_sweeps,
+ *    exaspim_geodesic_parents_finish, exaspim_trace_paths: the parental field of that field and the paths
+ *    read off it */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -1147,6 +1150,102 @@ size_t exaspim_geodesic_farthest_workspace_bytes(int32_t n_labels);
 int exaspim_geodesic_farthest(const int32_t* labels_dev, const float* field_dev, const int32_t dims[3],
                               int32_t n_labels, float* far_value_dev, int32_t* far_index_dev,
                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- parental field and root paths of every label (later within ABI 5) ------------------
+ *      The reference's skeletonize (inference.py:257-291) runs kimimaro's TEASAR, which takes one parental
+ *      field per label over its penalty field (dijkstra3d.parental_field) and reads every path off it from
+ *      a target back to the root (path_from_parents). This is the parental field of all labels at once, of
+ *      a field d that exaspim_geodesic_sweeps converged on exactly these labels, sources and cost, with a
+ *      definition that is exact in integers and independent of the schedule. Adjacency, K, valid sources
+ *      and the weights w(u -> v) are those of the section above.
+ *       1. An edge u -> v is tight iff u and v are adjacent, d[u] and d[v] are finite, v is not its label's
+ *          source, and fl32(d[u] + w(u -> v)) has the bit pattern of d[v]: one IEEE round-to-nearest
+ *          float32 addition, the one the field was built with.
+ *       2. hops h (int32) is the least solution of h[source] = 0, h[v] = 1 + min over tight u -> v of h[u]:
+ *          the breadth-first distance from the source in the directed graph of tight edges. Every voxel
+ *          with finite d has one (the edge that last lowered v in a Dijkstra is tight and comes from a
+ *          voxel settled earlier), and an integer least fixed point is unique and independent of any order.
+ *       3. parent (int32, C-order linear index): parent[source] = the source's own index; otherwise the
+ *          tight predecessor u with h[u] = h[v] - 1 that has the smallest linear index. hops fall by exactly
+ *          1 along parents, so there is no cycle even on a plateau where d[u] = d[v] because a cost was
+ *          absorbed; the chain from v reaches the source in h[v] steps, and re-adding the weights along it
+ *          from the source reproduces d at every voxel of it, bit for bit.
+ *       4. Everything else gets h = -1 and parent = -1: background, labels above K, labels without a valid
+ *          source, voxels with d = +inf.
+ *       5. An orphan is a voxel of a label in 1..K with finite d that is no source and has no tight
+ *          predecessor. It exists only if d is not the field of these inputs (another cost, a field that
+ *          is not converged, a source whose d is not 0). Orphans are counted, never guessed at.
+ *       6. The path of a target t with h[t] >= 0 is the h[t] + 1 voxels source = p_0, ..., p_h = t with
+ *          parent[p_i] = p_(i-1): voxel v stands at position h[v] of its path.
+ *      Checked against the two oracles in tests/parents_ref.py; not claimed to equal dijkstra3d's
+ *      parental_field or kimimaro, whose parents are one Dijkstra run's tie-breaks, 1-based, with 0 for
+ *      "none". Hops are relaxed on the finished field, not as (d, h) pairs in one relaxation: a pair's h can
+ *      be derived from a neighbour's earlier, larger d and survive when that neighbour falls and its own
+ *      hop count grows, and a min-only relaxation never raises it. */
+
+/* Starts the hops of the parental field defined above (inference.py:257-291: dijkstra3d.parental_field in
+ * kimimaro.skeletonize): hops_dev = -1 everywhere and 0 at every valid source whose field word is +0.0;
+ * the tiles that hold one or see it in their halo are flagged for the first sweep. A source row that is
+ * invalid, or whose field is not +0.0, counts as invalid. state_dev[0] = the number of tiles flagged,
+ * state_dev[1] = the number of invalid rows; state_dev holds three words, the third belongs to
+ * exaspim_geodesic_parents_finish. The workspace is that of exaspim_geodesic_workspace_bytes(dims); it
+ * carries the flags to exaspim_geodesic_parents_sweeps and must not be touched in between. labels_dev,
+ * sources_dev and field_dev are only read. Three launches on "stream", nothing allocated, nothing
+ * synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels,
+ * a negative n_labels or a misaligned buffer (workspace_dev 16 bytes, the rest 4); EXASPIM_E_WORKSPACE for
+ * a short workspace: all before anything is launched, and no output is touched. */
+int exaspim_geodesic_parents_begin(const int32_t* labels_dev, const int32_t dims[3], const int32_t* sources_dev,
+                                   int32_t n_labels, const float* field_dev, int32_t* hops_dev,
+                                   int32_t* state_dev /* [3] */, void* workspace_dev, size_t workspace_bytes,
+                                   void* stream);
+
+/* Runs "sweeps" >= 1 sweeps of the hops relaxation exaspim_geodesic_parents_begin started (the same labels,
+ * field, dims, n_labels and workspace; inference.py:257-291). A sweep is one workgroup per flagged tile: the
+ * 26 tests of a tight edge are taken once per voxel of the tile, hops with a one-voxel halo are relaxed
+ * in LDS as h[v] = min(h[v], 1 + min over tight u of h[u]), in unsigned arithmetic where -1 is the largest
+ * value, until nothing in the tile changes (at most 2049 rounds), the voxels that fell are stored, and the
+ * tiles that see one of them in their halo are flagged for the next sweep. state_dev[0] = the number of
+ * tiles flagged for the sweep after the last one, 0 meaning that hops_dev is the hops defined above;
+ * state_dev[1] = the invalid rows, as before. Every value written is 1 + the hops of a real tight path,
+ * hence an upper bound, and the writer flags the reader: no workgroup waits for another and the result
+ * does not depend on the schedule. cost_dev (float32, dims) must be what the field was built with, NULL for
+ * Euclidean steps. Two launches per sweep on "stream", nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer other than cost_dev, dims as above, a negative n_labels,
+ * sweeps < 1 or a misaligned buffer; EXASPIM_E_WORKSPACE for a short workspace: all before anything is
+ * launched, and no output is touched. */
+int exaspim_geodesic_parents_sweeps(const int32_t* labels_dev, const float* cost_dev /* may be NULL */,
+                                    const float* field_dev, const int32_t dims[3], int32_t n_labels,
+                                    int32_t* hops_dev, int32_t sweeps, int32_t* state_dev /* [3] */,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The parents of converged hops, as defined above (inference.py:257-291: the parental field TEASAR reads
+ * its paths from): per voxel with h >= 1 the tight predecessor with h - 1 and the smallest linear index,
+ * a source its own index, everything else -1. state_dev[2] = the number of orphans; state_dev[0] and [1]
+ * are left as they are. Every input is only read and parents_dev only written, so no result depends on a
+ * word the same launch rewrites. One memset and one launch on "stream", nothing allocated, nothing
+ * synchronised. EXASPIM_E_INVALID for a NULL pointer other than cost_dev, dims as above, a negative
+ * n_labels or a misaligned buffer: all before anything is launched, and no output is touched. */
+int exaspim_geodesic_parents_finish(const int32_t* labels_dev, const float* cost_dev /* may be NULL */,
+                                    const float* field_dev, const int32_t* hops_dev, const int32_t dims[3],
+                                    int32_t n_labels, int32_t* parents_dev, int32_t* state_dev /* [3] */,
+                                    void* stream);
+
+/* Reads the paths of n_targets targets off a parental field (inference.py:257-291: path_from_parents in
+ * kimimaro's TEASAR). offsets_dev is int64 (n_targets + 1): row i is written to
+ * paths_dev[offsets[i] .. offsets[i + 1]), source first, target last, and must be hops[targets[i]] + 1
+ * long; that offsets[n_targets] <= paths_capacity is the caller's to guarantee and is checked per row on the
+ * device. One thread per target walks at most hops[target] steps, so a corrupt parents array cannot spin
+ * it. state_dev[0] = the targets that are out of range, have h < 0, or whose row is not h + 1 long or does
+ * not lie within paths_capacity: such a row is left unwritten. state_dev[1] = the broken walks: one that
+ * leaves the volume, meets -1 or does not end on a self-parent; nothing is read out of range. Duplicate
+ * targets are allowed. targets_dev and paths_dev may be NULL if n_targets is 0. One memset and at most one
+ * launch on "stream", nothing allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL pointer, dims
+ * as above, a negative n_targets or paths_capacity, or a misaligned buffer (offsets_dev 8 bytes, the rest
+ * 4): all before anything is launched, and no output is touched. */
+int exaspim_trace_paths(const int32_t* parents_dev, const int32_t* hops_dev, const int32_t dims[3],
+                        const int32_t* targets_dev, int32_t n_targets, const int64_t* offsets_dev,
+                        int32_t* paths_dev, int64_t paths_capacity, int32_t* state_dev /* [2] */, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
