@@ -52,10 +52,11 @@ from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (
     _AgglomerationLabeller, _ComponentsLabeller, _components_on_device, _contract_dominant_on_device,
     _default_edge_capacity, _device_merged_table, _fill_holes_on_device, _geodesic_on_device,
     _geodesic_parents_on_device, _LabelSink, _last_threshold, _premerge_on_device, _premerged_table,
-    _region_graph_device, _watershed_on_device, affinities_to_components, affinities_to_components_streaming,
-    agglomerate, agglomerate_affinities, agglomerate_affinities_streaming, contract_dominant_edges,
-    distance_to_boundary, fill_holes, geodesic_field, geodesic_parents, premerge_region_graph, region_graph,
-    segment_table, trace_paths, watershed_fragments,
+    _region_graph_device, _skeleton_chain_on_device, _teasar_on_device, _watershed_on_device,
+    affinities_to_components, affinities_to_components_streaming, agglomerate, agglomerate_affinities,
+    agglomerate_affinities_streaming, contract_dominant_edges, distance_to_boundary, fill_holes, geodesic_field,
+    geodesic_parents, premerge_region_graph, region_graph, segment_table, skeleton_to_swc, skeletonize_labels,
+    teasar_branches, trace_paths, watershed_fragments,
 )
 from aind_exaspim_neuron_segmentation_amd.utils import img_util
 

@@ -1956,6 +1956,508 @@ def trace_paths(parents, hops, targets, *, return_device_tensors=False):
     return voxels, offsets
 
 
+def _checked_teasar_scalars(fn, scale, const, max_paths):
+    """scale and const are finite real numbers >= 0, max_paths is None or an integer >= 1."""
+    for name, value in (("scale", scale), ("const", const)):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{fn}: {name} must be a real number, got {type(value).__name__}")
+        if not np.isfinite(value) or value < 0:
+            raise ValueError(f"{fn}: {name} must be finite and not negative, got {value}")
+    if max_paths is not None:
+        if isinstance(max_paths, bool) or not isinstance(max_paths, (int, np.integer)):
+            raise TypeError(f"{fn}: max_paths must be an integer, got {type(max_paths).__name__}")
+        if max_paths < 1:
+            raise ValueError(f"{fn}: max_paths must be at least 1, got {max_paths}")
+
+
+def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths):
+    """
+    The front matter of teasar_branches, in _checked_geodesic_arguments'
+    manner: the scalars first, then every array before any of them is
+    uploaded, then tensors next to a labels tensor, then everything as
+    contiguous tensors on the labels' device. Returns (labels, dims, sources,
+    dbf, daf, parents, hops, boxes or None, scale, const).
+    """
+    _checked_teasar_scalars(fn, scale, const, max_paths)
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
+        if n_labels < 0:
+            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+
+    def check_sources(a):
+        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
+            rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
+            raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
+
+    def check_boxes(a, rows):
+        if a.ndim != 2 or tuple(a.shape) != (rows, 6):
+            raise ValueError(f"{fn}: boxes must be ({rows}, 6) as sources has {rows} rows, got {tuple(a.shape)}")
+
+    def check_volume(a, shape, what):
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{fn}: {what} must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
+
+    volumes = (("dbf", dbf, np.int32, torch.int32), ("daf", daf, np.float32, torch.float32),
+               ("parents", parents, np.int32, torch.int32), ("hops", hops, np.int32, torch.int32))
+    tables = (("sources", sources, np.int32, torch.int32), ("boxes", boxes, np.int32, torch.int32))
+
+    def check_dtype(what, a, np_dtype, torch_dtype):
+        if isinstance(a, np.ndarray) and a.dtype != np_dtype:
+            raise TypeError(f"{what} must be {np.dtype(np_dtype)}, got {a.dtype}")
+        if isinstance(a, torch.Tensor) and a.dtype != torch_dtype:
+            raise TypeError(f"{what} must be {np.dtype(np_dtype)}, got {a.dtype}")
+
+    def check_shapes(kind):
+        """Of the arguments that are of "kind", numpy arrays or tensors."""
+        for what, a, np_dtype, torch_dtype in tables + volumes:
+            if isinstance(a, kind):
+                check_dtype(what, a, np_dtype, torch_dtype)
+        if isinstance(sources, kind):
+            check_sources(sources)
+            if isinstance(boxes, (np.ndarray, torch.Tensor)):
+                check_boxes(boxes, sources.shape[0])
+        elif isinstance(boxes, kind) and isinstance(sources, (np.ndarray, torch.Tensor)) and sources.ndim == 1:
+            check_boxes(boxes, sources.shape[0])
+        for what, a, _, _ in volumes:
+            if isinstance(a, kind) and isinstance(labels, (np.ndarray, torch.Tensor)):
+                check_volume(a, labels.shape, what)
+
+    check_shapes(np.ndarray)      # every array is checked before any of them is uploaded
+    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
+        check_shapes(torch.Tensor)
+    labels, dims = _checked_labels(labels, fn)
+    device = labels.device
+    out = []
+    for what, a, np_dtype, torch_dtype in tables + volumes:
+        if a is None and what == "boxes":
+            out.append(None)
+            continue
+        a = _on_device(a, fn, what, (np_dtype,))
+        check_dtype(what, a, np_dtype, torch_dtype)
+        if what == "sources":
+            check_sources(a)
+        elif what == "boxes":
+            check_boxes(a, out[0].shape[0])
+        else:
+            check_volume(a, dims, what)
+        if a.device != device:
+            raise RuntimeError(f"{fn}: {what} must be on the labels' device {device}, got {a.device}")
+        out.append(a.contiguous())
+    sources, boxes, dbf, daf, parents, hops = out
+    return labels, dims, sources, dbf, daf, parents, hops, boxes, float(scale), float(const)
+
+
+def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths=None, stats=None,
+                      on_round=None):
+    """
+    teasar_branches on checked device tensors: exaspim_teasar_begin, then per
+    round exaspim_teasar_round, one 20-byte read of the state, the cumulative
+    sum of the lengths with torch and exaspim_teasar_apply. Everything stays on
+    the device.
+
+    Parameters
+    ----------
+    labels, sources, dbf, daf, parents, hops, boxes : torch.Tensor
+        As in teasar_branches, contiguous, on one HIP device.
+    scale, const : float
+    max_paths : int, optional
+    stats : dict, optional
+        As in teasar_branches.
+    on_round : callable, optional
+        Called after every round with (round, mask), mask the uint8 (D, H, W)
+        state of every voxel: bit 0 still valid, bit 1 on the skeleton.
+
+    Returns
+    -------
+    voxels, radii, before : torch.Tensor
+        int32 (N,): the vertices, their radii and the vertex before each (the
+        junction for a branch's first vertex, -1 for a root).
+    offsets : torch.Tensor
+        int64 (B + 1,).
+    branch_label, branch_round, branch_junction : torch.Tensor
+        int32 (B,).
+
+    Raises
+    ------
+    RuntimeError
+        For a broken walk or a refused row.
+    """
+    fn = "teasar_branches"
+    dims = tuple(int(v) for v in labels.shape)
+    n_labels = int(sources.numel()) - 1
+    device = labels.device
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = lib.exaspim_teasar_workspace_bytes(dims3, n_labels)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        mask = torch.empty(dims, dtype=torch.uint8, device=device)
+        state = torch.empty(5, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        targets = torch.empty(n_labels + 1, dtype=torch.int32, device=device)
+        lengths = torch.empty(n_labels + 1, dtype=torch.int64, device=device)
+        junction = torch.empty(n_labels + 1, dtype=torch.int32, device=device)
+        offsets = torch.zeros(n_labels + 2, dtype=torch.int64, device=device)
+        _native.check(
+            lib.exaspim_teasar_begin(labels.data_ptr(), sources.data_ptr(), hops.data_ptr(), daf.data_ptr(), dims3,
+                                     n_labels, mask.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
+            "exaspim_teasar_begin",
+        )
+        rounds, reads, refused = 0, 0, 0
+        per_round, live_history, new_history = [], [], []
+        while max_paths is None or rounds < max_paths:
+            _native.check(
+                lib.exaspim_teasar_round(labels.data_ptr(), daf.data_ptr(), parents.data_ptr(), hops.data_ptr(), dims3,
+                                         n_labels, mask.data_ptr(), targets.data_ptr(), lengths.data_ptr(),
+                                         junction.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
+                "exaspim_teasar_round",
+            )
+            live, broken, n_new, n_roots, refused = (int(v) for v in state.cpu())   # the round's one read
+            reads += 1
+            if broken or refused:
+                break
+            if live == 0:
+                break
+            rounds += 1
+            live_history.append(live)
+            new_history.append(n_new)
+            torch.cumsum(lengths, 0, out=offsets[1:])
+            voxels = torch.empty(n_new, dtype=torch.int32, device=device)
+            radii = torch.empty(n_new, dtype=torch.int32, device=device)
+            before = torch.empty(n_new, dtype=torch.int32, device=device)
+            _native.check(
+                lib.exaspim_teasar_apply(labels.data_ptr(), parents.data_ptr(), dbf.data_ptr(), boxes.data_ptr(), dims3,
+                                         n_labels, scale, const, mask.data_ptr(), targets.data_ptr(), lengths.data_ptr(),
+                                         junction.data_ptr(), offsets.data_ptr(), voxels.data_ptr(), radii.data_ptr(),
+                                         before.data_ptr(), n_new, n_new, n_roots, state.data_ptr(), stream),
+                "exaspim_teasar_apply",
+            )
+            # the labels that have a branch, ascending: a stable sort needs no read, "live" is known already
+            rows = torch.argsort((lengths == 0).to(torch.uint8), stable=True)[:live]
+            per_round.append((voxels, radii, before, lengths[rows], rows.to(torch.int32), junction[rows], rounds))
+            if on_round is not None:
+                on_round(rounds, mask)
+        else:
+            refused = int(state.cpu()[4])   # max_paths cut the loop: the last round's rows have not been read
+            reads += 1
+        if stats is not None:
+            stats.update(rounds=rounds, reads=reads, vertices=new_history, live_labels=live_history)
+        if broken or refused:
+            raise RuntimeError(f"{fn}: {broken} broken walk(s) and {refused} refused row(s): parents and hops are not "
+                               "the results of one geodesic_parents call on these labels and sources")
+
+        def joined(i, dtype):
+            parts = [r[i] for r in per_round]
+            return torch.cat(parts) if parts else torch.empty(0, dtype=dtype, device=device)
+
+        sizes = joined(3, torch.int64)
+        out_offsets = torch.zeros(sizes.numel() + 1, dtype=torch.int64, device=device)
+        if sizes.numel():
+            torch.cumsum(sizes, 0, out=out_offsets[1:])
+        branch_round = [torch.full((r[4].numel(),), r[6], dtype=torch.int32, device=device) for r in per_round]
+        branch_round = torch.cat(branch_round) if branch_round else torch.empty(0, dtype=torch.int32, device=device)
+    return (joined(0, torch.int32), joined(1, torch.int32), joined(2, torch.int32), out_offsets,
+            joined(4, torch.int32), branch_round, joined(5, torch.int32))
+
+
+def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, boxes=None, n_labels=None,
+                    max_paths=None, return_device_tensors=False, stats=None):
+    """
+    TEASAR's loop for every label at once, on the device: the choice of the
+    next target, the branch read off the parental field, and the rolling
+    invalidation, until no label has a valid voxel left. Only the skeleton's
+    vertices leave the card.
+
+    What this is: the loop of kimimaro's TEASAR, which the reference's
+    skeletonize (inference.py:257-291) runs per label on the host, in the
+    single-parental-field form: every path is read off ONE parental field,
+    which is kimimaro with fix_branching=False. Exactly, in integers:
+    K = len(sources) - 1. A voxel v is eligible iff its label L is in 1..K,
+    sources[L] names a voxel of L, hops[v] >= 0 and daf[v] is finite with
+    the sign bit clear (-0.0 is left out, as geodesic_field's farthest table
+    leaves it out). One byte of state per voxel holds "still valid", at first
+    the eligible voxels, and "on the skeleton", at first none. Round
+    t = 1, 2, ..., all labels in lock-step (labels never interact, so this
+    equals K serial loops):
+
+    1. Target: per label the valid voxel with the largest daf bit pattern,
+       ties to the smallest C-order linear index. A label without a valid
+       voxel is finished; when none is live the loop ends.
+    2. Branch: parents are walked from the target to the first voxel on the
+       skeleton (the junction) or to the source, a self-parent (round 1:
+       junction -1). The new vertices are the walked voxels without the
+       junction, listed in ascending hops. The walk takes at most
+       hops[target] steps and range-checks every index; one that leaves the
+       volume, meets -1 or does not end on a skeleton voxel or the source is
+       broken and raises.
+    3. Radius: r(p) = min(max(D, H, W), floor(fl64(fl64(scale *
+       sqrt64(max(dbf[p], 0))) + const))), one rounded double operation each,
+       numpy's np.floor(np.float64(scale) * np.sqrt(d2) + np.float64(const)).
+    4. Invalidation: every voxel q with labels[q] == L, inside L's bounding
+       box, within Chebyshev distance r(p) of a new vertex p of L becomes
+       invalid; other labels' voxels inside the cube are untouched. Then the
+       new vertices are marked as on the skeleton.
+
+    Stopping at the junction and clearing, per vertex, its cube minus the
+    cube of the vertex before it gives the same valid voxels after every
+    round and the same vertices as tracing every path to the root and
+    rolling a whole cube along all of it (tests/teasar_ref.py holds the two
+    forms to each other); the work per vertex is then a cube's surface.
+
+    What this is not: equal to kimimaro, which is no dependency of the
+    project or its tests. The reference runs kimimaro with its default
+    fix_branching=True, a Dijkstra per path on a penalty field zeroed along
+    the earlier paths; this is the fix_branching=False form. Soma mode (the
+    soma_* parameters and the spherical invalidation around a soma root),
+    fix_borders, anisotropy, several sources per label and a slab-streamed
+    form are not built.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    sources : torch.Tensor or numpy.ndarray
+        int32 (K + 1,): the roots, as for geodesic_field.
+    dbf : torch.Tensor or numpy.ndarray
+        int32 of the labels' shape: squared distances,
+        distance_to_boundary's result or any other field.
+    daf : torch.Tensor or numpy.ndarray
+        float32 of the labels' shape: the priority field; TEASAR uses the
+        Euclidean geodesic_field from the roots.
+    parents, hops : torch.Tensor or numpy.ndarray
+        int32 of the labels' shape: geodesic_parents of the penalty field.
+    scale, const : float
+        Finite and not negative.
+    boxes : torch.Tensor or numpy.ndarray, optional
+        int32 (K + 1, 6) from segment_table. Default is None:
+        segment_table(labels) is taken here.
+    n_labels : int, optional
+        K, if given checked against len(sources) - 1. Default is None.
+    max_paths : int, optional
+        Stop after this many rounds. Default is None.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+    stats : dict, optional
+        Receives "rounds", "reads" (of the 20-byte state, one per round),
+        "vertices" (new vertices per round) and "live_labels" (labels with a
+        branch per round).
+
+    Returns
+    -------
+    voxels : numpy.ndarray or torch.Tensor
+        int32 (N,): the new vertices, rounds concatenated, then labels
+        ascending, then hops ascending within a branch.
+    radii : numpy.ndarray or torch.Tensor
+        int32 (N,): the invalidation radius of each vertex.
+    offsets : numpy.ndarray or torch.Tensor
+        int64 (B + 1,): the branch boundaries in voxels.
+    branch_label, branch_round, branch_junction : numpy.ndarray or torch.Tensor
+        int32 (B,): each branch's label, round (from 1) and junction voxel,
+        -1 in round 1.
+
+    Raises
+    ------
+    TypeError
+        If an array or tensor has the wrong dtype, scale or const is not a
+        real number, or n_labels or max_paths is not an integer.
+    ValueError
+        If labels is not 3-D or is empty, a field has another shape, sources
+        is not (K + 1,), boxes is not (K + 1, 6), scale or const is negative
+        or not finite, max_paths < 1, or the volume has more than 2^31 - 1
+        voxels.
+    RuntimeError
+        If labels is a tensor on a CPU device, another argument is on
+        another device, there is no HIP device to upload an array to, or a
+        walk is broken.
+    """
+    labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const = _checked_teasar_arguments(
+        "teasar_branches", labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths)
+    if boxes is None:
+        boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
+    out = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const,
+                            None if max_paths is None else int(max_paths), stats)
+    out = out[:2] + out[3:]
+    if not return_device_tensors:
+        with torch.cuda.device(labels.device):
+            out = tuple(t.cpu().numpy() for t in out)
+    return out
+
+
+def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths):
+    """
+    The nine stages of skeletonize_labels on a checked device tensor, nothing
+    downloaded in between but the words each stage reads for itself. Returns
+    a dict of device tensors: "labels" (filled if asked), "dbf", "boxes",
+    "roots", "daf", "cost", "parents", "hops", and _teasar_on_device's
+    "voxels", "radii", "before", "offsets", "branch_label", "branch_round",
+    "branch_junction".
+    """
+    device = labels.device
+    with torch.cuda.device(device):
+        if fill_holes:
+            labels, _ = _fill_holes_on_device(labels)
+        k = max(int(labels.max()), 0)   # the one read of the front matter
+        dbf = distance_to_boundary(labels, return_device_tensor=True)
+        _, boxes, peak, _ = segment_table(labels, dbf, n_labels=k, return_device_tensors=True)
+        first = segment_table(labels, n_labels=k, return_device_tensors=True)[3]
+        _, _, roots = _geodesic_on_device(labels, first, farthest=True)
+        daf, far_value, _ = _geodesic_on_device(labels, roots, farthest=True)
+        rows = labels.clamp(0, k).to(torch.int64)   # labels above K do not occur; negative ones read row 0
+        root_peak = peak.to(torch.float32).sqrt()[rows]
+        far = far_value[rows]
+        zero = torch.zeros((), dtype=torch.float32, device=device)
+        depth = torch.where(root_peak > 0, (1 - dbf.to(torch.float32).sqrt() / root_peak) ** pdrf_exponent * pdrf_scale,
+                            zero)
+        cost = (depth + torch.where(far > 0, daf / far, zero)).to(torch.float32).contiguous()
+        del rows, root_peak, far, depth
+        pdrf, _, _ = _geodesic_on_device(labels, roots, cost)
+        parents, hops = _geodesic_parents_on_device(labels, roots, pdrf, cost)
+        del pdrf
+        names = ("voxels", "radii", "before", "offsets", "branch_label", "branch_round", "branch_junction")
+        out = dict(zip(names, _teasar_on_device(labels, roots, dbf, daf, parents, hops, boxes, scale, const, max_paths)))
+    out.update(labels=labels, dbf=dbf, boxes=boxes, roots=roots, daf=daf, cost=cost, parents=parents, hops=hops)
+    return out
+
+
+def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf_scale=100000.0, fill_holes=True,
+                       max_paths=None):
+    """
+    From labels to skeletons with nothing downloaded between the stages: what
+    the reference's skeletonize (inference.py:257-291) asks of
+    kimimaro.skeletonize, with the reference's teasar_params as defaults.
+
+    The chain: (1) fill_holes, if asked; (2) distance_to_boundary; (3)
+    segment_table; (4) the roots by geodesic_field's find-root recipe: each
+    label's first voxel as source, then that field's far_index; (5) the DAF,
+    geodesic_field from the roots, and its farthest values; (6) the penalty,
+    with torch float32 element-wise operations,
+    cost = pdrf_scale * (1 - sqrt(dbf) / sqrt(peak[L])) ** pdrf_exponent
+    + daf / far_value[L], the maxima per label gathered through labels and
+    either term 0 where its divisor is 0; (7) geodesic_field(cost=cost);
+    (8) geodesic_parents; (9) teasar_branches.
+
+    What this is not: kimimaro. The loop is the single-parental-field form of
+    TEASAR (kimimaro's fix_branching=False), not the reference's default
+    fix_branching=True, which re-runs a Dijkstra per path on a penalty zeroed
+    along the earlier paths. Soma detection and its spherical invalidation
+    (the soma_* parameters), fix_borders and anisotropy are not built, and
+    equality with kimimaro is not claimed. A piece of a label that the root's
+    piece does not touch gets no skeleton.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    scale, const : float, optional
+        The invalidation radius is scale * sqrt(dbf) + const voxels.
+        Defaults are 1.25 and 450.0.
+    pdrf_exponent : int, optional
+        Default is 4.
+    pdrf_scale : float, optional
+        Default is 100000.0.
+    fill_holes : bool, optional
+        Close the enclosed cavities of every label first. Default is True.
+    max_paths : int, optional
+        At most this many paths per label. Default is None.
+
+    Returns
+    -------
+    dict
+        label -> (vertices, parent, radius): vertices int32 (n, 3), array
+        indices in axis order (z, y, x); parent int32 (n,), the row of each
+        vertex's parent on the skeleton, -1 for the root; radius float32
+        (n,), sqrt(dbf). Labels without a skeleton are absent.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As fill_holes, distance_to_boundary, geodesic_field, geodesic_parents
+        and teasar_branches; TypeError or ValueError for a pdrf_exponent that
+        is no integer >= 0 or a pdrf_scale that is not finite and >= 0.
+    """
+    fn = "skeletonize_labels"
+    if isinstance(pdrf_exponent, bool) or not isinstance(pdrf_exponent, (int, np.integer)):
+        raise TypeError(f"{fn}: pdrf_exponent must be an integer, got {type(pdrf_exponent).__name__}")
+    if pdrf_exponent < 0:
+        raise ValueError(f"{fn}: pdrf_exponent must not be negative, got {pdrf_exponent}")
+    if isinstance(pdrf_scale, bool) or not isinstance(pdrf_scale, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{fn}: pdrf_scale must be a real number, got {type(pdrf_scale).__name__}")
+    if not np.isfinite(pdrf_scale) or pdrf_scale < 0:
+        raise ValueError(f"{fn}: pdrf_scale must be finite and not negative, got {pdrf_scale}")
+    _checked_teasar_scalars(fn, scale, const, max_paths)
+    labels, dims = _checked_labels(labels, fn)
+    chain = _skeleton_chain_on_device(labels, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
+                                      bool(fill_holes), None if max_paths is None else int(max_paths))
+    with torch.cuda.device(labels.device):
+        voxels, before, offsets, branch_label = (chain[k] for k in ("voxels", "before", "offsets", "branch_label"))
+        radius = chain["dbf"].reshape(-1)[voxels.to(torch.int64)].to(torch.float32).sqrt()
+        voxels, before, offsets, branch_label, radius = (
+            t.cpu().numpy() for t in (voxels, before, offsets, branch_label, radius))
+    vertex_label = np.repeat(branch_label, np.diff(offsets))
+    out = {}
+    for row in np.unique(vertex_label):
+        mine = np.nonzero(vertex_label == row)[0]
+        vox, prev = voxels[mine], before[mine]
+        order = np.argsort(vox, kind="stable")
+        at = np.searchsorted(vox[order], np.maximum(prev, 0))
+        parent = np.where(prev >= 0, order[np.minimum(at, len(order) - 1)], -1).astype(np.int32)
+        if not np.array_equal(vox[parent[prev >= 0]], prev[prev >= 0]):
+            raise RuntimeError(f"{fn}: a vertex of label {row} has a parent that is not on the skeleton")
+        vertices = np.stack(np.unravel_index(vox, dims), axis=1).astype(np.int32)
+        out[int(row)] = (vertices, parent, radius[mine].astype(np.float32))
+    return out
+
+
+def skeleton_to_swc(vertices, parent, radius):
+    """
+    One skeleton of skeletonize_labels as the text of an SWC file, on the
+    host: what the loop of the reference's skeletons_to_zipped_swcs writes
+    into its archive. One line per vertex, "id type x y z radius parent":
+    ids are 1-based rows, type is 0, the coordinates are the vertex's array
+    indices in axis order, and the parent is the 1-based row of the parent,
+    -1 for the root.
+
+    Parameters
+    ----------
+    vertices : numpy.ndarray
+        (n, 3), integers or floats.
+    parent : numpy.ndarray
+        (n,) integers: rows, -1 for a root.
+    radius : numpy.ndarray
+        (n,) floats.
+
+    Returns
+    -------
+    str
+        n lines, each ended by a newline.
+
+    Raises
+    ------
+    ValueError
+        If the shapes do not belong together or a parent is no row.
+    """
+    vertices, parent, radius = np.asarray(vertices), np.asarray(parent), np.asarray(radius)
+    n = vertices.shape[0] if vertices.ndim == 2 else -1
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or parent.shape != (n,) or radius.shape != (n,):
+        raise ValueError(f"skeleton_to_swc: vertices must be (n, 3) and parent and radius (n,), got "
+                         f"{vertices.shape}, {parent.shape} and {radius.shape}")
+    if not np.issubdtype(parent.dtype, np.integer):
+        raise ValueError(f"skeleton_to_swc: parent must hold integers, got {parent.dtype}")
+    if n and (parent.min() < -1 or parent.max() >= n):
+        raise ValueError("skeleton_to_swc: a parent is neither -1 nor a row of vertices")
+    lines = []
+    for i in range(n):
+        x, y, z = (f"{float(c):g}" for c in vertices[i])
+        up = int(parent[i])
+        lines.append(f"{i + 1} 0 {x} {y} {z} {float(radius[i]):g} {up + 1 if up >= 0 else -1}\n")
+    return "".join(lines)
+
+
 # Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes
 # of device memory each, so 256 MiB at most; a volume with fewer voxels gets as many ids as voxels.
 DEFAULT_ID_CAPACITY = 1 << 24

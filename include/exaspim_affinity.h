@@ -69,7 +69,9 @@ extern "C" {
  *    workspace queries): the geodesic distance-from-source field of every label and its farthest voxels;
  *    later within 5: exaspim_geodesic_parents_begin, exaspim_geodesic_parents_sweeps,
  *    exaspim_geodesic_parents_finish, exaspim_trace_paths: the parental field of that field and the paths
- *    read off it */
+ *    read off it;
+ *    later within 5: exaspim_teasar_begin, exaspim_teasar_round, exaspim_teasar_apply (and their workspace
+ *    query): TEASAR's loop of targets, branches and invalidation for every label at once */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -1246,6 +1248,85 @@ int exaspim_geodesic_parents_finish(const int32_t* labels_dev, const float* cost
 int exaspim_trace_paths(const int32_t* parents_dev, const int32_t* hops_dev, const int32_t dims[3],
                         const int32_t* targets_dev, int32_t n_targets, const int64_t* offsets_dev,
                         int32_t* paths_dev, int64_t paths_capacity, int32_t* state_dev /* [2] */, void* stream);
+
+/* ---- TEASAR's loop: targets, branches, invalidation ------------------------------------------
+ * What follows the fields and the parental field in the reference's skeletonize (inference.py:257-291:
+ * the loop of kimimaro's TEASAR), for all labels at once, in the single-parental-field form: every path is
+ * read off ONE parental field, which is kimimaro with fix_branching=False. The reference runs kimimaro with
+ * its default fix_branching=True, a Dijkstra per path on a penalty field zeroed along the earlier paths;
+ * that form, soma detection and its spherical invalidation, fix_borders and anisotropy are not built, and
+ * equality with kimimaro is not claimed.
+ *
+ * The definition, in integers. K = n_labels. A voxel v is eligible iff its label L is in 1..K, sources[L]
+ * names a voxel of L, hops[v] >= 0 and the bits of daf[v] are below 0x7F800000 (finite, sign bit clear: -0.0
+ * is left out as exaspim_geodesic_farthest leaves it out). mask_dev holds one byte per voxel: bit 0 "still
+ * valid", at first the eligible voxels, bit 1 "on the skeleton", at first none. Round t = 1, 2, ...: (1) the
+ * target of every label that still has a valid voxel is the valid voxel with the largest daf bits, ties to
+ * the smallest linear index; a label without one is finished. (2) The branch: walk parents from the target
+ * to the first voxel that is on the skeleton (the junction) or to the source, a self-parent reached after
+ * exactly hops[target] steps (junction -1); the new vertices are the walked voxels without the junction,
+ * listed junction side first. A walk that leaves the volume, meets -1 or a self-parent early, or does not
+ * end on a skeleton voxel or the source is broken: it is counted, writes nothing and finishes its label.
+ * (3) The radius of a new vertex p is r(p) = min(R, floor(fl64(fl64(scale * sqrt64(max(dbf[p], 0))) +
+ * const))), R = max(D, H, W), every operation one rounded double operation, the comparison taken in double.
+ * (4) Every voxel q with labels[q] == L inside row L of boxes whose Chebyshev distance to a new vertex p of
+ * L is at most r(p) loses bit 0; the new vertices lose bit 0 in any case (a box that leaves them out
+ * cannot make the loop endless) and get bit 1. The kernels clear, per vertex, its cube minus
+ * the cube of the vertex before it on the branch (the junction for the first one), which was cleared before:
+ * tests/teasar_ref.py holds this form to the one that stamps whole cubes along whole paths. With parents
+ * that lead from one label into another the result is unspecified, but every access stays in range. */
+
+/* Scratch bytes of the three calls below: 8 + 4 bytes per row, n_labels + 1 rows, each part rounded up to
+ * 16. 0 with the error text set for dims exaspim_fill_holes refuses or a negative n_labels. */
+size_t exaspim_teasar_workspace_bytes(const int32_t dims[3], int32_t n_labels);
+
+/* Writes the state byte of every voxel as defined above and clears state_dev (five words) and the
+ * workspace's per-label words. Every other argument is only read. One launch on "stream", nothing
+ * allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume
+ * of more than 2^31 - 1 voxels, a negative n_labels or a misaligned buffer (workspace_dev 16 bytes, mask_dev
+ * none, the rest 4); EXASPIM_E_WORKSPACE for a short workspace: all before anything is launched, and no
+ * output is touched. */
+int exaspim_teasar_begin(const int32_t* labels_dev, const int32_t* sources_dev /* [n_labels + 1] */,
+                         const int32_t* hops_dev, const float* daf_dev, const int32_t dims[3], int32_t n_labels,
+                         uint8_t* mask_dev, int32_t* state_dev /* [5] */, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+
+/* Steps (1) and (2) of one round, without writing the branch: targets_dev[L] = the target of label L or -1,
+ * lengths_dev[L] (int64) = the number of its new vertices, junction_dev[L] = its junction or -1, each of
+ * n_labels + 1 rows, row 0 being -1, 0, -1. state_dev[0] = the labels that have a branch this round,
+ * state_dev[1] = the broken walks of this round, state_dev[2] = the sum of lengths_dev, state_dev[3] = the
+ * branches without a junction; state_dev[4], the rows exaspim_teasar_apply refused since
+ * exaspim_teasar_begin, is left as it is. mask_dev is only read. The target pass reads the state byte first
+ * and labels and daf only where it says valid; the walk takes at most hops[target] steps and range-checks
+ * every index, so corrupt parents cannot spin it or lead it out of the volume. Three launches on "stream",
+ * nothing allocated, nothing synchronised. Refusals as exaspim_teasar_begin (lengths_dev 8 bytes). */
+int exaspim_teasar_round(const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
+                         const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels, const uint8_t* mask_dev,
+                         int32_t* targets_dev, int64_t* lengths_dev, int32_t* junction_dev,
+                         int32_t* state_dev /* [5] */, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Steps (2) to (4) of the round exaspim_teasar_round prepared. offsets_dev is int64 (n_labels + 2): 0
+ * followed by the inclusive cumulative sum of lengths_dev, so that label L's branch is written to
+ * voxels_dev, radii_dev and before_dev at [offsets[L], offsets[L + 1]), junction side first: the vertex, its
+ * radius, and the vertex before it (the junction or -1 for the first). n_new = state_dev[2] and n_roots =
+ * state_dev[3] as read after exaspim_teasar_round; the three arrays hold "capacity" >= n_new entries and may
+ * be NULL if n_new is 0. n_new stands in for the offsets' total, offsets[n_labels + 1], which lies on the
+ * device: the host refuses capacity < n_new, and a row whose offsets do not match its length or reach beyond
+ * n_new is counted in state_dev[4] and left unwritten, so every write is bounded by n_new <= capacity. boxes_dev is int32 (n_labels + 1, 6), half-open (z0, y0, x0, z1, y1, x1)
+ * as exaspim_segment_table writes them; a box is clipped to the volume. The invalidation runs over the
+ * round's new vertices in grid x and over the voxels of a vertex's at most six slabs in grid y; the whole
+ * cubes of round 1's roots have a launch of their own (skipped if n_roots is 0) with a larger grid y. Two
+ * workgroups may clear the same byte: both write the same value. At most three launches on "stream",
+ * nothing allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL pointer, dims as above, a negative
+ * n_labels, n_new or n_roots, scale or const that is not finite or is negative, capacity < n_new, or a
+ * misaligned buffer (lengths_dev and offsets_dev 8 bytes, mask_dev none, the rest 4): all before anything
+ * is launched, and no output is touched. */
+int exaspim_teasar_apply(const int32_t* labels_dev, const int32_t* parents_dev, const int32_t* dbf_dev,
+                         const int32_t* boxes_dev, const int32_t dims[3], int32_t n_labels, double scale,
+                         double konst, uint8_t* mask_dev, const int32_t* targets_dev, const int64_t* lengths_dev,
+                         const int32_t* junction_dev, const int64_t* offsets_dev, int32_t* voxels_dev,
+                         int32_t* radii_dev, int32_t* before_dev, int64_t n_new, int64_t capacity, int32_t n_roots,
+                         int32_t* state_dev /* [5] */, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
