@@ -2081,7 +2081,8 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
     Raises
     ------
     RuntimeError
-        For a broken walk or a refused row.
+        For a broken walk or a refused row, or a round that reports fewer new
+        vertices than live labels (the loop would not end).
     """
     fn = "teasar_branches"
     dims = tuple(int(v) for v in labels.shape)
@@ -2121,6 +2122,12 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
                 break
             if live == 0:
                 break
+            if n_new < live:
+                # a live label's target is valid, so not on the skeleton: its branch holds at least the target.
+                # Fewer vertices than branches is no answer to these arguments, and the loop would never end
+                raise RuntimeError(f"{fn}: round {rounds + 1} reports {live} live label(s) and {n_new} new vertices: "
+                                   "exaspim_teasar_round took a target that is already on the skeleton, so the per-label "
+                                   "keys or the state bytes it read are not the ones this call wrote")
             rounds += 1
             live_history.append(live)
             new_history.append(n_new)
@@ -2271,8 +2278,9 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
         voxels.
     RuntimeError
         If labels is a tensor on a CPU device, another argument is on
-        another device, there is no HIP device to upload an array to, or a
-        walk is broken.
+        another device, there is no HIP device to upload an array to, a
+        walk is broken, or a round reports fewer new vertices than live
+        labels.
     """
     labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const = _checked_teasar_arguments(
         "teasar_branches", labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths)

@@ -657,7 +657,7 @@ def test_skeletonize_labels_against_the_oracles(dev):
     np.testing.assert_array_equal(chain["roots"].cpu().numpy(), roots)
     daf = ref.relaxation(filled, roots)
     np.testing.assert_array_equal(ref.bits(chain["daf"].cpu().numpy()), ref.bits(daf))
-    cost = chain["cost"].cpu().numpy()      # an input of what follows: torch's pow rounding is not under test
+    cost = chain["cost"].cpu().numpy()      # an input of what follows; tests/test_gpu_penalty.py holds it to its oracle
     assert cost.dtype == np.float32 and np.isfinite(cost[np.isfinite(daf) & (filled > 0)]).all()
     field = ref.relaxation(filled, roots, cost)
     parents, hops, orphans, invalid = pref.jacobi(filled, roots, field, cost)
