@@ -263,6 +263,9 @@ SIGNATURES = {
     "exaspim_geodesic_parents_begin": (_i32, [_vp, _I32x3, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_geodesic_parents_sweeps": (_i32, [_vp, _vp, _vp, _I32x3, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_geodesic_parents_finish": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp]),
+    "exaspim_geodesic_reseed": (_i32, [_vp, _I32x3, _i32, _vp, ctypes.c_int64, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_geodesic_parents_begin_seeds": (_i32, [_vp, _I32x3, _i32, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _sz,
+                                                    _vp]),
     "exaspim_trace_paths": (_i32, [_vp, _vp, _I32x3, _vp, _i32, _vp, _vp, ctypes.c_int64, _vp, _vp]),
     "exaspim_teasar_workspace_bytes": (_sz, [_I32x3, _i32]),
     "exaspim_teasar_begin": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _sz, _vp]),

@@ -40,6 +40,16 @@
 //   parents_pick      one thread per voxel, global memory only: the parent, and the orphans (finite field, no
 //                     source, no tight predecessor) counted with one atomic per wave.
 //   trace_paths       one thread per target: at most hops[target] steps along parents, written back to front.
+//
+// Fields and hops seeded from a list (exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds; DESIGN
+// 6o): any number of seeds per label, duplicates allowed. Zeroing a converged field at further seeds and
+// sweeping again gives the field of all seeds, bit for bit: every old value is a sum along a real path from a
+// voxel that is still a seed, so an upper bound, and the relaxation stops only where no edge can lower one.
+//   reseed_clear      both flag arrays and the header cleared; the field is left as it is.
+//   reseed_seeds      a grid-stride thread per seed: a valid seed (in the volume, its label in 1..K) gets +0.0 and
+//                     flags as geodesic_sources does, an invalid one is counted and writes nothing. Two seeds of
+//                     one voxel store the same word.
+//   hops_seed_list    hops_seed over the list: a valid seed whose field word is +0.0 gets hops 0.
 #include "label_scan.h"
 
 namespace exaspim {
@@ -367,6 +377,59 @@ __global__ __launch_bounds__(kThreads) void hops_seed(const int* __restrict__ la
                 for (int tx = (x - 1) / kTX; tx <= (x + 1) / kTX; ++tx)
                     if (tz < tl.nz && ty < tl.ny && tx < tl.nx)
                         flag_tile(flags, &hdr->count[0], ((long long)tz * tl.ny + ty) * tl.nx + tx);
+    }
+}
+
+// ---- seeds from a list -----------------------------------------------------------------
+// the seed's tile and the tiles that see it in their halo, as geodesic_sources flags them
+__device__ __forceinline__ void flag_around(int s, const Dims& dm, const Tiles& tl, Header* hdr, int* flags) {
+    const int x = s % dm.w, y = (s / dm.w) % dm.h, z = s / (dm.w * dm.h);
+    for (int tz = (z - 1) / kTZ; tz <= (z + 1) / kTZ; ++tz)
+        for (int ty = (y - 1) / kTY; ty <= (y + 1) / kTY; ++ty)
+            for (int tx = (x - 1) / kTX; tx <= (x + 1) / kTX; ++tx)
+                if (tz < tl.nz && ty < tl.ny && tx < tl.nx)
+                    flag_tile(flags, &hdr->count[0], ((long long)tz * tl.ny + ty) * tl.nx + tx);
+}
+
+__global__ __launch_bounds__(kThreads) void reseed_clear(Header* hdr, int* flags, size_t n_flags) {
+    const size_t step = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (first == 0) *hdr = Header{0, {0, 0}, 0};
+    for (size_t i = first; i < n_flags; i += step) flags[i] = 0;
+}
+
+__global__ __launch_bounds__(kThreads) void reseed_seeds(const int* __restrict__ labels, const int* __restrict__ seeds,
+                                                        long long n_seeds, int n_labels, float* field, Dims dm,
+                                                        Tiles tl, Header* hdr, int* flags) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n_seeds; i += step) {
+        const int s = seeds[i];
+        int l = 0;
+        if (s >= 0 && s < dm.n) l = labels[s];
+        if (l < 1 || l > n_labels) {
+            atomicAdd(&hdr->invalid, 1);
+            continue;
+        }
+        field[s] = 0.0f;
+        flag_around(s, dm, tl, hdr, flags);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void hops_seed_list(const int* __restrict__ labels,
+                                                          const int* __restrict__ seeds, long long n_seeds,
+                                                          int n_labels, const float* __restrict__ field, int* hops,
+                                                          Dims dm, Tiles tl, Header* hdr, int* flags) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n_seeds; i += step) {
+        const int s = seeds[i];
+        int l = 0;
+        if (s >= 0 && s < dm.n) l = labels[s];
+        // a seed whose field word is not +0.0 belongs to another field: the row counts as invalid
+        if (l < 1 || l > n_labels || __float_as_uint(field[s]) != 0u) {
+            atomicAdd(&hdr->invalid, 1);
+            continue;
+        }
+        hops[s] = 0;
+        flag_around(s, dm, tl, hdr, flags);
     }
 }
 
@@ -758,6 +821,69 @@ extern "C" int exaspim_geodesic_parents_begin(const int32_t* labels_dev, const i
                                                                        2 * (size_t)tl.n);
     hops_seed<<<capped_grid((size_t)n_labels, kThreads), kThreads, 0, s>>>(labels_dev, sources_dev, n_labels, field_dev,
                                                                            hops_dev, dm, tl, hdr, flags);
+    geodesic_publish<<<1, 1, 0, s>>>(hdr, state_dev, 0);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_geodesic_reseed(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                                       const int32_t* seeds_dev, int64_t n_seeds, float* field_dev, int32_t* state_dev,
+                                       void* workspace_dev, size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(labels_dev && dims && field_dev && state_dev && workspace_dev, "geodesic_reseed: NULL argument");
+    Dims dm;
+    EXA_CHECK_ARG(geodesic_dims(dims, &dm), "geodesic_reseed: %s", kDimsMessage);
+    EXA_CHECK_ARG(n_labels >= 0, "geodesic_reseed: n_labels must not be negative, got %d", n_labels);
+    EXA_CHECK_ARG(n_seeds >= 0, "geodesic_reseed: n_seeds must not be negative, got %lld", (long long)n_seeds);
+    EXA_CHECK_ARG(n_seeds == 0 || seeds_dev, "geodesic_reseed: NULL argument");
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && aligned4(labels_dev, seeds_dev, field_dev, state_dev),
+                  "geodesic_reseed: misaligned buffer");
+    const size_t need = workspace_need(dm);
+    if (workspace_bytes < need) {
+        set_error("geodesic_reseed: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return EXASPIM_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const Tiles tl = tiles_of(dm);
+    Header* hdr = static_cast<Header*>(workspace_dev);
+    int* flags = reinterpret_cast<int*>(static_cast<char*>(workspace_dev) + align_up(sizeof(Header), 16));
+    reseed_clear<<<capped_grid(2 * (size_t)tl.n, kThreads), kThreads, 0, s>>>(hdr, flags, 2 * (size_t)tl.n);
+    if (n_seeds > 0)
+        reseed_seeds<<<capped_grid((size_t)n_seeds, kThreads), kThreads, 0, s>>>(
+            labels_dev, seeds_dev, (long long)n_seeds, n_labels, field_dev, dm, tl, hdr, flags);
+    geodesic_publish<<<1, 1, 0, s>>>(hdr, state_dev, 0);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" int exaspim_geodesic_parents_begin_seeds(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                                                    const int32_t* seeds_dev, int64_t n_seeds, const float* field_dev,
+                                                    int32_t* hops_dev, int32_t* state_dev, void* workspace_dev,
+                                                    size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(labels_dev && dims && field_dev && hops_dev && state_dev && workspace_dev,
+                  "geodesic_parents_begin_seeds: NULL argument");
+    Dims dm;
+    EXA_CHECK_ARG(geodesic_dims(dims, &dm), "geodesic_parents_begin_seeds: %s", kDimsMessage);
+    EXA_CHECK_ARG(n_labels >= 0, "geodesic_parents_begin_seeds: n_labels must not be negative, got %d", n_labels);
+    EXA_CHECK_ARG(n_seeds >= 0, "geodesic_parents_begin_seeds: n_seeds must not be negative, got %lld",
+                  (long long)n_seeds);
+    EXA_CHECK_ARG(n_seeds == 0 || seeds_dev, "geodesic_parents_begin_seeds: NULL argument");
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && aligned4(labels_dev, seeds_dev, field_dev, hops_dev) &&
+                      aligned4(state_dev),
+                  "geodesic_parents_begin_seeds: misaligned buffer");
+    const size_t need = workspace_need(dm);
+    if (workspace_bytes < need) {
+        set_error("geodesic_parents_begin_seeds: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return EXASPIM_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const Tiles tl = tiles_of(dm);
+    Header* hdr = static_cast<Header*>(workspace_dev);
+    int* flags = reinterpret_cast<int*>(static_cast<char*>(workspace_dev) + align_up(sizeof(Header), 16));
+    hops_init<<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, s>>>(hops_dev, (size_t)dm.n, hdr, flags,
+                                                                       2 * (size_t)tl.n);
+    if (n_seeds > 0)
+        hops_seed_list<<<capped_grid((size_t)n_seeds, kThreads), kThreads, 0, s>>>(
+            labels_dev, seeds_dev, (long long)n_seeds, n_labels, field_dev, hops_dev, dm, tl, hdr, flags);
     geodesic_publish<<<1, 1, 0, s>>>(hdr, state_dev, 0);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;

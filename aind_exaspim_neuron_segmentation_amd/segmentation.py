@@ -1488,14 +1488,18 @@ def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_swee
     return field, far_value, far_index
 
 
-def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_read, max_sweeps, field=None):
+def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_read, max_sweeps, field=None,
+                                seed_list=False):
     """
     The front matter geodesic_field and geodesic_parents share: every argument
     checked in one order, arrays before any device is asked for, then labels,
     sources and cost as contiguous tensors on one HIP device. "field", which
     geodesic_parents alone has, is float32 of the labels' shape as cost is and
-    is checked after it. Returns (labels, dims, sources, cost, field).
+    is checked after it. With seed_list "sources" is a list of seeds, int32
+    (S,) with S >= 0, whatever n_labels is. Returns (labels, dims, sources,
+    cost, field).
     """
+    listed = "seeds" if seed_list else "sources"
     for name, value in (("sweeps_per_read", sweeps_per_read), ("max_sweeps", max_sweeps)):
         if value is None and name == "max_sweeps":
             continue
@@ -1512,6 +1516,10 @@ def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_
             raise ValueError(f"n_labels must not be negative, got {n_labels}")
 
     def check_sources(a):
+        if seed_list:
+            if a.ndim != 1:
+                raise ValueError(f"{fn}: seeds must be (S,), got {tuple(a.shape)}")
+            return
         if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
             rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
             raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
@@ -1521,7 +1529,7 @@ def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_
             raise ValueError(f"{fn}: {what} must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
 
     # every array is checked before any of them is uploaded
-    for what, a, dtype in (("sources", sources, np.int32), ("cost", cost, np.float32),
+    for what, a, dtype in ((listed, sources, np.int32), ("cost", cost, np.float32),
                            ("field", field, np.float32)):
         if isinstance(a, np.ndarray) and a.dtype != dtype:
             raise TypeError(f"{what} must be {np.dtype(dtype)}, got {a.dtype}")
@@ -1533,7 +1541,7 @@ def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_
     if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
         if isinstance(sources, torch.Tensor):
             if sources.dtype != torch.int32:
-                raise TypeError(f"sources must be int32, got {sources.dtype}")
+                raise TypeError(f"{listed} must be int32, got {sources.dtype}")
             check_sources(sources)
         for what, a in (("cost", cost), ("field", field)):
             if isinstance(a, torch.Tensor):
@@ -1542,12 +1550,12 @@ def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_
                 check_cost(a, labels.shape, what)
     labels, dims = _checked_labels(labels, fn)
     device = labels.device
-    sources = _on_device(sources, fn, "sources", (np.int32,))
+    sources = _on_device(sources, fn, listed, (np.int32,))
     if sources.dtype != torch.int32:
-        raise TypeError(f"sources must be int32, got {sources.dtype}")
+        raise TypeError(f"{listed} must be int32, got {sources.dtype}")
     check_sources(sources)
     if sources.device != device:
-        raise RuntimeError(f"{fn}: sources must be on the labels' device {device}, got {sources.device}")
+        raise RuntimeError(f"{fn}: {listed} must be on the labels' device {device}, got {sources.device}")
     both = []
     for what, a in (("cost", cost), ("field", field)):
         if a is not None:
@@ -1672,7 +1680,7 @@ def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read
 
 
 def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_per_read=32, max_sweeps=None,
-                                stats=None):
+                                stats=None, seeds=None, n_labels=None, out=None, fn="geodesic_parents"):
     """
     geodesic_parents on checked device tensors: the field from
     _geodesic_on_device if none is given, exaspim_geodesic_parents_begin, then
@@ -1690,6 +1698,16 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
     stats : dict, optional
         Receives "sweeps", "reads" and "tiles_flagged" of the hops pass, and
         under "field" those of the field pass if it ran here.
+    seeds : torch.Tensor, optional
+        int32 (S,) on the labels' device: a list of seeds in place of
+        "sources", which is then ignored (exaspim_geodesic_parents_begin_seeds);
+        "field" and "n_labels" must be given. Default is None.
+    n_labels : int, optional
+        K with "seeds". Default is None: len(sources) - 1.
+    out : tuple of torch.Tensor, optional
+        (parents, hops) to write into. Default is None: they are allocated.
+    fn : str, optional
+        The name the messages carry.
 
     Returns
     -------
@@ -1703,9 +1721,9 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
     RuntimeError
         If max_sweeps is exceeded.
     """
-    fn = "geodesic_parents"
     dims = tuple(int(v) for v in labels.shape)
-    n_labels = int(sources.numel()) - 1
+    if seeds is None:
+        n_labels = int(sources.numel()) - 1
     device = labels.device
     if field is None:
         field_stats = {}
@@ -1720,16 +1738,32 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
     cost_ptr = None if cost is None else cost.data_ptr()
     with torch.cuda.device(device):
         stream = _stream(device)
-        hops = torch.empty(dims, dtype=torch.int32, device=device)
-        parents = torch.empty(dims, dtype=torch.int32, device=device)
+        if out is None:
+            hops = torch.empty(dims, dtype=torch.int32, device=device)
+            parents = torch.empty(dims, dtype=torch.int32, device=device)
+        else:
+            parents, hops = out
         state = torch.zeros(3, dtype=torch.int32, device=device)
         workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        _native.check(
-            lib.exaspim_geodesic_parents_begin(labels.data_ptr(), dims3, sources.data_ptr(), n_labels, field.data_ptr(),
-                                               hops.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
-            "exaspim_geodesic_parents_begin",
-        )
+        if seeds is None:
+            _native.check(
+                lib.exaspim_geodesic_parents_begin(labels.data_ptr(), dims3, sources.data_ptr(), n_labels,
+                                                   field.data_ptr(), hops.data_ptr(), state.data_ptr(),
+                                                   workspace.data_ptr(), need, stream),
+                "exaspim_geodesic_parents_begin",
+            )
+        else:
+            n_seeds = int(seeds.numel())
+            _native.check(
+                lib.exaspim_geodesic_parents_begin_seeds(labels.data_ptr(), dims3, n_labels,
+                                                         seeds.data_ptr() if n_seeds else None, n_seeds,
+                                                         field.data_ptr(), hops.data_ptr(), state.data_ptr(),
+                                                         workspace.data_ptr(), need, stream),
+                "exaspim_geodesic_parents_begin_seeds",
+            )
         flagged, invalid, _ = (int(v) for v in state.cpu())
+        if invalid and seeds is not None:
+            raise ValueError(f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} with a field of 0")
         if invalid:
             raise ValueError(f"{fn}: {invalid} row(s) of sources name no voxel of their label with a field of 0 "
                              "(a row L must be -1 or the linear index of a voxel with labels == L and field == 0)")
@@ -1760,7 +1794,7 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
             stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
         if orphans:
             raise ValueError(f"{fn}: {orphans} voxel(s) with a finite field have no tight predecessor: field is not "
-                             "the geodesic field of these labels, sources and cost")
+                             f"the geodesic field of these labels, {'sources' if seeds is None else 'seeds'} and cost")
     return parents, hops
 
 
@@ -1970,14 +2004,19 @@ def _checked_teasar_scalars(fn, scale, const, max_paths):
             raise ValueError(f"{fn}: max_paths must be at least 1, got {max_paths}")
 
 
-def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths):
+def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths,
+                              fields=None):
     """
     The front matter of teasar_branches, in _checked_geodesic_arguments'
     manner: the scalars first, then every array before any of them is
     uploaded, then tensors next to a labels tensor, then everything as
     contiguous tensors on the labels' device. Returns (labels, dims, sources,
-    dbf, daf, parents, hops, boxes or None, scale, const).
+    dbf, daf, parents, hops, boxes or None, scale, const). With
+    fields=(cost, field), teasar_branches_fix_branching's two float32 volumes,
+    these two, parents and hops may be None and are returned as None, and
+    (cost, field) is appended to the result.
     """
+    optional = ("boxes",) if fields is None else ("boxes", "parents", "hops", "cost", "field")
     _checked_teasar_scalars(fn, scale, const, max_paths)
     if n_labels is not None:
         if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
@@ -2000,6 +2039,8 @@ def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxe
 
     volumes = (("dbf", dbf, np.int32, torch.int32), ("daf", daf, np.float32, torch.float32),
                ("parents", parents, np.int32, torch.int32), ("hops", hops, np.int32, torch.int32))
+    if fields is not None:
+        volumes += (("cost", fields[0], np.float32, torch.float32), ("field", fields[1], np.float32, torch.float32))
     tables = (("sources", sources, np.int32, torch.int32), ("boxes", boxes, np.int32, torch.int32))
 
     def check_dtype(what, a, np_dtype, torch_dtype):
@@ -2030,7 +2071,7 @@ def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxe
     device = labels.device
     out = []
     for what, a, np_dtype, torch_dtype in tables + volumes:
-        if a is None and what == "boxes":
+        if a is None and what in optional:
             out.append(None)
             continue
         a = _on_device(a, fn, what, (np_dtype,))
@@ -2044,12 +2085,12 @@ def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxe
         if a.device != device:
             raise RuntimeError(f"{fn}: {what} must be on the labels' device {device}, got {a.device}")
         out.append(a.contiguous())
-    sources, boxes, dbf, daf, parents, hops = out
-    return labels, dims, sources, dbf, daf, parents, hops, boxes, float(scale), float(const)
+    sources, boxes, dbf, daf, parents, hops = out[:6]
+    return (labels, dims, sources, dbf, daf, parents, hops, boxes, float(scale), float(const)) + tuple(out[6:])
 
 
 def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths=None, stats=None,
-                      on_round=None):
+                      on_round=None, update=None, fn="teasar_branches"):
     """
     teasar_branches on checked device tensors: exaspim_teasar_begin, then per
     round exaspim_teasar_round, one 20-byte read of the state, the cumulative
@@ -2067,6 +2108,16 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
     on_round : callable, optional
         Called after every round with (round, mask), mask the uint8 (D, H, W)
         state of every voxel: bit 0 still valid, bit 1 on the skeleton.
+    update : callable, optional
+        The fix_branching form. exaspim_teasar_round of a round t >= 2 is first
+        run on the parents of the round before, only to learn whether a label
+        is live (those parents still end on the skeleton, and the call writes
+        nothing a second call does not write again); if one is,
+        update(t, vertices of round t - 1) returns the (parents, hops) of
+        round t and the call is repeated on them. Default is None: one
+        parental field for every round.
+    fn : str, optional
+        The name the messages carry.
 
     Returns
     -------
@@ -2084,7 +2135,6 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
         For a broken walk or a refused row, or a round that reports fewer new
         vertices than live labels (the loop would not end).
     """
-    fn = "teasar_branches"
     dims = tuple(int(v) for v in labels.shape)
     n_labels = int(sources.numel()) - 1
     device = labels.device
@@ -2109,19 +2159,34 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
         )
         rounds, reads, refused = 0, 0, 0
         per_round, live_history, new_history = [], [], []
-        while max_paths is None or rounds < max_paths:
+
+        def walk():
+            """exaspim_teasar_round on the current parents and the read of its state."""
             _native.check(
                 lib.exaspim_teasar_round(labels.data_ptr(), daf.data_ptr(), parents.data_ptr(), hops.data_ptr(), dims3,
                                          n_labels, mask.data_ptr(), targets.data_ptr(), lengths.data_ptr(),
                                          junction.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
                 "exaspim_teasar_round",
             )
-            live, broken, n_new, n_roots, refused = (int(v) for v in state.cpu())   # the round's one read
+            return tuple(int(v) for v in state.cpu())
+
+        while max_paths is None or rounds < max_paths:
+            live, broken, n_new, n_roots, refused = walk()   # the round's one read
             reads += 1
             if broken or refused:
                 break
             if live == 0:
                 break
+            if update is not None and rounds >= 1:
+                # the round exists: only now are its field, hops and parents built, and the walk taken on them
+                parents, hops = update(rounds + 1, per_round[-1][0])
+                live, broken, n_new, n_roots, refused = walk()
+                reads += 1
+                if broken or refused:
+                    break
+                if live == 0:
+                    raise RuntimeError(f"{fn}: round {rounds + 1} had a live label on the parents of the round before "
+                                       "and has none on its own: the state bytes changed between two calls")
             if n_new < live:
                 # a live label's target is valid, so not on the skeleton: its branch holds at least the target.
                 # Fewer vertices than branches is no answer to these arguments, and the loop would never end
@@ -2220,7 +2285,9 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
     the earlier paths; this is the fix_branching=False form. Soma mode (the
     soma_* parameters and the spherical invalidation around a soma root),
     fix_borders, anisotropy, several sources per label and a slab-streamed
-    form are not built.
+    form are not built. (The fix_branching=True form is
+    teasar_branches_fix_branching, on fields seeded from the skeleton:
+    geodesic_field_seeded and geodesic_parents_seeded.)
 
     Parameters
     ----------
@@ -2295,14 +2362,17 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
     return out
 
 
-def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths):
+def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths,
+                              fix_branching=False, stats=None):
     """
     The nine stages of skeletonize_labels on a checked device tensor, nothing
     downloaded in between but the words each stage reads for itself. Returns
     a dict of device tensors: "labels" (filled if asked), "dbf", "boxes",
     "roots", "daf", "cost", "parents", "hops", and _teasar_on_device's
     "voxels", "radii", "before", "offsets", "branch_label", "branch_round",
-    "branch_junction".
+    "branch_junction". With fix_branching the last stage is
+    teasar_branches_fix_branching's loop ("parents" and "hops" are round 1's);
+    "stats" receives the loop's.
     """
     device = labels.device
     with torch.cuda.device(device):
@@ -2324,9 +2394,14 @@ def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, f
         del rows, root_peak, far, depth
         pdrf, _, _ = _geodesic_on_device(labels, roots, cost)
         parents, hops = _geodesic_parents_on_device(labels, roots, pdrf, cost)
-        del pdrf
         names = ("voxels", "radii", "before", "offsets", "branch_label", "branch_round", "branch_junction")
-        out = dict(zip(names, _teasar_on_device(labels, roots, dbf, daf, parents, hops, boxes, scale, const, max_paths)))
+        if fix_branching:
+            loop = _fix_branching_on_device(labels, roots, dbf, daf, cost, pdrf, parents, hops, boxes, scale, const,
+                                            max_paths, stats)
+        else:
+            del pdrf
+            loop = _teasar_on_device(labels, roots, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats)
+        out = dict(zip(names, loop))
     out.update(labels=labels, dbf=dbf, boxes=boxes, roots=roots, daf=daf, cost=cost, parents=parents, hops=hops)
     return out
 
@@ -2354,7 +2429,9 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
     along the earlier paths. Soma detection and its spherical invalidation
     (the soma_* parameters), fix_borders and anisotropy are not built, and
     equality with kimimaro is not claimed. A piece of a label that the root's
-    piece does not touch gets no skeleton.
+    piece does not touch gets no skeleton. (skeletonize is this chain with the
+    fix_branching=True loop, teasar_branches_fix_branching, as its last
+    stage.)
 
     Parameters
     ----------
@@ -2388,7 +2465,12 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
         and teasar_branches; TypeError or ValueError for a pdrf_exponent that
         is no integer >= 0 or a pdrf_scale that is not finite and >= 0.
     """
-    fn = "skeletonize_labels"
+    return _skeletons_of_labels("skeletonize_labels", labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes,
+                                max_paths, False)
+
+
+def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching):
+    """skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host."""
     if isinstance(pdrf_exponent, bool) or not isinstance(pdrf_exponent, (int, np.integer)):
         raise TypeError(f"{fn}: pdrf_exponent must be an integer, got {type(pdrf_exponent).__name__}")
     if pdrf_exponent < 0:
@@ -2400,7 +2482,8 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
     _checked_teasar_scalars(fn, scale, const, max_paths)
     labels, dims = _checked_labels(labels, fn)
     chain = _skeleton_chain_on_device(labels, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
-                                      bool(fill_holes), None if max_paths is None else int(max_paths))
+                                      bool(fill_holes), None if max_paths is None else int(max_paths),
+                                      bool(fix_branching))
     with torch.cuda.device(labels.device):
         voxels, before, offsets, branch_label = (chain[k] for k in ("voxels", "before", "offsets", "branch_label"))
         radius = chain["dbf"].reshape(-1)[voxels.to(torch.int64)].to(torch.float32).sqrt()
@@ -2464,6 +2547,520 @@ def skeleton_to_swc(vertices, parent, radius):
         up = int(parent[i])
         lines.append(f"{i + 1} 0 {x} {y} {z} {float(radius[i]):g} {up + 1 if up >= 0 else -1}\n")
     return "".join(lines)
+
+
+# ---- fields seeded from a list, and TEASAR's fix_branching loop on them ----------------------------
+def _geodesic_seeded_on_device(fn, labels, n_labels, seeds, cost=None, field=None, sweeps_per_read=32,
+                               max_sweeps=None, stats=None):
+    """
+    geodesic_field_seeded on checked device tensors. Without "field" the field
+    is started by exaspim_geodesic_begin with every source -1; with it, the
+    given tensor, a converged field of these labels and cost, is re-seeded IN
+    PLACE. Then exaspim_geodesic_reseed, and exaspim_geodesic_sweeps
+    (sweeps_per_read) with one 8-byte read of the state until no tile is
+    flagged. Everything stays on the device.
+
+    Parameters
+    ----------
+    fn : str
+        The name the messages carry.
+    labels : torch.Tensor
+        int32 (D, H, W) on a HIP device.
+    n_labels : int
+        K.
+    seeds : torch.Tensor
+        int32 (S,), S >= 0, on the same device.
+    cost, sweeps_per_read, max_sweeps
+        As in _geodesic_on_device.
+    field : torch.Tensor, optional
+        float32 (D, H, W), contiguous, on the same device; written.
+    stats : dict, optional
+        Receives "sweeps", "reads" and "tiles_flagged".
+
+    Returns
+    -------
+    torch.Tensor
+        float32 (D, H, W): "field" if it was given.
+
+    Raises
+    ------
+    ValueError
+        For seeds that name no voxel of a label in 1..K.
+    RuntimeError
+        If max_sweeps is exceeded.
+    """
+    dims = tuple(int(v) for v in labels.shape)
+    device = labels.device
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = lib.exaspim_geodesic_workspace_bytes(dims3)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    cost_ptr = None if cost is None else cost.data_ptr()
+    n_seeds = int(seeds.numel())
+    with torch.cuda.device(device):
+        stream = _stream(device)
+        state = torch.empty(2, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        if field is None:
+            field = torch.empty(dims, dtype=torch.float32, device=device)
+            nowhere = torch.full((n_labels + 1,), -1, dtype=torch.int32, device=device)
+            _native.check(
+                lib.exaspim_geodesic_begin(labels.data_ptr(), dims3, nowhere.data_ptr(), n_labels, field.data_ptr(),
+                                           state.data_ptr(), workspace.data_ptr(), need, stream),
+                "exaspim_geodesic_begin",
+            )
+        _native.check(
+            lib.exaspim_geodesic_reseed(labels.data_ptr(), dims3, n_labels, seeds.data_ptr() if n_seeds else None,
+                                        n_seeds, field.data_ptr(), state.data_ptr(), workspace.data_ptr(), need,
+                                        stream),
+            "exaspim_geodesic_reseed",
+        )
+        flagged, invalid = (int(v) for v in state.cpu())   # the first read of the state
+        if invalid:
+            raise ValueError(f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} (a seed must be the "
+                             "linear index of a voxel whose label is in 1..K)")
+        sweeps, reads, history = 0, 1, [flagged]
+        while flagged:
+            if max_sweeps is not None and sweeps >= max_sweeps:
+                raise RuntimeError(f"{fn}: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
+                                   f"{flagged} tile(s) still flagged")
+            batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+            _native.check(
+                lib.exaspim_geodesic_sweeps(labels.data_ptr(), cost_ptr, dims3, n_labels, field.data_ptr(), batch,
+                                            state.data_ptr(), workspace.data_ptr(), need, stream),
+                "exaspim_geodesic_sweeps",
+            )
+            sweeps += batch
+            flagged = int(state.cpu()[0])
+            reads += 1
+            history.append(flagged)
+        if stats is not None:
+            stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
+    return field
+
+
+def _label_count(labels, n_labels, fn):
+    """K: n_labels checked, or the largest label, read from the device."""
+    if n_labels is None:
+        with torch.cuda.device(labels.device):
+            return max(int(labels.max()), 0)
+    return int(n_labels)
+
+
+def geodesic_field_seeded(labels, seeds, *, cost=None, field=None, n_labels=None, sweeps_per_read=32, max_sweeps=None,
+                          return_device_tensor=False, stats=None):
+    """
+    The geodesic distance of every voxel from the nearest seed of its label,
+    for all labels at once, on the device: geodesic_field with any number of
+    sources per label, and the way to add sources to a converged field.
+
+    What this is: the primitive under kimimaro's fix_branching=True, which
+    the reference's skeletonize (inference.py:257-291) runs: every path after
+    the first is a shortest path on a penalty field zeroed along the earlier
+    paths. Exactly, in float32: labels, adjacency, "cost" and the weights
+    w(u -> v) are geodesic_field's; K is n_labels, or the largest label.
+    "seeds" is a list of C-order linear indices, any number per label,
+    duplicates allowed; a seed is valid iff it lies in the volume and its
+    label is in 1..K. The field d is the least solution of d[s] = +0.0 at
+    every seed s and d[v] = min over adjacent u of fl32(d[u] + w(u -> v)):
+    bit for bit what a multi-source float32 heap Dijkstra returns, whatever
+    the order of relaxation. A seed's own cost is never read. Background gets
+    0.0; a label without a seed stays +inf.
+
+    The incremental form: with "field", the converged field of these labels
+    and cost and of seeds A, the result is the field of A and "seeds"
+    together, bit for bit: every old value is the float32 sum along a real
+    path from a voxel that is still a seed, hence an upper bound, and the
+    relaxation only lowers values until d[v] <= fl32(d[u] + w) holds on every
+    edge. The caller's field is copied, never written. Zeroing the cost along
+    a connected set that holds the root and keeping the root as the only
+    source (kimimaro's wording) gives the same field.
+
+    What this is not: kimimaro or dijkstra3d (neither is a dependency of the
+    project or its tests; equality is not claimed); a farthest table (take
+    geodesic_field's on a single-source field); anisotropic; slab-streamed.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    seeds : torch.Tensor or numpy.ndarray
+        int32 (S,), S >= 0; on the labels' device if a tensor.
+    cost : torch.Tensor or numpy.ndarray, optional
+        float32 of the labels' shape. Default is None: Euclidean steps.
+    field : torch.Tensor or numpy.ndarray, optional
+        float32 of the labels' shape: a converged field to add the seeds to.
+        Default is None: the field is built from scratch.
+    n_labels : int, optional
+        K. Default is None: the largest label, read from the device.
+    sweeps_per_read : int, optional
+        Sweeps launched between two reads of the state. Default is 32.
+    max_sweeps : int, optional
+        Raise RuntimeError if the field has not converged after this many
+        sweeps. Default is None.
+    return_device_tensor : bool, optional
+        Return a device tensor instead of a numpy array. Default is False.
+    stats : dict, optional
+        Receives "sweeps", "reads" and "tiles_flagged".
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        float32 (D, H, W).
+
+    Raises
+    ------
+    TypeError
+        If labels or seeds is not int32, cost or field is not float32, or
+        n_labels, sweeps_per_read or max_sweeps is not an integer.
+    ValueError
+        If labels is not 3-D or is empty, seeds is not 1-D, cost or field has
+        another shape, sweeps_per_read < 1, max_sweeps < 0, n_labels < 0, the
+        volume has more than 2^31 - 1 voxels, or a seed names no voxel of a
+        label in 1..K (found at the first read of the device).
+    RuntimeError
+        If labels is a tensor on a CPU device, another argument is on another
+        device, there is no HIP device to upload an array to, or max_sweeps
+        is exceeded.
+    """
+    fn = "geodesic_field_seeded"
+    labels, dims, seeds, cost, field = _checked_geodesic_arguments(
+        fn, labels, seeds, cost, n_labels, sweeps_per_read, max_sweeps, field, seed_list=True)
+    k = _label_count(labels, n_labels, fn)
+    with torch.cuda.device(labels.device):
+        if field is not None:
+            field = field.clone()
+        out = _geodesic_seeded_on_device(fn, labels, k, seeds, cost, field, int(sweeps_per_read),
+                                         None if max_sweeps is None else int(max_sweeps), stats)
+        return out if return_device_tensor else out.cpu().numpy()
+
+
+def geodesic_parents_seeded(labels, seeds, field, *, cost=None, n_labels=None, sweeps_per_read=32, max_sweeps=None,
+                            return_hops=False, return_device_tensors=False, stats=None):
+    """
+    The parental field of a seeded field, on the device: for every voxel the
+    neighbour that leads back to the nearest seed of its label.
+
+    What this is: geodesic_parents with "the source" read as "a seed", the
+    parental field kimimaro's fix_branching=True takes per path (the
+    reference's skeletonize, inference.py:257-291). "field" is the converged
+    geodesic_field_seeded of exactly these labels, seeds and cost. hops h is
+    the least solution of h[s] = 0 at every valid seed s whose field word is
+    +0.0 (any other seed counts as invalid) and h[v] = 1 + min over tight
+    u -> v of h[u]; no tight edge enters a seed; a seed is its own parent;
+    any other voxel's parent is the tight predecessor with one hop less and
+    the smallest linear index. The chain from v reaches a seed in h[v] steps,
+    and re-adding the weights along it reproduces the field bit for bit.
+    Everything else is geodesic_parents'.
+
+    What this is not: kimimaro or dijkstra3d.parental_field; equality is not
+    claimed.
+
+    Parameters
+    ----------
+    labels, seeds, cost, n_labels, sweeps_per_read, max_sweeps
+        As in geodesic_field_seeded.
+    field : torch.Tensor or numpy.ndarray
+        float32 of the labels' shape, on the labels' device if a tensor.
+    return_hops : bool, optional
+        Also return hops. Default is False.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+    stats : dict, optional
+        Receives "sweeps", "reads" and "tiles_flagged" of the hops pass.
+
+    Returns
+    -------
+    numpy.ndarray or torch.Tensor
+        int32 (D, H, W) parents; with return_hops the tuple (parents, hops).
+
+    Raises
+    ------
+    TypeError
+        As geodesic_field_seeded; also if field is None.
+    ValueError
+        As geodesic_field_seeded; also if a seed's field is not 0, or there
+        are orphans: field is not the seeded field of these labels, seeds and
+        cost.
+    RuntimeError
+        As geodesic_field_seeded.
+    """
+    fn = "geodesic_parents_seeded"
+    if field is None:
+        raise TypeError(f"{fn}: field must be a torch tensor or a numpy array, got NoneType")
+    labels, dims, seeds, cost, field = _checked_geodesic_arguments(
+        fn, labels, seeds, cost, n_labels, sweeps_per_read, max_sweeps, field, seed_list=True)
+    k = _label_count(labels, n_labels, fn)
+    parents, hops = _geodesic_parents_on_device(
+        labels, None, field, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps), stats,
+        seeds=seeds, n_labels=k, fn=fn)
+    with torch.cuda.device(labels.device):
+        out = (parents, hops) if return_hops else (parents,)
+        if not return_device_tensors:
+            out = tuple(t.cpu().numpy() for t in out)
+    return out if return_hops else out[0]
+
+
+# Sweeps between two reads of the state in an incremental field pass: a re-seeded field settles within a few
+# tiles of the new branch, and every sweep launched after it has converged is an empty launch.
+FIX_BRANCHING_FIELD_SWEEPS = 8
+
+
+def _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
+                             max_paths=None, stats=None, on_round=None):
+    """
+    teasar_branches_fix_branching on checked device tensors: _teasar_on_device
+    with an update before the walk of every round t >= 2 that exists. The
+    update re-seeds a copy of "field" with the vertices of round t - 1
+    (exaspim_geodesic_reseed and sweeps), then rebuilds hops and parents with
+    all vertices so far as seeds (exaspim_geodesic_parents_begin_seeds, sweeps,
+    finish) into tensors of its own. field, parents and hops, those of
+    (labels, sources, cost), are only read; the copies are made at the first
+    update, so a call with one round allocates none. Returns
+    _teasar_on_device's tuple; "stats" additionally receives "updates",
+    "field_sweeps" and "hops_sweeps" (one entry per update).
+    """
+    fn = "teasar_branches_fix_branching"
+    dims = tuple(int(v) for v in labels.shape)
+    n_labels = int(sources.numel()) - 1
+    device = labels.device
+    own, vertices, field_sweeps, hops_sweeps = {}, [], [], []
+
+    def update(t, fresh):
+        with torch.cuda.device(device):
+            if not own:
+                own["field"] = field.clone()
+                own["parents"] = torch.empty(dims, dtype=torch.int32, device=device)
+                own["hops"] = torch.empty(dims, dtype=torch.int32, device=device)
+            vertices.append(fresh)
+            field_stats, hops_stats = {}, {}
+            _geodesic_seeded_on_device(fn, labels, n_labels, fresh, cost, own["field"], FIX_BRANCHING_FIELD_SWEEPS,
+                                       None, field_stats)
+            # every vertex of every label: a finished label's zeroed voxels would otherwise count as orphans
+            out = _geodesic_parents_on_device(labels, None, own["field"], cost, stats=hops_stats,
+                                              seeds=torch.cat(vertices), n_labels=n_labels,
+                                              out=(own["parents"], own["hops"]), fn=fn)
+            field_sweeps.append(field_stats["sweeps"])
+            hops_sweeps.append(hops_stats["sweeps"])
+        return out
+
+    result = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats,
+                               on_round, update, fn)
+    if stats is not None:
+        stats.update(updates=len(field_sweeps), field_sweeps=field_sweeps, hops_sweeps=hops_sweeps)
+    return result
+
+
+def teasar_branches_fix_branching(labels, sources, dbf, daf, cost, *, scale, const, field=None, parents=None,
+                                  hops=None, boxes=None, n_labels=None, max_paths=None, return_device_tensors=False,
+                                  stats=None):
+    """
+    TEASAR's loop in the fix_branching=True form, for every label at once, on
+    the device: every path after the first is a shortest path of the penalty
+    field re-seeded from the skeleton, so a branch leaves the skeleton where
+    that is cheapest instead of running beside it towards the root.
+
+    What this is: the loop the reference's skeletonize (inference.py:257-291)
+    asks of kimimaro.skeletonize with its default fix_branching=True. Round 1
+    is teasar_branches' round 1, on the field, parents and hops of (labels,
+    sources, cost). Before the walk of round t >= 2, (1) the penalty field is
+    re-seeded with the vertices of round t - 1, incrementally
+    (geodesic_field_seeded's argument: the result is the field seeded from
+    the whole skeleton, which is also the field of the cost zeroed along the
+    skeleton with the root as the only source, kimimaro's wording), and (2)
+    hops and parents are rebuilt with all skeleton vertices of all labels as
+    seeds (geodesic_parents_seeded; finished labels included, so that
+    "no orphans" keeps its meaning). Targets, radii, cubes, the lock-step of
+    the labels and max_paths are exactly teasar_branches'; daf is never
+    touched. The walk stops at the first voxel on the skeleton, which with
+    seeded parents is the self-parent reached after exactly hops[target]
+    steps: the junction. No field, hops or parents work is launched for a
+    round that turns out not to exist: updates == rounds - 1, and where every
+    label has one path (the reference's const = 450 on a volume whose labels
+    fit a 450-voxel cube) the call costs what teasar_branches costs plus one
+    more pass over the state bytes.
+
+    What this is not: kimimaro, which is no dependency of the project or its
+    tests, and equality with it is not claimed; the definition is this
+    project's own, exact and free of any order, and checked against two host
+    oracles (tests/fix_branching_ref.py).
+    Soma mode, fix_borders, anisotropy and a slab-streamed form are not
+    built.
+
+    Parameters
+    ----------
+    labels, sources, dbf, daf, scale, const, boxes, n_labels, max_paths
+        As in teasar_branches.
+    cost : torch.Tensor or numpy.ndarray or None
+        float32 of the labels' shape: the penalty whose field the paths are
+        shortest paths of. None means Euclidean steps.
+    field : torch.Tensor or numpy.ndarray, optional
+        float32 of the labels' shape: geodesic_field(labels, sources,
+        cost=cost). Default is None: it is computed here. Never modified.
+    parents, hops : torch.Tensor or numpy.ndarray, optional
+        int32 of the labels' shape: geodesic_parents of that field. If either
+        is None both are computed here. Never modified.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+    stats : dict, optional
+        Receives teasar_branches' entries ("reads" counts two per round after
+        the first) and "updates", "field_sweeps" and "hops_sweeps": the sweeps
+        launched by the field pass and by the hops pass of each update.
+
+    Returns
+    -------
+    voxels, radii, offsets, branch_label, branch_round, branch_junction
+        As teasar_branches.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As teasar_branches, geodesic_field and geodesic_parents.
+    """
+    fn = "teasar_branches_fix_branching"
+    checked = _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels,
+                                        max_paths, fields=(cost, field))
+    labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const, cost, field = checked
+    if boxes is None:
+        boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
+    if field is None:
+        field, _, _ = _geodesic_on_device(labels, sources, cost)
+    if parents is None or hops is None:
+        parents, hops = _geodesic_parents_on_device(labels, sources, field, cost)
+    out = _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
+                                   None if max_paths is None else int(max_paths), stats)
+    out = out[:2] + out[3:]
+    if not return_device_tensors:
+        with torch.cuda.device(labels.device):
+            out = tuple(t.cpu().numpy() for t in out)
+    return out
+
+
+def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pdrf_exponent=4, pdrf_scale=100000.0,
+                fill_holes=True, max_paths=None):
+    """
+    The reference's skeletonize (inference.py:257-291) under its own name and
+    in its own form: skeletonize_labels' chain with, by default, the
+    fix_branching=True loop (teasar_branches_fix_branching) as its last
+    stage, and the reference's teasar_params as defaults.
+
+    What this is not: kimimaro. The skeletons are not osteoid Skeleton
+    objects but skeletonize_labels' plain tuples, and equality with kimimaro
+    is not claimed: the definition of every stage is this project's own.
+    Soma detection and its spherical invalidation (the soma_* parameters),
+    fix_borders and anisotropy are not built.
+
+    Parameters
+    ----------
+    segmentation : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    fix_branching : bool, optional
+        True: re-seed the penalty field from the skeleton before every path
+        after the first. False: skeletonize_labels' chain, one parental
+        field. Default is True.
+    scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths
+        As in skeletonize_labels.
+
+    Returns
+    -------
+    dict
+        label -> (vertices, parent, radius), as skeletonize_labels.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As skeletonize_labels; TypeError if fix_branching is not a bool.
+    """
+    if not isinstance(fix_branching, (bool, np.bool_)):
+        raise TypeError(f"skeletonize: fix_branching must be a bool, got {type(fix_branching).__name__}")
+    return _skeletons_of_labels("skeletonize", segmentation, scale, const, pdrf_exponent, pdrf_scale, fill_holes,
+                                max_paths, bool(fix_branching))
+
+
+def skeletons_to_zipped_swcs(skeleton_dict, zip_path):
+    """
+    Saves skeletons as SWC files inside a ZIP archive, on the host (the
+    reference's function of this name): one entry "<label>.swc" per skeleton,
+    its text skeleton_to_swc's. An existing file is overwritten.
+
+    Parameters
+    ----------
+    skeleton_dict : dict
+        label -> (vertices, parent, radius), as skeletonize returns it.
+    zip_path : str or path-like
+        The archive to write.
+
+    Raises
+    ------
+    ValueError
+        As skeleton_to_swc, before anything is written.
+    """
+    import zipfile
+
+    entries = [(f"{segment_id}.swc", skeleton_to_swc(*skeleton)) for segment_id, skeleton in skeleton_dict.items()]
+    with zipfile.ZipFile(zip_path, "w") as zip_writer:
+        for filename, text in entries:
+            zip_writer.writestr(filename, text)
+
+
+def segmentation_to_zipped_swcs(segmentation, zip_path):
+    """
+    From a segmentation to an archive of SWC files in one call (the
+    reference's function of this name): skeletonize, then
+    skeletons_to_zipped_swcs.
+
+    Parameters
+    ----------
+    segmentation : torch.Tensor or numpy.ndarray
+        As in skeletonize.
+    zip_path : str or path-like
+        The archive to write; an existing file is overwritten.
+    """
+    skeletons_to_zipped_swcs(skeletonize(segmentation), zip_path)
+
+
+def voxelize_skeletons(skeleton_dict, img_shape):
+    """
+    Skeletons as a labelled volume, on the host (the reference's function of
+    this name): every vertex's voxel holds its label, everything else 0. Where
+    two skeletons share a voxel the later entry of the dict wins.
+
+    Parameters
+    ----------
+    skeleton_dict : dict
+        label -> (vertices, parent, radius), or label -> anything with a
+        "vertices" attribute; vertices are (n, 3) array indices (z, y, x).
+    img_shape : tuple of int
+        (D, H, W).
+
+    Returns
+    -------
+    numpy.ndarray
+        Integers (numpy's default int), of shape img_shape.
+
+    Raises
+    ------
+    ValueError
+        If img_shape is not three positive integers, vertices are not (n, 3),
+        or an index lies outside the volume (the reference's indexing would
+        wrap a negative one around).
+    """
+    img_shape = tuple(int(v) for v in img_shape)
+    if len(img_shape) != 3 or min(img_shape) < 1:
+        raise ValueError(f"voxelize_skeletons: img_shape must be a non-empty (D, H, W), got {img_shape}")
+    img = np.zeros(img_shape, dtype=int)
+    for segment_id, skeleton in skeleton_dict.items():
+        vertices = skeleton.vertices if hasattr(skeleton, "vertices") else skeleton[0]
+        voxels = np.asarray(vertices).astype(int)
+        if voxels.ndim != 2 or voxels.shape[1] != 3:
+            raise ValueError(f"voxelize_skeletons: the vertices of {segment_id} must be (n, 3), got {voxels.shape}")
+        if voxels.size and (voxels.min() < 0 or (voxels >= np.array(img_shape)).any()):
+            raise ValueError(f"voxelize_skeletons: a vertex of {segment_id} lies outside the volume {img_shape}")
+        img[tuple(voxels.T)] = segment_id
+    return img
 
 
 # Provisional ids a streamed labelling may use unless the caller says otherwise (id_capacity): 16 bytes

@@ -70,6 +70,8 @@ extern "C" {
  *    later within 5: exaspim_geodesic_parents_begin, exaspim_geodesic_parents_sweeps,
  *    exaspim_geodesic_parents_finish, exaspim_trace_paths: the parental field of that field and the paths
  *    read off it;
+ *    later within 5: exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds: fields and hops seeded from
+ *    a list, any number of seeds per label, and a converged field re-seeded in place (TEASAR's fix_branching);
  *    later within 5: exaspim_teasar_begin, exaspim_teasar_round, exaspim_teasar_apply (and their workspace
  *    query): TEASAR's loop of targets, branches and invalidation for every label at once */
 #define EXASPIM_ABI_VERSION 5
@@ -1249,13 +1251,61 @@ int exaspim_trace_paths(const int32_t* parents_dev, const int32_t* hops_dev, con
                         const int32_t* targets_dev, int32_t n_targets, const int64_t* offsets_dev,
                         int32_t* paths_dev, int64_t paths_capacity, int32_t* state_dev /* [2] */, void* stream);
 
+/* ---- fields and hops seeded from a list (later within ABI 5) --------------------------------
+ *      The reference's skeletonize (inference.py:257-291) runs kimimaro.skeletonize with its default
+ *      fix_branching=True: every path after the first is a shortest path on a penalty field zeroed along the
+ *      earlier paths. That needs a field with several sources per label, and a way to add sources to a
+ *      converged one. seeds is int32 (n_seeds): C-order linear indices, any number per label, duplicates
+ *      allowed. A seed is valid iff 0 <= s < D*H*W and 1 <= labels[s] <= K. The seeded field is the field of
+ *      the section above with d[s] = +0.0 at every valid seed: the least fixed point of the same float32
+ *      relaxation, so bit for bit a multi-source float32 heap Dijkstra. A seed's own cost is never read; a
+ *      label without a seed stays +inf. Incremental form: if d is the converged field of seeds A, then d
+ *      with +0.0 stored at seeds B and relaxed again is the field of A u B, bit for bit: every old value is
+ *      the float32 sum along a real path from a voxel that is still a seed, hence an upper bound; the
+ *      relaxation only lowers values and ends with d[v] <= fl32(d[u] + w) on every edge, and induction
+ *      along an optimal path with the monotonicity of float32 addition gives d <= the answer. Seeded hops
+ *      and parents are those of the parental-field section with "the source" read as "a seed": h = 0 at
+ *      every valid seed whose field word is +0.0 (any other seed counts as invalid), no tight edge enters a
+ *      seed, and a seed is its own parent. Checked against the oracles in tests/fix_branching_ref.py; not
+ *      claimed to equal kimimaro. */
+
+/* Re-seeds a field (inference.py:257-291: the Dijkstra per path of kimimaro's fix_branching): clears the
+ * header and both flag arrays of the workspace, so a field converged at any earlier time may be passed,
+ * stores +0.0 at every valid seed and flags the seed's tile and the tiles that see it in their halo for the
+ * first sweep of exaspim_geodesic_sweeps, which then runs unchanged on the same workspace. An invalid seed
+ * writes nothing. state_dev[0] = the number of tiles flagged, state_dev[1] = the number of invalid seeds.
+ * A field built from scratch is exaspim_geodesic_begin with every source -1, then this call. labels_dev and
+ * seeds_dev are only read; seeds_dev may be NULL if n_seeds is 0. At most three launches on "stream",
+ * nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels,
+ * a negative n_labels or n_seeds, or a misaligned buffer (workspace_dev 16 bytes, the rest 4);
+ * EXASPIM_E_WORKSPACE if workspace_bytes is less than exaspim_geodesic_workspace_bytes(dims): all before
+ * anything is launched, and no output is touched. */
+int exaspim_geodesic_reseed(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                            const int32_t* seeds_dev, int64_t n_seeds, float* field_dev,
+                            int32_t* state_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+
+/* exaspim_geodesic_parents_begin with the list of seeds in place of the per-label table
+ * (inference.py:257-291: the parental field of every path's Dijkstra in kimimaro's fix_branching):
+ * hops_dev = -1 everywhere and 0 at every valid seed whose field word is +0.0; any other seed is counted
+ * in state_dev[1]. exaspim_geodesic_parents_sweeps and _finish then run unchanged. seeds_dev may be NULL if
+ * n_seeds is 0. At most three launches on "stream", nothing allocated, nothing synchronised. Refusals as
+ * exaspim_geodesic_reseed: all before anything is launched, and no output is touched. */
+int exaspim_geodesic_parents_begin_seeds(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                                         const int32_t* seeds_dev, int64_t n_seeds, const float* field_dev,
+                                         int32_t* hops_dev, int32_t* state_dev /* [3] */, void* workspace_dev,
+                                         size_t workspace_bytes, void* stream);
+
 /* ---- TEASAR's loop: targets, branches, invalidation ------------------------------------------
  * What follows the fields and the parental field in the reference's skeletonize (inference.py:257-291:
  * the loop of kimimaro's TEASAR), for all labels at once, in the single-parental-field form: every path is
  * read off ONE parental field, which is kimimaro with fix_branching=False. The reference runs kimimaro with
- * its default fix_branching=True, a Dijkstra per path on a penalty field zeroed along the earlier paths;
- * that form, soma detection and its spherical invalidation, fix_borders and anisotropy are not built, and
- * equality with kimimaro is not claimed.
+ * its default fix_branching=True, a Dijkstra per path on a penalty field zeroed along the earlier paths:
+ * that form is these three calls with the field re-seeded and the parents rebuilt before every round after
+ * the first (exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds). Soma detection and
+ * its spherical invalidation, fix_borders and anisotropy are not built, and equality with kimimaro is
+ * not claimed.
  *
  * The definition, in integers. K = n_labels. A voxel v is eligible iff its label L is in 1..K, sources[L]
  * names a voxel of L, hops[v] >= 0 and the bits of daf[v] are below 0x7F800000 (finite, sign bit clear: -0.0
