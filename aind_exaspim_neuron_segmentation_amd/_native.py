@@ -270,8 +270,12 @@ SIGNATURES = {
     "exaspim_teasar_workspace_bytes": (_sz, [_I32x3, _i32]),
     "exaspim_teasar_begin": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_teasar_round": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_teasar_round_given": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                          _vp]),
     "exaspim_teasar_apply": (_i32, [_vp, _vp, _vp, _vp, _I32x3, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i32, _vp, _vp]),
+    "exaspim_border_targets_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_border_targets": (_i32, [_vp, _I32x3, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

@@ -17,6 +17,10 @@
 //   teasar_branch_lengths  one thread per label: the target from the key, then the walk along parents to the
 //                          first skeleton voxel or the source, at most hops[target] steps, every index
 //                          range-checked; the number of new vertices, the junction, and the counters.
+//   teasar_given_lengths   exaspim_teasar_round_given's form of teasar_branch_lengths: a label whose
+//                          row of "given" is not -1 takes that voxel as its target if it is an eligible voxel of
+//                          the label, whether it is still valid or not; a row that is not is counted in the sixth
+//                          state word and read as -1; a given target on the skeleton is no branch.
 //   teasar_branch_write    one thread per label: the same walk, now writing voxels, radii and each entry's
 //                          previous vertex back to front, and setting the skeleton bit.
 //   teasar_invalidate<ROOTS>  the hot path. ROOTS = false: grid x over the round's new vertices, grid y over
@@ -38,6 +42,7 @@ namespace {
 constexpr unsigned kInfBits = 0x7F800000u;
 constexpr unsigned char kValid = 1, kSkeleton = 2;
 constexpr int kStateWords = 5;       // live, broken, new vertices, branches without a junction, refused rows
+constexpr int kGivenWord = 5;        // exaspim_teasar_round_given's sixth word: the given targets it refused
 constexpr unsigned kDiffGridY = 4;   // a difference of two cubes is a few faces
 // a whole cube may be the whole bounding box: about 2^18 workgroups over the labels and a cube's items
 unsigned root_grid_y(int n_labels) {
@@ -69,9 +74,11 @@ __global__ __launch_bounds__(kThreads) void teasar_init(const int* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(kThreads) void teasar_round_init(unsigned long long* keys, size_t rows, int* state) {
+__global__ __launch_bounds__(kThreads) void teasar_round_init(unsigned long long* keys, size_t rows, int* state,
+                                                             bool given) {
     const size_t step = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (first < 4) state[first] = 0;   // the refused rows of exaspim_teasar_apply add up over the rounds
+    if (given && first == (size_t)kGivenWord) state[first] = 0;
     for (size_t r = first; r < rows; r += step) keys[r] = 0;
 }
 
@@ -113,6 +120,49 @@ __global__ __launch_bounds__(kThreads) void teasar_targets(const unsigned char* 
     }
 }
 
+// The walk of step (2) from "target" along parents to the first skeleton voxel or the source: at most
+// hops[target] steps, whatever parents holds. Returns false for a broken walk.
+__device__ __forceinline__ bool walk_branch(int target, const int* __restrict__ parents, const int* __restrict__ hops,
+                                            const unsigned char* __restrict__ mask, int n, long long* count,
+                                            int* junc) {
+    const int h = hops[target];
+    bool broken = h < 0;
+    int cur = target;
+    for (int k = h; k >= 0; --k) {
+        if (mask[cur] & kSkeleton) {
+            *junc = cur;
+            break;
+        }
+        ++*count;
+        const int p = parents[cur];
+        if (k == 0) {
+            broken = p != cur;   // without a junction the walk ends on a self-parent, the source
+            break;
+        }
+        if (p < 0 || p >= n || p == cur) {
+            broken = true;
+            break;
+        }
+        cur = p;
+    }
+    return !broken;
+}
+
+// the walk's outcome into the label's rows and the round's counters
+__device__ __forceinline__ void count_branch(bool whole, size_t r, int* target, long long* count, int* junc,
+                                             int* finished, int* state) {
+    if (!whole) {
+        atomicAdd(state + 1, 1);
+        finished[r] = 1;
+        *target = *junc = -1;
+        *count = 0;
+    } else {
+        atomicAdd(state + 0, 1);
+        atomicAdd(state + 2, (int)*count);
+        if (*junc < 0) atomicAdd(state + 3, 1);
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void teasar_branch_lengths(const unsigned long long* __restrict__ keys,
                                                                  const int* __restrict__ parents,
                                                                  const int* __restrict__ hops,
@@ -127,35 +177,49 @@ __global__ __launch_bounds__(kThreads) void teasar_branch_lengths(const unsigned
         long long count = 0;
         if (r > 0 && (key >> 63) && !finished[r]) {
             target = (int)(0xFFFFFFFFu - (unsigned)key);   // below n: the key was made from a voxel's index
-            const int h = hops[target];
-            bool broken = h < 0;
-            int cur = target;
-            for (int k = h; k >= 0; --k) {   // at most h steps, whatever parents holds
-                if (mask[cur] & kSkeleton) {
-                    junc = cur;
-                    break;
+            const bool whole = walk_branch(target, parents, hops, mask, n, &count, &junc);
+            count_branch(whole, r, &target, &count, &junc, finished, state);
+        }
+        targets[r] = target;
+        lengths[r] = count;
+        junction[r] = junc;
+    }
+}
+
+// teasar_branch_lengths with this round's given target per label: given[r] == -1 leaves the label to its key.
+// Any other row must name an eligible voxel of label r, or it is counted in state[kGivenWord] and read as -1.
+// A given target that is on the skeleton already is no branch: the label has none this round, is not counted
+// and is not finished.
+__global__ __launch_bounds__(kThreads) void teasar_given_lengths(
+    const unsigned long long* __restrict__ keys, const int* __restrict__ given, const int* __restrict__ labels,
+    const float* __restrict__ daf, const int* __restrict__ parents, const int* __restrict__ hops,
+    const unsigned char* __restrict__ mask, int n, int n_labels, int* __restrict__ targets,
+    long long* __restrict__ lengths, int* __restrict__ junction, int* finished, int* state) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r <= (size_t)n_labels; r += step) {
+        const unsigned long long key = keys[r];
+        int target = -1, junc = -1;
+        long long count = 0;
+        if (r > 0 && !finished[r]) {
+            int g = given[r];
+            if (g != -1) {
+                const bool ok = g >= 0 && g < n && labels[g] == (int)r && hops[g] >= 0 &&
+                                __float_as_uint(daf[g]) < kInfBits;
+                if (!ok) {
+                    atomicAdd(state + kGivenWord, 1);
+                    g = -1;
                 }
-                ++count;
-                const int p = parents[cur];
-                if (k == 0) {
-                    broken = p != cur;   // without a junction the walk ends on a self-parent, the source
-                    break;
-                }
-                if (p < 0 || p >= n || p == cur) {
-                    broken = true;
-                    break;
-                }
-                cur = p;
             }
-            if (broken) {
-                atomicAdd(state + 1, 1);
-                finished[r] = 1;
-                target = junc = -1;
-                count = 0;
-            } else {
-                atomicAdd(state + 0, 1);
-                atomicAdd(state + 2, (int)count);
-                if (junc < 0) atomicAdd(state + 3, 1);
+            if (g >= 0) {
+                if (!(mask[g] & kSkeleton)) {
+                    target = g;
+                    const bool whole = walk_branch(target, parents, hops, mask, n, &count, &junc);
+                    count_branch(whole, r, &target, &count, &junc, finished, state);
+                }
+            } else if (key >> 63) {
+                target = (int)(0xFFFFFFFFu - (unsigned)key);
+                const bool whole = walk_branch(target, parents, hops, mask, n, &count, &junc);
+                count_branch(whole, r, &target, &count, &junc, finished, state);
             }
         }
         targets[r] = target;
@@ -343,37 +407,65 @@ extern "C" int exaspim_teasar_begin(const int32_t* labels_dev, const int32_t* so
     return EXASPIM_OK;
 }
 
-extern "C" int exaspim_teasar_round(const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
-                                    const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels,
-                                    const uint8_t* mask_dev, int32_t* targets_dev, int64_t* lengths_dev,
-                                    int32_t* junction_dev, int32_t* state_dev, void* workspace_dev,
-                                    size_t workspace_bytes, void* stream) {
+namespace {
+
+// exaspim_teasar_round (given_dev == nullptr) and exaspim_teasar_round_given
+int teasar_round(const char* name, const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
+                 const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels, const uint8_t* mask_dev,
+                 const int32_t* given_dev, bool given, int32_t* targets_dev, int64_t* lengths_dev,
+                 int32_t* junction_dev, int32_t* state_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
     EXA_CHECK_ARG(labels_dev && daf_dev && parents_dev && hops_dev && dims && mask_dev && targets_dev && lengths_dev &&
-                      junction_dev && state_dev && workspace_dev,
-                  "teasar_round: NULL argument");
+                      junction_dev && state_dev && workspace_dev && (given_dev || !given),
+                  "%s: NULL argument", name);
     Dims dm;
-    EXA_CHECK_ARG(valid_dims(dims, &dm), "teasar_round: %s", kDimsMessage);
-    EXA_CHECK_ARG(n_labels >= 0, "teasar_round: n_labels must not be negative, got %d", n_labels);
+    EXA_CHECK_ARG(valid_dims(dims, &dm), "%s: %s", name, kDimsMessage);
+    EXA_CHECK_ARG(n_labels >= 0, "%s: n_labels must not be negative, got %d", name, n_labels);
     EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && aligned4(labels_dev, daf_dev, parents_dev, hops_dev) &&
-                      aligned4(targets_dev, junction_dev, state_dev) && aligned8(lengths_dev),
-                  "teasar_round: misaligned buffer");
+                      aligned4(targets_dev, junction_dev, state_dev, given_dev) && aligned8(lengths_dev),
+                  "%s: misaligned buffer", name);
     const size_t need = workspace_need(n_labels);
     if (workspace_bytes < need) {
-        set_error("teasar_round: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        set_error("%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, need);
         return EXASPIM_E_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)n_labels + 1;
     unsigned long long* keys = static_cast<unsigned long long*>(workspace_dev);
     int* finished = reinterpret_cast<int*>(static_cast<char*>(workspace_dev) + keys_bytes(n_labels));
-    teasar_round_init<<<capped_grid(rows, kThreads), kThreads, 0, s>>>(keys, rows, state_dev);
+    teasar_round_init<<<capped_grid(rows, kThreads), kThreads, 0, s>>>(keys, rows, state_dev, given);
     teasar_targets<<<capped_grid((size_t)dm.n, kThreads), kThreads, 0, s>>>(mask_dev, labels_dev, daf_dev, (size_t)dm.n,
                                                                             n_labels, keys);
-    teasar_branch_lengths<<<capped_grid(rows, kThreads), kThreads, 0, s>>>(
-        keys, parents_dev, hops_dev, mask_dev, dm.n, n_labels, targets_dev, reinterpret_cast<long long*>(lengths_dev),
-        junction_dev, finished, state_dev);
+    if (given)
+        teasar_given_lengths<<<capped_grid(rows, kThreads), kThreads, 0, s>>>(
+            keys, given_dev, labels_dev, daf_dev, parents_dev, hops_dev, mask_dev, dm.n, n_labels, targets_dev,
+            reinterpret_cast<long long*>(lengths_dev), junction_dev, finished, state_dev);
+    else
+        teasar_branch_lengths<<<capped_grid(rows, kThreads), kThreads, 0, s>>>(
+            keys, parents_dev, hops_dev, mask_dev, dm.n, n_labels, targets_dev,
+            reinterpret_cast<long long*>(lengths_dev), junction_dev, finished, state_dev);
     EXA_CHECK_HIP(hipGetLastError());
     return EXASPIM_OK;
+}
+
+}  // namespace
+
+extern "C" int exaspim_teasar_round(const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
+                                    const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels,
+                                    const uint8_t* mask_dev, int32_t* targets_dev, int64_t* lengths_dev,
+                                    int32_t* junction_dev, int32_t* state_dev, void* workspace_dev,
+                                    size_t workspace_bytes, void* stream) {
+    return teasar_round("teasar_round", labels_dev, daf_dev, parents_dev, hops_dev, dims, n_labels, mask_dev, nullptr,
+                        false, targets_dev, lengths_dev, junction_dev, state_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int exaspim_teasar_round_given(const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
+                                          const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels,
+                                          const uint8_t* mask_dev, const int32_t* given_dev, int32_t* targets_dev,
+                                          int64_t* lengths_dev, int32_t* junction_dev, int32_t* state_dev,
+                                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+    return teasar_round("teasar_round_given", labels_dev, daf_dev, parents_dev, hops_dev, dims, n_labels, mask_dev,
+                        given_dev, true, targets_dev, lengths_dev, junction_dev, state_dev, workspace_dev,
+                        workspace_bytes, stream);
 }
 
 extern "C" int exaspim_teasar_apply(const int32_t* labels_dev, const int32_t* parents_dev, const int32_t* dbf_dev,

@@ -1397,6 +1397,108 @@ def segment_table(labels, dbf=None, *, n_labels=None, return_device_tensors=Fals
         return tuple(t.cpu().numpy() for t in (sizes, boxes, peak, peak_index))
 
 
+def _border_targets_on_device(labels, n_labels):
+    """
+    exaspim_border_targets on a checked device tensor, then the rows sorted by
+    (label, voxel) and deduplicated with torch. One read of the device, the
+    count. Returns two int32 (T,) device tensors.
+    """
+    dims = tuple(int(v) for v in labels.shape)
+    device = labels.device
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = lib.exaspim_border_targets_workspace_bytes(dims3)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    d, h, w = dims
+    capacity = 2 * (h * w + d * w + d * h)   # every face pixel a component of its own: it never overflows
+    with torch.cuda.device(device):
+        out_labels = torch.empty(capacity, dtype=torch.int32, device=device)
+        out_voxels = torch.empty(capacity, dtype=torch.int32, device=device)
+        state = torch.empty(2, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_border_targets(labels.data_ptr(), dims3, n_labels, out_labels.data_ptr(),
+                                       out_voxels.data_ptr(), capacity, state.data_ptr(), workspace.data_ptr(), need,
+                                       _stream(device)),
+            "exaspim_border_targets",
+        )
+        found = int(state.cpu()[0])   # the one read
+        if found < 0 or found > capacity:
+            raise RuntimeError(f"border_targets: {found} targets reported for {capacity} face pixels")
+        key = (out_labels[:found].to(torch.int64) << 32) | out_voxels[:found].to(torch.int64)
+        key = torch.unique_consecutive(torch.sort(key).values)
+        return (key >> 32).to(torch.int32), (key & 0xFFFFFFFF).to(torch.int32)
+
+
+def border_targets(labels, *, n_labels=None, return_device_tensors=False):
+    """
+    The centre of every cut: where a face of the volume cuts a label, the
+    voxel of the cut cross-section that lies deepest inside it, on the device.
+
+    What this is: what kimimaro.skeletonize(..., fix_borders=True) asks for
+    (the reference's skeletonize, inference.py:286): a skeleton that ends at
+    the centre of the cut, a point the block next door, which sees the same
+    plane of voxels, picks as well, so the skeletons of adjacent blocks can
+    be joined. Exactly, in integers: K = n_labels. The six faces are the
+    planes z = 0, z = D - 1, y = 0, y = H - 1, x = 0 and x = W - 1. A pixel
+    of a face is foreground iff its label is in 1..K. e(p) of a foreground
+    pixel is the least squared in-plane Euclidean distance to a pixel of the
+    same plane with another label, or to a position just outside the plane
+    (a black border). A face component is an 8-connected set of pixels of
+    one plane with one foreground label; its target is its pixel with the
+    largest e, ties to the smallest linear voxel index z * H * W + y * W + x.
+    The result is the set of (label, voxel index) over all components of all
+    six faces: a voxel that is the target of two faces appears once.
+
+    What this is not: kimimaro, which breaks ties by closeness to a
+    centroid; equality with it is not claimed. The result depends on the
+    face's plane of labels alone, which is what makes the two sides of a seam
+    agree.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    n_labels : int, optional
+        K. Default is max(labels.max(), 0), one read of the device. Labels
+        above K and labels <= 0 are background.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+
+    Returns
+    -------
+    target_labels, target_voxels : numpy.ndarray or torch.Tensor
+        int32 (T,): sorted by (label, voxel index), no pair twice.
+
+    Raises
+    ------
+    TypeError
+        If labels is not int32 or n_labels is not an integer.
+    ValueError
+        If labels is not 3-D or is empty, n_labels is negative, or the
+        volume has more than 2^31 - 1 voxels or face pixels.
+    RuntimeError
+        If labels is a tensor on a CPU device, or there is no HIP device to
+        upload an array to.
+    """
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+            raise TypeError(f"border_targets: n_labels must be an integer, got {type(n_labels).__name__}")
+        if n_labels < 0:
+            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+    labels, _ = _checked_labels(labels, "border_targets")
+    if n_labels is None:
+        with torch.cuda.device(labels.device):
+            n_labels = max(int(labels.max()), 0)
+    out = _border_targets_on_device(labels, int(n_labels))
+    if not return_device_tensors:
+        with torch.cuda.device(labels.device):
+            out = tuple(t.cpu().numpy() for t in out)
+    return out
+
+
 def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_sweeps=None, farthest=False,
                         stats=None):
     """
@@ -2089,13 +2191,58 @@ def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxe
     return (labels, dims, sources, dbf, daf, parents, hops, boxes, float(scale), float(const)) + tuple(out[6:])
 
 
+def _pre_check_targets_before(fn, targets_before):
+    """What of targets_before can be refused before anything is uploaded or launched."""
+    if targets_before is None:
+        return
+    if not isinstance(targets_before, (tuple, list)) or len(targets_before) != 2:
+        raise TypeError(f"{fn}: targets_before must be a pair (target_labels, target_voxels) as border_targets "
+                        f"returns it, got {type(targets_before).__name__}")
+    for what, a in zip(("target_labels", "target_voxels"), targets_before):
+        if not isinstance(a, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"{fn}: targets_before's {what} must be a torch tensor or a numpy array, got "
+                            f"{type(a).__name__}")
+        if a.dtype not in (np.int32, torch.int32):
+            raise TypeError(f"{fn}: targets_before's {what} must be int32, got {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"{fn}: targets_before's {what} must be 1-D, got {tuple(a.shape)}")
+    if targets_before[0].shape[0] != targets_before[1].shape[0]:
+        raise ValueError(f"{fn}: targets_before's two arrays must have one length, got "
+                         f"{targets_before[0].shape[0]} and {targets_before[1].shape[0]}")
+
+
+def _checked_targets_before(fn, targets_before, device):
+    """targets_before as None or two contiguous int32 (T,) tensors on "device"."""
+    _pre_check_targets_before(fn, targets_before)
+    if targets_before is None:
+        return None
+    out = []
+    for what, a in zip(("target_labels", "target_voxels"), targets_before):
+        a = _on_device(a, fn, what, (np.int32,))
+        if a.device != device:
+            raise RuntimeError(f"{fn}: targets_before's {what} must be on the labels' device {device}, got {a.device}")
+        out.append(a.contiguous())
+    return tuple(out)
+
+
 def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths=None, stats=None,
-                      on_round=None, update=None, fn="teasar_branches"):
+                      on_round=None, update=None, fn="teasar_branches", targets_before=None):
     """
     teasar_branches on checked device tensors: exaspim_teasar_begin, then per
     round exaspim_teasar_round, one 20-byte read of the state, the cumulative
     sum of the lengths with torch and exaspim_teasar_apply. Everything stays on
     the device.
+
+    With targets_before, two int32 (T,) device tensors (labels, voxels): after
+    exaspim_teasar_begin the rows whose voxel is not eligible are dropped, the
+    rest sorted by (label, voxel) and deduplicated with torch, and rounds
+    1..M, M the largest number of rows of one label (one read), run
+    exaspim_teasar_round_given (a 24-byte state) with, per label, its t-th
+    row or -1. A given round without a branch launches no
+    exaspim_teasar_apply and appends nothing, but counts as a round and is
+    reported to on_round; the loop ends only once t > M and no label is live.
+    With update, a given round is known to exist without the probe: update runs
+    before round t iff a round since the last update added vertices.
 
     Parameters
     ----------
@@ -2146,7 +2293,7 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
     with torch.cuda.device(device):
         stream = _stream(device)
         mask = torch.empty(dims, dtype=torch.uint8, device=device)
-        state = torch.empty(5, dtype=torch.int32, device=device)
+        state = torch.empty(5 if targets_before is None else 6, dtype=torch.int32, device=device)
         workspace = torch.empty(need, dtype=torch.uint8, device=device)
         targets = torch.empty(n_labels + 1, dtype=torch.int32, device=device)
         lengths = torch.empty(n_labels + 1, dtype=torch.int64, device=device)
@@ -2157,36 +2304,75 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
                                      n_labels, mask.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
             "exaspim_teasar_begin",
         )
-        rounds, reads, refused = 0, 0, 0
-        per_round, live_history, new_history = [], [], []
+        rounds, reads, refused, refused_given = 0, 0, 0, 0
+        per_round, live_history, new_history, empty_rounds = [], [], [], []
+        given_rounds = 0
+        if targets_before is not None:
+            # the table of given targets: eligible rows only, sorted by (label, voxel), each once
+            n = labels.numel()
+            t_labels, t_voxels = (t.to(torch.int64) for t in targets_before)
+            in_range = (t_labels >= 1) & (t_labels <= n_labels) & (t_voxels >= 0) & (t_voxels < n)
+            eligible = in_range & ((mask.reshape(-1)[t_voxels.clamp(0, n - 1)] & 1) != 0)
+            key = torch.unique_consecutive(torch.sort((t_labels[eligible] << 32) | t_voxels[eligible]).values)
+            given_voxels = (key & 0xFFFFFFFF).to(torch.int32)
+            counts = torch.bincount(key >> 32, minlength=n_labels + 1)
+            starts = torch.cumsum(counts, 0) - counts
+            bad, given_rounds = (int(v) for v in torch.stack([(~in_range).sum(), counts.max()]).cpu())   # one read
+            if bad:
+                raise ValueError(f"{fn}: {bad} row(s) of targets_before name a label outside 1..{n_labels} or a voxel "
+                                 f"outside the volume")
 
-        def walk():
-            """exaspim_teasar_round on the current parents and the read of its state."""
-            _native.check(
-                lib.exaspim_teasar_round(labels.data_ptr(), daf.data_ptr(), parents.data_ptr(), hops.data_ptr(), dims3,
-                                         n_labels, mask.data_ptr(), targets.data_ptr(), lengths.data_ptr(),
-                                         junction.data_ptr(), state.data_ptr(), workspace.data_ptr(), need, stream),
-                "exaspim_teasar_round",
-            )
+        def walk(round_given=None):
+            """exaspim_teasar_round (or _given) on the current parents and the read of its state."""
+            if round_given is None:
+                _native.check(
+                    lib.exaspim_teasar_round(labels.data_ptr(), daf.data_ptr(), parents.data_ptr(), hops.data_ptr(),
+                                             dims3, n_labels, mask.data_ptr(), targets.data_ptr(), lengths.data_ptr(),
+                                             junction.data_ptr(), state.data_ptr(), workspace.data_ptr(), need,
+                                             stream),
+                    "exaspim_teasar_round",
+                )
+            else:
+                row = (starts + (round_given - 1)).clamp(max=given_voxels.numel() - 1)
+                given = torch.where(counts >= round_given, given_voxels[row], -1).to(torch.int32).contiguous()
+                _native.check(
+                    lib.exaspim_teasar_round_given(labels.data_ptr(), daf.data_ptr(), parents.data_ptr(),
+                                                   hops.data_ptr(), dims3, n_labels, mask.data_ptr(), given.data_ptr(),
+                                                   targets.data_ptr(), lengths.data_ptr(), junction.data_ptr(),
+                                                   state.data_ptr(), workspace.data_ptr(), need, stream),
+                    "exaspim_teasar_round_given",
+                )
             return tuple(int(v) for v in state.cpu())
 
+        pending = False   # the last round with a branch has not been handed to update yet
         while max_paths is None or rounds < max_paths:
-            live, broken, n_new, n_roots, refused = walk()   # the round's one read
-            reads += 1
-            if broken or refused:
-                break
-            if live == 0:
-                break
-            if update is not None and rounds >= 1:
-                # the round exists: only now are its field, hops and parents built, and the walk taken on them
-                parents, hops = update(rounds + 1, per_round[-1][0])
-                live, broken, n_new, n_roots, refused = walk()
+            if rounds < given_rounds:
+                # a given round exists without a probe: its fields are built first, if the skeleton has grown
+                if update is not None and pending:
+                    parents, hops = update(rounds + 1, per_round[-1][0])
+                    pending = False
+                live, broken, n_new, n_roots, refused, refused_given = walk(rounds + 1)   # the round's one read
+                reads += 1
+                if broken or refused or refused_given:
+                    break
+            else:
+                live, broken, n_new, n_roots, refused = walk()[:5]   # the round's one read
                 reads += 1
                 if broken or refused:
                     break
                 if live == 0:
-                    raise RuntimeError(f"{fn}: round {rounds + 1} had a live label on the parents of the round before "
-                                       "and has none on its own: the state bytes changed between two calls")
+                    break
+                if update is not None and pending:
+                    # the round exists: only now are its field, hops and parents built, and the walk taken on them
+                    parents, hops = update(rounds + 1, per_round[-1][0])
+                    pending = False
+                    live, broken, n_new, n_roots, refused = walk()[:5]
+                    reads += 1
+                    if broken or refused:
+                        break
+                    if live == 0:
+                        raise RuntimeError(f"{fn}: round {rounds + 1} had a live label on the parents of the round "
+                                           "before and has none on its own: the state bytes changed between two calls")
             if n_new < live:
                 # a live label's target is valid, so not on the skeleton: its branch holds at least the target.
                 # Fewer vertices than branches is no answer to these arguments, and the loop would never end
@@ -2196,6 +2382,11 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
             rounds += 1
             live_history.append(live)
             new_history.append(n_new)
+            if live == 0:   # a given round whose targets are all on the skeleton: nothing to apply or append
+                empty_rounds.append(rounds)
+                if on_round is not None:
+                    on_round(rounds, mask)
+                continue
             torch.cumsum(lengths, 0, out=offsets[1:])
             voxels = torch.empty(n_new, dtype=torch.int32, device=device)
             radii = torch.empty(n_new, dtype=torch.int32, device=device)
@@ -2210,6 +2401,7 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
             # the labels that have a branch, ascending: a stable sort needs no read, "live" is known already
             rows = torch.argsort((lengths == 0).to(torch.uint8), stable=True)[:live]
             per_round.append((voxels, radii, before, lengths[rows], rows.to(torch.int32), junction[rows], rounds))
+            pending = True
             if on_round is not None:
                 on_round(rounds, mask)
         else:
@@ -2217,6 +2409,11 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
             reads += 1
         if stats is not None:
             stats.update(rounds=rounds, reads=reads, vertices=new_history, live_labels=live_history)
+            if targets_before is not None:
+                stats.update(given_rounds=given_rounds, empty_rounds=empty_rounds)
+        if refused_given:
+            raise RuntimeError(f"{fn}: exaspim_teasar_round_given refused {refused_given} given target(s) in round "
+                               f"{rounds + 1}: a row of targets_before names a voxel of another label")
         if broken or refused:
             raise RuntimeError(f"{fn}: {broken} broken walk(s) and {refused} refused row(s): parents and hops are not "
                                "the results of one geodesic_parents call on these labels and sources")
@@ -2284,10 +2481,12 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
     fix_branching=True, a Dijkstra per path on a penalty field zeroed along
     the earlier paths; this is the fix_branching=False form. Soma mode (the
     soma_* parameters and the spherical invalidation around a soma root),
-    fix_borders, anisotropy, several sources per label and a slab-streamed
+    anisotropy, several sources per label and a slab-streamed
     form are not built. (The fix_branching=True form is
     teasar_branches_fix_branching, on fields seeded from the skeleton:
     geodesic_field_seeded and geodesic_parents_seeded.)
+    Targets the loop does not choose itself, which fix_borders needs, are
+    teasar_branches_given.
 
     Parameters
     ----------
@@ -2349,12 +2548,22 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
         walk is broken, or a round reports fewer new vertices than live
         labels.
     """
+    return _teasar_branches("teasar_branches", labels, sources, dbf, daf, parents, hops, scale, const, boxes, n_labels,
+                            max_paths, return_device_tensors, stats, None)
+
+
+def _teasar_branches(fn, labels, sources, dbf, daf, parents, hops, scale, const, boxes, n_labels, max_paths,
+                     return_device_tensors, stats, targets_before):
+    """teasar_branches and teasar_branches_given: the arguments checked, the loop, the results downloaded."""
+    _pre_check_targets_before(fn, targets_before)
     labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const = _checked_teasar_arguments(
-        "teasar_branches", labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths)
+        fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths)
+    targets_before = _checked_targets_before(fn, targets_before, labels.device)
     if boxes is None:
         boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
     out = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const,
-                            None if max_paths is None else int(max_paths), stats)
+                            None if max_paths is None else int(max_paths), stats, fn=fn,
+                            targets_before=targets_before)
     out = out[:2] + out[3:]
     if not return_device_tensors:
         with torch.cuda.device(labels.device):
@@ -2362,8 +2571,67 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
     return out
 
 
+def teasar_branches_given(labels, sources, dbf, daf, parents, hops, targets_before, *, scale, const, boxes=None,
+                          n_labels=None, max_paths=None, return_device_tensors=False, stats=None):
+    """
+    teasar_branches with targets the loop does not choose itself: what
+    kimimaro calls manual_targets_before, which its fix_borders feeds with
+    the border targets (the reference's skeletonize, inference.py:286), so
+    that a skeleton ends at the centre of every cut.
+
+    What this is: teasar_branches' definition with one change to step (1),
+    per label, so that a label's result still does not depend on any other
+    label. The rows of targets_before whose voxel is not eligible are dropped
+    (a label in 26-disconnected pieces has such rows), the rest are taken per
+    label in ascending voxel index, each once. In
+    round t a label that has at least t given targets takes its t-th one in
+    place of step (1); a label that has run out takes the target of step (1)
+    as ever. A given target need not be still valid; the walk of step (2)
+    is unchanged. A given target that is on the skeleton already is no
+    branch: the label has none in that round and is not finished. Round 1
+    still puts every live label's source on the skeleton. The loop
+    ends only when every label has run out of given targets and none is
+    live. With no eligible row the calls and launches are teasar_branches'.
+
+    What this is not: kimimaro. Equality with it is not claimed, and
+    max_paths counts rounds, given rounds and rounds without any
+    branch included, which is not kimimaro's rule: it counts the paths
+    after the given ones.
+
+    Parameters
+    ----------
+    labels, sources, dbf, daf, parents, hops, scale, const, boxes, n_labels, max_paths, return_device_tensors
+        As in teasar_branches.
+    targets_before : tuple
+        (target_labels, target_voxels), int32 (T,) each, as border_targets
+        returns them: arrays, or tensors on the labels' device; any order,
+        a pair may occur twice. None means teasar_branches.
+    stats : dict, optional
+        teasar_branches' entries, and "given_rounds" (the largest number of
+        given targets of one label) and "empty_rounds" (the rounds in which
+        no label had a branch; they are counted in "rounds" and have 0 in
+        "vertices" and "live_labels").
+
+    Returns
+    -------
+    voxels, radii, offsets, branch_label, branch_round, branch_junction
+        As teasar_branches; branch_round counts every round, empty ones
+        included.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As teasar_branches; TypeError if targets_before is not a pair of
+        int32 arrays or tensors, ValueError if they are not 1-D of one
+        length or a row names a label outside 1..K or a voxel outside the
+        volume, RuntimeError if a row's voxel has another label.
+    """
+    return _teasar_branches("teasar_branches_given", labels, sources, dbf, daf, parents, hops, scale, const, boxes,
+                            n_labels, max_paths, return_device_tensors, stats, targets_before)
+
+
 def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths,
-                              fix_branching=False, stats=None):
+                              fix_branching=False, stats=None, fix_borders=False):
     """
     The nine stages of skeletonize_labels on a checked device tensor, nothing
     downloaded in between but the words each stage reads for itself. Returns
@@ -2372,7 +2640,9 @@ def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, f
     "voxels", "radii", "before", "offsets", "branch_label", "branch_round",
     "branch_junction". With fix_branching the last stage is
     teasar_branches_fix_branching's loop ("parents" and "hops" are round 1's);
-    "stats" receives the loop's.
+    "stats" receives the loop's. With fix_borders, border_targets of the
+    labels the chain skeletonises (after fill_holes) goes into the loop as
+    targets_before and is returned as "border_targets".
     """
     device = labels.device
     with torch.cuda.device(device):
@@ -2395,13 +2665,17 @@ def _skeleton_chain_on_device(labels, scale, const, pdrf_exponent, pdrf_scale, f
         pdrf, _, _ = _geodesic_on_device(labels, roots, cost)
         parents, hops = _geodesic_parents_on_device(labels, roots, pdrf, cost)
         names = ("voxels", "radii", "before", "offsets", "branch_label", "branch_round", "branch_junction")
+        given = _border_targets_on_device(labels, k) if fix_borders else None
         if fix_branching:
             loop = _fix_branching_on_device(labels, roots, dbf, daf, cost, pdrf, parents, hops, boxes, scale, const,
-                                            max_paths, stats)
+                                            max_paths, stats, targets_before=given)
         else:
             del pdrf
-            loop = _teasar_on_device(labels, roots, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats)
+            loop = _teasar_on_device(labels, roots, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats,
+                                     targets_before=given)
         out = dict(zip(names, loop))
+        if fix_borders:
+            out["border_targets"] = given
     out.update(labels=labels, dbf=dbf, boxes=boxes, roots=roots, daf=daf, cost=cost, parents=parents, hops=hops)
     return out
 
@@ -2427,8 +2701,10 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
     TEASAR (kimimaro's fix_branching=False), not the reference's default
     fix_branching=True, which re-runs a Dijkstra per path on a penalty zeroed
     along the earlier paths. Soma detection and its spherical invalidation
-    (the soma_* parameters), fix_borders and anisotropy are not built, and
-    equality with kimimaro is not claimed. A piece of a label that the root's
+    (the soma_* parameters) and anisotropy are not built, and
+    equality with kimimaro is not claimed. The reference passes
+    fix_borders=True; this function does not end skeletons at the centres of
+    the cuts, skeletonize_fix_borders does. A piece of a label that the root's
     piece does not touch gets no skeleton. (skeletonize is this chain with the
     fix_branching=True loop, teasar_branches_fix_branching, as its last
     stage.)
@@ -2469,8 +2745,11 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
                                 max_paths, False)
 
 
-def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching):
+def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching,
+                         fix_borders=False):
     """skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host."""
+    if not isinstance(fix_borders, (bool, np.bool_)):
+        raise TypeError(f"{fn}: fix_borders must be a bool, got {type(fix_borders).__name__}")
     if isinstance(pdrf_exponent, bool) or not isinstance(pdrf_exponent, (int, np.integer)):
         raise TypeError(f"{fn}: pdrf_exponent must be an integer, got {type(pdrf_exponent).__name__}")
     if pdrf_exponent < 0:
@@ -2483,7 +2762,7 @@ def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fi
     labels, dims = _checked_labels(labels, fn)
     chain = _skeleton_chain_on_device(labels, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
                                       bool(fill_holes), None if max_paths is None else int(max_paths),
-                                      bool(fix_branching))
+                                      bool(fix_branching), fix_borders=bool(fix_borders))
     with torch.cuda.device(labels.device):
         voxels, before, offsets, branch_label = (chain[k] for k in ("voxels", "before", "offsets", "branch_label"))
         radius = chain["dbf"].reshape(-1)[voxels.to(torch.int64)].to(torch.float32).sqrt()
@@ -2809,7 +3088,8 @@ FIX_BRANCHING_FIELD_SWEEPS = 8
 
 
 def _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
-                             max_paths=None, stats=None, on_round=None):
+                             max_paths=None, stats=None, on_round=None, targets_before=None,
+                             fn="teasar_branches_fix_branching"):
     """
     teasar_branches_fix_branching on checked device tensors: _teasar_on_device
     with an update before the walk of every round t >= 2 that exists. The
@@ -2820,9 +3100,10 @@ def _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, ho
     (labels, sources, cost), are only read; the copies are made at the first
     update, so a call with one round allocates none. Returns
     _teasar_on_device's tuple; "stats" additionally receives "updates",
-    "field_sweeps" and "hops_sweeps" (one entry per update).
+    "field_sweeps" and "hops_sweeps" (one entry per update). With
+    targets_before an update is skipped where no vertex has been added since
+    the last one (the round before was empty).
     """
-    fn = "teasar_branches_fix_branching"
     dims = tuple(int(v) for v in labels.shape)
     n_labels = int(sources.numel()) - 1
     device = labels.device
@@ -2847,7 +3128,7 @@ def _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, ho
         return out
 
     result = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats,
-                               on_round, update, fn)
+                               on_round, update, fn, targets_before)
     if stats is not None:
         stats.update(updates=len(field_sweeps), field_sweeps=field_sweeps, hops_sweeps=hops_sweeps)
     return result
@@ -2886,8 +3167,9 @@ def teasar_branches_fix_branching(labels, sources, dbf, daf, cost, *, scale, con
     tests, and equality with it is not claimed; the definition is this
     project's own, exact and free of any order, and checked against two host
     oracles (tests/fix_branching_ref.py).
-    Soma mode, fix_borders, anisotropy and a slab-streamed form are not
-    built.
+    Soma mode, anisotropy and a slab-streamed form are not built.
+    (With given targets, which fix_borders needs:
+    teasar_branches_fix_branching_given.)
 
     Parameters
     ----------
@@ -2919,10 +3201,19 @@ def teasar_branches_fix_branching(labels, sources, dbf, daf, cost, *, scale, con
     TypeError, ValueError, RuntimeError
         As teasar_branches, geodesic_field and geodesic_parents.
     """
-    fn = "teasar_branches_fix_branching"
+    return _teasar_branches_fix_branching("teasar_branches_fix_branching", labels, sources, dbf, daf, cost, scale,
+                                          const, field, parents, hops, boxes, n_labels, max_paths,
+                                          return_device_tensors, stats, None)
+
+
+def _teasar_branches_fix_branching(fn, labels, sources, dbf, daf, cost, scale, const, field, parents, hops, boxes,
+                                   n_labels, max_paths, return_device_tensors, stats, targets_before):
+    """teasar_branches_fix_branching and its _given form: the arguments checked, the loop, the results downloaded."""
+    _pre_check_targets_before(fn, targets_before)
     checked = _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels,
                                         max_paths, fields=(cost, field))
     labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const, cost, field = checked
+    targets_before = _checked_targets_before(fn, targets_before, labels.device)
     if boxes is None:
         boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
     if field is None:
@@ -2930,12 +3221,60 @@ def teasar_branches_fix_branching(labels, sources, dbf, daf, cost, *, scale, con
     if parents is None or hops is None:
         parents, hops = _geodesic_parents_on_device(labels, sources, field, cost)
     out = _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
-                                   None if max_paths is None else int(max_paths), stats)
+                                   None if max_paths is None else int(max_paths), stats,
+                                   targets_before=targets_before, fn=fn)
     out = out[:2] + out[3:]
     if not return_device_tensors:
         with torch.cuda.device(labels.device):
             out = tuple(t.cpu().numpy() for t in out)
     return out
+
+
+def teasar_branches_fix_branching_given(labels, sources, dbf, daf, cost, targets_before, *, scale, const, field=None,
+                                        parents=None, hops=None, boxes=None, n_labels=None, max_paths=None,
+                                        return_device_tensors=False, stats=None):
+    """
+    teasar_branches_fix_branching with given targets: the loop the
+    reference's skeletonize (inference.py:257-291) asks of
+    kimimaro.skeletonize with fix_branching=True and fix_borders=True, once
+    targets_before is border_targets' result.
+
+    What this is: teasar_branches_given's rule for the target (per label,
+    its t-th given target in round t, then the target of step (1)) on
+    teasar_branches_fix_branching's fields. A given round is known to exist
+    without the probe call. The update before round t re-seeds with every
+    vertex added since the last update and is skipped if there is none, so
+    once a round is empty updates == rounds - 1 no longer holds: updates ==
+    rounds - 1 - (the entries of stats["empty_rounds"] below rounds). A
+    given target on the skeleton is a seed of the rebuilt parents, its own
+    parent with hops 0: no branch.
+
+    What this is not: kimimaro; equality with it is not claimed, and
+    max_paths counts every round.
+
+    Parameters
+    ----------
+    labels, sources, dbf, daf, cost, scale, const, field, parents, hops, boxes, n_labels, max_paths, return_device_tensors
+        As in teasar_branches_fix_branching.
+    targets_before : tuple
+        As in teasar_branches_given.
+    stats : dict, optional
+        teasar_branches_fix_branching's entries and teasar_branches_given's
+        "given_rounds" and "empty_rounds".
+
+    Returns
+    -------
+    voxels, radii, offsets, branch_label, branch_round, branch_junction
+        As teasar_branches_given.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As teasar_branches_fix_branching and teasar_branches_given.
+    """
+    return _teasar_branches_fix_branching("teasar_branches_fix_branching_given", labels, sources, dbf, daf, cost, scale,
+                                          const, field, parents, hops, boxes, n_labels, max_paths,
+                                          return_device_tensors, stats, targets_before)
 
 
 def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pdrf_exponent=4, pdrf_scale=100000.0,
@@ -2949,8 +3288,11 @@ def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pd
     What this is not: kimimaro. The skeletons are not osteoid Skeleton
     objects but skeletonize_labels' plain tuples, and equality with kimimaro
     is not claimed: the definition of every stage is this project's own.
-    Soma detection and its spherical invalidation (the soma_* parameters),
-    fix_borders and anisotropy are not built.
+    Soma detection and its spherical invalidation (the soma_* parameters)
+    and anisotropy are not built. The reference passes fix_borders=True;
+    this function keeps the skeletons of earlier versions, and
+    skeletonize_fix_borders is the form that ends them at the centres of the
+    cuts.
 
     Parameters
     ----------
@@ -2978,6 +3320,51 @@ def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pd
         raise TypeError(f"skeletonize: fix_branching must be a bool, got {type(fix_branching).__name__}")
     return _skeletons_of_labels("skeletonize", segmentation, scale, const, pdrf_exponent, pdrf_scale, fill_holes,
                                 max_paths, bool(fix_branching))
+
+
+def skeletonize_fix_borders(segmentation, *, fix_borders=True, fix_branching=True, scale=1.25, const=450.0,
+                            pdrf_exponent=4, pdrf_scale=100000.0, fill_holes=True, max_paths=None):
+    """
+    skeletonize with the reference's fix_borders=True (inference.py:286):
+    wherever a face of the volume cuts a segment, the skeleton is made to
+    end at the centre of the cut cross-section. The block next door sees the
+    same plane of voxels and picks the same point, so the skeletons of
+    adjacent blocks can be joined; without it a branch ends at whichever
+    voxel of the cut is geodesically farthest from the root, a corner of the
+    cross-section about which the two sides of a seam disagree.
+
+    What this is: skeletonize's chain; border_targets of the labels the chain
+    skeletonises (after fill_holes) goes into the loop as given targets
+    (teasar_branches_fix_branching_given, or teasar_branches_given with
+    fix_branching=False). skeletonize and skeletonize_labels themselves keep
+    the skeletons of earlier versions, which is why this is a function of
+    its own although the reference passes the switch to the one call.
+
+    What this is not: kimimaro, which breaks the ties of a cut's centre by
+    closeness to a centroid; equality with it is not claimed. max_paths
+    counts every round, the given ones included.
+
+    Parameters
+    ----------
+    segmentation, fix_branching, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths
+        As in skeletonize.
+    fix_borders : bool, optional
+        False gives skeletonize. Default is True.
+
+    Returns
+    -------
+    dict
+        label -> (vertices, parent, radius), as skeletonize_labels.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As skeletonize; TypeError if fix_borders is not a bool.
+    """
+    if not isinstance(fix_branching, (bool, np.bool_)):
+        raise TypeError(f"skeletonize_fix_borders: fix_branching must be a bool, got {type(fix_branching).__name__}")
+    return _skeletons_of_labels("skeletonize_fix_borders", segmentation, scale, const, pdrf_exponent, pdrf_scale,
+                                fill_holes, max_paths, bool(fix_branching), fix_borders)
 
 
 def skeletons_to_zipped_swcs(skeleton_dict, zip_path):

@@ -1303,9 +1303,9 @@ int exaspim_geodesic_parents_begin_seeds(const int32_t* labels_dev, const int32_
  * read off ONE parental field, which is kimimaro with fix_branching=False. The reference runs kimimaro with
  * its default fix_branching=True, a Dijkstra per path on a penalty field zeroed along the earlier paths:
  * that form is these three calls with the field re-seeded and the parents rebuilt before every round after
- * the first (exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds). Soma detection and
- * its spherical invalidation, fix_borders and anisotropy are not built, and equality with kimimaro is
- * not claimed.
+ * the first (exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds). fix_borders is
+ * exaspim_border_targets fed to exaspim_teasar_round_given. Soma detection and its
+ * spherical invalidation and anisotropy are not built, and equality with kimimaro is not claimed.
  *
  * The definition, in integers. K = n_labels. A voxel v is eligible iff its label L is in 1..K, sources[L]
  * names a voxel of L, hops[v] >= 0 and the bits of daf[v] are below 0x7F800000 (finite, sign bit clear: -0.0
@@ -1355,6 +1355,24 @@ int exaspim_teasar_round(const int32_t* labels_dev, const float* daf_dev, const 
                          int32_t* targets_dev, int64_t* lengths_dev, int32_t* junction_dev,
                          int32_t* state_dev /* [5] */, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* exaspim_teasar_round with targets the loop did not choose itself (kimimaro's manual_targets_before, which
+ * fix_borders feeds with the border targets). given_dev is int32 (n_labels + 1): row L >= 0 is this
+ * round's target of label L, -1 means the rule of step (1); row 0 is not read. With every row -1 all outputs
+ * and state_dev[0..4] are those of exaspim_teasar_round, byte for byte. A given target need not be still valid
+ * (bit 0); the walk of step (2) is unchanged. A given target that is on the skeleton already is no branch: the
+ * label's rows are -1, 0, -1, it is not counted in state_dev[0] and it is not finished. A given row that is
+ * out of range, whose voxel is not labelled L, or that is not eligible (hops < 0, or daf bits >= 0x7F800000)
+ * is counted in state_dev[5], the sixth word, which this call clears first, and is read as -1. Round 1 still
+ * puts every live label's source on the skeleton (nothing is on it before, so every walk ends at the source),
+ * so branches without a junction occur only in round 1 and exaspim_teasar_apply runs unchanged. Three launches
+ * on "stream", nothing allocated, nothing synchronised. Refusals as exaspim_teasar_round, given_dev included. */
+int exaspim_teasar_round_given(const int32_t* labels_dev, const float* daf_dev, const int32_t* parents_dev,
+                               const int32_t* hops_dev, const int32_t dims[3], int32_t n_labels,
+                               const uint8_t* mask_dev, const int32_t* given_dev /* [n_labels + 1] */,
+                               int32_t* targets_dev, int64_t* lengths_dev, int32_t* junction_dev,
+                               int32_t* state_dev /* [6] */, void* workspace_dev, size_t workspace_bytes,
+                               void* stream);
+
 /* Steps (2) to (4) of the round exaspim_teasar_round prepared. offsets_dev is int64 (n_labels + 2): 0
  * followed by the inclusive cumulative sum of lengths_dev, so that label L's branch is written to
  * voxels_dev, radii_dev and before_dev at [offsets[L], offsets[L + 1]), junction side first: the vertex, its
@@ -1377,6 +1395,45 @@ int exaspim_teasar_apply(const int32_t* labels_dev, const int32_t* parents_dev, 
                          const int32_t* junction_dev, const int64_t* offsets_dev, int32_t* voxels_dev,
                          int32_t* radii_dev, int32_t* before_dev, int64_t n_new, int64_t capacity, int32_t n_roots,
                          int32_t* state_dev /* [5] */, void* stream);
+
+/* ---- border targets: the centre of every cut -------------------------------------------------
+ * What kimimaro.skeletonize(..., fix_borders=True) asks for (inference.py:286 of the reference): where a
+ * face of the volume cuts a label, the skeleton is to end at the centre of the cut, a point the block next
+ * door, which sees the same plane of voxels, picks as well. The definition is this project's own, exact in
+ * integers and free of any order; equality with kimimaro, which breaks ties by closeness to a centroid, is
+ * not claimed.
+ *
+ * K = n_labels. The six faces are the planes z = 0, z = D - 1 (H x W), y = 0, y = H - 1 (D x W), x = 0 and
+ * x = W - 1 (D x H), each a 2-D array of labels. A pixel is foreground iff its label is in 1..K. For a
+ * foreground pixel p, e(p) is the least squared in-plane Euclidean distance to a pixel of the same plane whose
+ * label differs from p's, or to a position just outside the plane (a black border: at row i, column j of an
+ * h x w plane e <= min((i + 1)^2, (h - i)^2, (j + 1)^2, (w - j)^2)); an integer, at most
+ * (min(h, w) / 2 + 1)^2. A face component is an 8-connected set of pixels of one plane with one foreground
+ * label; its target is its pixel with the largest e, ties to the smallest linear voxel index
+ * (z H W + y W + x). The result is the set of pairs (label, voxel index) over all components of all six
+ * faces; a voxel that is the target of two faces (on an edge or in a corner, or where a dimension is 1 and
+ * two faces coincide) appears once. e taken on labels equals e taken on components (DESIGN 6p has the proof),
+ * so only the argmax needs the components. */
+
+/* Scratch bytes of exaspim_border_targets: 4 x 4 + 8 bytes per face pixel, P = 2 (HW + DW + DH) of them,
+ * each part rounded up to 16. 0 with the error text set for dims exaspim_border_targets refuses. */
+size_t exaspim_border_targets_workspace_bytes(const int32_t dims[3]);
+
+/* The border targets of labels_dev as rows (out_labels_dev[i], out_voxels_dev[i]), in no defined order:
+ * callers compare as sets or sort. state_dev[0] = the number of targets found, which may exceed "capacity":
+ * rows past it are not written, every write is bounded by it, and the two arrays may be NULL if it is 0;
+ * capacity = P never overflows. state_dev[1] = 0 (spare). labels_dev is only read. Six launches on "stream"
+ * (gather, the distance along the columns and along the rows, an 8-connected union-find, a 64-bit atomic
+ * maximum per component, the rows through a counter), nothing allocated, nothing synchronised; the result
+ * is a pure function of the arguments.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels
+ * or faces of more than 2^31 - 1 pixels, a negative n_labels or capacity, or a misaligned buffer
+ * (workspace_dev 16 bytes, the rest 4); EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_border_targets_workspace_bytes(dims): all before anything is launched, and no output is touched. */
+int exaspim_border_targets(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                           int32_t* out_labels_dev, int32_t* out_voxels_dev, int32_t capacity,
+                           int32_t* state_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
