@@ -652,6 +652,210 @@ __global__ __launch_bounds__(kThreads) void fill(const int* labels, const int* _
     if (lane == 0 && holes) atomicAdd(counts, holes);
 }
 
+// ---- the 26-connected pieces of a label volume (exaspim_label_pieces) -----------------------
+// A piece is a maximal 26-connected set of voxels with one label in 1 .. K. No mask: the edges are read off
+// the labels. Every voxel looks at its 13 neighbours that come before it in linear order, four rows of three
+// (dz, dy) = (-1, -1), (-1, 0), (-1, 1), (0, -1) and the voxel before it along x. Within a row the middle voxel
+// stands for its two x neighbours where it carries the label itself: the three are then joined along x,
+// by whoever owns that edge, so one union is enough. Passes:
+//   pieces_tile_pass   the unions inside an 8 x 8 x 32 tile, in LDS; parent[v] = global index of the tile's root,
+//                      count[tile's root] = the voxels of its set inside the tile, a plain store;
+//   pieces_seam_merge  the unions whose other end lies in another tile, in global memory;
+//   flatten            as it is; a background voxel is a root of its own;
+//   pieces_sizes       count[root] += count[tile's root]: one atomic per tile a piece runs through, not one per
+//                      run of voxels as in sizes, which a few large pieces turn into a few hot words;
+//   scan_*             PieceRoot: foreground roots of at least dust voxels, numbered in index order;
+//   pieces_relabel     pieces[v] = number of root(v), 0 for background and dust; counts the dust roots.
+__device__ __forceinline__ int piece_label(int l, int k) { return (unsigned)l - 1u < (unsigned)k ? l : 0; }
+
+// LDS: the tile's labels, parents and counts and one flag per wave, 3 * 8192 + 16 bytes
+__global__ __launch_bounds__(kThreads) void pieces_tile_pass(const int* __restrict__ labels,
+                                                            int* __restrict__ parent, int* __restrict__ count,
+                                                            Dims dm, int n_labels, int tiles_x, int tiles_y,
+                                                            long long n_tiles) {
+    __shared__ int ll[kTileVox];
+    __shared__ int lp[kTileVox];
+    __shared__ int lc[kTileVox];
+    __shared__ int wave_any[kThreads / 64];
+    const int t = threadIdx.x, lane = t & 63, lx = t & 31, ly = t >> 5;   // voxel k of a thread: lz = k
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y);
+        const int tz = (int)(tile / ((long long)tiles_x * tiles_y));
+        const int x = tx * kTX + lx, y = ty * kTY + ly;
+        const bool column = x < dm.w && y < dm.h;
+        int lab[kPerThread];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int z = tz * kTZ + k;
+            lab[k] = 0;
+            if (column && z < dm.d) lab[k] = piece_label(labels[((size_t)z * dm.h + y) * dm.w + x], n_labels);
+            any |= lab[k] != 0;
+        }
+        const unsigned long long some = __ballot(any);
+        if (lane == 0) wave_any[t >> 6] = some != 0;
+        __syncthreads();
+        bool tile_any = false;
+#pragma unroll
+        for (int wv = 0; wv < kThreads / 64; ++wv) tile_any |= wave_any[wv] != 0;
+        if (!tile_any) {   // the same in every thread: nothing to unite, every voxel its own root
+#pragma unroll
+            for (int k = 0; k < kPerThread; ++k) {
+                const int z = tz * kTZ + k;
+                if (column && z < dm.d) {
+                    const size_t v = ((size_t)z * dm.h + y) * dm.w + x;
+                    parent[v] = (int)v;
+                }
+            }
+            __syncthreads();   // wave_any is written again by the next tile
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int i = t + kThreads * k;
+            // a row of 32 voxels is half a wave: start of this voxel's run of one label along x
+            const int before = __shfl_up(lab[k], 1);
+            const bool joined = lx > 0 && lab[k] != 0 && before == lab[k];
+            const unsigned long long ball = __ballot(joined);
+            const unsigned rowbits = (unsigned)(ball >> (lane & 32));
+            const unsigned off = ~rowbits & (0xFFFFFFFFu >> (31 - lx));   // bit 0 is never set in rowbits
+            ll[i] = lab[k];
+            lc[i] = 0;
+            lp[i] = (i & ~31) + 31 - __clz((int)off);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int i = t + kThreads * k;
+            const int mine = ll[i];
+            if (mine == 0) continue;
+            auto row = [&](int dz, int dy) {
+                if (k + dz < 0 || ly + dy < 0 || ly + dy >= kTY) return;   // another tile's: pieces_seam_merge
+                const int j = i + dz * (kTY * kTX) + dy * kTX;
+                if (ll[j] == mine) {
+                    unite<LdsLoad>(lp, i, j);
+                    return;
+                }
+                if (lx > 0 && ll[j - 1] == mine) unite<LdsLoad>(lp, i, j - 1);
+                if (lx < kTX - 1 && ll[j + 1] == mine) unite<LdsLoad>(lp, i, j + 1);
+            };
+            row(-1, -1);
+            row(-1, 0);
+            row(-1, 1);
+            row(0, -1);
+        }
+        __syncthreads();
+        // the voxel count of every tile-local root
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int i = t + kThreads * k;
+            if (ll[i] != 0) atomicAdd(lc + find_root<LdsLoad>(lp, i), 1);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPerThread; ++k) {
+            const int i = t + kThreads * k;
+            const int z = tz * kTZ + k;
+            if (column && z < dm.d) {
+                const int r = find_root<LdsLoad>(lp, i);
+                const int rz = tz * kTZ + (r >> 8), ry = ty * kTY + ((r >> 5) & (kTY - 1));
+                const int rx = tx * kTX + (r & 31);
+                const size_t v = ((size_t)z * dm.h + y) * dm.w + x;
+                parent[v] = (int)(((size_t)rz * dm.h + ry) * dm.w + rx);
+                if (r == i && ll[i] != 0) count[v] = lc[i];   // every other word of count stays 0
+            }
+        }
+        __syncthreads();   // ll, lp, lc and wave_any are reused by the next tile
+    }
+}
+
+// count[root] += count[v] for every tile-local root v that is not its piece's root (parent is flattened). A word
+// that is read here to be added is never added to: only a piece's root receives, and a root adds nothing.
+__global__ __launch_bounds__(kThreads) void pieces_sizes(const int* __restrict__ parent, int* count, int n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < (size_t)n; g += stride) {
+        const int r = parent[g];
+        if (r == (int)g) continue;
+        const int c = count[g];
+        if (c > 0) atomicAdd(count + r, c);
+    }
+}
+
+// One thread per voxel; only a foreground voxel on the low z, either y or either x face of its tile has an
+// earlier neighbour in another tile. A neighbour is read only where it lies inside the volume.
+__global__ __launch_bounds__(kThreads) void pieces_seam_merge(const int* __restrict__ labels, int* parent, Dims dm,
+                                                             int n_labels) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int hw = dm.h * dm.w;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < (size_t)dm.n; g += stride) {
+        const int i = (int)g;
+        const int rowi = i / dm.w, x = i - rowi * dm.w;
+        const int z = rowi / dm.h, y = rowi - z * dm.h;
+        const int lx = x & (kTX - 1), ly = y & (kTY - 1), lz = z & (kTZ - 1);
+        if (lz != 0 && ly != 0 && ly != kTY - 1 && lx != 0 && lx != kTX - 1) continue;
+        const int mine = piece_label(labels[g], n_labels);
+        if (mine == 0) continue;
+        auto row = [&](int dz, int dy) {
+            if (z + dz < 0 || y + dy < 0 || y + dy >= dm.h) return;
+            const bool outside = (dz < 0 && lz == 0) || (dy < 0 && ly == 0) || (dy > 0 && ly == kTY - 1);
+            const int j = i + dz * hw + dy * dm.w;
+            if (piece_label(labels[j], n_labels) == mine) {
+                if (outside) unite<GlobalLoad>(parent, i, j);
+                return;
+            }
+            if (x > 0 && (outside || lx == 0) && piece_label(labels[j - 1], n_labels) == mine)
+                unite<GlobalLoad>(parent, i, j - 1);
+            if (x < dm.w - 1 && (outside || lx == kTX - 1) && piece_label(labels[j + 1], n_labels) == mine)
+                unite<GlobalLoad>(parent, i, j + 1);
+        };
+        row(-1, -1);
+        row(-1, 0);
+        row(-1, 1);
+        row(0, -1);
+        if (lx == 0 && x > 0 && piece_label(labels[i - 1], n_labels) == mine) unite<GlobalLoad>(parent, i, i - 1);
+    }
+}
+
+// kept pieces: foreground roots of at least dust voxels; aux[v] = the piece's number (1 ...), 0 for every other
+// voxel. aux holds pieces_sizes' count at a root: the piece's voxels.
+struct PieceRoot {
+    const int* parent;
+    const int* labels;
+    int* aux;
+    int n_labels;
+    long long dust;
+    __device__ __forceinline__ bool operator()(size_t v) const {
+        return parent[v] == (int)v && piece_label(labels[v], n_labels) != 0 && (long long)aux[v] >= dust;
+    }
+    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const { aux[v] = flag ? rank + 1 : 0; }
+};
+
+// pieces is the flattened parent array: a thread reads only its own entry of it before writing it. A foreground
+// root whose aux is 0 is a dust piece: counted per wave, one add each.
+__global__ __launch_bounds__(kThreads) void pieces_relabel(const int* __restrict__ labels, int* pieces,
+                                                          const int* __restrict__ aux, int* dust_count, int n_labels,
+                                                          int n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const size_t rounds = ((size_t)n + stride - 1) / stride;   // whole waves stay in the loop together
+    size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int dust = 0;
+    for (size_t it = 0; it < rounds; ++it, g += stride) {
+        bool dusty = false;
+        if (g < (size_t)n) {
+            int out = 0;
+            if (piece_label(labels[g], n_labels) != 0) {
+                const int r = pieces[g];
+                out = aux[r];
+                dusty = out == 0 && r == (int)g;
+            }
+            pieces[g] = out;
+        }
+        dust += __popcll(__ballot(dusty));
+    }
+    if (lane == 0 && dust) atomicAdd(dust_count, dust);
+}
+
 // ---- streamed slabs -----------------------------------------------------------------
 // state words on the device
 constexpr int kIdsUsed = 0, kOverflow = 1, kSegments = 2, kSlabIds = 3;
@@ -789,6 +993,22 @@ HolesLayout holes_layout_of(const Dims& dm) {
     l.hi_off = 2 * words;
     l.mask_off = 3 * words;
     l.bytes = l.mask_off + align_up((size_t)dm.n, 256);
+    return l;
+}
+
+// exaspim_label_pieces: the voxel counts, which become the piece numbers, and the scan's block sums; the parent
+// array is the caller's output volume
+struct PiecesLayout {
+    size_t aux_off, sums_off, bytes;
+    long long n_scan_blocks;
+};
+
+PiecesLayout pieces_layout_of(const Dims& dm) {
+    PiecesLayout l;
+    l.n_scan_blocks = ((long long)dm.n + kScanBlock - 1) / kScanBlock;
+    l.aux_off = 0;
+    l.sums_off = align_up((size_t)dm.n * 4, 256);
+    l.bytes = l.sums_off + align_up((size_t)l.n_scan_blocks * 4, 256);
     return l;
 }
 
@@ -1038,6 +1258,58 @@ extern "C" int exaspim_fill_holes(const int32_t* labels_dev, const int32_t dims[
     }
     return launch_fill_holes_passes(labels_dev, dims, out_dev, counts_dev, workspace_dev, 0, kFillHolesPasses - 1,
                                     (hipStream_t)stream);
+}
+
+extern "C" size_t exaspim_label_pieces_workspace_bytes(const int32_t dims[3]) {
+    Dims dm;
+    if (!valid_dims(dims, &dm)) {
+        set_error("label_pieces_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return pieces_layout_of(dm).bytes;
+}
+
+extern "C" int exaspim_label_pieces(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                                    int64_t dust_threshold, int32_t* pieces_dev, int32_t* state_dev,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(labels_dev && dims && pieces_dev && state_dev && workspace_dev, "label_pieces: NULL argument");
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(dims, &dm), "label_pieces: dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(n_labels >= 0, "label_pieces: n_labels must not be negative, got %d", n_labels);
+    EXA_CHECK_ARG(dust_threshold >= 0, "label_pieces: dust_threshold must not be negative, got %lld",
+                  (long long)dust_threshold);
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 &&
+                      (((uintptr_t)labels_dev | (uintptr_t)pieces_dev | (uintptr_t)state_dev) & 3) == 0,
+                  "label_pieces: misaligned buffer");
+    EXA_CHECK_ARG(pieces_dev != labels_dev, "label_pieces: pieces_dev must not be labels_dev");
+    const PiecesLayout l = pieces_layout_of(dm);
+    if (workspace_bytes < l.bytes) {
+        set_error("label_pieces: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+        return EXASPIM_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace_dev);
+    int* aux = reinterpret_cast<int*>(ws + l.aux_off);
+    int* sums = reinterpret_cast<int*>(ws + l.sums_off);
+    int* parent = pieces_dev;
+    EXA_CHECK_HIP(hipMemsetAsync(aux, 0, (size_t)dm.n * 4, s));
+    EXA_CHECK_HIP(hipMemsetAsync(state_dev, 0, 2 * sizeof(int32_t), s));
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    pieces_tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(labels_dev, parent, aux, dm, n_labels,
+                                                                          tiles_x, tiles_y, n_tiles);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads);
+    pieces_seam_merge<<<grid, kThreads, 0, s>>>(labels_dev, parent, dm, n_labels);
+    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+    pieces_sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    const unsigned scan_grid = (unsigned)l.n_scan_blocks;
+    const PieceRoot kept{parent, labels_dev, aux, n_labels, (long long)dust_threshold};
+    scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, state_dev);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    pieces_relabel<<<grid, kThreads, 0, s>>>(labels_dev, parent, aux, state_dev + 1, n_labels, dm.n);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
 }
 
 // ---- the streamed form ---------------------------------------------------------------------------

@@ -53,14 +53,15 @@ from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (
     _AgglomerationLabeller, _border_targets_on_device, _ComponentsLabeller, _components_on_device,
     _contract_dominant_on_device,
     _default_edge_capacity, _device_merged_table, _fill_holes_on_device, _fix_branching_on_device,
-    _geodesic_on_device, _geodesic_parents_on_device, _geodesic_seeded_on_device, _LabelSink, _last_threshold,
+    _geodesic_on_device, _geodesic_parents_on_device, _geodesic_seeded_on_device, _label_pieces_on_device, _LabelSink,
+    _last_threshold,
     _premerge_on_device, _premerged_table, _region_graph_device, _skeleton_chain_on_device, _teasar_on_device,
     _watershed_on_device, affinities_to_components, affinities_to_components_streaming, agglomerate,
     agglomerate_affinities, agglomerate_affinities_streaming, border_targets, contract_dominant_edges,
     distance_to_boundary,
-    fill_holes, geodesic_field, geodesic_field_seeded, geodesic_parents, geodesic_parents_seeded,
+    fill_holes, label_pieces, geodesic_field, geodesic_field_seeded, geodesic_parents, geodesic_parents_seeded,
     premerge_region_graph, region_graph, segment_table, segmentation_to_zipped_swcs, skeleton_to_swc, skeletonize,
-    skeletonize_fix_borders, skeletonize_labels, skeletons_to_zipped_swcs, teasar_branches,
+    skeletonize_fix_borders, skeletonize_labels, skeletonize_pieces, skeletons_to_zipped_swcs, teasar_branches,
     teasar_branches_fix_branching, teasar_branches_fix_branching_given, teasar_branches_given, trace_paths,
     voxelize_skeletons, watershed_fragments,
 )

@@ -1499,6 +1499,137 @@ def border_targets(labels, *, n_labels=None, return_device_tensors=False):
     return out
 
 
+def _label_pieces_on_device(labels, n_labels, dust_threshold=0):
+    """
+    exaspim_label_pieces on a checked device tensor. Returns the int32
+    (D, H, W) volume of piece numbers and the int32 (2,) state (kept pieces,
+    dust pieces), both left on the device: nothing is synchronised.
+    """
+    dims = tuple(int(v) for v in labels.shape)
+    device = labels.device
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = lib.exaspim_label_pieces_workspace_bytes(dims3)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    with torch.cuda.device(device):
+        pieces = torch.empty(dims, dtype=torch.int32, device=device)
+        state = torch.empty(2, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_label_pieces(labels.data_ptr(), dims3, int(n_labels), int(dust_threshold), pieces.data_ptr(),
+                                     state.data_ptr(), workspace.data_ptr(), need, _stream(device)),
+            "exaspim_label_pieces",
+        )
+    return pieces, state
+
+
+def _piece_tables_on_device(labels, pieces, state):
+    """
+    The tables of label_pieces from its volume: P (the one read of the
+    device), then segment_table of the pieces and a gather of the labels at
+    the first voxels. Returns (P, piece_label, piece_size, piece_first) with
+    device tensors of P rows.
+    """
+    with torch.cuda.device(labels.device):
+        n_pieces = int(state.cpu()[0])   # the one read
+        sizes, _, _, first = segment_table(pieces, n_labels=n_pieces, return_device_tensors=True)
+        piece_size, piece_first = sizes[1:].contiguous(), first[1:].contiguous()
+        piece_label = labels.reshape(-1)[piece_first.to(torch.int64)].contiguous()
+    return n_pieces, piece_label, piece_size, piece_first
+
+
+def _checked_pieces_scalars(fn, n_labels, dust_threshold):
+    """n_labels (or None) and dust_threshold of label_pieces and skeletonize_pieces, before any device is asked for."""
+    if n_labels is not None:
+        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
+            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
+        if n_labels < 0:
+            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+        if n_labels > 2**31 - 1:
+            raise ValueError(f"{fn}: n_labels must be at most 2^31 - 1, got {n_labels}")
+    if isinstance(dust_threshold, bool) or not isinstance(dust_threshold, (int, np.integer)):
+        raise TypeError(f"{fn}: dust_threshold must be an integer, got {type(dust_threshold).__name__}")
+    if dust_threshold < 0:
+        raise ValueError(f"{fn}: dust_threshold must not be negative, got {dust_threshold}")
+    return min(int(dust_threshold), 2**63 - 1)
+
+
+def label_pieces(labels, *, n_labels=None, dust_threshold=0, return_device_tensors=False):
+    """
+    Every 26-connected piece of every label, numbered, without the dust, on
+    the device.
+
+    What this is: what kimimaro.skeletonize does before anything else (the
+    reference's call, inference.py:272-290, leaves dust_threshold at
+    kimimaro's 1000): the volume is relabelled by 26-connected components
+    and the small ones are dropped, so that a label in several pieces gets a
+    skeleton per piece. Exactly, in integers: K = n_labels. A voxel is
+    foreground iff its label is in 1..K. A piece is a maximal 26-connected
+    set of foreground voxels with one label; its size is its voxel count, its
+    first voxel its smallest linear index z * H * W + y * W + x. A piece is
+    kept iff size >= dust_threshold (0 and 1 keep everything), otherwise it
+    is dust. Kept pieces are numbered 1..P in ascending order of first
+    voxel; every voxel of a kept piece holds that number, every other voxel
+    0. A pure function of the input.
+
+    Two consequences hold exactly: distance_to_boundary(pieces) equals
+    distance_to_boundary(labels) at every voxel of a kept piece, and
+    border_targets(pieces) is border_targets(labels) restricted to kept
+    pieces, with the label column mapped to piece numbers.
+
+    What this is not: cc3d or kimimaro; equality with either is not claimed,
+    and neither is a dependency. No slab-streamed form.
+
+    Parameters
+    ----------
+    labels : torch.Tensor or numpy.ndarray
+        int32 (D, H, W): a tensor on a HIP device, or a numpy array, which
+        is uploaded to cuda:0. It is only read.
+    n_labels : int, optional
+        K. Default is max(labels.max(), 0), one more read of the device.
+        Labels above K and labels <= 0 are background.
+    dust_threshold : int, optional
+        Pieces of fewer voxels are dropped. Default is 0.
+    return_device_tensors : bool, optional
+        Return device tensors instead of numpy arrays. Default is False.
+
+    Returns
+    -------
+    pieces : numpy.ndarray or torch.Tensor
+        int32 (D, H, W).
+    piece_label : numpy.ndarray or torch.Tensor
+        int32 (P,): the label of piece i + 1.
+    piece_size : numpy.ndarray or torch.Tensor
+        int64 (P,): its voxel count.
+    piece_first : numpy.ndarray or torch.Tensor
+        int32 (P,): its first voxel, strictly ascending.
+
+    Raises
+    ------
+    TypeError
+        If labels is not int32, or n_labels or dust_threshold is not an
+        integer.
+    ValueError
+        If labels is not 3-D, is empty or has more than 2^31 - 1 voxels, or
+        n_labels or dust_threshold is negative.
+    RuntimeError
+        If labels is a tensor on a CPU device, or there is no HIP device to
+        upload an array to.
+    """
+    dust_threshold = _checked_pieces_scalars("label_pieces", n_labels, dust_threshold)
+    labels, _ = _checked_labels(labels, "label_pieces")
+    with torch.cuda.device(labels.device):
+        if n_labels is None:
+            n_labels = max(int(labels.max()), 0)
+        pieces, state = _label_pieces_on_device(labels, int(n_labels), dust_threshold)
+        _, piece_label, piece_size, piece_first = _piece_tables_on_device(labels, pieces, state)
+        out = (pieces, piece_label, piece_size, piece_first)
+        if not return_device_tensors:
+            out = tuple(t.cpu().numpy() for t in out)
+    return out
+
+
 def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_sweeps=None, farthest=False,
                         stats=None):
     """
@@ -2705,7 +2836,8 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
     equality with kimimaro is not claimed. The reference passes
     fix_borders=True; this function does not end skeletons at the centres of
     the cuts, skeletonize_fix_borders does. A piece of a label that the root's
-    piece does not touch gets no skeleton. (skeletonize is this chain with the
+    piece does not touch gets no skeleton; skeletonize_pieces gives every piece
+    one. (skeletonize is this chain with the
     fix_branching=True loop, teasar_branches_fix_branching, as its last
     stage.)
 
@@ -2746,8 +2878,11 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
 
 
 def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching,
-                         fix_borders=False):
-    """skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host."""
+                         fix_borders=False, pieces_dust=None):
+    """
+    skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host.
+    With pieces_dust (skeletonize_pieces' checked dust_threshold) the chain runs on the labels' pieces.
+    """
     if not isinstance(fix_borders, (bool, np.bool_)):
         raise TypeError(f"{fn}: fix_borders must be a bool, got {type(fix_borders).__name__}")
     if isinstance(pdrf_exponent, bool) or not isinstance(pdrf_exponent, (int, np.integer)):
@@ -2759,11 +2894,19 @@ def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fi
     if not np.isfinite(pdrf_scale) or pdrf_scale < 0:
         raise ValueError(f"{fn}: pdrf_scale must be finite and not negative, got {pdrf_scale}")
     _checked_teasar_scalars(fn, scale, const, max_paths)
+    if pieces_dust is not None:
+        return _skeletons_of_pieces(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths,
+                                    fix_branching, fix_borders, pieces_dust)
     labels, dims = _checked_labels(labels, fn)
     chain = _skeleton_chain_on_device(labels, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
                                       bool(fill_holes), None if max_paths is None else int(max_paths),
                                       bool(fix_branching), fix_borders=bool(fix_borders))
-    with torch.cuda.device(labels.device):
+    return _chain_to_skeletons(fn, chain, dims)
+
+
+def _chain_to_skeletons(fn, chain, dims):
+    """The dict of _skeletons_of_labels from _skeleton_chain_on_device's tensors, put together on the host."""
+    with torch.cuda.device(chain["labels"].device):
         voxels, before, offsets, branch_label = (chain[k] for k in ("voxels", "before", "offsets", "branch_label"))
         radius = chain["dbf"].reshape(-1)[voxels.to(torch.int64)].to(torch.float32).sqrt()
         voxels, before, offsets, branch_label, radius = (
@@ -3292,7 +3435,8 @@ def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pd
     and anisotropy are not built. The reference passes fix_borders=True;
     this function keeps the skeletons of earlier versions, and
     skeletonize_fix_borders is the form that ends them at the centres of the
-    cuts.
+    cuts. skeletonize_pieces skeletonises every 26-connected piece of a
+    label, not the root's alone.
 
     Parameters
     ----------
@@ -3342,7 +3486,9 @@ def skeletonize_fix_borders(segmentation, *, fix_borders=True, fix_branching=Tru
 
     What this is not: kimimaro, which breaks the ties of a cut's centre by
     closeness to a centroid; equality with it is not claimed. max_paths
-    counts every round, the given ones included.
+    counts every round, the given ones included. A piece of a label
+    that the root's piece does not touch gets no skeleton and its border
+    targets are dropped; skeletonize_pieces is the form that keeps them.
 
     Parameters
     ----------
@@ -3365,6 +3511,95 @@ def skeletonize_fix_borders(segmentation, *, fix_borders=True, fix_branching=Tru
         raise TypeError(f"skeletonize_fix_borders: fix_branching must be a bool, got {type(fix_branching).__name__}")
     return _skeletons_of_labels("skeletonize_fix_borders", segmentation, scale, const, pdrf_exponent, pdrf_scale,
                                 fill_holes, max_paths, bool(fix_branching), fix_borders)
+
+
+def _skeletons_of_pieces(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching,
+                         fix_borders, dust_threshold):
+    """
+    skeletonize_pieces after its checks: fill_holes on the labels, their
+    pieces, the chain on the pieces, and every label's forest put together on
+    the host from the trees of its pieces.
+    """
+    labels, dims = _checked_labels(labels, fn)
+    with torch.cuda.device(labels.device):
+        if fill_holes:
+            labels, _ = _fill_holes_on_device(labels)
+        k = max(int(labels.max()), 0)
+        pieces, state = _label_pieces_on_device(labels, k, dust_threshold)
+        n_pieces, piece_label, _, _ = _piece_tables_on_device(labels, pieces, state)
+        if n_pieces == 0:
+            return {}
+        piece_label = piece_label.cpu().numpy()
+    chain = _skeleton_chain_on_device(pieces, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
+                                      False, None if max_paths is None else int(max_paths), bool(fix_branching),
+                                      fix_borders=bool(fix_borders))
+    trees = _chain_to_skeletons(fn, chain, dims)
+    out = {}
+    for piece in sorted(trees):   # ascending piece number
+        out.setdefault(int(piece_label[piece - 1]), []).append(trees[piece])
+    for label, mine in out.items():
+        starts = np.cumsum([0] + [len(tree[1]) for tree in mine[:-1]])
+        out[label] = (np.concatenate([tree[0] for tree in mine]),
+                      np.concatenate([np.where(tree[1] >= 0, tree[1] + start, -1).astype(np.int32)
+                                      for tree, start in zip(mine, starts)]),
+                      np.concatenate([tree[2] for tree in mine]))
+    return out
+
+
+def skeletonize_pieces(segmentation, *, dust_threshold=1000, fix_borders=True, fix_branching=True, scale=1.25,
+                       const=450.0, pdrf_exponent=4, pdrf_scale=100000.0, fill_holes=True, max_paths=None):
+    """
+    skeletonize_fix_borders on every 26-connected piece of every label, with
+    kimimaro's default dust_threshold: the reference's call
+    (inference.py:272-290) leaves that at 1000, and kimimaro.skeletonize
+    relabels the volume by 26-connected components, drops those below the
+    threshold and merges the component skeletons back under the original
+    label. A neurite that leaves a block and comes back is two pieces of one
+    label inside that block: the other functions skeletonise the root's
+    piece alone and drop the border targets of the rest; this one gives every
+    kept piece its tree and its cut centres.
+
+    What this is: (1) fill_holes on the labels, if asked, so that a floating
+    piece inside a cavity of its own label is absorbed first; (2)
+    label_pieces(dust_threshold=dust_threshold); (3) skeletonize_fix_borders'
+    chain on the volume of pieces, without a second fill_holes; (4) on the
+    host, the entry of a label is a forest: the trees of its kept pieces
+    concatenated in ascending piece number, each tree's rows exactly those
+    the chain gives that piece, parents offset into the concatenation, one
+    -1 per tree. A label with only dust is absent. max_paths counts per
+    piece, every round, the given ones included. skeleton_to_swc,
+    skeletons_to_zipped_swcs and voxelize_skeletons take forests as they are.
+
+    What this is not: kimimaro or cc3d; equality with either is not claimed:
+    the definition of every stage is this project's own. Soma detection,
+    anisotropy and joining skeletons across blocks are not built.
+    skeletonize, skeletonize_labels, skeletonize_fix_borders and
+    segmentation_to_zipped_swcs keep the skeletons of earlier versions.
+
+    Parameters
+    ----------
+    segmentation, fix_borders, fix_branching, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths
+        As in skeletonize_fix_borders.
+    dust_threshold : int, optional
+        Pieces of fewer voxels get no skeleton. Default is 1000.
+
+    Returns
+    -------
+    dict
+        label -> (vertices, parent, radius), as skeletonize_labels, with
+        one parent of -1 per kept piece of the label.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As skeletonize_fix_borders; TypeError or ValueError for a
+        dust_threshold that is no integer >= 0.
+    """
+    if not isinstance(fix_branching, (bool, np.bool_)):
+        raise TypeError(f"skeletonize_pieces: fix_branching must be a bool, got {type(fix_branching).__name__}")
+    dust_threshold = _checked_pieces_scalars("skeletonize_pieces", None, dust_threshold)
+    return _skeletons_of_labels("skeletonize_pieces", segmentation, scale, const, pdrf_exponent, pdrf_scale,
+                                fill_holes, max_paths, bool(fix_branching), fix_borders, pieces_dust=dust_threshold)
 
 
 def skeletons_to_zipped_swcs(skeleton_dict, zip_path):

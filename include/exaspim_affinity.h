@@ -1435,6 +1435,41 @@ int exaspim_border_targets(const int32_t* labels_dev, const int32_t dims[3], int
                            int32_t* state_dev /* [2] */, void* workspace_dev, size_t workspace_bytes,
                            void* stream);
 
+/* ---- pieces: the 26-connected components of every label, without the dust ---------------------
+ * What kimimaro.skeletonize does before anything else (the reference's call, inference.py:272-290, leaves
+ * dust_threshold at kimimaro's 1000): it relabels the volume by 26-connected components, drops the small ones
+ * and skeletonises each of the others. The definition is this project's own, exact in integers; equality with
+ * cc3d or kimimaro is not claimed, and neither is a dependency.
+ *
+ * K = n_labels. A voxel is foreground iff its label is in 1..K; labels above K and values <= 0 are background.
+ * A piece is a maximal 26-connected set of foreground voxels with one label. Its size is its voxel count, its
+ * first voxel its smallest linear index z H W + y W + x. A piece is kept iff size >= dust_threshold
+ * (0 and 1 keep everything), otherwise it is dust. Kept pieces are numbered 1..P, in
+ * ascending order of first voxel. Every voxel of a kept piece holds the piece's number, every other voxel 0.
+ * The result is a pure function of the input.
+ *
+ * Two consequences hold exactly (DESIGN 6q has the proofs): exaspim_dbf of the pieces equals exaspim_dbf of
+ * the labels at every voxel of a kept piece, whatever became of the dust; and exaspim_border_targets of the
+ * pieces is that of the labels restricted to kept pieces, the label column mapped to piece numbers. */
+
+/* Scratch bytes of exaspim_label_pieces: 4 bytes per voxel and 4 per 2048 voxels, each part rounded up to
+ * 256. 0 with the error text set for dims exaspim_label_pieces refuses. */
+size_t exaspim_label_pieces_workspace_bytes(const int32_t dims[3]);
+
+/* pieces_dev[v] = the number of the kept piece of voxel v, or 0. state_dev[0] = P, the number of kept pieces;
+ * state_dev[1] = the number of dust pieces. labels_dev is only read; pieces_dev holds the union-find's parents
+ * until the last launch and must not be labels_dev. Eight launches on "stream" (the unions inside 8 x 8 x 32
+ * tiles in LDS, the unions across tile faces, edges and corners, flatten, the sizes, a three-pass prefix sum over
+ * the kept roots, the final numbering) and two memsets, nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for a NULL pointer, a dim that is not positive, a volume of more than 2^31 - 1 voxels, a
+ * negative n_labels or dust_threshold, pieces_dev == labels_dev, or a misaligned buffer (workspace_dev 16
+ * bytes, the rest 4); EXASPIM_E_WORKSPACE if workspace_bytes is less than
+ * exaspim_label_pieces_workspace_bytes(dims): all before anything is launched, and no output is touched. */
+int exaspim_label_pieces(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                         int64_t dust_threshold, int32_t* pieces_dev,
+                         int32_t* state_dev /* [2]: kept pieces P, dust pieces */, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
 /* vol[z,y,x] = splitmix64(seed + global linear index) % 2000 as uint16. */
