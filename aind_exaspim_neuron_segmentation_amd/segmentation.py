@@ -72,6 +72,50 @@ def _on_device(a, fn, what="affinities", dtypes=_AFF_DTYPES, check=None, arrays_
     return a
 
 
+def _workspace_bytes(name, *args):
+    """What the library's size query "name" (an ..._workspace_bytes function) asks for these arguments; a 0 is
+    its refusal, raised as ValueError with the library's message."""
+    need = getattr(_native.lib(), name)(*args)
+    if need == 0:
+        raise ValueError(_native.last_error())
+    return need
+
+
+def _downloaded(out, device, keep_on_device=False):
+    """The download tail: the tuple "out" of tensors on "device" as numpy arrays, or as it is if they are to stay."""
+    if keep_on_device:
+        return out
+    with torch.cuda.device(device):
+        return tuple(t.cpu().numpy() for t in out)
+
+
+def _checked_integer(fn, name, value, least=None, most_bits=None, optional=False):
+    """
+    The one check of an integer argument "name" of the public function "fn":
+    TypeError unless it is an int or a numpy integer (a bool is neither),
+    ValueError below "least" or above 2^most_bits - 1. None passes iff
+    "optional". n_labels' "negative" message alone names no function; tests
+    match on it as it stands.
+    """
+    if value is None and optional:
+        return
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{fn}: {name} must be an integer, got {type(value).__name__}")
+    if least is not None and value < least:
+        who = name if name == "n_labels" else f"{fn}: {name}"
+        raise ValueError(f"{who} must {'not be negative' if least == 0 else f'be at least {least}'}, got {value}")
+    if most_bits is not None and value > 2**most_bits - 1:
+        raise ValueError(f"{fn}: {name} must be at most 2^{most_bits} - 1, got {value}")
+
+
+def _checked_real(fn, name, value):
+    """The one check of a real argument: TypeError unless it is a real number, ValueError unless finite and >= 0."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{fn}: {name} must be a real number, got {type(value).__name__}")
+    if not np.isfinite(value) or value < 0:
+        raise ValueError(f"{fn}: {name} must be finite and not negative, got {value}")
+
+
 def _apply_table(labels, table):
     """labels[i] = table[labels[i]] in place (exaspim_apply_label_table), both int32 on one device; returns labels."""
     with torch.cuda.device(labels.device):
@@ -97,9 +141,7 @@ def _label_on_device(affinities, workspace_bytes, kernel, middle):
     affinities = affinities.contiguous()
     device = affinities.device
     lib = _native.lib()
-    need = getattr(lib, workspace_bytes)(_native.int3(dims))
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes(workspace_bytes, _native.int3(dims))
     with torch.cuda.device(device):
         labels = torch.empty(dims, dtype=torch.int32, device=device)
         count = torch.empty(1, dtype=torch.int32, device=device)
@@ -376,9 +418,7 @@ def _region_graph_device(labels, affinities, n_labels, edge_capacity=None):
     labels, affinities = labels.contiguous(), affinities.contiguous()
     device = labels.device
     lib = _native.lib()
-    need = lib.exaspim_region_graph_workspace_bytes(_native.int3(dims), n_labels, capacity)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_region_graph_workspace_bytes", _native.int3(dims), n_labels, capacity)
     with torch.cuda.device(device):
         edges = torch.empty((capacity, 2), dtype=torch.int32, device=device)
         counts = torch.empty(capacity, dtype=torch.int64, device=device)
@@ -598,9 +638,7 @@ def _rounds_on_device(kernel, extra, fn, is_last, edges, counts, sums, sizes, n_
         if not total_checked and n_edges:
             _check_total_count(counts[:n_edges], fn)
         composed = None
-        need = getattr(lib, kernel + "_workspace_bytes")(n_labels, capacity)
-        if need == 0:
-            raise ValueError(_native.last_error())
+        need = _workspace_bytes(kernel + "_workspace_bytes", n_labels, capacity)
         workspace = torch.empty(need, dtype=torch.uint8, device=device)
         state = torch.empty(3, dtype=torch.int32, device=device)
         spare = None   # the buffers the round after next may write: never the caller's
@@ -1111,6 +1149,97 @@ def _checked_labels(labels, fn, what="labels"):
     return labels.contiguous(), tuple(int(v) for v in labels.shape)
 
 
+_TORCH_DTYPES = {np.int32: torch.int32, np.float32: torch.float32}
+
+
+# Shape rules of _checked_arrays' rows: rule(a, reference's shape) is None, or what the argument "must ..."
+def _like_labels(a, shape):
+    """Of the labels' shape."""
+    return None if tuple(a.shape) == tuple(shape) else f"have the labels' shape {tuple(shape)}"
+
+
+def _row_per_label(n_labels):
+    """(K + 1,): one row per label and row 0, n_labels + 1 of them if n_labels is given."""
+    def rule(a, _):
+        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
+            return "be (K + 1,)" if n_labels is None else f"be (n_labels + 1 = {n_labels + 1},)"
+    return rule
+
+
+def _listed(a, _):
+    """(S,): a list of any length, an empty one included."""
+    return None if a.ndim == 1 else "be (S,)"
+
+
+def _six_per_row(a, shape):
+    """(rows, 6), rows those of the table it goes with."""
+    return None if tuple(a.shape) == (shape[0], 6) else f"be ({shape[0]}, 6) as sources has {shape[0]} rows"
+
+
+def _checked_arrays(fn, labels, rows):
+    """
+    The front matter of every function that takes arrays next to a labels
+    volume, once, after the caller has checked its scalars: (2) every numpy
+    array is checked before any of them is uploaded; (3) if labels is a
+    tensor, every tensor next to it is checked before an array next to it is
+    uploaded; (4) labels go through _checked_labels; (5) every argument is
+    uploaded, checked for dtype, shape and device and made contiguous, in the
+    order of the rows. Within (2) and (3) the dtypes of all rows come first,
+    then their shapes.
+
+    A row is (name, value, numpy dtype, shape rule, reference, optional). The
+    rule is checked against the shape of its reference: None (the rule needs
+    none), "labels", or the name of an earlier row, which must be 1-D. A rule
+    that refers to a row is checked in (2) or (3) as soon as either of the
+    two is an array, or a tensor. An optional argument may be None.
+
+    Returns (labels, dims, values): the values as contiguous tensors on the
+    labels' device, None for an absent one, in the order of the rows.
+    """
+    given = {name: value for name, value, *_ in rows}
+
+    def check_dtype(name, a, dtype):
+        if a.dtype != (dtype if isinstance(a, np.ndarray) else _TORCH_DTYPES[dtype]):
+            raise TypeError(f"{name} must be {np.dtype(dtype)}, got {a.dtype}")
+
+    def check_shape(name, a, rule, shape):
+        must = rule(a, shape)
+        if must is not None:
+            raise ValueError(f"{fn}: {name} must {must}, got {tuple(a.shape)}")
+
+    def check_all(kind):
+        """Of the arguments that are of "kind", numpy arrays or tensors."""
+        for name, a, dtype, _, _, _ in rows:
+            if isinstance(a, kind):
+                check_dtype(name, a, dtype)
+        for name, a, _, rule, reference, _ in rows:
+            if reference is None or reference == "labels":
+                if isinstance(a, kind) and (reference is None or isinstance(labels, (np.ndarray, torch.Tensor))):
+                    check_shape(name, a, rule, None if reference is None else labels.shape)
+            else:
+                other = given[reference]
+                if ((isinstance(a, kind) or isinstance(other, kind)) and isinstance(a, (np.ndarray, torch.Tensor))
+                        and isinstance(other, (np.ndarray, torch.Tensor)) and other.ndim == 1):
+                    check_shape(name, a, rule, other.shape)
+
+    check_all(np.ndarray)      # every array is checked before any of them is uploaded
+    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
+        check_all(torch.Tensor)
+    labels, dims = _checked_labels(labels, fn)
+    device = labels.device
+    out = {"labels": labels}
+    for name, a, dtype, rule, reference, optional in rows:
+        if a is not None or not optional:
+            a = _on_device(a, fn, name, (dtype,))
+            check_dtype(name, a, dtype)
+            check_shape(name, a, rule, None if reference is None else out[reference].shape)
+            if a.device != device:
+                raise RuntimeError(f"{fn}: {name} must be on the labels' device {device}, got {a.device}")
+            a = a.contiguous()
+        out[name] = a
+    return labels, dims, [out[name] for name, *_ in rows]
+
+
 def _fill_holes_on_device(labels):
     """
     exaspim_fill_holes on a device tensor: the filled labels and the two
@@ -1134,9 +1263,7 @@ def _fill_holes_on_device(labels):
     labels, dims = _checked_labels(labels, "fill_holes")
     device = labels.device
     lib = _native.lib()
-    need = lib.exaspim_fill_holes_workspace_bytes(_native.int3(dims))
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_fill_holes_workspace_bytes", _native.int3(dims))
     with torch.cuda.device(device):
         filled = torch.empty(dims, dtype=torch.int32, device=device)
         counts = torch.empty(2, dtype=torch.int64, device=device)
@@ -1280,9 +1407,7 @@ def distance_to_boundary(labels, *, black_border=False, return_device_tensor=Fal
     labels, dims = _checked_labels(labels, "distance_to_boundary")
     device = labels.device
     lib = _native.lib()
-    need = lib.exaspim_dbf_workspace_bytes(_native.int3(dims))
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_dbf_workspace_bytes", _native.int3(dims))
     with torch.cuda.device(device):
         dbf = torch.empty(dims, dtype=torch.int32, device=device)
         workspace = torch.empty(need, dtype=torch.uint8, device=device)
@@ -1377,9 +1502,7 @@ def segment_table(labels, dbf=None, *, n_labels=None, return_device_tensors=Fals
     if n_labels < 0:
         raise ValueError(f"n_labels must not be negative, got {n_labels}")
     lib = _native.lib()
-    need = lib.exaspim_segment_table_workspace_bytes(n_labels)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_segment_table_workspace_bytes", n_labels)
     with torch.cuda.device(device):
         sizes = torch.empty(n_labels + 1, dtype=torch.int64, device=device)
         boxes = torch.empty((n_labels + 1, 6), dtype=torch.int32, device=device)
@@ -1392,9 +1515,7 @@ def segment_table(labels, dbf=None, *, n_labels=None, return_device_tensors=Fals
                                       peak_index.data_ptr(), workspace.data_ptr(), need, _stream(device)),
             "exaspim_segment_table",
         )
-        if return_device_tensors:
-            return sizes, boxes, peak, peak_index
-        return tuple(t.cpu().numpy() for t in (sizes, boxes, peak, peak_index))
+    return _downloaded((sizes, boxes, peak, peak_index), device, return_device_tensors)
 
 
 def _border_targets_on_device(labels, n_labels):
@@ -1407,9 +1528,7 @@ def _border_targets_on_device(labels, n_labels):
     device = labels.device
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_border_targets_workspace_bytes(dims3)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_border_targets_workspace_bytes", dims3)
     d, h, w = dims
     capacity = 2 * (h * w + d * w + d * h)   # every face pixel a component of its own: it never overflows
     with torch.cuda.device(device):
@@ -1483,20 +1602,10 @@ def border_targets(labels, *, n_labels=None, return_device_tensors=False):
         If labels is a tensor on a CPU device, or there is no HIP device to
         upload an array to.
     """
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"border_targets: n_labels must be an integer, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
+    _checked_integer("border_targets", "n_labels", n_labels, least=0, optional=True)
     labels, _ = _checked_labels(labels, "border_targets")
-    if n_labels is None:
-        with torch.cuda.device(labels.device):
-            n_labels = max(int(labels.max()), 0)
-    out = _border_targets_on_device(labels, int(n_labels))
-    if not return_device_tensors:
-        with torch.cuda.device(labels.device):
-            out = tuple(t.cpu().numpy() for t in out)
-    return out
+    out = _border_targets_on_device(labels, _label_count(labels, n_labels, "border_targets"))
+    return _downloaded(out, labels.device, return_device_tensors)
 
 
 def _label_pieces_on_device(labels, n_labels, dust_threshold=0):
@@ -1509,9 +1618,7 @@ def _label_pieces_on_device(labels, n_labels, dust_threshold=0):
     device = labels.device
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_label_pieces_workspace_bytes(dims3)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_label_pieces_workspace_bytes", dims3)
     with torch.cuda.device(device):
         pieces = torch.empty(dims, dtype=torch.int32, device=device)
         state = torch.empty(2, dtype=torch.int32, device=device)
@@ -1541,17 +1648,8 @@ def _piece_tables_on_device(labels, pieces, state):
 
 def _checked_pieces_scalars(fn, n_labels, dust_threshold):
     """n_labels (or None) and dust_threshold of label_pieces and skeletonize_pieces, before any device is asked for."""
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
-        if n_labels > 2**31 - 1:
-            raise ValueError(f"{fn}: n_labels must be at most 2^31 - 1, got {n_labels}")
-    if isinstance(dust_threshold, bool) or not isinstance(dust_threshold, (int, np.integer)):
-        raise TypeError(f"{fn}: dust_threshold must be an integer, got {type(dust_threshold).__name__}")
-    if dust_threshold < 0:
-        raise ValueError(f"{fn}: dust_threshold must not be negative, got {dust_threshold}")
+    _checked_integer(fn, "n_labels", n_labels, least=0, most_bits=31, optional=True)
+    _checked_integer(fn, "dust_threshold", dust_threshold, least=0)
     return min(int(dust_threshold), 2**63 - 1)
 
 
@@ -1624,10 +1722,35 @@ def label_pieces(labels, *, n_labels=None, dust_threshold=0, return_device_tenso
             n_labels = max(int(labels.max()), 0)
         pieces, state = _label_pieces_on_device(labels, int(n_labels), dust_threshold)
         _, piece_label, piece_size, piece_first = _piece_tables_on_device(labels, pieces, state)
-        out = (pieces, piece_label, piece_size, piece_first)
-        if not return_device_tensors:
-            out = tuple(t.cpu().numpy() for t in out)
-    return out
+    return _downloaded((pieces, piece_label, piece_size, piece_first), labels.device, return_device_tensors)
+
+
+def _swept_until_settled(launch, state, sweeps_per_read, max_sweeps, fn, refusal):
+    """
+    The sweep loop of the three field passes after their begin call: the first
+    read of "state" (word 0 the tiles flagged, word 1 the rows the begin call
+    refused: ValueError(refusal(that count)) if any), then launch(batch) and
+    one read of word 0 until no tile is flagged, the batch sweeps_per_read
+    clipped to what max_sweeps leaves; RuntimeError in the name of "fn" once
+    max_sweeps have run and a tile is still flagged. Returns what the callers
+    put into "stats": sweeps (launched), reads (of the state) and
+    tiles_flagged (the count found at each read, the one after begin first).
+    """
+    flagged, invalid = (int(v) for v in state.cpu()[:2])   # the first read of the state
+    if invalid:
+        raise ValueError(refusal(invalid))
+    sweeps, reads, history = 0, 1, [flagged]
+    while flagged:
+        if max_sweeps is not None and sweeps >= max_sweeps:
+            raise RuntimeError(f"{fn}: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
+                               f"{flagged} tile(s) still flagged")
+        batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+        launch(batch)
+        sweeps += batch
+        flagged = int(state.cpu()[0])
+        reads += 1
+        history.append(flagged)
+    return dict(sweeps=sweeps, reads=reads, tiles_flagged=history)
 
 
 def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_sweeps=None, farthest=False,
@@ -1671,9 +1794,7 @@ def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_swee
     device = labels.device
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_geodesic_workspace_bytes(dims3)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_geodesic_workspace_bytes", dims3)
     with torch.cuda.device(device):
         stream = _stream(device)
         field = torch.empty(dims, dtype=torch.float32, device=device)
@@ -1684,28 +1805,21 @@ def _geodesic_on_device(labels, sources, cost=None, sweeps_per_read=32, max_swee
                                        state.data_ptr(), workspace.data_ptr(), need, stream),
             "exaspim_geodesic_begin",
         )
-        flagged, invalid = (int(v) for v in state.cpu())   # the first read of the state
-        if invalid:
-            raise ValueError(f"geodesic_field: {invalid} row(s) of sources name no voxel of their label "
-                             "(a row L must be -1 or the linear index of a voxel with labels == L)")
-        sweeps, reads, history = 0, 1, [flagged]
-        while flagged:
-            if max_sweeps is not None and sweeps >= max_sweeps:
-                raise RuntimeError(f"geodesic_field: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
-                                   f"{flagged} tile(s) still flagged")
-            batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+
+        def sweeps(batch):
             _native.check(
                 lib.exaspim_geodesic_sweeps(labels.data_ptr(), None if cost is None else cost.data_ptr(), dims3,
                                             n_labels, field.data_ptr(), batch, state.data_ptr(),
                                             workspace.data_ptr(), need, stream),
                 "exaspim_geodesic_sweeps",
             )
-            sweeps += batch
-            flagged = int(state.cpu()[0])
-            reads += 1
-            history.append(flagged)
+
+        swept = _swept_until_settled(
+            sweeps, state, sweeps_per_read, max_sweeps, "geodesic_field",
+            lambda invalid: f"geodesic_field: {invalid} row(s) of sources name no voxel of their label "
+                            "(a row L must be -1 or the linear index of a voxel with labels == L)")
         if stats is not None:
-            stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
+            stats.update(swept)
         far_value = far_index = None
         if farthest:
             far_need = lib.exaspim_geodesic_farthest_workspace_bytes(n_labels)
@@ -1732,75 +1846,17 @@ def _checked_geodesic_arguments(fn, labels, sources, cost, n_labels, sweeps_per_
     (S,) with S >= 0, whatever n_labels is. Returns (labels, dims, sources,
     cost, field).
     """
-    listed = "seeds" if seed_list else "sources"
     for name, value in (("sweeps_per_read", sweeps_per_read), ("max_sweeps", max_sweeps)):
-        if value is None and name == "max_sweeps":
-            continue
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-            raise TypeError(f"{fn}: {name} must be an integer, got {type(value).__name__}")
-    if sweeps_per_read < 1:
-        raise ValueError(f"{fn}: sweeps_per_read must be at least 1, got {sweeps_per_read}")
-    if max_sweeps is not None and max_sweeps < 0:
-        raise ValueError(f"{fn}: max_sweeps must not be negative, got {max_sweeps}")
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
-
-    def check_sources(a):
-        if seed_list:
-            if a.ndim != 1:
-                raise ValueError(f"{fn}: seeds must be (S,), got {tuple(a.shape)}")
-            return
-        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
-            rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
-            raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
-
-    def check_cost(a, shape, what="cost"):
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError(f"{fn}: {what} must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
-
-    # every array is checked before any of them is uploaded
-    for what, a, dtype in ((listed, sources, np.int32), ("cost", cost, np.float32),
-                           ("field", field, np.float32)):
-        if isinstance(a, np.ndarray) and a.dtype != dtype:
-            raise TypeError(f"{what} must be {np.dtype(dtype)}, got {a.dtype}")
-    if isinstance(sources, np.ndarray):
-        check_sources(sources)
-    for what, a in (("cost", cost), ("field", field)):
-        if isinstance(a, np.ndarray) and isinstance(labels, (np.ndarray, torch.Tensor)):
-            check_cost(a, labels.shape, what)
-    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
-        if isinstance(sources, torch.Tensor):
-            if sources.dtype != torch.int32:
-                raise TypeError(f"{listed} must be int32, got {sources.dtype}")
-            check_sources(sources)
-        for what, a in (("cost", cost), ("field", field)):
-            if isinstance(a, torch.Tensor):
-                if a.dtype != torch.float32:
-                    raise TypeError(f"{what} must be float32, got {a.dtype}")
-                check_cost(a, labels.shape, what)
-    labels, dims = _checked_labels(labels, fn)
-    device = labels.device
-    sources = _on_device(sources, fn, listed, (np.int32,))
-    if sources.dtype != torch.int32:
-        raise TypeError(f"{listed} must be int32, got {sources.dtype}")
-    check_sources(sources)
-    if sources.device != device:
-        raise RuntimeError(f"{fn}: {listed} must be on the labels' device {device}, got {sources.device}")
-    both = []
-    for what, a in (("cost", cost), ("field", field)):
-        if a is not None:
-            a = _on_device(a, fn, what, (np.float32,))
-            if a.dtype != torch.float32:
-                raise TypeError(f"{what} must be float32, got {a.dtype}")
-            check_cost(a, dims, what)
-            if a.device != device:
-                raise RuntimeError(f"{fn}: {what} must be on the labels' device {device}, got {a.device}")
-            a = a.contiguous()
-        both.append(a)
-    return labels, dims, sources.contiguous(), both[0], both[1]
+        _checked_integer(fn, name, value, optional=name == "max_sweeps")   # both are integers before either's range
+    _checked_integer(fn, "sweeps_per_read", sweeps_per_read, least=1)
+    _checked_integer(fn, "max_sweeps", max_sweeps, least=0, optional=True)
+    _checked_integer(fn, "n_labels", n_labels, least=0, optional=True)
+    listed = (("seeds", sources, np.int32, _listed, None, False) if seed_list else
+              ("sources", sources, np.int32, _row_per_label(n_labels), None, False))
+    labels, dims, (sources, cost, field) = _checked_arrays(fn, labels, (
+        listed, ("cost", cost, np.float32, _like_labels, "labels", True),
+        ("field", field, np.float32, _like_labels, "labels", True)))
+    return labels, dims, sources, cost, field
 
 
 def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read=32, max_sweeps=None,
@@ -1905,10 +1961,7 @@ def geodesic_field(labels, sources, *, cost=None, n_labels=None, sweeps_per_read
     field, far_value, far_index = _geodesic_on_device(
         labels, sources, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps),
         bool(return_farthest), stats)
-    with torch.cuda.device(device):
-        out = (field, far_value, far_index) if return_farthest else (field,)
-        if not return_device_tensors:
-            out = tuple(t.cpu().numpy() for t in out)
+    out = _downloaded((field, far_value, far_index) if return_farthest else (field,), device, return_device_tensors)
     return out if return_farthest else out[0]
 
 
@@ -1965,9 +2018,7 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
             stats["field"] = field_stats
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_geodesic_workspace_bytes(dims3)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_geodesic_workspace_bytes", dims3)
     cost_ptr = None if cost is None else cost.data_ptr()
     with torch.cuda.device(device):
         stream = _stream(device)
@@ -1994,37 +2045,31 @@ def _geodesic_parents_on_device(labels, sources, field=None, cost=None, sweeps_p
                                                          workspace.data_ptr(), need, stream),
                 "exaspim_geodesic_parents_begin_seeds",
             )
-        flagged, invalid, _ = (int(v) for v in state.cpu())
-        if invalid and seeds is not None:
-            raise ValueError(f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} with a field of 0")
-        if invalid:
-            raise ValueError(f"{fn}: {invalid} row(s) of sources name no voxel of their label with a field of 0 "
-                             "(a row L must be -1 or the linear index of a voxel with labels == L and field == 0)")
-        sweeps, reads, history = 0, 1, [flagged]
-        while flagged:
-            if max_sweeps is not None and sweeps >= max_sweeps:
-                raise RuntimeError(f"{fn}: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
-                                   f"{flagged} tile(s) still flagged")
-            batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+
+        def sweeps(batch):
             _native.check(
                 lib.exaspim_geodesic_parents_sweeps(labels.data_ptr(), cost_ptr, field.data_ptr(), dims3, n_labels,
                                                     hops.data_ptr(), batch, state.data_ptr(), workspace.data_ptr(),
                                                     need, stream),
                 "exaspim_geodesic_parents_sweeps",
             )
-            sweeps += batch
-            flagged = int(state.cpu()[0])
-            reads += 1
-            history.append(flagged)
+
+        def refusal(invalid):
+            if seeds is not None:
+                return f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} with a field of 0"
+            return (f"{fn}: {invalid} row(s) of sources name no voxel of their label with a field of 0 "
+                    "(a row L must be -1 or the linear index of a voxel with labels == L and field == 0)")
+
+        swept = _swept_until_settled(sweeps, state, sweeps_per_read, max_sweeps, fn, refusal)
         _native.check(
             lib.exaspim_geodesic_parents_finish(labels.data_ptr(), cost_ptr, field.data_ptr(), hops.data_ptr(), dims3,
                                                 n_labels, parents.data_ptr(), state.data_ptr(), stream),
             "exaspim_geodesic_parents_finish",
         )
         orphans = int(state.cpu()[2])
-        reads += 1
+        swept["reads"] += 1
         if stats is not None:
-            stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
+            stats.update(swept)
         if orphans:
             raise ValueError(f"{fn}: {orphans} voxel(s) with a finite field have no tight predecessor: field is not "
                              f"the geodesic field of these labels, {'sources' if seeds is None else 'seeds'} and cost")
@@ -2112,10 +2157,7 @@ def geodesic_parents(labels, sources, *, field=None, cost=None, n_labels=None, s
         "geodesic_parents", labels, sources, cost, n_labels, sweeps_per_read, max_sweeps, field)
     parents, hops = _geodesic_parents_on_device(
         labels, sources, field, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps), stats)
-    with torch.cuda.device(labels.device):
-        out = (parents, hops) if return_hops else (parents,)
-        if not return_device_tensors:
-            out = tuple(t.cpu().numpy() for t in out)
+    out = _downloaded((parents, hops) if return_hops else (parents,), labels.device, return_device_tensors)
     return out if return_hops else out[0]
 
 
@@ -2218,23 +2260,14 @@ def trace_paths(parents, hops, targets, *, return_device_tensors=False):
         if refused or broken:
             raise RuntimeError(f"{fn}: {broken} broken walk(s) and {refused} refused row(s): parents and hops are not "
                                "the results of one geodesic_parents call")
-        if not return_device_tensors:
-            return voxels.cpu().numpy(), offsets.cpu().numpy()
-    return voxels, offsets
+    return _downloaded((voxels, offsets), device, return_device_tensors)
 
 
 def _checked_teasar_scalars(fn, scale, const, max_paths):
     """scale and const are finite real numbers >= 0, max_paths is None or an integer >= 1."""
-    for name, value in (("scale", scale), ("const", const)):
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
-            raise TypeError(f"{fn}: {name} must be a real number, got {type(value).__name__}")
-        if not np.isfinite(value) or value < 0:
-            raise ValueError(f"{fn}: {name} must be finite and not negative, got {value}")
-    if max_paths is not None:
-        if isinstance(max_paths, bool) or not isinstance(max_paths, (int, np.integer)):
-            raise TypeError(f"{fn}: max_paths must be an integer, got {type(max_paths).__name__}")
-        if max_paths < 1:
-            raise ValueError(f"{fn}: max_paths must be at least 1, got {max_paths}")
+    _checked_real(fn, "scale", scale)
+    _checked_real(fn, "const", const)
+    _checked_integer(fn, "max_paths", max_paths, least=1, optional=True)
 
 
 def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths,
@@ -2249,75 +2282,18 @@ def _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxe
     these two, parents and hops may be None and are returned as None, and
     (cost, field) is appended to the result.
     """
-    optional = ("boxes",) if fields is None else ("boxes", "parents", "hops", "cost", "field")
     _checked_teasar_scalars(fn, scale, const, max_paths)
-    if n_labels is not None:
-        if isinstance(n_labels, bool) or not isinstance(n_labels, (int, np.integer)):
-            raise TypeError(f"{fn}: n_labels must be an integer, got {type(n_labels).__name__}")
-        if n_labels < 0:
-            raise ValueError(f"n_labels must not be negative, got {n_labels}")
-
-    def check_sources(a):
-        if a.ndim != 1 or a.shape[0] < 1 or (n_labels is not None and a.shape[0] != n_labels + 1):
-            rows = "K + 1" if n_labels is None else f"n_labels + 1 = {n_labels + 1}"
-            raise ValueError(f"{fn}: sources must be ({rows},), got {tuple(a.shape)}")
-
-    def check_boxes(a, rows):
-        if a.ndim != 2 or tuple(a.shape) != (rows, 6):
-            raise ValueError(f"{fn}: boxes must be ({rows}, 6) as sources has {rows} rows, got {tuple(a.shape)}")
-
-    def check_volume(a, shape, what):
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError(f"{fn}: {what} must have the labels' shape {tuple(shape)}, got {tuple(a.shape)}")
-
-    volumes = (("dbf", dbf, np.int32, torch.int32), ("daf", daf, np.float32, torch.float32),
-               ("parents", parents, np.int32, torch.int32), ("hops", hops, np.int32, torch.int32))
+    _checked_integer(fn, "n_labels", n_labels, least=0, optional=True)
+    rows = [("sources", sources, np.int32, _row_per_label(n_labels), None, False),
+            ("boxes", boxes, np.int32, _six_per_row, "sources", True),
+            ("dbf", dbf, np.int32, _like_labels, "labels", False),
+            ("daf", daf, np.float32, _like_labels, "labels", False),
+            ("parents", parents, np.int32, _like_labels, "labels", fields is not None),
+            ("hops", hops, np.int32, _like_labels, "labels", fields is not None)]
     if fields is not None:
-        volumes += (("cost", fields[0], np.float32, torch.float32), ("field", fields[1], np.float32, torch.float32))
-    tables = (("sources", sources, np.int32, torch.int32), ("boxes", boxes, np.int32, torch.int32))
-
-    def check_dtype(what, a, np_dtype, torch_dtype):
-        if isinstance(a, np.ndarray) and a.dtype != np_dtype:
-            raise TypeError(f"{what} must be {np.dtype(np_dtype)}, got {a.dtype}")
-        if isinstance(a, torch.Tensor) and a.dtype != torch_dtype:
-            raise TypeError(f"{what} must be {np.dtype(np_dtype)}, got {a.dtype}")
-
-    def check_shapes(kind):
-        """Of the arguments that are of "kind", numpy arrays or tensors."""
-        for what, a, np_dtype, torch_dtype in tables + volumes:
-            if isinstance(a, kind):
-                check_dtype(what, a, np_dtype, torch_dtype)
-        if isinstance(sources, kind):
-            check_sources(sources)
-            if isinstance(boxes, (np.ndarray, torch.Tensor)):
-                check_boxes(boxes, sources.shape[0])
-        elif isinstance(boxes, kind) and isinstance(sources, (np.ndarray, torch.Tensor)) and sources.ndim == 1:
-            check_boxes(boxes, sources.shape[0])
-        for what, a, _, _ in volumes:
-            if isinstance(a, kind) and isinstance(labels, (np.ndarray, torch.Tensor)):
-                check_volume(a, labels.shape, what)
-
-    check_shapes(np.ndarray)      # every array is checked before any of them is uploaded
-    if isinstance(labels, torch.Tensor):   # a tensor is refused before an array next to it is uploaded
-        check_shapes(torch.Tensor)
-    labels, dims = _checked_labels(labels, fn)
-    device = labels.device
-    out = []
-    for what, a, np_dtype, torch_dtype in tables + volumes:
-        if a is None and what in optional:
-            out.append(None)
-            continue
-        a = _on_device(a, fn, what, (np_dtype,))
-        check_dtype(what, a, np_dtype, torch_dtype)
-        if what == "sources":
-            check_sources(a)
-        elif what == "boxes":
-            check_boxes(a, out[0].shape[0])
-        else:
-            check_volume(a, dims, what)
-        if a.device != device:
-            raise RuntimeError(f"{fn}: {what} must be on the labels' device {device}, got {a.device}")
-        out.append(a.contiguous())
+        rows += [("cost", fields[0], np.float32, _like_labels, "labels", True),
+                 ("field", fields[1], np.float32, _like_labels, "labels", True)]
+    labels, dims, out = _checked_arrays(fn, labels, rows)
     sources, boxes, dbf, daf, parents, hops = out[:6]
     return (labels, dims, sources, dbf, daf, parents, hops, boxes, float(scale), float(const)) + tuple(out[6:])
 
@@ -2418,9 +2394,7 @@ def _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, co
     device = labels.device
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_teasar_workspace_bytes(dims3, n_labels)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_teasar_workspace_bytes", dims3, n_labels)
     with torch.cuda.device(device):
         stream = _stream(device)
         mask = torch.empty(dims, dtype=torch.uint8, device=device)
@@ -2684,22 +2658,32 @@ def teasar_branches(labels, sources, dbf, daf, parents, hops, *, scale, const, b
 
 
 def _teasar_branches(fn, labels, sources, dbf, daf, parents, hops, scale, const, boxes, n_labels, max_paths,
-                     return_device_tensors, stats, targets_before):
-    """teasar_branches and teasar_branches_given: the arguments checked, the loop, the results downloaded."""
+                     return_device_tensors, stats, targets_before, fields=None):
+    """
+    teasar_branches and teasar_branches_given: the arguments checked, the loop, the results downloaded. With
+    fields=(cost, field), teasar_branches_fix_branching and its _given form: what is None of field, parents and
+    hops is computed first, and the loop is _fix_branching_on_device's.
+    """
     _pre_check_targets_before(fn, targets_before)
-    labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const = _checked_teasar_arguments(
-        fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels, max_paths)
+    checked = _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels,
+                                        max_paths, fields)
+    labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const = checked[:10]
     targets_before = _checked_targets_before(fn, targets_before, labels.device)
     if boxes is None:
         boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
-    out = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const,
-                            None if max_paths is None else int(max_paths), stats, fn=fn,
-                            targets_before=targets_before)
-    out = out[:2] + out[3:]
-    if not return_device_tensors:
-        with torch.cuda.device(labels.device):
-            out = tuple(t.cpu().numpy() for t in out)
-    return out
+    max_paths = None if max_paths is None else int(max_paths)
+    if fields is None:
+        out = _teasar_on_device(labels, sources, dbf, daf, parents, hops, boxes, scale, const, max_paths, stats,
+                                fn=fn, targets_before=targets_before)
+    else:
+        cost, field = checked[10:]
+        if field is None:
+            field, _, _ = _geodesic_on_device(labels, sources, cost)
+        if parents is None or hops is None:
+            parents, hops = _geodesic_parents_on_device(labels, sources, field, cost)
+        out = _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
+                                       max_paths, stats, targets_before=targets_before, fn=fn)
+    return _downloaded(out[:2] + out[3:], labels.device, return_device_tensors)
 
 
 def teasar_branches_given(labels, sources, dbf, daf, parents, hops, targets_before, *, scale, const, boxes=None,
@@ -2877,26 +2861,21 @@ def skeletonize_labels(labels, *, scale=1.25, const=450.0, pdrf_exponent=4, pdrf
                                 max_paths, False)
 
 
-def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching,
-                         fix_borders=False, pieces_dust=None):
-    """
-    skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host.
-    With pieces_dust (skeletonize_pieces' checked dust_threshold) the chain runs on the labels' pieces.
-    """
+def _checked_chain_scalars(fn, scale, const, pdrf_exponent, pdrf_scale, max_paths, fix_borders):
+    """The scalars of the skeletonize functions, before any device is asked for."""
     if not isinstance(fix_borders, (bool, np.bool_)):
         raise TypeError(f"{fn}: fix_borders must be a bool, got {type(fix_borders).__name__}")
-    if isinstance(pdrf_exponent, bool) or not isinstance(pdrf_exponent, (int, np.integer)):
-        raise TypeError(f"{fn}: pdrf_exponent must be an integer, got {type(pdrf_exponent).__name__}")
-    if pdrf_exponent < 0:
-        raise ValueError(f"{fn}: pdrf_exponent must not be negative, got {pdrf_exponent}")
-    if isinstance(pdrf_scale, bool) or not isinstance(pdrf_scale, (int, float, np.integer, np.floating)):
-        raise TypeError(f"{fn}: pdrf_scale must be a real number, got {type(pdrf_scale).__name__}")
-    if not np.isfinite(pdrf_scale) or pdrf_scale < 0:
-        raise ValueError(f"{fn}: pdrf_scale must be finite and not negative, got {pdrf_scale}")
+    _checked_integer(fn, "pdrf_exponent", pdrf_exponent, least=0)
+    _checked_real(fn, "pdrf_scale", pdrf_scale)
     _checked_teasar_scalars(fn, scale, const, max_paths)
-    if pieces_dust is not None:
-        return _skeletons_of_pieces(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths,
-                                    fix_branching, fix_borders, pieces_dust)
+
+
+def _skeletons_of_labels(fn, labels, scale, const, pdrf_exponent, pdrf_scale, fill_holes, max_paths, fix_branching,
+                         fix_borders=False):
+    """
+    skeletonize_labels and skeletonize: the arguments checked, the chain, and the dict put together on the host.
+    """
+    _checked_chain_scalars(fn, scale, const, pdrf_exponent, pdrf_scale, max_paths, fix_borders)
     labels, dims = _checked_labels(labels, fn)
     chain = _skeleton_chain_on_device(labels, float(scale), float(const), int(pdrf_exponent), float(pdrf_scale),
                                       bool(fill_holes), None if max_paths is None else int(max_paths),
@@ -3015,9 +2994,7 @@ def _geodesic_seeded_on_device(fn, labels, n_labels, seeds, cost=None, field=Non
     device = labels.device
     lib = _native.lib()
     dims3 = _native.int3(dims)
-    need = lib.exaspim_geodesic_workspace_bytes(dims3)
-    if need == 0:
-        raise ValueError(_native.last_error())
+    need = _workspace_bytes("exaspim_geodesic_workspace_bytes", dims3)
     cost_ptr = None if cost is None else cost.data_ptr()
     n_seeds = int(seeds.numel())
     with torch.cuda.device(device):
@@ -3038,27 +3015,20 @@ def _geodesic_seeded_on_device(fn, labels, n_labels, seeds, cost=None, field=Non
                                         stream),
             "exaspim_geodesic_reseed",
         )
-        flagged, invalid = (int(v) for v in state.cpu())   # the first read of the state
-        if invalid:
-            raise ValueError(f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} (a seed must be the "
-                             "linear index of a voxel whose label is in 1..K)")
-        sweeps, reads, history = 0, 1, [flagged]
-        while flagged:
-            if max_sweeps is not None and sweeps >= max_sweeps:
-                raise RuntimeError(f"{fn}: not converged after {sweeps} sweeps (max_sweeps={max_sweeps}), "
-                                   f"{flagged} tile(s) still flagged")
-            batch = sweeps_per_read if max_sweeps is None else min(sweeps_per_read, max_sweeps - sweeps)
+
+        def sweeps(batch):
             _native.check(
                 lib.exaspim_geodesic_sweeps(labels.data_ptr(), cost_ptr, dims3, n_labels, field.data_ptr(), batch,
                                             state.data_ptr(), workspace.data_ptr(), need, stream),
                 "exaspim_geodesic_sweeps",
             )
-            sweeps += batch
-            flagged = int(state.cpu()[0])
-            reads += 1
-            history.append(flagged)
+
+        swept = _swept_until_settled(
+            sweeps, state, sweeps_per_read, max_sweeps, fn,
+            lambda invalid: f"{fn}: {invalid} seed(s) name no voxel of a label in 1..{n_labels} (a seed must be the "
+                            "linear index of a voxel whose label is in 1..K)")
         if stats is not None:
-            stats.update(sweeps=sweeps, reads=reads, tiles_flagged=history)
+            stats.update(swept)
     return field
 
 
@@ -3218,10 +3188,7 @@ def geodesic_parents_seeded(labels, seeds, field, *, cost=None, n_labels=None, s
     parents, hops = _geodesic_parents_on_device(
         labels, None, field, cost, int(sweeps_per_read), None if max_sweeps is None else int(max_sweeps), stats,
         seeds=seeds, n_labels=k, fn=fn)
-    with torch.cuda.device(labels.device):
-        out = (parents, hops) if return_hops else (parents,)
-        if not return_device_tensors:
-            out = tuple(t.cpu().numpy() for t in out)
+    out = _downloaded((parents, hops) if return_hops else (parents,), labels.device, return_device_tensors)
     return out if return_hops else out[0]
 
 
@@ -3344,33 +3311,8 @@ def teasar_branches_fix_branching(labels, sources, dbf, daf, cost, *, scale, con
     TypeError, ValueError, RuntimeError
         As teasar_branches, geodesic_field and geodesic_parents.
     """
-    return _teasar_branches_fix_branching("teasar_branches_fix_branching", labels, sources, dbf, daf, cost, scale,
-                                          const, field, parents, hops, boxes, n_labels, max_paths,
-                                          return_device_tensors, stats, None)
-
-
-def _teasar_branches_fix_branching(fn, labels, sources, dbf, daf, cost, scale, const, field, parents, hops, boxes,
-                                   n_labels, max_paths, return_device_tensors, stats, targets_before):
-    """teasar_branches_fix_branching and its _given form: the arguments checked, the loop, the results downloaded."""
-    _pre_check_targets_before(fn, targets_before)
-    checked = _checked_teasar_arguments(fn, labels, sources, dbf, daf, parents, hops, boxes, scale, const, n_labels,
-                                        max_paths, fields=(cost, field))
-    labels, dims, sources, dbf, daf, parents, hops, boxes, scale, const, cost, field = checked
-    targets_before = _checked_targets_before(fn, targets_before, labels.device)
-    if boxes is None:
-        boxes = segment_table(labels, n_labels=int(sources.numel()) - 1, return_device_tensors=True)[1]
-    if field is None:
-        field, _, _ = _geodesic_on_device(labels, sources, cost)
-    if parents is None or hops is None:
-        parents, hops = _geodesic_parents_on_device(labels, sources, field, cost)
-    out = _fix_branching_on_device(labels, sources, dbf, daf, cost, field, parents, hops, boxes, scale, const,
-                                   None if max_paths is None else int(max_paths), stats,
-                                   targets_before=targets_before, fn=fn)
-    out = out[:2] + out[3:]
-    if not return_device_tensors:
-        with torch.cuda.device(labels.device):
-            out = tuple(t.cpu().numpy() for t in out)
-    return out
+    return _teasar_branches("teasar_branches_fix_branching", labels, sources, dbf, daf, parents, hops, scale, const,
+                            boxes, n_labels, max_paths, return_device_tensors, stats, None, (cost, field))
 
 
 def teasar_branches_fix_branching_given(labels, sources, dbf, daf, cost, targets_before, *, scale, const, field=None,
@@ -3415,9 +3357,9 @@ def teasar_branches_fix_branching_given(labels, sources, dbf, daf, cost, targets
     TypeError, ValueError, RuntimeError
         As teasar_branches_fix_branching and teasar_branches_given.
     """
-    return _teasar_branches_fix_branching("teasar_branches_fix_branching_given", labels, sources, dbf, daf, cost, scale,
-                                          const, field, parents, hops, boxes, n_labels, max_paths,
-                                          return_device_tensors, stats, targets_before)
+    return _teasar_branches("teasar_branches_fix_branching_given", labels, sources, dbf, daf, parents, hops, scale,
+                            const, boxes, n_labels, max_paths, return_device_tensors, stats, targets_before,
+                            (cost, field))
 
 
 def skeletonize(segmentation, *, fix_branching=True, scale=1.25, const=450.0, pdrf_exponent=4, pdrf_scale=100000.0,
@@ -3598,8 +3540,9 @@ def skeletonize_pieces(segmentation, *, dust_threshold=1000, fix_borders=True, f
     if not isinstance(fix_branching, (bool, np.bool_)):
         raise TypeError(f"skeletonize_pieces: fix_branching must be a bool, got {type(fix_branching).__name__}")
     dust_threshold = _checked_pieces_scalars("skeletonize_pieces", None, dust_threshold)
-    return _skeletons_of_labels("skeletonize_pieces", segmentation, scale, const, pdrf_exponent, pdrf_scale,
-                                fill_holes, max_paths, bool(fix_branching), fix_borders, pieces_dust=dust_threshold)
+    _checked_chain_scalars("skeletonize_pieces", scale, const, pdrf_exponent, pdrf_scale, max_paths, fix_borders)
+    return _skeletons_of_pieces("skeletonize_pieces", segmentation, scale, const, pdrf_exponent, pdrf_scale,
+                                fill_holes, max_paths, bool(fix_branching), fix_borders, dust_threshold)
 
 
 def skeletons_to_zipped_swcs(skeleton_dict, zip_path):
@@ -3816,9 +3759,7 @@ class ComponentsStream:
             raise ValueError(f"empty slab {dims}")
         slab = slab.contiguous()
         lib = _native.lib()
-        need = lib.exaspim_components_stream_slab_workspace_bytes(_native.int3(dims))
-        if need == 0:
-            raise ValueError(_native.last_error())
+        need = _workspace_bytes("exaspim_components_stream_slab_workspace_bytes", _native.int3(dims))
         with torch.cuda.device(self.device):
             if out is None:
                 out = torch.empty(dims, dtype=torch.int32, device=self.device)
@@ -4189,9 +4130,7 @@ class RegionGraphStream:
         table = table.contiguous()
         capacity = self.edge_capacity
         lib = _native.lib()
-        need = lib.exaspim_region_graph_stream_finish_workspace_bytes(capacity)
-        if need == 0:
-            raise ValueError(_native.last_error())
+        need = _workspace_bytes("exaspim_region_graph_stream_finish_workspace_bytes", capacity)
         with torch.cuda.device(self.device):
             edges = torch.empty((capacity, 2), dtype=torch.int32, device=self.device)
             counts = torch.empty(capacity, dtype=torch.int64, device=self.device)

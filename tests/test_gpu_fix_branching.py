@@ -256,6 +256,25 @@ def test_the_python_layer_is_incremental_on_a_copy(dev):
                                           cost=(cost * np.float32(2)).astype(np.float32))
 
 
+def test_max_sweeps_cuts_the_seeded_sweep_loop(dev):
+    """The serpentine of test_gpu_geodesic.py: eight rows, one after another, so the two tiles take turns."""
+    labels = ref.serpentine()
+    assert labels.shape == (16, 16, 64)
+    seeds = np.array([3 * 16 * 64], dtype=np.int32)      # (3, 0, 0), the source there
+    stats = {}
+    want = inference.geodesic_field_seeded(labels, seeds, n_labels=1, sweeps_per_read=1, stats=stats)
+    print(f"seeded serpentine: {stats}")
+    assert stats["sweeps"] > 3 and stats["sweeps"] == stats["reads"] - 1 and stats["tiles_flagged"][-1] == 0
+    with pytest.raises(RuntimeError, match=r"^geodesic_field_seeded: not converged after 3 sweeps"):
+        inference.geodesic_field_seeded(labels, seeds, n_labels=1, sweeps_per_read=2, max_sweeps=3)
+    clipped = {}
+    got = inference.geodesic_field_seeded(labels, seeds, n_labels=1, sweeps_per_read=7, max_sweeps=stats["sweeps"],
+                                          stats=clipped)
+    assert clipped["sweeps"] == stats["sweeps"] and clipped["tiles_flagged"][-1] == 0      # 7, 7, ... and the rest
+    assert clipped["reads"] == 1 + -(-stats["sweeps"] // 7)
+    np.testing.assert_array_equal(ref.bits(got), ref.bits(want))
+
+
 # ---- 3. seeded hops and parents ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["euclid", "cost"])
 @pytest.mark.parametrize("shape", [SMALL, BIG], ids=["small", "big"])
