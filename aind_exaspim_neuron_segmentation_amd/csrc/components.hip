@@ -32,6 +32,8 @@
 // Enclosed cavities (exaspim_fill_holes) are the components of a labelled volume's background:
 // edge_mask_background writes the mask byte from the labels, passes (b) to (d) run on it as they are into
 // a parent array in the workspace, and survey_faces, survey and fill decide per cavity and write the labels.
+#include <algorithm>
+
 #include "label_scan.h"
 
 namespace exaspim {
@@ -856,6 +858,83 @@ __global__ __launch_bounds__(kThreads) void pieces_relabel(const int* __restrict
     if (lane == 0 && dust) atomicAdd(dust_count, dust);
 }
 
+// ---- pieces with open faces (exaspim_label_pieces_open) ---------------------------------------
+// A piece with a voxel on an open face goes on in the block next door: its size here says nothing, so it is
+// kept whatever its count. The passes are exaspim_label_pieces' with one more after pieces_sizes:
+//   pieces_mark_open   one thread per pixel of the open faces: count[root] |= kOpenMark;
+//   scan_*             OpenPieceRoot: foreground roots that are marked or of at least dust voxels.
+// A count is at most 2^31 - 1, so the sign bit is free (kSeamMark of the streamed slabs is the precedent).
+constexpr int kOpenMark = (int)0x80000000;
+constexpr unsigned kOpenGrid = 2048;   // a few workgroups per CU that stride over the pixels, as border.hip's
+
+// The pixels of the open faces, packed plane after plane in the order of border.hip: z = 0, z = D - 1 (H x W
+// each), y = 0, y = H - 1 (D x W), x = 0, x = W - 1 (D x H). first[f] is face f's first packed pixel, first[6]
+// the total; a closed face is empty: first[f + 1] == first[f].
+struct OpenPlanes {
+    long long first[7];
+};
+
+OpenPlanes open_planes_of(const Dims& dm, uint32_t open_faces) {
+    const long long size[3] = {(long long)dm.h * dm.w, (long long)dm.d * dm.w, (long long)dm.d * dm.h};
+    OpenPlanes op;
+    op.first[0] = 0;
+    for (int f = 0; f < 6; ++f) op.first[f + 1] = op.first[f] + ((open_faces >> f) & 1u ? size[f >> 1] : 0);
+    return op;
+}
+
+// Every thread of a face that is one piece aims at one word: the word is read first and the atomic issued only
+// where the mark is not there yet (DESIGN 6q on hot words). The plain read may be stale, which costs one more
+// atomicOr of a bit that is already set. Nobody else writes count during this launch, and parent is final.
+__global__ __launch_bounds__(kThreads) void pieces_mark_open(const int* __restrict__ labels,
+                                                            const int* __restrict__ parent, int* count, Dims dm,
+                                                            int n_labels, OpenPlanes op) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)op.first[6]; i += stride) {
+        int face = 0;
+        long long first = 0;
+#pragma unroll
+        for (int f = 1; f < 6; ++f) {   // the last face that starts at or before i: it is not empty
+            if ((long long)i >= op.first[f]) face = f, first = op.first[f];
+        }
+        const int local = (int)((long long)i - first);   // below the plane's pixels <= d h w
+        int z, y, x;
+        if (face < 2) {
+            y = local / dm.w, x = local - y * dm.w, z = face == 0 ? 0 : dm.d - 1;
+        } else if (face < 4) {
+            z = local / dm.w, x = local - z * dm.w, y = face == 2 ? 0 : dm.h - 1;
+        } else {
+            z = local / dm.h, y = local - z * dm.h, x = face == 4 ? 0 : dm.w - 1;
+        }
+        const size_t v = ((size_t)z * dm.h + y) * dm.w + x;
+        if (piece_label(labels[v], n_labels) == 0) continue;
+        int* word = count + parent[v];
+        if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) atomicOr(word, kOpenMark);
+    }
+}
+
+// kept pieces of a block: foreground roots that are marked open or of at least dust voxels. small counts the
+// marked ones below dust: one add per such piece, by the thread that numbers it.
+struct OpenPieceRoot {
+    const int* parent;
+    const int* labels;
+    int* aux;
+    int* small;
+    int n_labels;
+    long long dust;
+    __device__ __forceinline__ bool operator()(size_t v) const {
+        if (parent[v] != (int)v || piece_label(labels[v], n_labels) == 0) return false;
+        const int c = aux[v];
+        return c < 0 || (long long)c >= dust;
+    }
+    __device__ __forceinline__ void operator()(size_t v, bool flag, int rank) const {
+        if (flag) {
+            const int c = aux[v];
+            if (c < 0 && (long long)(c & ~kOpenMark) < dust) atomicAdd(small, 1);
+        }
+        aux[v] = flag ? rank + 1 : 0;
+    }
+};
+
 // ---- streamed slabs -----------------------------------------------------------------
 // state words on the device
 constexpr int kIdsUsed = 0, kOverflow = 1, kSegments = 2, kSlabIds = 3;
@@ -1304,6 +1383,66 @@ extern "C" int exaspim_label_pieces(const int32_t* labels_dev, const int32_t dim
     pieces_sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
     const unsigned scan_grid = (unsigned)l.n_scan_blocks;
     const PieceRoot kept{parent, labels_dev, aux, n_labels, (long long)dust_threshold};
+    scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, state_dev);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
+    pieces_relabel<<<grid, kThreads, 0, s>>>(labels_dev, parent, aux, state_dev + 1, n_labels, dm.n);
+    EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+extern "C" size_t exaspim_label_pieces_open_workspace_bytes(const int32_t dims[3]) {
+    Dims dm;
+    if (!valid_dims(dims, &dm)) {
+        set_error("label_pieces_open_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return pieces_layout_of(dm).bytes;
+}
+
+extern "C" int exaspim_label_pieces_open(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                                         int64_t dust_threshold, uint32_t open_faces, int32_t* pieces_dev,
+                                         int32_t* state_dev, void* workspace_dev, size_t workspace_bytes,
+                                         void* stream) {
+    EXA_CHECK_ARG(labels_dev && dims && pieces_dev && state_dev && workspace_dev, "label_pieces_open: NULL argument");
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(dims, &dm),
+                  "label_pieces_open: dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(n_labels >= 0, "label_pieces_open: n_labels must not be negative, got %d", n_labels);
+    EXA_CHECK_ARG(dust_threshold >= 0, "label_pieces_open: dust_threshold must not be negative, got %lld",
+                  (long long)dust_threshold);
+    EXA_CHECK_ARG(open_faces < 64u, "label_pieces_open: open_faces has six bits, got %u", open_faces);
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 &&
+                      (((uintptr_t)labels_dev | (uintptr_t)pieces_dev | (uintptr_t)state_dev) & 3) == 0,
+                  "label_pieces_open: misaligned buffer");
+    EXA_CHECK_ARG(pieces_dev != labels_dev, "label_pieces_open: pieces_dev must not be labels_dev");
+    const PiecesLayout l = pieces_layout_of(dm);
+    if (workspace_bytes < l.bytes) {
+        set_error("label_pieces_open: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+        return EXASPIM_E_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace_dev);
+    int* aux = reinterpret_cast<int*>(ws + l.aux_off);
+    int* sums = reinterpret_cast<int*>(ws + l.sums_off);
+    int* parent = pieces_dev;
+    EXA_CHECK_HIP(hipMemsetAsync(aux, 0, (size_t)dm.n * 4, s));
+    EXA_CHECK_HIP(hipMemsetAsync(state_dev, 0, 3 * sizeof(int32_t), s));
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    pieces_tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(labels_dev, parent, aux, dm, n_labels,
+                                                                          tiles_x, tiles_y, n_tiles);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads);
+    pieces_seam_merge<<<grid, kThreads, 0, s>>>(labels_dev, parent, dm, n_labels);
+    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+    pieces_sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    if (open_faces) {
+        const OpenPlanes op = open_planes_of(dm, open_faces);
+        const unsigned open_grid = std::min(capped_grid((size_t)op.first[6], kThreads), kOpenGrid);
+        pieces_mark_open<<<open_grid, kThreads, 0, s>>>(labels_dev, parent, aux, dm, n_labels, op);
+    }
+    const unsigned scan_grid = (unsigned)l.n_scan_blocks;
+    const OpenPieceRoot kept{parent, labels_dev, aux, state_dev + 2, n_labels, (long long)dust_threshold};
     scan_count<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);
     scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.n_scan_blocks, state_dev);
     scan_assign<<<scan_grid, kThreads, 0, s>>>(kept, sums, (size_t)dm.n);

@@ -53,7 +53,8 @@ from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (
     _AgglomerationLabeller, _border_targets_on_device, _ComponentsLabeller, _components_on_device,
     _contract_dominant_on_device,
     _default_edge_capacity, _device_merged_table, _fill_holes_on_device, _fix_branching_on_device,
-    _geodesic_on_device, _geodesic_parents_on_device, _geodesic_seeded_on_device, _label_pieces_on_device, _LabelSink,
+    _geodesic_on_device, _geodesic_parents_on_device, _geodesic_seeded_on_device, _label_pieces_on_device,
+    _label_pieces_open_on_device, _LabelSink, join_block_skeletons, label_pieces_open, skeletonize_blocks,
     _last_threshold,
     _premerge_on_device, _premerged_table, _region_graph_device, _skeleton_chain_on_device, _teasar_on_device,
     _watershed_on_device, affinities_to_components, affinities_to_components_streaming, agglomerate,

@@ -3513,8 +3513,9 @@ def skeletonize_pieces(segmentation, *, dust_threshold=1000, fix_borders=True, f
     skeletons_to_zipped_swcs and voxelize_skeletons take forests as they are.
 
     What this is not: kimimaro or cc3d; equality with either is not claimed:
-    the definition of every stage is this project's own. Soma detection,
-    anisotropy and joining skeletons across blocks are not built.
+    the definition of every stage is this project's own. Soma detection
+    and anisotropy are not built; skeletonize_blocks is the form for a
+    volume in blocks, with the trees joined across the cuts.
     skeletonize, skeletonize_labels, skeletonize_fix_borders and
     segmentation_to_zipped_swcs keep the skeletons of earlier versions.
 
@@ -3543,6 +3544,500 @@ def skeletonize_pieces(segmentation, *, dust_threshold=1000, fix_borders=True, f
     _checked_chain_scalars("skeletonize_pieces", scale, const, pdrf_exponent, pdrf_scale, max_paths, fix_borders)
     return _skeletons_of_pieces("skeletonize_pieces", segmentation, scale, const, pdrf_exponent, pdrf_scale,
                                 fill_holes, max_paths, bool(fix_branching), fix_borders, dust_threshold)
+
+
+def _checked_open_faces(fn, open_faces):
+    """open_faces of label_pieces_open as the C call's mask: bit f for face f. Six bools, nothing else."""
+    if isinstance(open_faces, (str, bytes)) or not hasattr(open_faces, "__len__"):
+        raise TypeError(f"{fn}: open_faces must be a sequence of six bools, got {type(open_faces).__name__}")
+    faces = list(open_faces)
+    if len(faces) != 6:
+        raise ValueError(f"{fn}: open_faces must have six entries (z = 0, z = D - 1, y = 0, y = H - 1, x = 0, "
+                         f"x = W - 1), got {len(faces)}")
+    for face in faces:
+        if not isinstance(face, (bool, np.bool_)):
+            raise TypeError(f"{fn}: open_faces must be a sequence of six bools, got an entry of type "
+                            f"{type(face).__name__}")
+    return sum(1 << f for f, face in enumerate(faces) if face)
+
+
+def _label_pieces_open_on_device(labels, n_labels, open_mask, dust_threshold=0):
+    """
+    exaspim_label_pieces_open on a checked device tensor; open_mask is the
+    C call's: bit f for face f. Returns the int32 (D, H, W) volume of piece
+    numbers and the int32 (3,) state (kept pieces, dust pieces, pieces kept
+    although below the threshold), both left on the device: nothing is
+    synchronised.
+    """
+    dims = tuple(int(v) for v in labels.shape)
+    device = labels.device
+    lib = _native.lib()
+    dims3 = _native.int3(dims)
+    need = _workspace_bytes("exaspim_label_pieces_open_workspace_bytes", dims3)
+    with torch.cuda.device(device):
+        pieces = torch.empty(dims, dtype=torch.int32, device=device)
+        state = torch.empty(3, dtype=torch.int32, device=device)
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(
+            lib.exaspim_label_pieces_open(labels.data_ptr(), dims3, int(n_labels), int(dust_threshold), int(open_mask),
+                                          pieces.data_ptr(), state.data_ptr(), workspace.data_ptr(), need,
+                                          _stream(device)),
+            "exaspim_label_pieces_open",
+        )
+    return pieces, state
+
+
+def _face_planes(volume, mask):
+    """The planes of a (D, H, W) tensor or array that the faces of "mask" name, as views, in face order."""
+    planes = (volume[0], volume[-1], volume[:, 0], volume[:, -1], volume[:, :, 0], volume[:, :, -1])
+    return [plane for f, plane in enumerate(planes) if mask >> f & 1]
+
+
+def label_pieces_open(labels, open_faces, *, n_labels=None, dust_threshold=0, return_device_tensors=False):
+    """
+    label_pieces for one block of a larger volume: a piece that touches an
+    open face, a face behind which the volume goes on, is kept whatever its
+    size, on the device.
+
+    What this is: label_pieces' definition with one change. The faces are
+    border_targets': z = 0, z = D - 1, y = 0, y = H - 1, x = 0, x = W - 1. A
+    piece is open iff at least one of its voxels lies on a face whose entry
+    of open_faces is True (where a dimension is 1 and two faces coincide,
+    either entry opens the plane). A piece is kept iff it is open or size >=
+    dust_threshold: inside a block the size of a piece that is cut says
+    nothing about the whole piece, so the dust rule must not judge it;
+    skeletonize_blocks judges the whole piece after the join. Numbering and
+    everything else are label_pieces'; with no face open the first four
+    results are label_pieces' exactly. A pure function of the input.
+
+    What this is not: cc3d or kimimaro; equality with either is not claimed.
+
+    Parameters
+    ----------
+    labels, n_labels, dust_threshold, return_device_tensors
+        As in label_pieces.
+    open_faces : sequence of six bools
+        In the face order above.
+
+    Returns
+    -------
+    pieces, piece_label, piece_size, piece_first
+        As label_pieces.
+    piece_open : numpy.ndarray or torch.Tensor
+        bool (P,): whether piece i + 1 has a voxel on an open face.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As label_pieces; TypeError if open_faces is not a sequence of bools,
+        ValueError if it has not six entries.
+    """
+    dust_threshold = _checked_pieces_scalars("label_pieces_open", n_labels, dust_threshold)
+    mask = _checked_open_faces("label_pieces_open", open_faces)
+    labels, _ = _checked_labels(labels, "label_pieces_open")
+    with torch.cuda.device(labels.device):
+        if n_labels is None:
+            n_labels = max(int(labels.max()), 0)
+        pieces, state = _label_pieces_open_on_device(labels, int(n_labels), mask, dust_threshold)
+        n_pieces, piece_label, piece_size, piece_first = _piece_tables_on_device(labels, pieces, state)
+        touched = torch.zeros(n_pieces + 1, dtype=torch.bool, device=labels.device)
+        for plane in _face_planes(pieces, mask):
+            touched[plane.reshape(-1).to(torch.int64)] = True
+        piece_open = touched[1:].contiguous()
+    return _downloaded((pieces, piece_label, piece_size, piece_first, piece_open), labels.device,
+                       return_device_tensors)
+
+
+def _block_spans(n, b):
+    """The blocks of skeletonize_blocks along an axis of n voxels with block length b: (start, end) pairs."""
+    spans, start = [], 0
+    while not spans or start < n - 1:
+        spans.append((start, min(start + b, n)))
+        start += b - 1
+    return spans
+
+
+_TREE_KEYS = ("block", "piece", "label", "owned_size", "vertices", "parent", "radius", "border_rows")
+
+
+def _checked_tree_records(trees):
+    """join_block_skeletons' records, checked and sorted by (block, piece)."""
+    fn = "join_block_skeletons"
+    if not isinstance(trees, (list, tuple)):
+        raise TypeError(f"{fn}: trees must be a list of records, got {type(trees).__name__}")
+    out = []
+    for i, tree in enumerate(trees):
+        if not isinstance(tree, dict):
+            raise TypeError(f"{fn}: record {i} must be a dict, got {type(tree).__name__}")
+        missing = [k for k in _TREE_KEYS if k not in tree]
+        if missing:
+            raise ValueError(f"{fn}: record {i} lacks {', '.join(missing)}")
+        for k in ("block", "piece", "label", "owned_size"):
+            _checked_integer(fn, f"record {i}'s {k}", tree[k], least=1 if k == "piece" else 0)
+        vertices, parent, radius, rows = (np.asarray(tree[k]) for k in ("vertices", "parent", "radius", "border_rows"))
+        n = len(parent)
+        if vertices.ndim != 2 or vertices.shape != (n, 3) or parent.ndim != 1 or radius.shape != (n,) or n == 0:
+            raise ValueError(f"{fn}: record {i} must have vertices (n, 3), parent (n,) and radius (n,) with n >= 1")
+        if vertices.dtype.kind not in "iu" or parent.dtype.kind not in "iu" or rows.dtype.kind not in "iub":
+            raise TypeError(f"{fn}: record {i}'s vertices, parent and border_rows must be integers")
+        if vertices.min() < 0:
+            raise ValueError(f"{fn}: record {i} has a negative coordinate")
+        if np.count_nonzero(parent == -1) != 1 or parent.min() < -1 or parent.max() >= n:
+            raise ValueError(f"{fn}: record {i}'s parent must hold one -1 and otherwise rows of the record")
+        rows = rows.astype(np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n or len(np.unique(rows)) != len(rows)):
+            raise ValueError(f"{fn}: record {i}'s border_rows must be distinct rows of the record")
+        out.append(dict(block=int(tree["block"]), piece=int(tree["piece"]), label=int(tree["label"]),
+                        owned_size=int(tree["owned_size"]), vertices=vertices.astype(np.int64),
+                        parent=parent.astype(np.int64), radius=radius.astype(np.float32), border_rows=rows))
+    out.sort(key=lambda t: (t["block"], t["piece"]))
+    for a, b in zip(out, out[1:]):
+        if (a["block"], a["piece"]) == (b["block"], b["piece"]):
+            raise ValueError(f"{fn}: two records for piece {a['piece']} of block {a['block']}")
+    return out
+
+
+def join_block_skeletons(trees, dust_threshold=0, stats=None):
+    """
+    The trees of skeletonize_blocks' blocks joined at the cuts, on the host:
+    every label's forest for the whole volume.
+
+    What this is, exactly. A record is a dict with "block" (the block's
+    number in block order), "piece" (its number in the block), "label",
+    "owned_size" (the piece's voxels that this block owns), "vertices"
+    (n, 3) in global (z, y, x), "parent" (n,) with one -1, "radius" (n,) and
+    "border_rows", the rows that are border targets in their own block. The
+    order of the list does not matter: trees are taken in ascending (block,
+    piece). A joint is a global voxel at which two or more trees of one label
+    have a border-target vertex. Joints are taken in ascending (z, y, x),
+    which is ascending linear index; within a joint the first tree is the
+    anchor and every other tree is united with it (union-find), its vertex
+    there identified with the anchor's, the radius the smaller of the two:
+    each block's field saw only its own side, so each is an upper bound. A
+    tree that is already in the anchor's component is skipped: both vertices
+    stay and the skip is counted, because the output is a forest and cannot
+    hold the ring. A component's root is the root of its first tree, its
+    parents are re-oriented from there, its rows are its trees' rows in
+    order, an identified vertex at its first occurrence. A component whose
+    trees' owned sizes sum to less than dust_threshold is dropped. A
+    label's entry is its components in order of first tree, one -1 each.
+
+    What this is not: igneous' or kimimaro's merge; equality with either is
+    not claimed. The duplicate vertex of a skipped joint is not removed.
+
+    Parameters
+    ----------
+    trees : list of dict
+        The records.
+    dust_threshold : int, optional
+        Default is 0.
+    stats : dict, optional
+        Receives "trees", "joints", "skipped_joints", "dust_components" and
+        "join_seconds".
+
+    Returns
+    -------
+    dict
+        label -> (vertices int32 (n, 3), parent int32 (n,), radius float32
+        (n,)), what skeleton_to_swc, skeletons_to_zipped_swcs and
+        voxelize_skeletons take.
+
+    Raises
+    ------
+    TypeError, ValueError
+        For records that are not as described, a dust_threshold that is no
+        integer >= 0, or stats that is not a dict.
+    """
+    fn = "join_block_skeletons"
+    started = time.perf_counter()
+    _checked_integer(fn, "dust_threshold", dust_threshold, least=0)
+    if stats is not None and not isinstance(stats, dict):
+        raise TypeError(f"{fn}: stats must be a dict, got {type(stats).__name__}")
+    trees = _checked_tree_records(trees)
+    counts = np.array([len(t["parent"]) for t in trees], dtype=np.int64)
+    first_node = np.concatenate([[0], np.cumsum(counts)])
+    n_nodes = int(first_node[-1])
+    tree_of = np.repeat(np.arange(len(trees)), counts)
+    vertices = np.concatenate([t["vertices"] for t in trees]) if trees else np.zeros((0, 3), np.int64)
+    radius = np.concatenate([t["radius"] for t in trees]) if trees else np.zeros(0, np.float32)
+    parent = np.concatenate([np.where(t["parent"] >= 0, t["parent"] + s, -1)
+                             for t, s in zip(trees, first_node)]) if trees else np.zeros(0, np.int64)
+    label = np.array([t["label"] for t in trees], dtype=np.int64)
+
+    # the joints: border-target vertices of one label at one voxel, in ascending (label, voxel, tree)
+    at = np.concatenate([t["border_rows"] + s for t, s in zip(trees, first_node)]) if trees else np.zeros(0, np.int64)
+    at = at[np.lexsort((at, vertices[at, 2], vertices[at, 1], vertices[at, 0], label[tree_of[at]]))]
+    key = np.column_stack([label[tree_of[at]], vertices[at]])
+    new = np.ones(len(at), dtype=bool)
+    new[1:] = (key[1:] != key[:-1]).any(axis=1)
+    groups = np.split(at, np.nonzero(new)[0][1:]) if len(at) else []
+    joints = [g for g in groups if tree_of[g[0]] != tree_of[g[-1]]]      # sorted by tree: two trees at least
+    # label by label, ascending voxel within each: no tree has two labels, so this is the order of ascending voxel
+    leader = list(range(len(trees)))
+
+    def find(t):
+        while leader[t] != t:
+            leader[t] = leader[leader[t]]
+            t = leader[t]
+        return t
+
+    same = np.arange(n_nodes)
+    skipped = 0
+    for group in joints:
+        anchor = int(group[0])
+        for node in group[1:]:
+            a, b = find(int(tree_of[anchor])), find(int(tree_of[node]))
+            if a == b:
+                skipped += 1
+                continue
+            leader[max(a, b)] = min(a, b)      # the leader is the component's first tree
+            same[node] = anchor
+            radius[anchor] = min(radius[anchor], radius[node])
+    component = np.array([find(t) for t in range(len(trees))], dtype=np.int64)
+    owned = np.zeros(len(trees), dtype=object)
+    for t, c in enumerate(component):
+        owned[c] += trees[t]["owned_size"]
+
+    # parents re-oriented from every component's root at once: a breadth-first search over the forest
+    kept = same == np.arange(n_nodes)
+    child = np.nonzero(parent >= 0)[0]
+    ends = np.stack([same[child], same[parent[child]]])
+    ends = np.concatenate([ends, ends[::-1]], axis=1)
+    order = np.argsort(ends[0], kind="stable")
+    source, target = ends[0][order], ends[1][order]
+    begin = np.searchsorted(source, np.arange(n_nodes + 1))
+    leaders = component == np.arange(len(trees))      # a component's first tree: its root is the component's
+    roots = np.nonzero(parent == -1)[0][leaders]      # one -1 per tree, in tree order
+    towards = np.full(n_nodes, -2, dtype=np.int64)
+    towards[roots] = -1
+    front = roots
+    while len(front):
+        lengths = begin[front + 1] - begin[front]
+        edge = np.repeat(begin[front] - np.concatenate([[0], np.cumsum(lengths)[:-1]]), lengths) + np.arange(
+            int(lengths.sum()))
+        here, there = np.repeat(front, lengths), target[edge]
+        fresh = towards[there] == -2
+        towards[there[fresh]] = here[fresh]
+        front = there[fresh]
+    if (towards[kept] == -2).any():
+        raise RuntimeError(f"{fn}: a vertex is not connected to its component's root")
+
+    # rows: by label in order of first surviving tree, by component in order of first tree, then as they come
+    alive = np.array([owned[c] >= dust_threshold for c in component], dtype=bool)
+    rows = np.nonzero(kept & alive[tree_of])[0] if n_nodes else np.zeros(0, np.int64)
+    rows = rows[np.argsort(component[tree_of[rows]], kind="stable")]
+    out = {}
+    for t in np.nonzero(alive & leaders)[0]:
+        out.setdefault(int(label[t]), None)
+    position = np.full(n_nodes, -1, dtype=np.int64)
+    row_label = label[tree_of[rows]]
+    for value in out:
+        mine = rows[row_label == value]
+        position[mine] = np.arange(len(mine))
+        up = towards[mine]
+        out[value] = (vertices[mine].astype(np.int32),
+                      np.where(up >= 0, position[np.maximum(up, 0)], -1).astype(np.int32), radius[mine])
+    if stats is not None:
+        stats.update(trees=len(trees), joints=len(joints), skipped_joints=skipped,
+                     dust_components=int(np.count_nonzero(leaders & ~alive)),
+                     join_seconds=time.perf_counter() - started)
+    return out
+
+
+def _checked_block_source(fn, segmentation, block_shape, device):
+    """
+    skeletonize_blocks' segmentation, block_shape and device, before any
+    device is asked for: ((D, H, W), block_shape, device, read), where
+    read(z0, z1, y0, y1, x0, x1) gives that block as a contiguous int32
+    device tensor and reads nothing else of the segmentation.
+    """
+    on_device = isinstance(segmentation, torch.Tensor)
+    if not on_device and not (hasattr(segmentation, "shape") and hasattr(segmentation, "dtype")
+                              and hasattr(segmentation, "__getitem__")):
+        raise TypeError(f"{fn}: segmentation must be a torch tensor, a numpy array or an object with shape, dtype and "
+                        f"three-slice indexing, got {type(segmentation).__name__}")
+    if segmentation.dtype != (torch.int32 if on_device else np.int32):
+        raise TypeError(f"segmentation must be int32, got {segmentation.dtype}")
+    shape = tuple(int(v) for v in segmentation.shape)
+    if len(shape) != 3:
+        raise ValueError(f"{fn}: segmentation must be (D, H, W), got {shape}")
+    if min(shape) < 1:
+        raise ValueError(f"{fn}: empty volume {shape}")
+    if isinstance(block_shape, (str, bytes)) or not hasattr(block_shape, "__len__") or len(block_shape) != 3:
+        raise ValueError(f"{fn}: block_shape must be three integers, got {block_shape!r}")
+    for b in block_shape:
+        _checked_integer(fn, "block_shape", b, least=2)
+    block_shape = tuple(int(b) for b in block_shape)
+    if int(np.prod([min(b, n) for b, n in zip(block_shape, shape)], dtype=object)) > 2**31 - 1:
+        raise ValueError(f"{fn}: a block of {block_shape} has more than 2^31 - 1 voxels")
+    if on_device:
+        if segmentation.device.type != "cuda":
+            raise RuntimeError(f"{fn} (MI355X) has no CPU path: segmentation must be on a HIP device, got "
+                               f"{segmentation.device}")
+        if device is not None and torch.device(device) != segmentation.device:
+            raise ValueError(f"{fn}: device {device} is not the segmentation's, {segmentation.device}")
+        device = segmentation.device
+    else:
+        device = _upload_device(fn) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"{fn} (MI355X) has no CPU path: device must be a HIP device, got {device}")
+
+    def read(z0, z1, y0, y1, x0, x1):
+        crop = segmentation[z0:z1, y0:y1, x0:x1]
+        if on_device:
+            return crop.contiguous()
+        crop = np.asarray(crop)
+        if crop.dtype != np.int32 or crop.shape != (z1 - z0, y1 - y0, x1 - x0):
+            raise TypeError(f"{fn}: segmentation[{z0}:{z1}, {y0}:{y1}, {x0}:{x1}] gave {crop.dtype} {crop.shape}")
+        return torch.from_numpy(np.ascontiguousarray(crop)).to(device)
+
+    return shape, block_shape, device, read
+
+
+def skeletonize_blocks(segmentation, block_shape=(512, 512, 512), *, dust_threshold=1000, fix_branching=True,
+                       scale=1.25, const=450.0, pdrf_exponent=4, pdrf_scale=100000.0, fill_holes=True,
+                       max_paths=None, device=None, stats=None):
+    """
+    skeletonize_pieces for a volume that does not fit the device in one
+    piece, or has more than 2^31 - 1 voxels: block by block, the trees joined
+    at the cuts. The reference's last step (inference.py:240-291)
+    for the volumes predict_streaming and agglomerate_affinities_streaming
+    were built for.
+
+    What this is. Along an axis of n voxels with block length b, block i
+    starts at i (b - 1), for i = 0, 1, ... while the start is below n - 1
+    (one block for n = 1), and ends at min(start + b, n): adjacent blocks
+    share exactly one plane and every block has at least two. A block's low
+    face is open iff it is not the first, its high face iff it is not the
+    last. Blocks run in raster order of (iz, iy, ix), the block order. Per
+    block: the crop is uploaded; fill_holes, if asked, runs on the block, so a
+    cavity that a cut opens is not filled (fill_holes never changes a voxel
+    of a face, so both sides of a cut keep seeing the same plane); a block
+    without a positive label is skipped; label_pieces_open with the block's
+    open faces and dust_threshold; each piece's owned size, its voxels
+    outside the block's open high planes, so that every voxel of the volume
+    is owned by exactly one block; skeletonize_pieces' chain with
+    fix_borders=True on the pieces. Every tree goes to the host with its
+    vertices in global coordinates and its border-target rows, and nothing
+    of a block stays on the device. join_block_skeletons then joins the
+    trees where both sides of a cut ended a branch at the same voxel, and
+    drops the components whose owned sizes sum to less than dust_threshold:
+    the dust rule judges the whole piece, not what one block sees of it.
+
+    What holds (DESIGN 6r has the proofs): with one block the result is
+    skeletonize_pieces(fix_borders=True) array for array; with
+    max_paths=None every cut cross-section's centre is a vertex on both
+    sides; with fill_holes=False as well, the components are exactly the
+    26-connected pieces of the whole volume and the dust decisions are
+    label_pieces' on the whole volume; every child and parent are
+    26-adjacent and every vertex lies in its label.
+
+    What this is not: the skeleton of the undivided volume (fields and
+    invalidation see one block), kimimaro, or igneous' merge; equality with
+    any of them is not claimed. Soma mode, anisotropy, a sharded form, overlaps
+    of more than one plane and 64-bit labels are not built. A ring across a
+    cut keeps a duplicate vertex (a skipped joint).
+
+    Parameters
+    ----------
+    segmentation : numpy.ndarray, torch.Tensor or array-like
+        int32 (D, H, W): a numpy array; a memmap or zarr-like object with
+        shape, dtype and three-slice indexing, of which only
+        segmentation[z0:z1, y0:y1, x0:x1] is ever read; or a tensor on a HIP
+        device. D H W may exceed 2^31 - 1; a block may not.
+    block_shape : tuple of int, optional
+        Every entry at least 2. Default is (512, 512, 512).
+    dust_threshold : int, optional
+        Pieces of the whole volume with fewer voxels get no skeleton.
+        Default is 1000.
+    fix_branching, scale, const, pdrf_exponent, pdrf_scale, max_paths
+        As in skeletonize_pieces; max_paths counts per piece of a block.
+    fill_holes : bool, optional
+        Per block. Default is True.
+    device : torch.device, optional
+        Where blocks of a host volume are uploaded to. Default is cuda:0.
+    stats : dict, optional
+        Receives "blocks", "blocks_skipped" (no positive label, or nothing
+        but dust), "open_small_pieces" (pieces kept in their block although
+        below the threshold), "chain_seconds", and join_block_skeletons'
+        "trees", "joints", "skipped_joints", "dust_components" and
+        "join_seconds".
+
+    Returns
+    -------
+    dict
+        label -> (vertices, parent, radius), as skeletonize_pieces, the
+        vertices in the coordinates of the whole volume.
+
+    Raises
+    ------
+    TypeError, ValueError, RuntimeError
+        As skeletonize_pieces; TypeError for a segmentation that is not
+        int32 or has no shape, dtype and indexing, or stats that is not a
+        dict; ValueError for a block_shape that is not three integers >= 2 or
+        holds more than 2^31 - 1 voxels.
+    """
+    fn = "skeletonize_blocks"
+    if not isinstance(fix_branching, (bool, np.bool_)):
+        raise TypeError(f"{fn}: fix_branching must be a bool, got {type(fix_branching).__name__}")
+    if stats is not None and not isinstance(stats, dict):
+        raise TypeError(f"{fn}: stats must be a dict, got {type(stats).__name__}")
+    dust_threshold = _checked_pieces_scalars(fn, None, dust_threshold)
+    _checked_chain_scalars(fn, scale, const, pdrf_exponent, pdrf_scale, max_paths, True)
+    shape, block_shape, device, read = _checked_block_source(fn, segmentation, block_shape, device)
+    spans = [_block_spans(n, b) for n, b in zip(shape, block_shape)]
+    trees, blocks, skipped, open_small, chain_seconds = [], 0, 0, 0, 0.0
+    for iz, (z0, z1) in enumerate(spans[0]):
+        for iy, (y0, y1) in enumerate(spans[1]):
+            for ix, (x0, x1) in enumerate(spans[2]):
+                block, blocks = blocks, blocks + 1
+                faces = [iz > 0, iz < len(spans[0]) - 1, iy > 0, iy < len(spans[1]) - 1, ix > 0,
+                         ix < len(spans[2]) - 1]
+                mask = sum(1 << f for f, face in enumerate(faces) if face)
+                labels = read(z0, z1, y0, y1, x0, x1)
+                dims = tuple(int(v) for v in labels.shape)
+                with torch.cuda.device(device):
+                    if fill_holes:
+                        labels, _ = _fill_holes_on_device(labels)
+                    k = max(int(labels.max()), 0)
+                    if k == 0:
+                        skipped += 1
+                        continue
+                    pieces, state = _label_pieces_open_on_device(labels, k, mask, dust_threshold)
+                    n_pieces, piece_label, _, _ = _piece_tables_on_device(labels, pieces, state)
+                    open_small += int(state.cpu()[2])
+                    if n_pieces == 0:
+                        skipped += 1
+                        continue
+                    own = pieces.clone()
+                    for plane in _face_planes(own, mask & 0b101010):
+                        plane.zero_()
+                    owned = segment_table(own, n_labels=n_pieces, return_device_tensors=True)[0][1:].cpu().numpy()
+                    piece_label = piece_label.cpu().numpy()
+                    del own, labels
+                    started = time.perf_counter()
+                    chain = _skeleton_chain_on_device(pieces, float(scale), float(const), int(pdrf_exponent),
+                                                      float(pdrf_scale), False,
+                                                      None if max_paths is None else int(max_paths),
+                                                      bool(fix_branching), fix_borders=True)
+                    found = _chain_to_skeletons(fn, chain, dims)
+                    target_piece, target_voxel = (t.cpu().numpy() for t in chain["border_targets"])
+                    chain_seconds += time.perf_counter() - started
+                    del chain, pieces, state
+                for piece in sorted(found):
+                    vertices, parent, radius = found[piece]
+                    voxel = np.ravel_multi_index(tuple(vertices.T), dims)
+                    rows = np.nonzero(np.isin(voxel, target_voxel[target_piece == piece]))[0]
+                    trees.append(dict(block=block, piece=int(piece), label=int(piece_label[piece - 1]),
+                                      owned_size=int(owned[piece - 1]),
+                                      vertices=vertices + np.array([z0, y0, x0], dtype=np.int32), parent=parent,
+                                      radius=radius, border_rows=rows))
+    joined = {}
+    out = join_block_skeletons(trees, dust_threshold, joined)
+    if stats is not None:
+        stats.update(joined, blocks=blocks, blocks_skipped=skipped, open_small_pieces=open_small,
+                     chain_seconds=chain_seconds)
+    return out
 
 
 def skeletons_to_zipped_swcs(skeleton_dict, zip_path):

@@ -1470,6 +1470,38 @@ int exaspim_label_pieces(const int32_t* labels_dev, const int32_t dims[3], int32
                          int32_t* state_dev /* [2]: kept pieces P, dust pieces */, void* workspace_dev,
                          size_t workspace_bytes, void* stream);
 
+/* ---- pieces with open faces: the pieces of one block of a larger volume -----------------------
+ * A volume too large for one call is skeletonised block by block, adjacent blocks sharing one plane. Inside a
+ * block a piece that touches a shared plane goes on next door: its size here says nothing about the whole
+ * piece, so the dust rule must not judge it. The definition is the one of the section above with one change.
+ *
+ * Bit f of open_faces names face f in the order of the border targets: z = 0, z = D - 1, y = 0, y = H - 1,
+ * x = 0, x = W - 1. A piece is open iff at least one of its voxels lies on a face whose bit is set; where a
+ * dimension is 1 and two faces coincide, either bit opens the plane. A piece is kept iff it is open or
+ * size >= dust_threshold. Numbering (ascending order of first voxel) and the output volume are unchanged.
+ * With open_faces == 0 pieces_dev and state_dev[0..1] are those of the call above byte for byte and
+ * state_dev[2] is 0. The result is a pure function of the arguments.
+ *
+ * What this is not: a dust rule for the whole piece. Whoever joins the blocks sums what each block owns of a
+ * piece and judges the sum (skeletonize_blocks in segmentation.py does); equality with cc3d, kimimaro or
+ * igneous is not claimed. */
+
+/* Scratch bytes of the call below: those of the call above. 0 with the error text set for refused dims. */
+size_t exaspim_label_pieces_open_workspace_bytes(const int32_t dims[3]);
+
+/* pieces_dev[v] = the number of the kept piece of voxel v, or 0. state_dev[0] = P, the number of kept pieces;
+ * state_dev[1] = the number of dust pieces; state_dev[2] = the number of pieces kept although below the
+ * threshold. The launches of the call above on "stream", as they are, and one more after the sizes where
+ * open_faces is not 0: one thread per pixel of the open faces marks the sign bit of its root's count, which
+ * the prefix sum's predicate reads. Two memsets, nothing allocated, nothing synchronised.
+ * EXASPIM_E_INVALID for what the call above refuses, or an open_faces with a bit above bit 5;
+ * EXASPIM_E_WORKSPACE if workspace_bytes is too small: all before anything is launched, and no output is
+ * touched. */
+int exaspim_label_pieces_open(const int32_t* labels_dev, const int32_t dims[3], int32_t n_labels,
+                              int64_t dust_threshold, uint32_t open_faces, int32_t* pieces_dev,
+                              int32_t* state_dev /* [3] */, void* workspace_dev, size_t workspace_bytes,
+                              void* stream);
+
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 
 /* vol[z,y,x] = splitmix64(seed + global linear index) % 2000 as uint16. */
