@@ -91,6 +91,17 @@ class ComponentsStreamDesc(ctypes.Structure):
     ]
 
 
+class WatershedStreamDesc(ctypes.Structure):
+    """exaspim_watershed_stream: a components stream, the two thresholds and the carried plane of z affinities."""
+
+    _fields_ = [
+        ("base", ComponentsStreamDesc),
+        ("low", ctypes.c_float),
+        ("high", ctypes.c_float),
+        ("seam_aff_dev", ctypes.c_void_p),
+    ]
+
+
 class RegionGraphStreamDesc(ctypes.Structure):
     """exaspim_region_graph_stream: the caller-owned state of a slab-by-slab region graph."""
 
@@ -249,6 +260,9 @@ SIGNATURES = {
     "exaspim_watershed_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_watershed_fragments": (_i32, [_vp, _i32, _I32x3, ctypes.c_float, ctypes.c_float, ctypes.c_int64, _vp,
                                            _vp, _vp, _sz, _vp]),
+    "exaspim_watershed_stream_slab_workspace_bytes": (_sz, [_I32x3]),
+    "exaspim_watershed_stream_slab": (_i32, [ctypes.POINTER(WatershedStreamDesc), _vp, _i32, _I32x3, _i32, _vp,
+                                             _vp, _sz, _vp]),
     "exaspim_dbf_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_dbf": (_i32, [_vp, _I32x3, _i32, _vp, _vp, _sz, _vp]),
     "exaspim_segment_table_workspace_bytes": (_sz, [_i32]),

@@ -27,7 +27,10 @@
 //
 // Watershed fragments (exaspim_watershed_fragments) differ in pass (a) alone:
 // edge_mask_watershed writes the same mask byte from each voxel's steepest edge and its neighbours',
-// and passes (b) to (g) run on it as they are.
+// and passes (b) to (g) run on it as they are. Their streamed form (exaspim_watershed_stream_slab)
+// is the streamed components with edge_mask_watershed_slab as pass (a): it reads one carried plane of z
+// affinities below the slab, hands two bits per edge across the seam above it to the next slab, which
+// resolves them, and seam_affinity carries the plane on.
 //
 // Enclosed cavities (exaspim_fill_holes) are the components of a labelled volume's background:
 // edge_mask_background writes the mask byte from the labels, passes (b) to (d) run on it as they are into
@@ -258,6 +261,214 @@ __global__ __launch_bounds__(kThreads) void edge_mask_watershed(const T* __restr
         }
         __syncthreads();   // code is reused by the next tile
     }
+}
+
+// ---- (a'') watershed edge mask of a streamed slab (exaspim_watershed_stream_slab) -----------
+// edge_mask_watershed for planes [z0, z0 + d) of a volume. What differs is the two faces across z:
+//   below  carry_aff is the previous slab's last plane of z affinities as float32 (NULL for the volume's first
+//          slab): the -z edges of the slab's plane 0;
+//   above  unless the slab ends the volume (final), the z entries of its last plane are real edges and are
+//          offered as +z. Their bit in the mask stays clear, as in the streamed components: the edge is
+//          handed on as two bits per (y, x) in seam, bit 0 eligible, bit 1 sure (eligible and >= high or the
+//          steepest edge of its lower end).
+// carry_bits holds those two bits of the previous slab. Once a tile's codes are in LDS, one thread per (y, x) of
+// plane 0 turns them into the edge's final state in place: 1 iff sure, or eligible and that voxel's steepest
+// edge is -z. seam_mark and seam_union, later launches, read that byte. No other thread reads or writes it.
+struct SlabSeam {
+    const float* carry_aff;      // float32[h * w], NULL: the volume's first slab
+    unsigned char* carry_bits;   // uint8[h * w], resolved in place; NULL with carry_aff
+    unsigned char* seam;         // uint8[h * w], written; NULL: the volume's last slab (final)
+};
+
+// steepest_at for a slab: plane 0 takes -z from the carried plane, the last plane offers its real +z
+template <typename T>
+__device__ __forceinline__ unsigned steepest_at_slab(const T* __restrict__ aff, const Dims& dm, int z, int y, int x,
+                                                     float low, const float* __restrict__ carry_aff, bool final) {
+    const size_t n = (size_t)dm.n, hw = (size_t)dm.h * dm.w;
+    const size_t p = (size_t)y * dm.w + x, i = (size_t)z * hw + p;
+    float mz = low;
+    if (z > 0) mz = widen<T>(aff[i - hw]);
+    else if (carry_aff) mz = carry_aff[p];
+    const float my = y > 0 ? widen<T>(aff[n + i - dm.w]) : low;
+    const float mx = x > 0 ? widen<T>(aff[2 * n + i - 1]) : low;
+    const float px = x < dm.w - 1 ? widen<T>(aff[2 * n + i]) : low;
+    const float py = y < dm.h - 1 ? widen<T>(aff[n + i]) : low;
+    const float pz = (z < dm.d - 1 || !final) ? widen<T>(aff[i]) : low;
+    return steepest(mz, my, mx, px, py, pz, low);
+}
+
+// What a voxel knows of its three high edges travels with its code in the same LDS byte, where the sibling
+// holds six words of bits per round in registers across the barrier: the seam's work needs those registers,
+// and 64 of them are the eighth wave per SIMD. Per axis a state, 0 not eligible, 1 eligible, 2 sure (eligible
+// and (>= high or this voxel's steepest edge)); byte = code | (sz + 3 sy + 9 sx) << 3, at most 6 | 26 << 3.
+__device__ __forceinline__ unsigned pack_states(unsigned code, unsigned sz, unsigned sy, unsigned sx) {
+    return code | ((sz + 3u * sy + 9u * sx) << 3);
+}
+
+// the three states of a byte; s / 9 and r / 3 as multiply and shift, exact for s <= 26 and r <= 8
+__device__ __forceinline__ void unpack_states(unsigned byte, unsigned& sz, unsigned& sy, unsigned& sx) {
+    const unsigned s = byte >> 3;
+    sx = (s * 57u) >> 9;
+    const unsigned r = s - 9u * sx;
+    sy = (r * 11u) >> 5;
+    sz = r - 3u * sy;
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(kThreads) void edge_mask_watershed_slab(const T* __restrict__ aff,
+                                                                    unsigned char* __restrict__ mask, Dims dm,
+                                                                    float low, float high, int tiles_x, int tiles_y,
+                                                                    long long n_tiles, SlabSeam sm) {
+    struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
+    struct alignas(VEC) Bytes { unsigned char b[VEC]; };
+    struct alignas(16) Floats { float v[4]; };
+    constexpr int kGroupsPerRow = kTX / VEC;
+    constexpr int kRounds = kTileVox / (kThreads * VEC);
+    __shared__ __attribute__((aligned(16))) unsigned char code[kCodeBytes];
+    const size_t n = (size_t)dm.n, hw = (size_t)dm.h * dm.w;
+    const bool final = sm.seam == nullptr;
+    // the XCD tile order of edge_mask_watershed
+    const unsigned full = gridDim.x & ~7u;
+    const unsigned first = blockIdx.x < full ? (blockIdx.x & 7u) * (full >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    for (long long tile = first; tile < n_tiles; tile += gridDim.x) {
+        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y);
+        const int tz = (int)(tile / ((long long)tiles_x * tiles_y));
+        const int z0 = tz * kTZ, y0 = ty * kTY, x0 = tx * kTX;
+        // The thread's index, opaque to the compiler and taken again for every tile: what is derived from it
+        // (rows, LDS addresses, their constants) is otherwise hoisted out of this loop and held in registers
+        // through it; this way it is a few VALU instructions per tile.
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int j = t + kThreads * r;
+            const int row = j / kGroupsPerRow, lx = (j - row * kGroupsPerRow) * VEC;
+            const int ly = row & (kTY - 1), lz = row >> 3;
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            Bytes c;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) c.b[k] = 0;
+            if (z < dm.d && y < dm.h && x < dm.w) {
+                const size_t p = (size_t)y * dm.w + x, i = (size_t)z * hw + p;
+                // the +z edges of the slab's last plane are real unless it is the volume's last
+                const bool zin = z < dm.d - 1 || !final, yin = y < dm.h - 1;
+                const bool below = z == 0 && sm.carry_aff != nullptr;   // plane 0 of a slab that is not the first
+                const Pack az = *reinterpret_cast<const Pack*>(aff + i);
+                const Pack ay = *reinterpret_cast<const Pack*>(aff + n + i);
+                const Pack ax = *reinterpret_cast<const Pack*>(aff + 2 * n + i);
+                Pack bz = az, by = ay;   // overwritten where the lower neighbour exists
+                // The carried plane is float32, narrowed back to the slab's type: exact, it was widened from it.
+                if constexpr (VEC * sizeof(T) == 16) {
+                    // one 16-byte load, of the plane below in the slab or of the first four carried values
+                    const void* zsrc = below ? (const void*)(sm.carry_aff + p) : (const void*)(aff + i - hw);
+                    if (z > 0 || below) bz = *reinterpret_cast<const Pack*>(zsrc);
+                    if constexpr (sizeof(T) == 2) {
+                        if (below) {
+                            Floats lo;
+                            __builtin_memcpy(&lo, &bz, 16);
+                            const Floats hi = *reinterpret_cast<const Floats*>(sm.carry_aff + p + 4);
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                bz.v[k] = (T)lo.v[k];
+                                bz.v[4 + k] = (T)hi.v[k];
+                            }
+                        }
+                    }
+                } else {
+                    if (z > 0) bz = *reinterpret_cast<const Pack*>(aff + i - hw);
+                    if (below) bz.v[0] = (T)sm.carry_aff[p];
+                }
+                if (y > 0) by = *reinterpret_cast<const Pack*>(aff + n + i - dm.w);
+                float prev_x = x > 0 ? widen<T>(aff[2 * n + i - 1]) : low;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float pz = zin ? widen<T>(az.v[k]) : low;
+                    const float py = yin ? widen<T>(ay.v[k]) : low;
+                    const float px = x + k < dm.w - 1 ? widen<T>(ax.v[k]) : low;
+                    const float mz = z > 0 || below ? widen<T>(bz.v[k]) : low;
+                    const float my = y > 0 ? widen<T>(by.v[k]) : low;
+                    const unsigned cv = steepest(mz, my, prev_x, px, py, pz, low);
+                    prev_x = px;   // only read where x + k + 1 exists, and then px is the in-volume value
+                    const unsigned ez = pz > low, ey = py > low, ex = px > low;
+                    c.b[k] = (unsigned char)pack_states(cv, ez + (ez & (unsigned)(pz >= high || cv == kToHighZ)),
+                                                        ey + (ey & (unsigned)(py >= high || cv == kToHighY)),
+                                                        ex + (ex & (unsigned)(px >= high || cv == kToHighX)));
+                }
+            }
+            *reinterpret_cast<Bytes*>(code + (lz * (kTY + 1) + ly) * kCodeRow + lx) = c;
+        }
+        // the halo: plane z0 + 8, plane y0 + 8, column x0 + 32 (no corners: no edge of the tile ends there);
+        // a bare code, the states of a halo voxel are its own tile's
+        for (int j = t; j < kHaloZ + kHaloY + kHaloX; j += kThreads) {
+            int lz, ly, lx;
+            if (j < kHaloZ) {
+                lz = kTZ; ly = j >> 5; lx = j & (kTX - 1);
+            } else if (j < kHaloZ + kHaloY) {
+                lz = (j - kHaloZ) >> 5; ly = kTY; lx = j & (kTX - 1);
+            } else {
+                lz = (j - kHaloZ - kHaloY) >> 3; ly = j & (kTY - 1); lx = kTX;
+            }
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            unsigned cv = 0;
+            if (z < dm.d && y < dm.h && x < dm.w) cv = steepest_at_slab<T>(aff, dm, z, y, x, low, sm.carry_aff, final);
+            code[(lz * (kTY + 1) + ly) * kCodeRow + lx] = (unsigned char)cv;
+        }
+        __syncthreads();
+        // The two seams, where this tile touches one: a plane of the tile is 8 x 32 voxels, one per thread, and
+        // what a seam edge needs of its end in this slab is that voxel's byte.
+        {
+            const int ly = t >> 5, lx = t & (kTX - 1);
+            const int y = y0 + ly, x = x0 + lx;
+            const size_t p = (size_t)y * dm.w + x;
+            if (tz == 0 && sm.carry_bits && y < dm.h && x < dm.w) {
+                // the edge below plane 0 is on iff sure, or eligible and this voxel's steepest edge
+                const unsigned cb = sm.carry_bits[p], cv = code[ly * kCodeRow + lx] & 7u;
+                sm.carry_bits[p] = (unsigned char)(((cb >> 1) | (cb & (unsigned)(cv == kToLowZ))) & 1u);
+            }
+            const int lz = dm.d - 1 - z0;   // the slab's last plane, if it is in this tile
+            if (!final && lz < kTZ && y < dm.h && x < dm.w) {
+                unsigned sz, sy, sx;
+                unpack_states(code[(lz * (kTY + 1) + ly) * kCodeRow + lx], sz, sy, sx);
+                sm.seam[p] = (unsigned char)((sz != 0) | ((sz == 2) << 1));   // bit 0 eligible, bit 1 sure
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int j = t + kThreads * r;
+            const int row = j / kGroupsPerRow, lx = (j - row * kGroupsPerRow) * VEC;
+            const int ly = row & (kTY - 1), lz = row >> 3;
+            const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+            if (z < dm.d && y < dm.h && x < dm.w) {
+                const unsigned char* here = code + (lz * (kTY + 1) + ly) * kCodeRow + lx;
+                const Bytes mine = *reinterpret_cast<const Bytes*>(here);
+                const bool zin = z < dm.d - 1;   // the last plane's z edges are the seam's, not the mask's
+                Bytes out;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    unsigned m = kBitOn, sz, sy, sx;
+                    unpack_states(mine.b[k], sz, sy, sx);
+                    const unsigned up_z = here[k + (kTY + 1) * kCodeRow] & 7u, up_y = here[k + kCodeRow] & 7u;
+                    const unsigned up_x = here[k + 1] & 7u;
+                    if (zin && (sz == 2 || (sz == 1 && up_z == kToLowZ))) m |= kBitZ;
+                    if (sy == 2 || (sy == 1 && up_y == kToLowY)) m |= kBitY;
+                    if (sx == 2 || (sx == 1 && up_x == kToLowX)) m |= kBitX;
+                    out.b[k] = (unsigned char)m;
+                }
+                *reinterpret_cast<Bytes*>(mask + ((size_t)z * dm.h + y) * dm.w + x) = out;
+            }
+        }
+        __syncthreads();   // code is reused by the next tile
+    }
+}
+
+// seam_aff[p] = float32 of the z affinity of the slab's last plane: the next slab's -z edges. A launch of its
+// own after the mask, which reads the plane the slab before this one left there.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void seam_affinity(const T* __restrict__ last_plane, float* __restrict__ seam_aff,
+                                                         size_t hw) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += stride)
+        seam_aff[p] = widen<T>(last_plane[p]);
 }
 
 // ---- the lock-free union --------------------------------------------------------------------
@@ -1584,5 +1795,123 @@ extern "C" int exaspim_components_stream_apply(const exaspim_components_stream* 
     apply_table<<<capped_grid((n + 3) / 4, kThreads), kThreads, 0, (hipStream_t)stream>>>(labels_dev, st->table_dev,
                                                                                         st->capacity, n);
     EXA_CHECK_HIP(hipGetLastError());
+    return EXASPIM_OK;
+}
+
+// ---- watershed fragments of a volume that arrives in z slabs -----------------------------------
+namespace exaspim {
+namespace {
+
+template <typename T>
+void launch_watershed_slab_mask(const void* src, unsigned char* mask, const Dims& dm, float low, float high,
+                                const SlabSeam& sm, float* seam_aff, hipStream_t stream) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const T* p = static_cast<const T*>(src);
+    const size_t hw = (size_t)dm.h * dm.w;
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    const unsigned grid = capped_grid((size_t)n_tiles, 1);
+    // the carried plane of affinities is read in 16-byte groups as well
+    if (dm.w % VEC == 0 && (((uintptr_t)src | (uintptr_t)sm.carry_aff) & 15) == 0)
+        edge_mask_watershed_slab<T, VEC><<<grid, kThreads, 0, stream>>>(p, mask, dm, low, high, tiles_x, tiles_y,
+                                                                        n_tiles, sm);
+    else
+        edge_mask_watershed_slab<T, 1><<<grid, kThreads, 0, stream>>>(p, mask, dm, low, high, tiles_x, tiles_y,
+                                                                      n_tiles, sm);
+    if (sm.seam)
+        seam_affinity<T><<<capped_grid(hw, kThreads), kThreads, 0, stream>>>(p + ((size_t)dm.n - hw), seam_aff, hw);
+}
+
+}  // namespace
+}  // namespace exaspim
+
+extern "C" size_t exaspim_watershed_stream_slab_workspace_bytes(const int32_t slab_dims[3]) {
+    Dims dm;
+    if (!valid_dims(slab_dims, &dm)) {
+        set_error("watershed_stream_slab_workspace_bytes: dims must be positive with a product of at most 2^31 - 1");
+        return 0;
+    }
+    return slab_layout_of(dm).bytes;
+}
+
+extern "C" int exaspim_watershed_stream_slab(exaspim_watershed_stream* wst, const void* aff_dev, int32_t aff_dtype,
+                                             const int32_t slab_dims[3], int32_t z0, int32_t* labels_dev,
+                                             void* workspace_dev, size_t workspace_bytes, void* stream) {
+    EXA_CHECK_ARG(wst, "watershed_stream_slab: NULL stream descriptor");
+    exaspim_components_stream* st = &wst->base;
+    const char* fault = stream_fault(st);
+    EXA_CHECK_ARG(!fault, "watershed_stream_slab: %s", fault);
+    EXA_CHECK_ARG(st->channels == 3, "watershed_stream_slab: channels must be 3, got %d", st->channels);
+    EXA_CHECK_ARG(wst->seam_aff_dev && ((uintptr_t)wst->seam_aff_dev & 3) == 0,
+                  "watershed_stream_slab: NULL or misaligned seam_aff_dev");
+    EXA_CHECK_ARG(wst->low == wst->low && wst->high == wst->high, "watershed_stream_slab: low or high is a NaN");
+    EXA_CHECK_ARG(aff_dev && labels_dev && workspace_dev && slab_dims, "watershed_stream_slab: NULL argument");
+    EXA_CHECK_ARG(aff_dtype == EXASPIM_AFF_F32 || aff_dtype == EXASPIM_AFF_F16,
+                  "watershed_stream_slab: aff_dtype %d is neither EXASPIM_AFF_F32 nor EXASPIM_AFF_F16", aff_dtype);
+    Dims dm;
+    EXA_CHECK_ARG(valid_dims(slab_dims, &dm),
+                  "watershed_stream_slab: slab dims must be positive with a product of at most 2^31 - 1");
+    EXA_CHECK_ARG(dm.h == st->dims[1] && dm.w == st->dims[2],
+                  "watershed_stream_slab: the slab is %d x %d in (y, x), the volume %d x %d", dm.h, dm.w,
+                  st->dims[1], st->dims[2]);
+    EXA_CHECK_ARG(z0 == st->next_z, "watershed_stream_slab: slabs go in z order, the next one starts at %d, not %d",
+                  st->next_z, z0);
+    EXA_CHECK_ARG((long long)z0 + dm.d <= st->dims[0],
+                  "watershed_stream_slab: planes [%d, %lld) leave the volume of depth %d", z0, (long long)z0 + dm.d,
+                  st->dims[0]);
+    EXA_CHECK_ARG(((uintptr_t)workspace_dev & 15) == 0 && ((uintptr_t)labels_dev & 3) == 0 &&
+                      ((uintptr_t)aff_dev & (aff_dtype == EXASPIM_AFF_F32 ? 3 : 1)) == 0,
+                  "watershed_stream_slab: misaligned buffer");
+    const SlabLayout l = slab_layout_of(dm);
+    if (workspace_bytes < l.bytes) {
+        set_error("watershed_stream_slab: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+        return EXASPIM_E_WORKSPACE;
+    }
+    const int min_eff = clamped_min_size(floored_min_size(3, st->min_size));
+    const bool first = z0 == 0, last = z0 + dm.d == st->dims[0];
+
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = static_cast<char*>(workspace_dev);
+    int* aux = reinterpret_cast<int*>(ws + l.base.aux_off);
+    unsigned char* mask = reinterpret_cast<unsigned char*>(ws + l.base.mask_off);
+    int* sums = reinterpret_cast<int*>(ws + l.base.sums_off);
+    // seam: this slab's eligible and sure bits, every eligible one a mark on the lower side (the upper end's
+    // choice is not known yet); carry: the previous slab's, resolved by the mask kernel to on or off
+    unsigned char* seam = last ? nullptr : reinterpret_cast<unsigned char*>(ws + l.seam_off);
+    unsigned char* carry = first ? nullptr : st->seam_bits_dev;
+    int* parent = labels_dev;
+    const size_t hw = (size_t)dm.h * dm.w;
+
+    if (first) {   // a new volume: no ids yet, id 0 is the background's
+        EXA_CHECK_HIP(hipMemsetAsync(st->state_dev, 0, 4 * sizeof(int32_t), s));
+        EXA_CHECK_HIP(hipMemsetAsync(st->id_parent_dev, 0, sizeof(int32_t), s));
+        EXA_CHECK_HIP(hipMemsetAsync(st->id_count_dev, 0, sizeof(int64_t), s));
+    }
+    EXA_CHECK_HIP(hipMemsetAsync(aux, 0, (size_t)dm.n * 4, s));
+    const SlabSeam sm{first ? nullptr : wst->seam_aff_dev, carry, seam};
+    if (aff_dtype == EXASPIM_AFF_F32)
+        launch_watershed_slab_mask<float>(aff_dev, mask, dm, wst->low, wst->high, sm, wst->seam_aff_dev, s);
+    else
+        launch_watershed_slab_mask<_Float16>(aff_dev, mask, dm, wst->low, wst->high, sm, wst->seam_aff_dev, s);
+    const int tiles_x = (dm.w + kTX - 1) / kTX, tiles_y = (dm.h + kTY - 1) / kTY;
+    const long long n_tiles = (long long)tiles_x * tiles_y * ((dm.d + kTZ - 1) / kTZ);
+    tile_pass<<<capped_grid((size_t)n_tiles, 1), kThreads, 0, s>>>(mask, parent, dm, tiles_x, tiles_y, n_tiles);
+    const unsigned grid = capped_grid((size_t)dm.n, kThreads), plane_grid = capped_grid(hw, kThreads);
+    face_merge<<<grid, kThreads, 0, s>>>(mask, parent, dm);
+    flatten<<<grid, kThreads, 0, s>>>(parent, dm.n);
+    sizes<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    if (carry || seam) seam_mark<<<plane_grid, kThreads, 0, s>>>(parent, mask, aux, dm, carry, seam);
+    const SlabRoot ids{parent, mask, aux, min_eff, st->state_dev + kIdsUsed, st->capacity, st->id_parent_dev,
+                       reinterpret_cast<long long*>(st->id_count_dev)};
+    const unsigned scan_grid = (unsigned)l.base.n_scan_blocks;
+    scan_count<<<scan_grid, kThreads, 0, s>>>(ids, sums, (size_t)dm.n);
+    scan_block_sums<<<1, kSumThreads, 0, s>>>(sums, l.base.n_scan_blocks, st->state_dev + kSlabIds);
+    scan_assign<<<scan_grid, kThreads, 0, s>>>(ids, sums, (size_t)dm.n);
+    relabel<<<grid, kThreads, 0, s>>>(parent, aux, dm.n);
+    if (carry) seam_union<<<plane_grid, kThreads, 0, s>>>(parent, mask, st->seam_ids_dev, carry, st->id_parent_dev, hw);
+    slab_advance<<<seam ? plane_grid : 1, kThreads, 0, s>>>(parent + ((size_t)dm.n - hw), seam, st->seam_ids_dev,
+                                                           st->seam_bits_dev, hw, st->state_dev, st->capacity);
+    EXA_CHECK_HIP(hipGetLastError());
+    st->next_z = z0 + dm.d;
     return EXASPIM_OK;
 }

@@ -49,7 +49,7 @@ from aind_exaspim_neuron_segmentation_amd._device import _carrier, _stream
 from aind_exaspim_neuron_segmentation_amd.machine_learning.unet3d import UNet3D
 from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (importable from here as before)
     DBF_INF, DEFAULT_EDGE_CAPACITY, DEFAULT_ID_CAPACITY, FIX_BRANCHING_FIELD_SWEEPS, MAX_TOTAL_COUNT, ComponentsStream,
-    RegionGraphStream,
+    RegionGraphStream, WatershedStream, _checked_fragment_options, _fragment_stream, watershed_fragments_streaming,
     _AgglomerationLabeller, _border_targets_on_device, _ComponentsLabeller, _components_on_device,
     _contract_dominant_on_device,
     _default_edge_capacity, _device_merged_table, _fill_holes_on_device, _fix_branching_on_device,
@@ -2100,6 +2100,12 @@ def predict_agglomerate_streaming(
     id_capacity=None,
     edge_capacity=None,
     keep_labels_resident=None,
+    fragments="components",
+    aff_threshold_low=0.1,
+    aff_threshold_high=0.9999,
+    premerge_size=0,
+    premerge_rounds=4,
+    device_merge_rounds=0,
 ):
     """
     predict_streaming followed by agglomerate_affinities without the
@@ -2137,6 +2143,13 @@ def predict_agglomerate_streaming(
         See RegionGraphStream.
     keep_labels_resident : bool, optional
         As in predict_components_streaming.
+    fragments, aff_threshold_low, aff_threshold_high, premerge_size,
+    premerge_rounds, device_merge_rounds
+        As in agglomerate_affinities; the result then equals that call with
+        the same values on predict_streaming's affinities, bit for bit.
+        fragments="watershed" labels the slabs with a WatershedStream
+        (DESIGN 6s). With the defaults nothing but what is described above
+        is launched.
 
     Returns
     -------
@@ -2147,15 +2160,17 @@ def predict_agglomerate_streaming(
     """
     thresholds = list(agglomeration_thresholds)
     _last_threshold(thresholds)
+    low, high, merging = _checked_fragment_options(fragments, aff_threshold_low, aff_threshold_high, premerge_size,
+                                                   premerge_rounds, device_merge_rounds)
     if not affinity_mode:
         raise ValueError("predict_agglomerate_streaming needs affinity_mode=True: "
                          "a foreground map has no affinities to score")
     device = _hip_device(model)
     volume = _open_volume(source, shape, dtype)
-    cs = ComponentsStream(volume[1], fragment_threshold, 0, device=device, id_capacity=id_capacity)
+    cs = _fragment_stream(fragments, volume[1], fragment_threshold, low, high, device, id_capacity)
     rgs = RegionGraphStream(volume[1], device=device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
     return _label_predicted_slabs(
-        _AgglomerationLabeller(cs, rgs, thresholds, min_segment_size), "agglomerate_finish", write_block,
+        _AgglomerationLabeller(cs, rgs, thresholds, min_segment_size, **merging), "agglomerate_finish", write_block,
         keep_labels_resident, timings,
         volume, model, True, batch_size, brightness_clip, normalization_percentiles, patch_shape, overlap,
         trim, verbose, n_streams, copy_threads=copy_threads, keep_input_resident=keep_input_resident)

@@ -4183,10 +4183,20 @@ class ComponentsStream:
         number of voxels if that is less.
     """
 
+    # what a subclass with another slab call replaces (WatershedStream)
+    _name = "ComponentsStream"
+    _slab_call = "exaspim_components_stream_slab"
+
     def __init__(self, shape, threshold=0.5, min_segment_size=100, *, foreground=False, device=None,
                  id_capacity=None):
-        shape, device, id_capacity = _stream_geometry("ComponentsStream", shape, device, id_capacity)
-        self.shape, self.device, self.foreground, self.id_capacity = shape, device, bool(foreground), id_capacity
+        self.foreground = bool(foreground)
+        self._allocate(shape, device, id_capacity, _native.ComponentsStreamDesc(), threshold, min_segment_size)
+        self._slab_desc = self.desc
+
+    def _allocate(self, shape, device, id_capacity, desc, threshold, min_segment_size):
+        """The device state and the descriptor "desc" (an exaspim_components_stream) that points to it."""
+        shape, device, id_capacity = _stream_geometry(self._name, shape, device, id_capacity)
+        self.shape, self.device, self.id_capacity = shape, device, id_capacity
         self.finished = False
         plane = shape[1] * shape[2]
         with torch.cuda.device(device):
@@ -4197,9 +4207,9 @@ class ComponentsStream:
             self.seam_ids = torch.empty(plane, dtype=torch.int32, device=device)
             self.seam_bits = torch.empty(plane, dtype=torch.uint8, device=device)
         self.workspace = None
-        d = self.desc = _native.ComponentsStreamDesc()
+        d = self.desc = desc
         d.dims[:] = shape
-        d.channels = 1 if foreground else 3
+        d.channels = 1 if self.foreground else 3
         d.threshold = float(np.float32(threshold))
         d.capacity = id_capacity
         d.min_size = int(min_segment_size)
@@ -4238,7 +4248,7 @@ class ComponentsStream:
             int32 (d, H, W) provisional ids (0: certainly background).
         """
         if self.finished:
-            raise RuntimeError("ComponentsStream: push() after finish()")
+            raise RuntimeError(f"{self._name}: push() after finish()")
         if not isinstance(slab, torch.Tensor):
             raise TypeError(f"push needs a torch tensor, got {type(slab).__name__}")
         if slab.dtype not in _AFF_CODES:
@@ -4254,7 +4264,7 @@ class ComponentsStream:
             raise ValueError(f"empty slab {dims}")
         slab = slab.contiguous()
         lib = _native.lib()
-        need = _workspace_bytes("exaspim_components_stream_slab_workspace_bytes", _native.int3(dims))
+        need = _workspace_bytes(self._slab_call + "_workspace_bytes", _native.int3(dims))
         with torch.cuda.device(self.device):
             if out is None:
                 out = torch.empty(dims, dtype=torch.int32, device=self.device)
@@ -4263,11 +4273,11 @@ class ComponentsStream:
                 raise ValueError(f"out must be a contiguous int32 {dims} tensor on {self.device}")
             ws = self._scratch(need)
             _native.check(
-                lib.exaspim_components_stream_slab(
-                    ctypes.byref(self.desc), slab.data_ptr(), _AFF_CODES[slab.dtype], _native.int3(dims),
+                getattr(lib, self._slab_call)(
+                    ctypes.byref(self._slab_desc), slab.data_ptr(), _AFF_CODES[slab.dtype], _native.int3(dims),
                     self.next_z if z0 is None else int(z0), out.data_ptr(), ws.data_ptr(), need,
                     _stream(self.device)),
-                "exaspim_components_stream_slab",
+                self._slab_call,
             )
         return out
 
@@ -4289,7 +4299,7 @@ class ComponentsStream:
             If the volume needed more provisional ids than id_capacity.
         """
         if self.finished:
-            raise RuntimeError("ComponentsStream: finish() called twice")
+            raise RuntimeError(f"{self._name}: finish() called twice")
         lib = _native.lib()
         need = lib.exaspim_components_stream_finish_workspace_bytes(self.id_capacity)
         with torch.cuda.device(self.device):
@@ -4303,7 +4313,7 @@ class ComponentsStream:
             used, overflow, count, _ = (int(v) for v in self.state.cpu())
         if overflow:
             raise RuntimeError(
-                f"ComponentsStream: the volume needs more than id_capacity={self.id_capacity} provisional ids; "
+                f"{self._name}: the volume needs more than id_capacity={self.id_capacity} provisional ids; "
                 "the labels handed out are unusable. Label it again with a larger id_capacity (or deeper slabs)")
         self.ids_used = used
         return self.table, count
@@ -4311,7 +4321,7 @@ class ComponentsStream:
     def apply(self, labels):
         """Provisional ids -> final labels, in place, on a contiguous int32 device tensor of any shape."""
         if not self.finished:
-            raise RuntimeError("ComponentsStream: apply() before finish()")
+            raise RuntimeError(f"{self._name}: apply() before finish()")
         if (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.device != self.device
                 or not labels.is_contiguous()):
             raise ValueError(f"apply needs a contiguous int32 tensor on {self.device}")
@@ -4322,6 +4332,60 @@ class ComponentsStream:
                 "exaspim_components_stream_apply",
             )
         return labels
+
+
+class WatershedStream(ComponentsStream):
+    """
+    watershed_fragments for a volume that arrives in z slabs: the
+    final labels equal, bit for bit, those of the whole volume, which may
+    have more than 2^31 - 1 voxels and never has to be anywhere in one piece.
+    push, finish, apply, next_z and ids_used are ComponentsStream's.
+
+        ws = WatershedStream((D, H, W), 0.1, 0.9999)
+        for slab in slabs_in_z_order:          # (3, d, H, W) device tensors
+            provisional = ws.push(slab)
+        table, k = ws.finish()
+        ws.apply(provisional)
+
+    No plane of the next slab is needed: channel 0 at voxel v is the edge
+    v -- v + e_z, so a slab holds the +z edges of its own last plane. What is
+    carried is that plane's z affinities as float32 (the next slab's -z
+    edges) and two bits per (y, x), eligible and sure, which the next slab
+    resolves once it knows the choice of the edge's upper end.
+
+    Parameters
+    ----------
+    shape : Tuple[int]
+        (D, H, W) of the whole volume; H * W and every slab must stay within
+        2^31 - 1 voxels, D * H * W need not.
+    aff_threshold_low, aff_threshold_high, min_segment_size
+        As in watershed_fragments.
+    device : torch.device, optional
+        Default is cuda:0.
+    id_capacity : int, optional
+        As in ComponentsStream, with one difference that costs ids, never
+        labels: below a seam a slab cannot know whether an eligible z edge
+        will be switched on from above, so every slab-local fragment with an
+        ELIGIBLE edge across the seam gets an id (the conservative rule of
+        foreground mode), not only those with an on edge. Above a seam the
+        rule is exact. Watershed fragments are small, so count about one id
+        per voxel of a seam plane.
+    """
+
+    _name = "WatershedStream"
+    _slab_call = "exaspim_watershed_stream_slab"
+
+    def __init__(self, shape, aff_threshold_low=0.1, aff_threshold_high=0.9999, min_segment_size=0, *, device=None,
+                 id_capacity=None):
+        low, high = float(np.float32(aff_threshold_low)), float(np.float32(aff_threshold_high))
+        if low != low or high != high:
+            raise ValueError(f"aff_threshold_low and aff_threshold_high must not be NaN, got {low} and {high}")
+        self.foreground = False
+        d = self._slab_desc = _native.WatershedStreamDesc()
+        self._allocate(shape, device, id_capacity, d.base, 0.0, min_segment_size)
+        with torch.cuda.device(self.device):
+            self.seam_aff = torch.empty(self.shape[1] * self.shape[2], dtype=torch.float32, device=self.device)
+        d.low, d.high, d.seam_aff_dev = low, high, self.seam_aff.data_ptr()
 
 
 def _labels_fit_on_device(device, shape):
@@ -4469,6 +4533,62 @@ def affinities_to_components_streaming(source, threshold=0.5, min_segment_size=1
     return _label_host_slabs(_ComponentsLabeller(cs), source, slab_depth, write_block, keep_labels_resident)
 
 
+def _checked_host_affinities(fn, source, slab_depth):
+    """(source, (D, H, W), slab_depth) of a streamed function that needs (3, D, H, W) affinities on the host."""
+    if not hasattr(source, "shape") or not hasattr(source, "dtype"):
+        source = np.asarray(source)
+    if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise TypeError(f"affinities must be float32 or float16, got {source.dtype}")
+    shape = tuple(int(v) for v in source.shape)
+    if len(shape) != 4 or shape[0] != 3:
+        raise ValueError(f"{fn} needs (3, D, H, W) affinities, got {shape}; a foreground map has no affinities")
+    slab_depth = int(slab_depth)
+    if slab_depth < 1:
+        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
+    return source, shape[-3:], slab_depth
+
+
+def watershed_fragments_streaming(source, aff_threshold_low=0.1, aff_threshold_high=0.9999, min_segment_size=0, *,
+                                  slab_depth, write_block=None, id_capacity=None, device=None,
+                                  keep_labels_resident=None):
+    """
+    watershed_fragments for affinities that sit in a host array, a memmap or
+    a zarr-like array too large for the device (or for 2^31 - 1 voxels): z
+    slabs of "slab_depth" planes are uploaded and labelled one after the
+    other (WatershedStream), and the result is the whole volume's, bit for
+    bit, whatever the slab depth.
+
+    Parameters
+    ----------
+    source : array-like
+        float32 or float16 (3, D, H, W); only source[..., z0:z1, :, :] is ever
+        read. A foreground map has no affinities.
+    aff_threshold_low, aff_threshold_high, min_segment_size
+        As in watershed_fragments.
+    slab_depth : int
+        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
+    write_block, device, keep_labels_resident
+        As in affinities_to_components_streaming.
+    id_capacity : int, optional
+        See WatershedStream.
+
+    Returns
+    -------
+    numpy.ndarray
+        int32 (D, H, W) final labels; or, with "write_block", the tuple
+        (table, K): table int32 with final = table[provisional], K kept
+        fragments.
+    """
+    source, vshape, slab_depth = _checked_host_affinities("watershed_fragments_streaming", source, slab_depth)
+    low, high = float(np.float32(aff_threshold_low)), float(np.float32(aff_threshold_high))
+    if low != low or high != high:
+        raise ValueError(f"aff_threshold_low and aff_threshold_high must not be NaN, got {low} and {high}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("watershed_fragments_streaming (MI355X) has no CPU path and no HIP device is present")
+    ws = WatershedStream(vshape, low, high, min_segment_size, device=device, id_capacity=id_capacity)
+    return _label_host_slabs(_ComponentsLabeller(ws), source, slab_depth, write_block, keep_labels_resident)
+
+
 class RegionGraphStream:
     """
     region_graph for a volume that arrives in z slabs: every slab
@@ -4607,6 +4727,26 @@ class RegionGraphStream:
             If the slabs had more distinct pairs of adjacent ids than
             edge_capacity.
         """
+        edges, counts, sums, sizes, n_edges = self.finish_on_device(table, n_labels)
+        with torch.cuda.device(self.device):
+            return _download_graph(edges, counts, sums, sizes, n_edges)
+
+    def finish_on_device(self, table, n_labels):
+        """
+        finish() without the download: the same launches and the same one read
+        of the state, and the graph of the final labels stays on the device
+        (as _region_graph_device is to _region_graph_on_device).
+
+        Returns
+        -------
+        edges, counts, sums : torch.Tensor
+            int32 (edge_capacity, 2), int64 (edge_capacity,), int64
+            (edge_capacity,) holding uint64 bits: the first n_edges rows in an
+            unspecified order.
+        sizes : torch.Tensor
+            int64 (n_labels + 1,).
+        n_edges : int
+        """
         if isinstance(table, np.ndarray):
             if table.dtype != np.dtype(np.int32):
                 raise TypeError(f"table must be int32, got {table.dtype}")
@@ -4647,14 +4787,19 @@ class RegionGraphStream:
                     f"edge_capacity={capacity}. Shallow slabs need more slots than the final graph has edges: "
                     "two ids of one fragment look like two fragments until finish. Run it again with a larger "
                     "edge_capacity (a power of two) or deeper slabs")
-            return _download_graph(edges, counts, sums, sizes, n_edges)
+        return edges, counts, sums, sizes, n_edges
 
 
-def _agglomerate_streams(cs, rgs, thresholds, min_segment_size):
+def _agglomerate_streams(cs, rgs, thresholds, min_segment_size, premerge_size=0, premerge_rounds=4,
+                         device_merge_rounds=0):
     """
     After the last slab of both streams: the fragments' graph, its merging on
     the host, and the table provisional id -> segment, composed on the device
-    by sending the fragment table itself through the segment table.
+    by sending the fragment table itself through the segment table. With
+    premerge_size or device_merge_rounds the graph stays on the device for
+    the pre-merge and the dominant rounds, as in _device_merged_table, only
+    the reduced graph is downloaded, and the rounds' maps are composed onto
+    the fragment table on the device as well.
 
     Returns
     -------
@@ -4664,19 +4809,40 @@ def _agglomerate_streams(cs, rgs, thresholds, min_segment_size):
         S, the number of kept segments.
     """
     fragment_table, n_fragments = cs.finish()
-    edges, counts, sums, sizes = rgs.finish(fragment_table[: cs.ids_used + 1], n_fragments)
-    segment_table, n_segments = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
+    if not premerge_size and not device_merge_rounds:
+        edges, counts, sums, sizes = rgs.finish(fragment_table[: cs.ids_used + 1], n_fragments)
+        segment_table, n_segments = agglomerate(edges, counts, sums, sizes, thresholds, min_segment_size)
+        with torch.cuda.device(cs.device):
+            table = _apply_table(fragment_table[: cs.ids_used + 1].clone(),
+                                 torch.from_numpy(segment_table).to(cs.device))
+        return table, n_segments
+    edges, counts, sums, sizes, n_edges = rgs.finish_on_device(fragment_table[: cs.ids_used + 1], n_fragments)
+    capacity = rgs.edge_capacity
     with torch.cuda.device(cs.device):
-        table = _apply_table(fragment_table[: cs.ids_used + 1].clone(), torch.from_numpy(segment_table).to(cs.device))
+        table = fragment_table[: cs.ids_used + 1].clone()
+        if premerge_size:
+            edges, counts, sums, sizes, n_edges, composed, _ = _premerge_on_device(
+                edges, counts, sums, sizes, n_edges, thresholds[-1], premerge_size, premerge_rounds, capacity)
+            _apply_table(table, composed)
+        if device_merge_rounds:
+            # a contraction keeps the total count or lowers it: what the pre-merge has checked stays checked
+            edges, counts, sums, sizes, n_edges, dominant, _ = _contract_dominant_on_device(
+                edges, counts, sums, sizes, n_edges, thresholds[-1], device_merge_rounds, capacity,
+                total_checked=bool(premerge_size))
+            _apply_table(table, dominant)
+        graph = _download_graph(edges, counts, sums, sizes, n_edges)
+        segment_table, n_segments = agglomerate(*graph, thresholds, min_segment_size)
+        _apply_table(table, torch.from_numpy(segment_table).to(cs.device))
     return table, n_segments
 
 
 class _AgglomerationLabeller:
-    """Mean-affinity agglomeration: a ComponentsStream with no size filter and a RegionGraphStream of its ids."""
+    """Mean-affinity agglomeration: a ComponentsStream or a WatershedStream with no size filter and a
+    RegionGraphStream of its ids; "merging": the keywords of _agglomerate_streams' device rounds."""
 
-    def __init__(self, cs, rgs, thresholds, min_segment_size):
+    def __init__(self, cs, rgs, thresholds, min_segment_size, **merging):
         self.cs, self.rgs, self.device, self.shape = cs, rgs, cs.device, cs.shape
-        self.thresholds, self.min_segment_size = thresholds, min_segment_size
+        self.thresholds, self.min_segment_size, self.merging = thresholds, min_segment_size, merging
 
     def push(self, slab, z0, out):
         labels = self.cs.push(slab, z0, out)
@@ -4684,12 +4850,36 @@ class _AgglomerationLabeller:
         return labels
 
     def finish(self):
-        return _agglomerate_streams(self.cs, self.rgs, self.thresholds, self.min_segment_size)
+        return _agglomerate_streams(self.cs, self.rgs, self.thresholds, self.min_segment_size, **self.merging)
+
+
+def _checked_fragment_options(fragments, aff_threshold_low, aff_threshold_high, premerge_size, premerge_rounds,
+                              device_merge_rounds):
+    """The fragment and device-merging keywords of the streamed agglomerations, checked as agglomerate_affinities
+    checks them: (low, high) rounded to float32 and the keywords of _agglomerate_streams."""
+    premerge_size, premerge_rounds = _checked_premerge(premerge_size, premerge_rounds)
+    device_merge_rounds = _checked_rounds("device_merge_rounds", device_merge_rounds, 0)
+    if fragments not in ("components", "watershed"):
+        raise ValueError(f'fragments must be "components" or "watershed", got {fragments!r}')
+    low, high = float(np.float32(aff_threshold_low)), float(np.float32(aff_threshold_high))
+    if fragments == "watershed" and (low != low or high != high):
+        raise ValueError(f"aff_threshold_low and aff_threshold_high must not be NaN, got {low} and {high}")
+    return low, high, dict(premerge_size=premerge_size, premerge_rounds=premerge_rounds,
+                           device_merge_rounds=device_merge_rounds)
+
+
+def _fragment_stream(fragments, shape, fragment_threshold, low, high, device, id_capacity):
+    """The stream of fragments, no size filter: connected components at a threshold or watershed basins."""
+    if fragments == "watershed":
+        return WatershedStream(shape, low, high, 0, device=device, id_capacity=id_capacity)
+    return ComponentsStream(shape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
 
 
 def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8, 0.9], min_segment_size=100, *,
                                      fragment_threshold=0.5, slab_depth, write_block=None, id_capacity=None,
-                                     edge_capacity=None, device=None, keep_labels_resident=None):
+                                     edge_capacity=None, device=None, keep_labels_resident=None,
+                                     fragments="components", aff_threshold_low=0.1, aff_threshold_high=0.9999,
+                                     premerge_size=0, premerge_rounds=4, device_merge_rounds=0):
     """
     agglomerate_affinities for affinities that sit in a host array, a memmap
     or a zarr-like array too large for the device (or for 2^31 - 1 voxels):
@@ -4722,6 +4912,15 @@ def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8,
         Default is cuda:0.
     keep_labels_resident : bool, optional
         As in affinities_to_components_streaming.
+    fragments, aff_threshold_low, aff_threshold_high, premerge_size,
+    premerge_rounds, device_merge_rounds
+        As in agglomerate_affinities, and with the same result as the
+        whole-volume call with the same values, bit for bit.
+        fragments="watershed" labels the slabs with a WatershedStream
+         instead of a ComponentsStream; with premerge_size or
+        device_merge_rounds the graph of fragments stays on the device for
+        those rounds after the last slab. With the defaults nothing but
+        what is described above is launched.
 
     Returns
     -------
@@ -4732,6 +4931,8 @@ def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8,
     """
     thresholds = list(agglomeration_thresholds)
     _last_threshold(thresholds)
+    low, high, merging = _checked_fragment_options(fragments, aff_threshold_low, aff_threshold_high, premerge_size,
+                                                   premerge_rounds, device_merge_rounds)
     if not hasattr(source, "shape") or not hasattr(source, "dtype"):
         source = np.asarray(source)
     if np.dtype(source.dtype) not in (np.dtype(np.float32), np.dtype(np.float16)):
@@ -4746,7 +4947,7 @@ def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8,
         raise ValueError(f"slab_depth must be positive, got {slab_depth}")
     if not torch.cuda.is_available():
         raise RuntimeError("agglomerate_affinities_streaming (MI355X) has no CPU path and no HIP device is present")
-    cs = ComponentsStream(vshape, fragment_threshold, 0, device=device, id_capacity=id_capacity)
+    cs = _fragment_stream(fragments, vshape, fragment_threshold, low, high, device, id_capacity)
     rgs = RegionGraphStream(vshape, device=cs.device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
-    return _label_host_slabs(_AgglomerationLabeller(cs, rgs, thresholds, min_segment_size), source, slab_depth,
-                             write_block, keep_labels_resident)
+    return _label_host_slabs(_AgglomerationLabeller(cs, rgs, thresholds, min_segment_size, **merging), source,
+                             slab_depth, write_block, keep_labels_resident)

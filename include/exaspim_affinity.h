@@ -73,7 +73,9 @@ extern "C" {
  *    later within 5: exaspim_geodesic_reseed, exaspim_geodesic_parents_begin_seeds: fields and hops seeded from
  *    a list, any number of seeds per label, and a converged field re-seeded in place (TEASAR's fix_branching);
  *    later within 5: exaspim_teasar_begin, exaspim_teasar_round, exaspim_teasar_apply (and their workspace
- *    query): TEASAR's loop of targets, branches and invalidation for every label at once */
+ *    query): TEASAR's loop of targets, branches and invalidation for every label at once;
+ *    later within 5: exaspim_watershed_stream_slab and its workspace query (struct
+ *    exaspim_watershed_stream): watershed fragments of a volume that arrives in z slabs */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -817,6 +819,61 @@ int exaspim_watershed_fragments(const void* aff_dev, int32_t aff_dtype, const in
                                 float low, float high, int64_t min_size,
                                 int32_t* labels_dev, int32_t* n_fragments_dev,
                                 void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- the same fragments for a volume that arrives in z slabs -----------------
+ *      (later within ABI 5). The slabs of a dims[0] x dims[1] x dims[2] volume are pushed in z
+ *      order as for exaspim_components_stream_slab. After exaspim_components_stream_finish and
+ *      exaspim_components_stream_apply on &ws->base the labels equal, bit for bit, what
+ *      exaspim_watershed_fragments gives on the whole volume with the same low, high and min_size, for every
+ *      list of cuts, K (state_dev[2]) included; the volume may have more than 2^31 - 1 voxels (a slab may not).
+ *      The four rules above hold word for word.
+ *
+ *      No plane of the next slab is needed. Channel 0 at voxel v is the edge v -- v + e_z, so the slab holds
+ *      the +z edges of its own last plane. What a slab lacks are the -z edges of its first plane: the previous
+ *      slab's last plane of channel 0, carried as float32 in seam_aff_dev (float16 widened exactly). Per slab
+ *      [z0, z1) the steepest edges are chosen among every edge inside the slab, the real channel-0 values of
+ *      plane z1 - 1 as +z edges unless z1 = dims[0] (there they are ignored whatever they hold), and the
+ *      carried plane as the -z edges of plane z0 unless z0 = 0.
+ *
+ *      A seam edge can be switched on by the choice of its upper end, which the lower slab cannot know. For a
+ *      last plane that is not the volume's the call leaves two bits per (y, x) in base.seam_bits_dev: bit 0
+ *      eligible, bit 1 sure (eligible and >= high or the steepest edge of its lower end). The next call turns
+ *      them into 1 (on: sure, or eligible and the first-plane voxel's steepest edge is -z) or 0 in place,
+ *      before the ids are joined across the seam.
+ *
+ *      Ids. On the upper side of a seam a slab-local fragment gets a provisional id iff it is larger than
+ *      min_size on its own or has an on edge to the carried plane: exact. On the lower side it gets one iff it
+ *      is larger than min_size or has an ELIGIBLE edge across the seam, whether that edge ends up on or not:
+ *      the conservative rule of exaspim_components_stream_slab's foreground mode. The final labels are the
+ *      same (an id that is never joined passes or fails the size filter on its own count); the price is ids:
+ *      size base.capacity for one id per voxel of a seam plane with an eligible z edge, not per on edge.
+ *
+ *      base.channels must be 3; base.threshold is ignored. z0 = 0 resets the state; the carried planes are
+ *      never read before they are written, so none of the buffers needs initialising. */
+typedef struct exaspim_watershed_stream {
+    exaspim_components_stream base;  /* channels must be 3; threshold is ignored                            */
+    float low;                       /* eligible iff float32(a) > low                                       */
+    float high;                      /* an eligible edge with a >= high is on                               */
+    float* seam_aff_dev;             /* float32[dims[1] * dims[2]]: the last pushed plane's z affinities    */
+} exaspim_watershed_stream;
+
+/* Scratch bytes of one slab call: exaspim_components_stream_slab_workspace_bytes' figure. 0 (and a message)
+ * if a dim is not positive or the slab has more than 2^31 - 1 voxels. */
+size_t exaspim_watershed_stream_slab_workspace_bytes(const int32_t slab_dims[3]);
+
+/* Pushes planes [z0, z0 + slab_dims[0]) of the volume: aff_dev is the contiguous (3, slab_dims) tensor of
+ * aff_dtype, labels_dev (int32, slab_dims) receives the provisional ids. Arguments, ordering, overflow and
+ * alignment as for exaspim_components_stream_slab (the wide loads also need seam_aff_dev and
+ * base.seam_bits_dev 16-byte aligned). One launch for the edge mask (exaspim_watershed_fragments' tiles, no
+ * atomics; it also resolves the carried seam bits), one that carries the last plane's z affinities, then the
+ * streamed components' passes: launches on "stream" only, no inter-workgroup waiting, nothing allocated,
+ * nothing synchronised, and the id count never visits the host. EXASPIM_E_WORKSPACE for fewer bytes than
+ * exaspim_watershed_stream_slab_workspace_bytes(slab_dims); EXASPIM_E_INVALID for everything
+ * exaspim_components_stream_slab refuses and for base.channels other than 3, a NULL or misaligned
+ * seam_aff_dev, a NaN low or high: all before anything is launched and with ws unchanged. */
+int exaspim_watershed_stream_slab(exaspim_watershed_stream* ws, const void* aff_dev, int32_t aff_dtype,
+                                  const int32_t slab_dims[3], int32_t z0, int32_t* labels_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- size-floor pre-merge of a region graph -----------------------------------
  *      (later within ABI 5). Watershed fragments of a large volume are millions of tiny basins,
