@@ -294,6 +294,11 @@ SIGNATURES = {
     "exaspim_label_pieces": (_i32, [_vp, _I32x3, _i32, ctypes.c_int64, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_label_pieces_open_workspace_bytes": (_sz, [_I32x3]),
     "exaspim_label_pieces_open": (_i32, [_vp, _I32x3, _i32, ctypes.c_int64, ctypes.c_uint32, _vp, _vp, _vp, _sz, _vp]),
+    "exaspim_label_overlaps_workspace_bytes": (_sz, [ctypes.c_int64]),
+    "exaspim_label_overlaps_reset": (_i32, [ctypes.c_int64, _vp, _sz, _vp]),
+    "exaspim_label_overlaps_add": (_i32, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _sz, _vp]),
+    "exaspim_label_overlaps_finish": (_i32, [ctypes.c_int64, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "exaspim_label_overlaps": (_i32, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "exaspim_synth_volume_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
     "exaspim_synth_volume_neurite_u16": (_i32, [_vp, ctypes.POINTER(Block), ctypes.c_uint64, _vp]),
 }

@@ -65,6 +65,8 @@ from aind_exaspim_neuron_segmentation_amd.segmentation import (  # noqa: F401  (
     skeletonize_fix_borders, skeletonize_labels, skeletonize_pieces, skeletons_to_zipped_swcs, teasar_branches,
     teasar_branches_fix_branching, teasar_branches_fix_branching_given, teasar_branches_given, trace_paths,
     voxelize_skeletons, watershed_fragments,
+    DEFAULT_PAIR_CAPACITY, OverlapStream, compare_segmentations, label_overlaps, label_overlaps_streaming,
+    overlap_scores,
 )
 from aind_exaspim_neuron_segmentation_amd.utils import img_util
 

@@ -24,7 +24,12 @@ with exactly defined parts.
   RegionGraphStream) and the one streaming driver behind
   affinities_to_components_streaming and agglomerate_affinities_streaming
   here and predict_components_streaming and predict_agglomerate_streaming
-  in inference.py.
+  in inference.py;
+* how much two label volumes differ: the overlap table of ordered label
+  pairs on the device, whole or piece by piece, and the variation of
+  information, adapted Rand error and largest-overlap agreement read off it
+  on the host (label_overlaps, OverlapStream, label_overlaps_streaming,
+  compare_segmentations, overlap_scores).
 
 Every name is importable from inference.py as before. This module does not
 import inference.py and reads none of its plan switches. There is no CPU
@@ -4951,3 +4956,383 @@ def agglomerate_affinities_streaming(source, agglomeration_thresholds=[0.6, 0.8,
     rgs = RegionGraphStream(vshape, device=cs.device, id_capacity=cs.id_capacity, edge_capacity=edge_capacity)
     return _label_host_slabs(_AgglomerationLabeller(cs, rgs, thresholds, min_segment_size, **merging), source,
                              slab_depth, write_block, keep_labels_resident)
+
+
+# ---- the overlap table of two label volumes, and the scores read off it ---------------------------
+DEFAULT_PAIR_CAPACITY = 1 << 22
+_MAX_ADD_VOXELS = 2**31 - 1
+_BACKGROUND_MODES = ("a", "both_zero", "none")
+
+
+def _default_pair_capacity(voxels):
+    want = 2 * int(voxels)
+    return min(DEFAULT_PAIR_CAPACITY, 1 << max(want - 1, 0).bit_length())
+
+
+def _checked_pair_capacity(fn, pair_capacity, voxels=None):
+    if pair_capacity is None:
+        return DEFAULT_PAIR_CAPACITY if voxels is None else _default_pair_capacity(voxels)
+    _checked_integer(fn, "pair_capacity", pair_capacity)
+    pair_capacity = int(pair_capacity)
+    if not 1 <= pair_capacity <= 1 << 30 or pair_capacity & (pair_capacity - 1):
+        raise ValueError(f"{fn}: pair_capacity must be a power of two in 1 .. 2^30, got {pair_capacity}")
+    return pair_capacity
+
+
+class OverlapStream:
+    """
+    The overlap table of two label volumes that arrive piece by piece (DESIGN
+    6u): label_overlaps' table of everything added so far, which may be more
+    than 2^31 - 1 voxels and never has to be anywhere in one piece.
+
+        table = OverlapStream(1 << 20)
+        for a_block, b_block in blocks:            # equal shapes, any shapes
+            table.add(a_block, b_block)
+        pairs, counts = table.finish()
+
+    The table is additive over voxels and its counts are integers, so the
+    result does not depend on how the voxels are cut into blocks or on the
+    order of the blocks. finish() only reads the table: it may be called
+    twice, and again after further add()s.
+
+    Parameters
+    ----------
+    pair_capacity : int
+        Slots of the device hash table, a power of two in 1 .. 2^30; 16 bytes
+        each. It must hold every distinct pair (a', b').
+    device : torch.device, optional
+        Default is cuda:0.
+    """
+
+    def __init__(self, pair_capacity, device=None):
+        self.pair_capacity = _checked_pair_capacity("OverlapStream", pair_capacity)
+        device = _upload_device("OverlapStream") if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"OverlapStream (MI355X) has no CPU path: device must be a HIP device, got {device}")
+        self.device = device
+        self.voxels = 0
+        self._bytes = _workspace_bytes("exaspim_label_overlaps_workspace_bytes", self.pair_capacity)
+        with torch.cuda.device(device):
+            self._workspace = torch.empty(self._bytes, dtype=torch.uint8, device=device)
+            _native.check(
+                _native.lib().exaspim_label_overlaps_reset(self.pair_capacity, self._workspace.data_ptr(),
+                                                           self._bytes, _stream(device)),
+                "exaspim_label_overlaps_reset",
+            )
+
+    def _block(self, block, what):
+        if isinstance(block, np.ndarray):
+            if block.dtype != np.int32:
+                raise TypeError(f"{what} must be int32, got {block.dtype}")
+            return _carrier(block).to(self.device)
+        if not isinstance(block, torch.Tensor):
+            raise TypeError(f"{what} must be a torch tensor or a numpy array, got {type(block).__name__}")
+        if block.dtype != torch.int32:
+            raise TypeError(f"{what} must be int32, got {block.dtype}")
+        if block.device != self.device:
+            raise RuntimeError(f"OverlapStream.add (MI355X) has no CPU path: {what} must be on {self.device}, got "
+                               f"{block.device}")
+        return block.contiguous()
+
+    def add(self, a_block, b_block):
+        """Adds the voxels of two int32 blocks of equal shape, device tensors or numpy arrays, to the table."""
+        a, b = self._block(a_block, "a_block"), self._block(b_block, "b_block")
+        if a.shape != b.shape:
+            raise ValueError(f"OverlapStream.add: a_block and b_block must have one shape, got "
+                             f"{tuple(a.shape)} and {tuple(b.shape)}")
+        a, b = a.reshape(-1), b.reshape(-1)
+        lib = _native.lib()
+        with torch.cuda.device(self.device):
+            for start in range(0, a.numel(), _MAX_ADD_VOXELS):
+                n = min(_MAX_ADD_VOXELS, a.numel() - start)
+                _native.check(
+                    lib.exaspim_label_overlaps_add(a.data_ptr() + 4 * start, b.data_ptr() + 4 * start, n,
+                                                   self.pair_capacity, self._workspace.data_ptr(), self._bytes,
+                                                   _stream(self.device)),
+                    "exaspim_label_overlaps_add",
+                )
+        self.voxels += a.numel()
+
+    def finish_on_device(self):
+        """(pairs int32 (capacity, 2), counts int64 (capacity,), P): the first P rows, in an unspecified order."""
+        capacity, device = self.pair_capacity, self.device
+        with torch.cuda.device(device):
+            pairs = torch.empty((capacity, 2), dtype=torch.int32, device=device)
+            counts = torch.empty(capacity, dtype=torch.int64, device=device)
+            state = torch.empty(2, dtype=torch.int32, device=device)
+            _native.check(
+                _native.lib().exaspim_label_overlaps_finish(capacity, self._workspace.data_ptr(), self._bytes,
+                                                            pairs.data_ptr(), counts.data_ptr(), state.data_ptr(),
+                                                            _stream(device)),
+                "exaspim_label_overlaps_finish",
+            )
+            n_pairs, overflow = (int(v) for v in state.cpu())   # the one read of the device state
+        if overflow:
+            raise RuntimeError(
+                f"label_overlaps: the volumes have more distinct pairs of labels than pair_capacity={capacity}; "
+                "run it again with a larger pair_capacity (a power of two)")
+        return pairs, counts, n_pairs
+
+    def finish(self, return_device_tensors=False):
+        """
+        The table of everything added so far: pairs int32 (P, 2), rows
+        (a', b') sorted by (a', b'), and counts int64 (P,). With
+        return_device_tensors the first P rows as device tensors in the
+        table's own, unspecified order.
+        """
+        pairs, counts, n_pairs = self.finish_on_device()
+        if return_device_tensors:
+            return pairs[:n_pairs], counts[:n_pairs]
+        with torch.cuda.device(self.device):
+            pairs_h = pairs[:n_pairs].cpu().numpy().reshape(-1, 2)
+            counts_h = counts[:n_pairs].cpu().numpy()
+        order = np.lexsort((pairs_h[:, 1], pairs_h[:, 0]))   # slot order depends on arrival: sort by (a', b')
+        return np.ascontiguousarray(pairs_h[order]), np.ascontiguousarray(counts_h[order])
+
+
+def label_overlaps(a, b, *, pair_capacity=None, return_device_tensors=False):
+    """
+    The overlap table of two label volumes on the device: for
+    every ordered pair (label in a, label in b) that occurs at some voxel,
+    the number of voxels that carry it.
+
+    For a label value v, v' = v if v > 0 else 0: everything <= 0 is
+    background, as in fill_holes. For every voxel count[(a', b')] += 1. The
+    pair is ordered: (1, 2) and (2, 1) are different rows. Every positive
+    int32 is a legal label; no label becomes an address. Counts are 64-bit
+    integers, so the result does not depend on the order in which the device
+    adds them, and they sum to D * H * W.
+
+    Parameters
+    ----------
+    a, b : torch.Tensor or numpy.ndarray
+        int32 (D, H, W) of equal shape. Device tensors (on one HIP device)
+        are used where they are; numpy arrays are uploaded to cuda:0.
+    pair_capacity : int, optional
+        Slots of the device hash table, a power of two; 16 bytes each.
+        Default is the smaller of 2^22 and the next power of two >= 2 * D *
+        H * W.
+    return_device_tensors : bool, optional
+        Return the rows as device tensors, in the table's own unspecified
+        order.
+
+    Returns
+    -------
+    pairs : numpy.ndarray
+        int32 (P, 2), rows (a', b') sorted by (a', b').
+    counts : numpy.ndarray
+        int64 (P,).
+
+    Raises
+    ------
+    RuntimeError
+        If the volumes have more distinct pairs than pair_capacity; the
+        message asks for a larger one.
+    """
+    a, dims = _checked_labels(a, "label_overlaps", "a")
+    b, dims_b = _checked_labels(b, "label_overlaps", "b")
+    if dims != dims_b:
+        raise ValueError(f"label_overlaps: a and b must have one shape, got {dims} and {dims_b}")
+    if a.device != b.device:
+        raise RuntimeError(f"label_overlaps (MI355X) has no CPU path: a and b must be on one HIP device, got "
+                           f"{a.device} and {b.device}")
+    capacity = _checked_pair_capacity("label_overlaps", pair_capacity, int(np.prod(dims, dtype=np.int64)))
+    stream = OverlapStream(capacity, a.device)
+    stream.add(a, b)
+    return stream.finish(return_device_tensors)
+
+
+def _checked_label_source(fn, source, what):
+    """(source, (D, H, W)) of a streamed function that needs int32 labels on the host."""
+    if not hasattr(source, "shape") or not hasattr(source, "dtype") or not hasattr(source, "__getitem__"):
+        source = np.asarray(source)
+    if isinstance(source, torch.Tensor) or np.dtype(source.dtype) != np.dtype(np.int32):
+        raise TypeError(f"{fn}: {what} must be a host array of int32, got {type(source).__name__} of {source.dtype}")
+    shape = tuple(int(v) for v in source.shape)
+    if len(shape) != 3:
+        raise ValueError(f"{fn}: {what} must be (D, H, W), got {shape}")
+    if min(shape) < 1:
+        raise ValueError(f"{fn}: empty volume {shape}")
+    return source, shape
+
+
+def label_overlaps_streaming(source_a, source_b, *, slab_depth, pair_capacity=None, device=None):
+    """
+    label_overlaps for volumes that sit in host arrays, memmaps or zarr-like
+    arrays too large for the device (or for 2^31 - 1 voxels): z slabs of
+    "slab_depth" planes of both are uploaded and added one after the other
+    (OverlapStream). The table is additive over voxels, so the result is the
+    whole volume's, array for array, whatever the slab depth.
+
+    Parameters
+    ----------
+    source_a, source_b : array-like
+        int32 (D, H, W) of equal shape; only source[z0:z1] is ever read.
+    slab_depth : int
+        Planes per slab; slab_depth * H * W must stay within 2^31 - 1.
+    pair_capacity : int, optional
+        As in label_overlaps; the default is 2^22 or the next power of two
+        >= 2 * D * H * W if that is less.
+    device : torch.device, optional
+        Default is cuda:0.
+
+    Returns
+    -------
+    pairs, counts : numpy.ndarray
+        As label_overlaps gives them.
+    """
+    fn = "label_overlaps_streaming"
+    source_a, shape = _checked_label_source(fn, source_a, "source_a")
+    source_b, shape_b = _checked_label_source(fn, source_b, "source_b")
+    if shape != shape_b:
+        raise ValueError(f"{fn}: source_a and source_b must have one shape, got {shape} and {shape_b}")
+    _checked_integer(fn, "slab_depth", slab_depth)
+    slab_depth = int(slab_depth)
+    if slab_depth < 1:
+        raise ValueError(f"slab_depth must be positive, got {slab_depth}")
+    if min(slab_depth, shape[0]) * shape[1] * shape[2] > _MAX_ADD_VOXELS:
+        raise ValueError(f"{fn}: a slab of {slab_depth} planes of {shape[1:]} has more than 2^31 - 1 voxels")
+    capacity = _checked_pair_capacity(fn, pair_capacity, shape[0] * shape[1] * shape[2])
+    stream = OverlapStream(capacity, device)
+    for z0 in range(0, shape[0], slab_depth):
+        z1 = min(z0 + slab_depth, shape[0])
+        blocks = []
+        for source, what in ((source_a, "source_a"), (source_b, "source_b")):
+            block = np.asarray(source[z0:z1])
+            if block.dtype != np.int32 or block.shape != (z1 - z0,) + shape[1:]:
+                raise TypeError(f"{fn}: {what}[{z0}:{z1}] gave {block.dtype} {block.shape}")
+            blocks.append(block)
+        stream.add(*blocks)
+    return stream.finish()
+
+
+def overlap_scores(pairs, counts, *, background="a"):
+    """
+    The scores of two labelings read off their overlap table, on the host
+    (no GPU): the variation of information with its split and merge terms,
+    the adapted Rand error with its precision and recall, the Rand index,
+    the largest-overlap agreement and "the same partition up to names".
+
+    background says which rows count. "a" drops the rows with a' = 0: the
+    SNEMI3D / CREMI convention with a the ground truth, whose background is
+    not scored; b's 0 is then an ordinary segment. "both_zero" drops only
+    the row (0, 0). "none" drops nothing. Write n_ij for the counts of the
+    kept rows, a_i and b_j for their marginals and N for their sum.
+
+    Parameters
+    ----------
+    pairs : numpy.ndarray
+        Integer (P, 2), rows (a', b'), each pair at most once.
+    counts : numpy.ndarray
+        Integer (P,), positive.
+    background : {"a", "both_zero", "none"}
+
+    Returns
+    -------
+    dict
+        n : int, N.
+        segments_a, segments_b, pairs : int, the numbers of distinct a', of
+            distinct b' and of kept rows.
+        voi_split : float, H(B|A) = H(A,B) - H(A) in bits (log2): float64,
+            math.fsum over the rows sorted by (a', b').
+        voi_merge : float, H(A|B), computed the same way.
+        voi : float, voi_split + voi_merge.
+        rand_precision : float, (sum n_ij^2 - N) / (sum b_j^2 - N).
+        rand_recall : float, (sum n_ij^2 - N) / (sum a_i^2 - N).
+        adapted_rand_error : float, 1 - 2 p r / (p + r).
+        rand_index : float, the fraction of voxel pairs on which the two
+            labelings agree (together in both or apart in both):
+            1 - (sum a_i^2 + sum b_j^2 - 2 sum n_ij^2) / (N (N - 1)).
+        largest_overlap_agreement : float, whatever "background" says: the
+            sum over a' >= 1 of the largest count of a row (a', b'), b' = 0
+            included, divided by (the table's total - the count of (0, 0)).
+        same_partition : bool, true iff every a' occurs in exactly one kept
+            row and every b' in exactly one: the kept table is a bijection
+            between the labels.
+    The Rand quantities are exact: Python integers and fractions.Fraction
+    until the final float(). Where a denominator is 0 (no voxel pair to
+    judge: N < 2, or every segment a single voxel) precision, recall and the
+    Rand index are 1.0, the error is 0.0 where p + r is 0 as well, and an
+    empty agreement is 1.0; an empty table has voi 0.0 and same_partition
+    True.
+
+    What this is not: no claim of equality with skimage's, CREMI's or
+    funlib's numbers beyond the formulas stated here; no matching by
+    Hungarian assignment; no per-segment error lists.
+    """
+    import math
+    from fractions import Fraction
+
+    if background not in _BACKGROUND_MODES:
+        raise ValueError(f"overlap_scores: background must be one of {_BACKGROUND_MODES}, got {background!r}")
+    pairs, counts = np.asarray(pairs), np.asarray(counts)
+    if pairs.dtype.kind not in "iu" or counts.dtype.kind not in "iu":
+        raise TypeError(f"overlap_scores: pairs and counts must be integer arrays, got {pairs.dtype} and {counts.dtype}")
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or counts.shape != (pairs.shape[0],):
+        raise ValueError(f"overlap_scores: pairs must be (P, 2) and counts (P,), got {pairs.shape} and {counts.shape}")
+    rows = sorted(zip((int(v) for v in pairs[:, 0]), (int(v) for v in pairs[:, 1]), (int(v) for v in counts)))
+    if any(c <= 0 for _, _, c in rows):
+        raise ValueError("overlap_scores: counts must be positive")
+    if any(rows[i][:2] == rows[i + 1][:2] for i in range(len(rows) - 1)):
+        raise ValueError("overlap_scores: a pair occurs in more than one row")
+
+    # the largest-overlap agreement looks at the whole table
+    total = sum(c for _, _, c in rows)
+    zero = sum(c for i, j, c in rows if i == 0 and j == 0)
+    best = {}
+    for i, j, c in rows:
+        if i >= 1 and c > best.get(i, 0):
+            best[i] = c
+    agreement = float(Fraction(sum(best.values()), total - zero)) if total > zero else 1.0
+
+    if background == "a":
+        rows = [r for r in rows if r[0] != 0]
+    elif background == "both_zero":
+        rows = [r for r in rows if r[0] != 0 or r[1] != 0]
+    n = sum(c for _, _, c in rows)
+    a_sizes, b_sizes, a_rows, b_rows = {}, {}, {}, {}
+    for i, j, c in rows:
+        a_sizes[i] = a_sizes.get(i, 0) + c
+        b_sizes[j] = b_sizes.get(j, 0) + c
+        a_rows[i] = a_rows.get(i, 0) + 1
+        b_rows[j] = b_rows.get(j, 0) + 1
+
+    # H(B|A) = -sum n_ij / N log2(n_ij / a_i), one term per row, each >= 0
+    split = math.fsum(c / n * (math.log2(a_sizes[i]) - math.log2(c)) for i, j, c in rows) if n else 0.0
+    merge = math.fsum(c / n * (math.log2(b_sizes[j]) - math.log2(c)) for i, j, c in rows) if n else 0.0
+
+    sum_ij = sum(c * c for _, _, c in rows)
+    sum_a = sum(c * c for c in a_sizes.values())
+    sum_b = sum(c * c for c in b_sizes.values())
+    precision = Fraction(sum_ij - n, sum_b - n) if sum_b > n else Fraction(1)
+    recall = Fraction(sum_ij - n, sum_a - n) if sum_a > n else Fraction(1)
+    error = 1 - 2 * precision * recall / (precision + recall) if precision + recall > 0 else Fraction(0)
+    rand = 1 - Fraction(sum_a + sum_b - 2 * sum_ij, n * (n - 1)) if n > 1 else Fraction(1)
+    return {
+        "n": n,
+        "segments_a": len(a_sizes),
+        "segments_b": len(b_sizes),
+        "pairs": len(rows),
+        "voi_split": split,
+        "voi_merge": merge,
+        "voi": split + merge,
+        "rand_precision": float(precision),
+        "rand_recall": float(recall),
+        "adapted_rand_error": float(error),
+        "rand_index": float(rand),
+        "largest_overlap_agreement": agreement,
+        "same_partition": all(v == 1 for v in a_rows.values()) and all(v == 1 for v in b_rows.values()),
+    }
+
+
+def compare_segmentations(a, b, *, background="a", pair_capacity=None):
+    """
+    overlap_scores of label_overlaps(a, b): the table on the device, the
+    scores on the host. a is the ground truth where there is one
+    (background="a" leaves its background out, the SNEMI3D / CREMI
+    convention). See overlap_scores for the fields and for what this is not.
+    """
+    if background not in _BACKGROUND_MODES:
+        raise ValueError(f"compare_segmentations: background must be one of {_BACKGROUND_MODES}, got {background!r}")
+    pairs, counts = label_overlaps(a, b, pair_capacity=pair_capacity)
+    return overlap_scores(pairs, counts, background=background)

@@ -75,7 +75,9 @@ extern "C" {
  *    later within 5: exaspim_teasar_begin, exaspim_teasar_round, exaspim_teasar_apply (and their workspace
  *    query): TEASAR's loop of targets, branches and invalidation for every label at once;
  *    later within 5: exaspim_watershed_stream_slab and its workspace query (struct
- *    exaspim_watershed_stream): watershed fragments of a volume that arrives in z slabs */
+ *    exaspim_watershed_stream): watershed fragments of a volume that arrives in z slabs;
+ *    later within 5: exaspim_label_overlaps, exaspim_label_overlaps_reset / _add / _finish (and their
+ *    workspace query): the overlap table of two label volumes, whole or piece by piece */
 #define EXASPIM_ABI_VERSION 5
 
 /* error codes */
@@ -1558,6 +1560,61 @@ int exaspim_label_pieces_open(const int32_t* labels_dev, const int32_t dims[3], 
                               int64_t dust_threshold, uint32_t open_faces, int32_t* pieces_dev,
                               int32_t* state_dev /* [3] */, void* workspace_dev, size_t workspace_bytes,
                               void* stream);
+
+/* ---- the overlap table of two label volumes (later within ABI 5) -------------------------------
+ * How much two labelings of the same voxels differ -- the variation of information, the adapted Rand error,
+ * the largest-overlap agreement, "the same partition up to names" -- is a function of one small integer table,
+ * and this is the table.
+ *
+ * a and b are flat int32 arrays of n voxels; the table has no geometry. For a label value v, v' = v if v > 0
+ * else 0: everything <= 0 is background, as in exaspim_fill_holes. For every voxel, count[(a', b')] += 1. The
+ * key is an ordered pair: (1, 2) and (2, 1) are different rows. Every positive int32 is a legal label,
+ * 2^31 - 1 included; there is no n_labels and no label ever becomes an address. Counts are 64-bit integers:
+ * the table is exact in integers, a pure function of the voxels added whatever order the atomics land in, and
+ * the sum of all counts equals the number of voxels added. It is additive over voxels, so a volume added in
+ * pieces of any lengths gives the table of the whole, and the total may exceed 2^31 - 1 voxels.
+ *
+ * The table lives in the workspace between calls: an open-addressing table of pair_capacity slots (a power of
+ * two in 1 .. 2^30, the caller's choice) of a 64-bit key and a 64-bit count, an overflow word, and the block
+ * sums of the scan. More distinct pairs than slots: the contributions that find no slot are dropped, never
+ * written anywhere else, and state_dev[1] becomes 1; the output is then unusable.
+ *     reset    the table empty.
+ *     add      n voxels of a_dev and b_dev into the table, 0 <= n <= 2^31 - 1; n = 0 launches nothing. a_dev
+ *              and b_dev need 4-byte alignment only (a z slab sliced from a contiguous volume starts
+ *              anywhere); 16-byte loads are used wherever both addresses allow it.
+ *     finish   the occupied slots as rows: row i of pairs_dev (int32, pair_capacity x 2) = (a', b'),
+ *              count_dev[i] (int64), the first P in an UNSPECIFIED order (sort them after the download);
+ *              state_dev[0] = P, state_dev[1] = the overflow flag. finish only reads the table: the scan's
+ *              block sums are the only workspace words it writes, so it may be called twice with the same
+ *              result, and again after further adds, when it reports the larger total.
+ * exaspim_label_overlaps is reset + add + finish.
+ *
+ * What this is not: no claim of equality with skimage's, CREMI's or funlib's numbers beyond the formulas
+ * stated (overlap_scores in segmentation.py states them); no matching by Hungarian assignment; no
+ * per-segment error lists.
+ *
+ * Launches and memsets on "stream", nothing allocated, nothing synchronised. EXASPIM_E_INVALID for a NULL
+ * pointer, a pair_capacity that is not a power of two in 1 .. 2^30, n outside 0 .. 2^31 - 1 or a misaligned
+ * buffer (workspace_dev 16 bytes, count_dev 8, the rest 4); EXASPIM_E_WORKSPACE if workspace_bytes is less
+ * than exaspim_label_overlaps_workspace_bytes(pair_capacity): all decided from the argument values before
+ * anything is launched. */
+
+/* Scratch bytes of the four calls below: 16 bytes per slot, 256 for the overflow word and 4 per 2048 slots,
+ * each part rounded up to 256. 0 (and a message) if pair_capacity is not a power of two in 1 .. 2^30. */
+size_t exaspim_label_overlaps_workspace_bytes(int64_t pair_capacity);
+
+int exaspim_label_overlaps_reset(int64_t pair_capacity, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+int exaspim_label_overlaps_add(const int32_t* a_dev, const int32_t* b_dev, int64_t n, int64_t pair_capacity,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+int exaspim_label_overlaps_finish(int64_t pair_capacity, void* workspace_dev, size_t workspace_bytes,
+                                  int32_t* pairs_dev, int64_t* count_dev,
+                                  int32_t* state_dev /* [2]: rows P, overflow */, void* stream);
+
+int exaspim_label_overlaps(const int32_t* a_dev, const int32_t* b_dev, int64_t n, int64_t pair_capacity,
+                           int32_t* pairs_dev, int64_t* count_dev, int32_t* state_dev /* [2] */,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- synthetic input for benchmarks and tests --------------------------- */
 

@@ -116,17 +116,11 @@ def main():
         return "whole_watershed_premerge" + ("" if floor == floors[0] else f"_{floor}")
 
     def agreement(exact, merged):
-        """Largest-overlap agreement of two label volumes over the voxels either calls foreground."""
-        either = (exact > 0) | (merged > 0)
-        total = int(either.sum())
-        if total == 0:
-            return 1.0
-        a, b = exact[either].to(torch.int64), merged[either].to(torch.int64)
-        pairs, counts = torch.unique(a * (int(b.max()) + 1) + b, return_counts=True)
-        seg = pairs // (int(b.max()) + 1)
-        best = torch.zeros(int(seg.max()) + 1, dtype=torch.int64, device=dev)
-        best.scatter_reduce_(0, seg, counts, "amax")
-        return float(best[1:].sum()) / total
+        """Largest-overlap agreement of two label volumes over the voxels either calls foreground: the overlap
+        table on the device. The packed-torch.unique form this used to be is tools/overlaps_rate.py's
+        baseline."""
+        return inference.compare_segmentations(exact, merged)["largest_overlap_agreement"]
+
     res = {"size": n, "reps": args.reps, "device": torch.cuda.get_device_name(0), "low": LOW, "high": HIGH,
            "components_threshold": COMPONENTS_THRESHOLD, "thresholds": thresholds, "min_segment_size": min_size,
            "cases": {}}
